@@ -7,9 +7,13 @@ edges, 1,600 actors) whose flat input buffers are already resident in HBM.  The 
 once in a hipGraph and replayed per step.  N > 1: one process per GPU (torchrun), every rank runs its
 own batch (scenes are independent graphs: no data-path collective), value = all scenes / max time.
 
-Prints ONE JSON line on rank 0 (contract in the task brief) carrying `roofline` for the dominant
-kernel (the fused LaneConv layer, k_agg_mlp) and `cpu_baseline` (the oracle = CPU restatement of the
-reference on the same batch, timed on this box's host cores, rank 0 only).
+Prints ONE JSON line on rank 0 (contract in the task brief).  A plain run sets up, warms up, times
+--steps steps and prints the headline figure (`metric`, `value`, `unit`, `ms_per_step`, ...) and nothing
+else.  --full adds the figures that take runs of their own: `roofline` for the dominant kernel (the
+LaneConv layer), per-kernel and per-stage times, the single-stream and steady-state figures, the other
+arithmetic modes, the whole-Net / training-step timings and `cpu_baseline` (the oracle = CPU
+restatement of the reference on the same batch, timed on the host cores, rank 0 only).
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -32,6 +36,7 @@ PEAK_NOTE = {"f32": "fp32-input MFMA (v_mfma_f32_32x32x2_f32), 157.3 TF dense",
              "f16x2": "fp16 MFMA dense 2.5 PF / 3 products of the 2-way split (fp32-grade result)",
              "bf16": "bf16 MFMA dense 2.5 PF"}
 PEAK_HBM_GBPS = 8000.0             # HBM3E spec
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all files together
 
 
 def measured_traffic(workload, mma, impl="fused"):
@@ -238,6 +243,28 @@ def roofline_of(layer_us, n_nodes, sum_e, mma, workload, impl, launches):
     }
 
 
+def snapshot_outputs(out):
+    """Device copies of the floating-point tensors a caller of the forward receives ({"nodes", "actors"})."""
+    return {k: v.detach().clone() for k, v in out.items() if torch.is_tensor(v) and v.is_floating_point()}
+
+
+def dump_outputs(outs, path, budget=DUMP_BUDGET_BYTES):
+    """Writes every tensor of `outs` as path/<name>.npy (float64 stays float64, everything else float32).  When the
+    arrays together exceed `budget` bytes, each keeps a fixed, seeded sample of its rows (in row order)."""
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for k, v in outs.items():
+        v = v.detach().cpu()
+        arrs[k] = v.numpy() if v.dtype == torch.float64 else v.float().numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    for k, a in sorted(arrs.items()):
+        if total > budget and a.ndim >= 1 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * budget / total))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, "%s.npy" % k), np.ascontiguousarray(a))
+    return sorted(arrs)
+
+
 def time_steps(step, steps, warmup, barrier, dev, marks=None):
     """W untimed steps, then exactly K steps between barrier + synchronize on both sides; max over ranks.
     marks: a list that receives, per timed step, the host time at which the step was issued (seconds from t0) and
@@ -286,11 +313,13 @@ def replay_trace(lanes, steps):
                     "on lane j (its i-th forward)"}
 
 
-def run_mode(args, mma, mods, scenes, fb, actors, dev, rank, steps, warmup, trace=False):
-    """One arithmetic mode: S forwards in flight (the headline figure) and one forward at a time, both captured in
-    hipGraphs.  In the 16-bit-plane modes both run LaneConv on the weight-stationary kernel ("tiled"; at S2 its
-    "short" shape: 48-row blocks, one launch per layer); f32 and bf16x3 run the one-launch row-tile kernel
-    ("fused").  --laneconv forces either.  DESIGN.md sections 3.3 / 4."""
+def run_mode(args, mma, mods, scenes, fb, actors, dev, rank, steps, warmup, trace=False, single=True,
+             keep_outputs=False):
+    """One arithmetic mode: S forwards in flight (the headline figure) and, if `single`, one forward at a time, both
+    captured in hipGraphs.  In the 16-bit-plane modes both run LaneConv on the weight-stationary kernel ("tiled"; at S2
+    its "short" shape: 48-row blocks, one launch per layer); f32 and bf16x3 run the one-launch row-tile kernel
+    ("fused").  --laneconv forces either.  DESIGN.md sections 3.3 / 4.
+    keep_outputs: res["outputs"] = device copies of what the last timed step computed."""
     from lanegcn_amd import data as gen
     from lanegcn_amd import dist as D
     from lanegcn_amd import ops
@@ -303,9 +332,15 @@ def run_mode(args, mma, mods, scenes, fb, actors, dev, rank, steps, warmup, trac
     eng_one = HotPathEngine(mods["map_net"], mods["a2m"], mods["m2m"], mods["m2a"], mods["a2a"], lane_impl=impl_one)
     res = {"laneconv_impl": {"in_flight": impl_multi, "single": impl_one}}
     if args.no_graph:
-        step = lambda: eng_one.forward(fb, actors, mapnet_only=args.mapnet_only)
+        last = [None]
+
+        def step():
+            last[0] = eng_one.forward(fb, actors, mapnet_only=args.mapnet_only)
+
         elapsed = time_steps(step, steps, warmup, D.barrier, dev)
         res.update(ms_per_step=elapsed / steps * 1e3, elapsed=elapsed, streams=1)
+        if keep_outputs:
+            res["outputs"] = snapshot_outputs(last[0])
         res["laneconv_impl"]["in_flight"] = impl_one
         return res, eng_one
     # the lane streams are created FIRST: torch hands out its pool streams in order and ROCm maps consecutive HIP
@@ -346,6 +381,8 @@ def run_mode(args, mma, mods, scenes, fb, actors, dev, rank, steps, warmup, trac
     elapsed = time_steps(step, steps, warmup, D.barrier, dev)
     res.update(ms_per_step=elapsed / steps * 1e3, elapsed=elapsed, streams=S)
     res["graph_pool_MB_per_lane"] = [round(x, 1) for x in pools]
+    if keep_outputs:      # the last timed step ran lane (counter - 1) % S; later replays below overwrite its buffers
+        res["outputs"] = snapshot_outputs(lanes[(counter[0] - 1) % len(lanes)][2])
     if trace:
         # the same K steps once more, untimed on the host, with a HIP event behind every replay: when each step finished
         # on the device, measured from an event recorded on the idle GPU (attributes the fill / drain of the S lanes)
@@ -356,6 +393,8 @@ def run_mode(args, mma, mods, scenes, fb, actors, dev, rank, steps, warmup, trac
         res["steady_ms_per_step"] = time_steps(step, n_st, 0, D.barrier, dev) / n_st * 1e3
     # the range guard's device flag is part of every captured forward: none of them may have tripped
     assert not any(int(l[2]["nonfinite"].item()) for l in lanes if "nonfinite" in l[2]), "non-finite features in mode %s" % mma
+    if not single:
+        return res, eng_one
     if impl_one == impl_multi:
         g1, o1 = lanes[0][1], lanes[0][2]
     else:
@@ -499,7 +538,7 @@ def main():
     ap.add_argument("--mapnet-only", action="store_true",
                     help="step = graph_gather + CSR plan + MapNet only (BASELINE config 'MapNet LaneConv only', use with S1)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (--full; 0 = skip)")
     ap.add_argument("--streams", type=int, default=4,
                     help="forward graphs kept in flight on separate HIP streams (each on its own batch)")
     ap.add_argument("--mma", default=None, choices=["f32", "bf16x3", "f16x2", "bf16"],
@@ -507,8 +546,13 @@ def main():
     ap.add_argument("--laneconv", default=None, choices=["fused", "tiled"],
                     help="force one LaneConv implementation (default: fused with several forwards in flight, tiled for one)")
     ap.add_argument("--other-modes", default="f32,bf16x3,bf16",
-                    help="arithmetic modes reported next to the headline one in `modes` (comma list, '' = none)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the drop-in Net.forward / training-step timings")
+                    help="arithmetic modes reported next to the headline one in `modes` (--full; comma list, '' = none)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the drop-in Net.forward / training-step timings (--full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: roofline, per-kernel / per-stage times, "
+                         "single-stream and steady-state figures, other modes, whole-Net / training timings, CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -541,18 +585,24 @@ def main():
     actors = actors_cpu.to(dev)
     log("rank %d: batch ready (N=%d nodes, A=%d actors, sumE=%d)" % (rank, fb.n_nodes, fb.n_actors, sum(fb.n_edges)))
 
-    head, eng = run_mode(args, mma, mods, scenes, fb, actors, dev, rank, args.steps, args.warmup, trace=(world == 1))
+    head, eng = run_mode(args, mma, mods, scenes, fb, actors, dev, rank, args.steps, args.warmup,
+                         trace=args.full and world == 1, single=args.full,
+                         keep_outputs=bool(args.dump_outputs) and rank == 0)
     elapsed = head["elapsed"]
     log("rank %d: %d steps in %.4f s (%s)" % (rank, args.steps, elapsed, mma))
+    if args.dump_outputs and rank == 0:
+        log("outputs of the last timed step -> %s: %s" % (args.dump_outputs,
+                                                           ", ".join(dump_outputs(head.pop("outputs"), args.dump_outputs))))
 
-    # per-kernel durations (HIP events on the launch stream), eager launches of the single-forward engine
-    with ops.kernel_timer() as kt:
-        for _ in range(10):
-            eng.forward(fb, actors, mapnet_only=args.mapnet_only)
-    ksum = kt.summary()
-    lc_us, lc_launches, stages_tab, modes, extras = {}, {}, None, {}, {}
+    ksum, lc_us, lc_launches, stages_tab, modes, extras = {}, {}, {}, None, {}, {}
     n_scenes = len(scenes)
-    if rank == 0:
+    if args.full:
+        # per-kernel durations (HIP events on the launch stream), eager launches of the single-forward engine
+        with ops.kernel_timer() as kt:
+            for _ in range(10):
+                eng.forward(fb, actors, mapnet_only=args.mapnet_only)
+        ksum = kt.summary()
+    if args.full and rank == 0:
         st = eng.forward(fb, actors, stages=not args.mapnet_only, mapnet_only=args.mapnet_only)
         torch.cuda.synchronize()
         assert all(torch.isfinite(v).all() for v in st.values() if torch.is_tensor(v) and v.is_floating_point())
@@ -561,7 +611,7 @@ def main():
         for impl in (("fused",) if mma in ("f32", "bf16x3") else ("fused", "tiled")):      # tiled: two- / one-plane modes
             lc_us[impl], lc_launches[impl] = laneconv_launch_us(eng, fb, f_map, f_m2m, impl)
         stages_tab = None if args.mapnet_only or world > 1 else stage_table(eng, fb, actors)
-    if world == 1 and not args.mapnet_only and not args.no_graph:
+    if args.full and world == 1 and not args.mapnet_only and not args.no_graph:
         for m in [v for v in args.other_modes.split(",") if v and v != mma]:
             r, e_m = run_mode(args, m, mods, scenes, fb, actors, dev, rank, max(40, args.steps // 2), args.warmup)
             stm = e_m.forward(fb, actors, stages=True)
@@ -590,16 +640,6 @@ def main():
                 else "hot path forward (graph_gather+CSR plan+MapNet+A2M+M2M+M2A+A2A)")
         workload_desc = ("%s: %s, %d scenes/GPU, %d lane nodes, %d edges, %d actors, random-init weights, inputs "
                          "resident in HBM, %s" % (args.workload, what, n_scenes, fb.n_nodes, sum_e, fb.n_actors, how))
-        names = {"fused": ("lgcn::k_agg_mlp<1>" if mma == "f32" else "lgcn::k_agg_mlp_bf<RB,F,1>") + " (one-launch LaneConv layer)",
-                 "tiled": "lgcn::k_lc_tile<F,V,FIN>" + (" + lgcn::k_lc_combine<F>" if lc_launches.get("tiled", 1) > 1 else "") +
-                          " (weight-stationary LaneConv layer)"}
-        dom = head["laneconv_impl"]["in_flight"]
-        roofline = roofline_of(lc_us[dom], fb.n_nodes, sum_e, mma, args.workload, dom, lc_launches[dom])
-        roofline["kernel"] = names[dom] + ", 8 layers/step: the LaneConv of the timed configuration"
-        roofline["avg_launch_us_eager_event_pairs"] = float(np.mean(ksum["laneconv"])) * 1e3
-        roofline["note"] = ("traffic = HBM bytes per layer from the PMC passes (profiles/pmc_traffic.json); it is below the "
-                            "algorithmic bytes because the gathers of a row hit L2; what binds the one-launch kernel is the "
-                            "L2 -> CU weight stream, what binds the weight-stationary one is MFMA issue (DESIGN.md section 4)")
         line = {
             "metric": "Argoverse scenes/sec forward (batch=32, ~10k lane nodes)",
             "value": args.gpus * n_scenes * args.steps / elapsed,
@@ -613,18 +653,30 @@ def main():
             "mma": mma, "data": "synthetic",
             "config": {"workload": workload_desc,
                        "scenes_per_gpu": n_scenes, "parallelism": "dp%d (independent scene shards)" % args.gpus},
-            "roofline": roofline,
-            "laneconv": {"impl": head["laneconv_impl"], "layer_us": lc_us, "launches_per_layer": lc_launches,
-                         "roofline_by_impl": {k: {kk: roofline_of(v, fb.n_nodes, sum_e, mma, args.workload, k, 1)[kk]
-                                                  for kk in ("bound", "achieved", "peak", "unit", "frac")}
-                                              for k, v in lc_us.items()}},
-            "kernel_avg_us": {k: float(np.mean(v)) * 1e3 for k, v in ksum.items()},
-            "streams": head["streams"],
         }
+        if args.full:
+            names = {"fused": ("lgcn::k_agg_mlp<1>" if mma == "f32" else "lgcn::k_agg_mlp_bf<RB,F,1>") + " (one-launch LaneConv layer)",
+                     "tiled": "lgcn::k_lc_tile<F,V,FIN>" + (" + lgcn::k_lc_combine<F>" if lc_launches.get("tiled", 1) > 1 else "") +
+                              " (weight-stationary LaneConv layer)"}
+            dom = head["laneconv_impl"]["in_flight"]
+            roofline = roofline_of(lc_us[dom], fb.n_nodes, sum_e, mma, args.workload, dom, lc_launches[dom])
+            roofline["kernel"] = names[dom] + ", 8 layers/step: the LaneConv of the timed configuration"
+            roofline["avg_launch_us_eager_event_pairs"] = float(np.mean(ksum["laneconv"])) * 1e3
+            roofline["note"] = ("traffic = HBM bytes per layer from the PMC passes (profiles/pmc_traffic.json); it is below the "
+                                "algorithmic bytes because the gathers of a row hit L2; what binds the one-launch kernel is the "
+                                "L2 -> CU weight stream, what binds the weight-stationary one is MFMA issue (DESIGN.md section 4)")
+            line["roofline"] = roofline
+            line["laneconv"] = {"impl": head["laneconv_impl"], "layer_us": lc_us, "launches_per_layer": lc_launches,
+                                "roofline_by_impl": {k: {kk: roofline_of(v, fb.n_nodes, sum_e, mma, args.workload, k, 1)[kk]
+                                                         for kk in ("bound", "achieved", "peak", "unit", "frac")}
+                                                     for k, v in lc_us.items()}}
+            line["kernel_avg_us"] = {k: float(np.mean(v)) * 1e3 for k, v in ksum.items()}
+        line["streams"] = head["streams"]
         if stages_tab is not None:
             line["stages"] = stages_tab
         if "graph_pool_MB_per_lane" in head:      # device memory a captured forward keeps (its private pool), per lane
             line["graph_pool_MB_per_lane"] = head["graph_pool_MB_per_lane"]
+            line["settle_replays_per_lane"] = SETTLE_ROUNDS
         if "steady_ms_per_step" in head:
             line["value_steady"] = args.gpus * n_scenes / (head["steady_ms_per_step"] * 1e-3)
             line["steady_ms_per_step"] = head["steady_ms_per_step"]
@@ -634,7 +686,6 @@ def main():
                                   "figure is 119-120 k, with 64 it is 129-131 k, DESIGN.md section 4).  value_steady: the same "
                                   "step over max(200, K) steps.  A timed region starts on an idle chip and ends when the last "
                                   "forward has drained: those fixed costs weigh 1 / K (replay_trace)" % SETTLE_ROUNDS)
-            line["settle_replays_per_lane"] = SETTLE_ROUNDS
             line["replay_trace"] = head["replay_trace"]
         if "single_ms_per_step" in head:
             line["single_stream"] = {"value": args.gpus * n_scenes / (head["single_ms_per_step"] * 1e-3), "unit": "scenes/s",
@@ -642,7 +693,7 @@ def main():
         if modes:
             line["modes"] = modes
         line.update(extras)
-        if args.cpu_seconds > 0 and world == 1:      # reported baseline: rank 0, N = 1 only
+        if args.full and args.cpu_seconds > 0 and world == 1:      # reported baseline: rank 0, N = 1 only
             line["cpu_baseline"] = cpu_baseline(scenes, actors_cpu, mods, args.cpu_seconds)
             line["speedup_vs_cpu_all_cores"] = line["value"] / args.gpus / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)

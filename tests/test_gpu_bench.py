@@ -1,13 +1,16 @@
-"""bench.py contract check on the GPU box: one JSON line with the driver's keys, `roofline` and `cpu_baseline`.
+"""bench.py contract check on the GPU box: one JSON line with the driver's keys; with --full also `roofline` and
+`cpu_baseline`; --dump-outputs writes the last timed step's outputs.
 
 Runs the real script as a child process (short step count, bounded CPU sample) so a change in the engine's
 outputs cannot break the round-end bench unnoticed.
 """
 import json
 import os
+import re
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +28,7 @@ def _run(extra):
 
 
 def test_bench_default_line():
-    out = _run(["--cpu-seconds", "2"])
+    out = _run(["--full", "--cpu-seconds", "2"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in out, key
@@ -46,5 +49,32 @@ def test_bench_default_line():
 
 
 def test_bench_single_stream_eager_mapnet():
-    out = _run(["--streams", "1", "--no-graph", "--mapnet-only", "--workload", "S1", "--cpu-seconds", "0"])
+    out = _run(["--full", "--streams", "1", "--no-graph", "--mapnet-only", "--workload", "S1", "--cpu-seconds", "0"])
     assert out["value"] > 0 and "S1" in out["config"]["workload"]
+
+
+def test_bench_plain_line_and_dump(tmp_path):
+    """A plain run prints the headline keys only (nothing that takes runs of its own) and --dump-outputs writes the
+    last timed step's hot-path outputs; a second run with the same arguments computes the same values."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        out = _run(["--dump-outputs", str(d)])
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in out, key
+        assert out["steps"] == 5 and out["warmup"] == 2 and out["value"] > 0 and out["ms_per_step"] > 0
+        assert abs(out["value"] - out["n_gpus"] * out["config"]["scenes_per_gpu"] / (out["ms_per_step"] * 1e-3)) \
+            <= 1e-6 * out["value"]
+        for key in ("roofline", "cpu_baseline", "modes", "stages", "single_stream", "value_steady", "kernel_avg_us"):
+            assert key not in out, key
+        got = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(got) == {"nodes", "actors"}, sorted(got)
+        n_nodes = int(re.search(r"(\d+) lane nodes", out["config"]["workload"]).group(1))
+        n_actors = int(re.search(r"(\d+) actors", out["config"]["workload"]).group(1))
+        assert got["nodes"].dtype == np.float32 and got["nodes"].shape == (n_nodes, 128)
+        assert got["actors"].dtype == np.float32 and got["actors"].shape == (n_actors, 128)
+        assert all(np.isfinite(a).all() for a in got.values())
+        dumps.append(got)
+    for k in ("nodes", "actors"):
+        a, b = dumps[0][k], dumps[1][k]
+        assert float(np.abs(a - b).max()) <= 1e-4 * max(1.0, float(np.abs(a).max())), k

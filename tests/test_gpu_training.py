@@ -375,19 +375,26 @@ def test_train_driver_smoke_and_resume(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
+    import lanegcn_amd  # noqa: F401
+    from lanegcn_amd import lanegcn as M
     train_dp = importlib.import_module("train_dp")
     save = str(tmp_path / "run")
-    rc = train_dp.main(["--max-iters", "3", "--batch-size", "2", "--save-dir", save, "--dataset-len", "8"])
-    assert rc == 0
-    ckpts = sorted(os.listdir(save))
-    assert len(ckpts) == 1 and ckpts[0].endswith(".ckpt")
-    ck = torch.load(os.path.join(save, ckpts[0]), map_location="cpu", weights_only=True)
-    assert set(ck) == {"epoch", "state_dict", "opt_state"} and len(ck["state_dict"]) == 405
-    assert all(not v.is_cuda for v in ck["state_dict"].values())
-    rc = train_dp.main(["--max-iters", "1", "--batch-size", "2", "--save-dir", save, "--dataset-len", "8",
-                        "--resume", os.path.join(save, ckpts[0])])
-    assert rc == 0
-    assert train_dp.main(["--eval", "--weight", os.path.join(save, ckpts[0]), "--dataset-len", "4"]) == 0
+    saved = dict(M.config)     # the driver writes batch_size / save_dir / epoch into the shared config
+    try:
+        rc = train_dp.main(["--max-iters", "3", "--batch-size", "2", "--save-dir", save, "--dataset-len", "8"])
+        assert rc == 0
+        ckpts = sorted(os.listdir(save))
+        assert len(ckpts) == 1 and ckpts[0].endswith(".ckpt")
+        ck = torch.load(os.path.join(save, ckpts[0]), map_location="cpu", weights_only=True)
+        assert set(ck) == {"epoch", "state_dict", "opt_state"} and len(ck["state_dict"]) == 405
+        assert all(not v.is_cuda for v in ck["state_dict"].values())
+        rc = train_dp.main(["--max-iters", "1", "--batch-size", "2", "--save-dir", save, "--dataset-len", "8",
+                            "--resume", os.path.join(save, ckpts[0])])
+        assert rc == 0
+        assert train_dp.main(["--eval", "--weight", os.path.join(save, ckpts[0]), "--dataset-len", "4"]) == 0
+    finally:
+        M.config.clear()
+        M.config.update(saved)
 
 
 @pytest.mark.parametrize("mode", ["f32", "bf16x3", "f16x2", "bf16"])

@@ -234,7 +234,9 @@ def test_conv_entry_points_validate_before_launching(lib):
     assert call(n=0) == 0                                                            # nothing to do: no launch
     assert call(n=-1) == EINVAL and call(mode=3) == EINVAL and call(mode=-1) == EINVAL
     assert call(lin=8) == ESHAPE and call(lin=40) == ESHAPE                          # lout must be 5, 10 or 20
-    assert call(lin=20, stride=2, ks=1) != ESHAPE and call(stride=3) == ESHAPE and call(stride=0) == ESHAPE
+    # n = 0: the shapes are checked first, then nothing is launched (a valid call with n > 0 would launch on the
+    # placeholder pointers)
+    assert call(n=0, lin=20, stride=2, ks=1) == 0 and call(stride=3) == ESHAPE and call(stride=0) == ESHAPE
     assert call(cin=200) == ESHAPE and call(cout=96) == ESHAPE and call(ks=2) == ESHAPE
     assert call(lin=10, stride=2, mode=2, res=256) == ESHAPE                          # x2 upsampling needs an even lout
     assert call(x=None) == EINVAL and call(out=None) == EINVAL and call(g=None) == EINVAL

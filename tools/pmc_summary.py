@@ -1,7 +1,7 @@
 """Summarise rocprofv3 --pmc output directories into the CSV / JSON files kept under profiles/.
 
 Each counter group is collected in its OWN run (never together with a trace):
-    rocprofv3 --pmc FETCH_SIZE  --output-format csv -d DIR_F -- python bench.py --steps 20 --warmup 2 --cpu-seconds 0 --no-graph
+    rocprofv3 --pmc FETCH_SIZE  --output-format csv -d DIR_F -- python bench.py --full --steps 20 --warmup 2 --cpu-seconds 0 --no-graph
     rocprofv3 --pmc WRITE_SIZE  --output-format csv -d DIR_W -- python bench.py ... (same command)
     rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d DIR_S -- ...
     rocprofv3 --pmc TCC_REQ_sum TCC_HIT_sum TCC_MISS_sum --output-format csv -d DIR_T -- ...

@@ -10,10 +10,10 @@ if [ ! -f lanegcn-1_amd/liblgcn_stamps.so ] || [ lanegcn-1_amd/liblgcn_stamps.so
     exit 1
 fi
 # 1. the driver's own command, then the steady-state figure (longer run), then the 256-scene batch on one stream
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$out/bench_s2.json" 2> "$out/bench_s2.err"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$out/bench_s2.json" 2> "$out/bench_s2.err"
 echo "bench rc=$?"; tail -c 600 "$out/bench_s2.json" | head -c 300; echo
-python bench.py --steps 400 --warmup 40 --other-modes "" --no-extras --cpu-seconds 0 > "$out/bench_s2_steady.json" 2> /dev/null
-python bench.py --scenes 256 --streams 1 --steps 30 --warmup 5 --other-modes "" --no-extras --cpu-seconds 0 > "$out/bench_s2x8.json" 2> /dev/null
+python bench.py --full --steps 400 --warmup 40 --other-modes "" --no-extras --cpu-seconds 0 > "$out/bench_s2_steady.json" 2> /dev/null
+python bench.py --full --scenes 256 --streams 1 --steps 30 --warmup 5 --other-modes "" --no-extras --cpu-seconds 0 > "$out/bench_s2x8.json" 2> /dev/null
 echo "benches done"
 # 2. in-kernel stamp timeline of the LaneConv tile kernel (diagnostic build)
 python tools/stamps_lc.py 1 f16x2 32 2 2>&1 | grep -v amdgpu.ids > "$out/stamps_lc_tile_short.txt"
@@ -21,11 +21,11 @@ python tools/stamps_lc.py 1 f16x2 32 2 2>&1 | grep -v amdgpu.ids > "$out/stamps_
 bash tools/pmc_lc.sh short 1:2 > "$out/pmc.log" 2>&1
 cp gpurun_out/pmc_short_counters.csv "$out/" 2>/dev/null
 # 4. kernel traces of the bench: one forward at a time, four in flight
-bash tools/prof_bench.sh prof_1s --streams 1 --steps 60 --warmup 5 --other-modes "" --no-extras --cpu-seconds 0 > /dev/null 2>&1
+bash tools/prof_bench.sh prof_1s --full --streams 1 --steps 60 --warmup 5 --other-modes "" --no-extras --cpu-seconds 0 > /dev/null 2>&1
 db=$(find gpurun_out/prof_1s -name "*_results.db" | sort | tail -1)
 cp gpurun_out/prof_1s_kernel_stats.csv "$out/kernel_stats_bench_1stream.csv"
 python tools/trace_summary.py "$db" 0.5 /dev/null > "$out/trace_1stream.txt"
-bash tools/prof_bench.sh prof_4s --steps 160 --warmup 10 --other-modes "" --no-extras --cpu-seconds 0 > /dev/null 2>&1
+bash tools/prof_bench.sh prof_4s --full --steps 160 --warmup 10 --other-modes "" --no-extras --cpu-seconds 0 > /dev/null 2>&1
 db=$(find gpurun_out/prof_4s -name "*_results.db" | sort | tail -1)
 cp gpurun_out/prof_4s_kernel_stats.csv "$out/kernel_stats_bench_4streams.csv"
 python tools/trace_summary.py "$db" 0.5 /dev/null > "$out/trace_4streams.txt"

@@ -436,9 +436,6 @@ typedef struct {
     int32_t mma;
     float *part;                      /* workspace                               */
     float *out;                       /* [N,128]                                 */
-    int32_t waves;                    /* 0 / 8: 8-wave workgroups (K in two parts); 16: 16-wave workgroups, K in four
-                                         parts -- the "short" shape with n_groups = 1 only (else LGCN_EINVAL): four
-                                         waves per SIMD from ONE workgroup, for one forward at a time */
 } lgcn_laneconv_t;
 int lgcn_lc_config(int mma, int variant, int32_t *rows_per_block, int32_t *cap);
 int64_t lgcn_lc_plan_elems(int64_t n_nodes, int rows_per_block, int cap);
@@ -479,7 +476,7 @@ int lgcn_mapnet_input(const float *ctrs, const float *feats, int64_t n_rows,
  * V = ctx W_c0[:,256:384]^T (per context row) were hoisted out of the pair
  * loop (row-wise Linear commutes with the gather).  ctx.1 (:654) is applied
  * after the segment sum by lgcn_agg_mlp (it is linear).
- * m: [cap,128] output rows.
+ * m: [cap,128] output rows.  LGCN_MMA_F32 only (others: LGCN_ESHAPE -- use lgcn_att_pairs_ws / lgcn_att_pairs_wi).
  */
 int lgcn_att_pairs(const float *agt_ctrs, const float *ctx_ctrs,
                    const int32_t *hi, const int32_t *wi,
@@ -491,9 +488,8 @@ int lgcn_att_pairs(const float *agt_ctrs, const float *ctx_ctrs,
                    float eps, int mma, float *m, void *stream);
 
 /*
- * lgcn_att_pairs with both 128 x 128 weights held in registers by persistent workgroups (64-pair tiles): the same
- * m_p, without the 128 KB of weight fragments that lgcn_att_pairs streams through the CU per 32-pair tile.
- * Split-precision modes only (F32: LGCN_ESHAPE).
+ * The m_p of lgcn_att_pairs in the split-precision modes, with both 128 x 128 weights held in registers by persistent
+ * workgroups (64-pair tiles) instead of streamed through the CU per tile.  Split-precision modes only (F32: LGCN_ESHAPE).
  *   seg = 0 : m[p] = m_p for every pair p < *n_pairs (as lgcn_att_pairs).
  *   seg = 16: hi must be sorted (lgcn_pairs_build output).  Within every 16-aligned group of pair rows the rows of
  *             one target are summed in pair order; the sum is written at the row of the piece's first pair and the
@@ -547,34 +543,6 @@ int lgcn_pred_loss_fwd(const float *cls, const float *reg, const float *gt, cons
 int lgcn_pred_loss_bwd(const float *cls, const float *reg, const float *gt, const unsigned char *has, int64_t n_act,
                        int n_mod, int n_t, float cls_coef, float reg_coef, const int32_t *sel, const float *g_cls,
                        const float *g_reg, float *dcls, float *dreg, void *stream);
-
-/*
- * Att.forward for given pairs in ONE launch per tile of target rows (lanegcn.py:691-709): query path, per-pair MLP,
- * segment sum over the target's pairs (hi is sorted: contiguous), node epilogue.  Same arithmetic as
- * lgcn_agg_mlp_pair (U) + lgcn_att_pairs + lgcn_agg_mlp (tail), but the pair rows m_p stay on the CU:
- *   U[t]  = ReLU(GN_q(W_q a[t])) W_c0q^T            W_c0q = ctx.0 columns 128..255
- *   m_p   = ReLU(GN_c(W_c0e e_p + U[hi_p] + V[wi_p]))   e_p as in lgcn_att_pairs, V [S,128] from the caller
- *   out[t] = ReLU(GN_l(W_lin ReLU(GN_n(W_agt a[t] + W_c1 sum_{p: hi_p = t} m_p))) + a[t])
- * rowptr [T+1]: rowptr[t] = first pair with hi >= t (lgcn_pairs_build), rowptr[T] = P; values are clamped to cap.
- * targets_per_block: 8, 16 or 32 target rows (and all their pairs) per workgroup: small for few targets with many
- * pairs each (A2A), 32 for many targets with few pairs (A2M).  Split-precision modes only (F32: LGCN_ESHAPE).
- * The segment sums are formed in pair order by one thread group per target: no atomics, bitwise repeatable.
- */
-typedef struct {
-    const float *agts;                /* [T,128] target rows (also the residual) */
-    int64_t n_agt;
-    const float *agt_ctrs, *ctx_ctrs; /* [T,2], [S,2] */
-    const int32_t *hi, *wi, *rowptr;
-    int64_t cap;
-    const float *wpq, *gq, *bq, *wpc0q;
-    const float *wd0, *bd0, *wpd2, *gd, *btd, *wpc0e, *V, *gc, *btc;
-    const float *wpagt, *wpc1, *gn, *bn, *wplin, *gl, *bl;
-    float eps;
-    int32_t mma;
-    int32_t targets_per_block;
-    float *out;                       /* [T,128] */
-} lgcn_att_fused_t;
-int lgcn_att_fused(const lgcn_att_fused_t *p_host, void *stream);
 
 /* ------------------------------------------------------------------ */
 /* Backward building blocks (fp32; the row-GEMMs of the backward are     */

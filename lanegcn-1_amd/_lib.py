@@ -76,16 +76,8 @@ class LaneConv(C.Structure):      # lgcn_laneconv_t
         ("rows_per_block", C.c_int32), ("cap", C.c_int32), ("n_units", C.c_int32), ("n_groups", C.c_int32),
         ("gstart", C.c_int32 * (LC_UNITS + 1)),
         ("gn1_g", C.c_void_p), ("gn1_b", C.c_void_p), ("wp2", C.c_void_p), ("gn2_g", C.c_void_p), ("gn2_b", C.c_void_p),
-        ("eps", C.c_float), ("mma", C.c_int32), ("part", C.c_void_p), ("out", C.c_void_p), ("waves", C.c_int32),
+        ("eps", C.c_float), ("mma", C.c_int32), ("part", C.c_void_p), ("out", C.c_void_p),
     ]
-
-
-class AttFused(C.Structure):      # lgcn_att_fused_t
-    _fields_ = ([("agts", C.c_void_p), ("n_agt", C.c_int64), ("agt_ctrs", C.c_void_p), ("ctx_ctrs", C.c_void_p),
-                 ("hi", C.c_void_p), ("wi", C.c_void_p), ("rowptr", C.c_void_p), ("cap", C.c_int64)]
-                + [(n, C.c_void_p) for n in ("wpq", "gq", "bq", "wpc0q", "wd0", "bd0", "wpd2", "gd", "btd", "wpc0e", "V",
-                                             "gc", "btc", "wpagt", "wpc1", "gn", "bn", "wplin", "gl", "bl")]
-                + [("eps", C.c_float), ("mma", C.c_int32), ("targets_per_block", C.c_int32), ("out", C.c_void_p)])
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
@@ -122,7 +114,6 @@ SIGNATURES = {
     "lgcn_gather_rows": (C.c_int, [_P, _P, _P, _L, _P, _P]),
     "lgcn_gather_sum": (C.c_int, [_P, _P, _P, _L, _P, _P]),
     "lgcn_pair_add": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _P, _P]),
-    "lgcn_att_fused": (C.c_int, [C.POINTER(AttFused), _P]),
     "lgcn_check_finite": (C.c_int, [_P, _L, _P, _L, _P, _I, _P]),
     "lgcn_mapnet_input": (C.c_int, [_P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),

@@ -360,23 +360,19 @@ struct LcGeom {
                   "row block does not fit the LDS");
 };
 
-// KP = parts K is split into = waves per channel quarter: 2 (8 waves, every shape) or 4 (16 waves, round 3: the "short"
-// shape for ONE forward at a time -- four waves per SIMD from a single workgroup, each with half the MFMAs, weight
-// loads and LDS reads per unit; the four partial tiles meet in two steps in the epilogue).
-template <int F, int V, bool FIN, int KP = 2>
-__global__ __launch_bounds__(256 * KP) __attribute__((amdgpu_waves_per_eu(V == 1 ? 2 : 4)))
+template <int F, int V, bool FIN>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(V == 1 ? 2 : 4)))
 void k_lc_tile(const LcTileParams p) {
     using G = LcGeom<F, V>;
     constexpr int RBN = G::RBN, CAP = G::CAP, NP = G::NP, ROWB = G::ROWB, M = G::M, HRB = G::HRB, HR = G::HR, PH = G::PH;
-    constexpr int NT = 256 * KP, KSW = 4 / KP;         // threads (4 channel quarters x KP parts of K, one wave each); K-steps (of 32) per wave
+    constexpr int NT = 512, KSW = 2;                   // threads (4 channel quarters x 2 halves of K, one wave each); K-steps (of 32) per wave
     constexpr int HWS = NT / 32, RPS = NT / 8;         // half-waves (one source row each per loader step); rows per row-phase sweep
     constexpr int NIT = (CAP + HWS - 1) / HWS;
     constexpr bool DBUF = V == 1;                      // tall: a second weight-slice register set (256 VGPRs to spend)
-    static_assert(KP == 2 || (KP == 4 && !DBUF), "K in two parts (8 waves) or four (16 waves, not the tall shape)");
     constexpr int NLC = RBN > 8 ? 2 : 1;               // uint4 words of the per-row index
     __shared__ __attribute__((aligned(16))) unsigned char smem[G::SMEM];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cq = wave & 3, kh = wave >> 2;          // channel quarter, part of K (0 .. KP - 1)
+    const int cq = wave & 3, kh = wave >> 2;          // channel quarter, half of K
     const int kq = lane >> 4;
     const int item0 = xcd_chunk_remap(blockIdx.x, p.n_blocks * p.n_groups);
     const int b = item0 / p.n_groups, g = item0 % p.n_groups;
@@ -608,31 +604,15 @@ void k_lc_tile(const LcTileParams p) {
     float *T0 = reinterpret_cast<float *>(smem + G::TOFF);
     float *Tk = T0 + (kh & 1) * (HR * kLDA);
     constexpr int SW = (HR + RPS - 1) / RPS;        // sweeps of RPS rows (8 threads per row)
-    // the K parts' accumulators -> the two fp32 tiles T0 | T1.  Four parts: parts 0, 1 store, a barrier, parts 2, 3 add
-    // theirs onto T0 / T1 (every element is touched by exactly one lane of one wave per step: no atomics).  Ends with the
-    // tiles complete and a workgroup barrier passed.
+    // the K halves' accumulators -> the two fp32 tiles T0 | T1; ends with the tiles complete and a workgroup barrier passed
     auto tiles_from_acc = [&](int ph) {
-        if (KP == 2 || kh < 2) {
 #pragma unroll
-            for (int rb = 0; rb < HRB; ++rb)
+        for (int rb = 0; rb < HRB; ++rb)
 #pragma unroll
-                for (int cb = 0; cb < 2; ++cb)
-                    *reinterpret_cast<f32x4 *>(Tk + (16 * rb + (lane & 15)) * kLDA + 32 * cq + 16 * cb + 4 * (lane >> 4)) =
-                        acc[ph * HRB + rb][cb];
-        }
+            for (int cb = 0; cb < 2; ++cb)
+                *reinterpret_cast<f32x4 *>(Tk + (16 * rb + (lane & 15)) * kLDA + 32 * cq + 16 * cb + 4 * (lane >> 4)) =
+                    acc[ph * HRB + rb][cb];
         lds_barrier();
-        if (KP == 4) {
-            if (kh >= 2) {
-#pragma unroll
-                for (int rb = 0; rb < HRB; ++rb)
-#pragma unroll
-                    for (int cb = 0; cb < 2; ++cb) {
-                        f32x4 *q = reinterpret_cast<f32x4 *>(Tk + (16 * rb + (lane & 15)) * kLDA + 32 * cq + 16 * cb + 4 * (lane >> 4));
-                        *q = *q + acc[ph * HRB + rb][cb];
-                    }
-            }
-            lds_barrier();
-        }
     };
     auto tile_row = [&](int sweep) {
         RowVals r = row_load(T0 + sweep * RPS * kLDA, tid);
@@ -887,7 +867,6 @@ int lgcn_laneconv_fwd(const lgcn_laneconv_t *ph, void *stream) {
     }
     if (q.n_rows < 0 || variant < 0 || q.cap < M || q.cap > capv || q.n_rows > 0x7fffffff) return LGCN_EINVAL;
     if (!lc_groups_ok(q.n_units, q.n_groups, q.gstart)) return LGCN_EINVAL;
-    if (q.waves != 0 && q.waves != 8 && !(q.waves == 16 && variant == 2 && q.n_groups == 1)) return LGCN_EINVAL;
     if (q.n_rows == 0) return LGCN_OK;
     const void *ptrs[] = {q.x, q.plan, q.out, q.wp2, q.gn1_g, q.gn1_b, q.gn2_g, q.gn2_b};
     for (const void *v : ptrs) { LGCN_CHECK_PTR(v); LGCN_CHECK_ALIGN16(v); }
@@ -925,8 +904,7 @@ int lgcn_laneconv_fwd(const lgcn_laneconv_t *ph, void *stream) {
     } while (0)
 #define LGCN_LC(F_)                                                                                          \
     do {                                                                                                     \
-        if (q.waves == 16) hipLaunchKernelGGL((k_lc_tile<F_, 2, true, 4>), dim3(grid1), dim3(1024), 0, st, t); \
-        else if (q.n_groups == 1) LGCN_LCV(F_, true);                                                        \
+        if (q.n_groups == 1) LGCN_LCV(F_, true);                                                             \
         else {                                                                                               \
             LGCN_LCV(F_, false);                                                                             \
             hipLaunchKernelGGL((k_lc_combine<F_>), dim3(n_tiles), dim3(256), 0, st, c, n_tiles);             \

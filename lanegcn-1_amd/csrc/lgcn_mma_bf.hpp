@@ -72,13 +72,6 @@ __device__ __forceinline__ unsigned long long stamp() {
 #define LGCN_STAMP(slot) do { } while (0)
 #endif
 
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));  // v_cvt_pk_bf16_f32 (RNE)
-}
-__device__ __forceinline__ float bf16_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
 // Split 4 consecutive channels of one row into the format's planes and store them.
 template <int F>
 __device__ __forceinline__ void split_store(uint16_t *planes, int plane_elems, int row, int col, float4 v) {

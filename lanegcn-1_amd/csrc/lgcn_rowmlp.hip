@@ -656,6 +656,7 @@ int lgcn_att_pairs(const float *agt_ctrs, const float *ctx_ctrs, const int32_t *
                    const float *gd, const float *btd, const float *wpc0e, const float *U, const float *V,
                    const float *gc, const float *btc, float eps, int mma, float *m, void *stream) {
     if (cap < 0 || !valid_mma(mma)) return LGCN_EINVAL;
+    if (mma != LGCN_MMA_F32) return LGCN_ESHAPE;      // split-precision modes: lgcn_att_pairs_ws / lgcn_att_pairs_wi
     if (cap == 0) return LGCN_OK;
     if (cap > 0x7ffffff0) return LGCN_ESHAPE;
     const void *ptrs[] = {agt_ctrs, ctx_ctrs, hi, wi, n_pairs, wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, m};
@@ -663,7 +664,6 @@ int lgcn_att_pairs(const float *agt_ctrs, const float *ctx_ctrs, const int32_t *
     const void *al[] = {wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, m};
     for (const void *q : al) LGCN_CHECK_ALIGN16(q);
     PairParams p{agt_ctrs, ctx_ctrs, hi, wi, n_pairs, cap, wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, eps, m};
-    if (mma != LGCN_MMA_F32) return att_pairs_bf(p, mma, (hipStream_t)stream);
     int64_t tiles = (cap + kTM32 - 1) / kTM32;
     const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
     hipLaunchKernelGGL(k_att_pairs, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);

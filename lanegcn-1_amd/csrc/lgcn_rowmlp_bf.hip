@@ -621,77 +621,6 @@ __global__ __launch_bounds__(256) void k_mapnet_input_bf(const InputParams p, in
     }
 }
 
-template <int RB, int F>
-__global__ __launch_bounds__(256) void k_att_pairs_bf(const PairParams p) {
-    using TL = Tile<RB, F>;
-    constexpr int ROWS = TL::ROWS;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[TL::ABUF_BYTES + TL::T_BYTES];
-    uint16_t *A = reinterpret_cast<uint16_t *>(smem);
-    float *T = reinterpret_cast<float *>(smem + TL::ABUF_BYTES);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int64_t P = *p.n_pairs;
-    if (P < 0 || P > p.cap) P = p.cap;
-    const int64_t n_tiles = (P + ROWS - 1) / ROWS;
-    f32x4 acc[RB][2];
-    const uint4 *wd2 = reinterpret_cast<const uint4 *>(p.wpd2), *wc0 = reinterpret_cast<const uint4 *>(p.wpc0e);
-    BPair<F> bf;
-    if ((int64_t)blockIdx.x < n_tiles) ring_prime<F>(bf, wd2, wave, lane);
-
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int64_t pr0 = tile * ROWS;
-#pragma unroll
-        for (int c0 = 0; c0 < ROWS; c0 += 32) {
-            const int row = c0 + (tid >> 3);
-            if (row < ROWS) {
-                float dx = 0.f, dy = 0.f;
-                if (pr0 + row < P) {
-                    const float2 a = reinterpret_cast<const float2 *>(p.agt_ctrs)[p.hi[pr0 + row]];
-                    const float2 c = reinterpret_cast<const float2 *>(p.ctx_ctrs)[p.wi[pr0 + row]];
-                    dx = a.x - c.x; dy = a.y - c.y;
-                }
-                lin2_relu_split<F>(A, TL::PLANE, row, tid, dx, dy, p.wd0, p.bd0);
-            }
-        }
-        lds_barrier();
-        acc_zero<RB>(acc);
-        gemm_pass<RB, F>(A, wd2, wc0, bf, wave, lane, acc);
-        acc_store<RB>(T, acc, lane, wave);
-        lds_barrier();   // all waves done reading A; T complete
-#pragma unroll
-        for (int c0 = 0; c0 < ROWS; c0 += 32) {
-            const int row = c0 + (tid >> 3);
-            if (row < ROWS) {
-                RowVals r = row_load(T + c0 * kLDA, tid);
-                row_gn(r, tid, p.gd, p.btd, p.eps);
-                row_relu(r);
-                row_split_store<F>(A, TL::PLANE, row, tid, r);
-            }
-        }
-        lds_barrier();
-        acc_zero<RB>(acc);
-        gemm_pass<RB, F>(A, wc0, wd2, bf, wave, lane, acc);   // prefetches the next tile's first fragments
-        acc_store<RB>(T, acc, lane, wave);   // T's readers (previous row phase) passed the barrier above
-        lds_barrier();
-#pragma unroll
-        for (int c0 = 0; c0 < ROWS; c0 += 32) {
-            const int row = c0 + (tid >> 3);
-            if (row < ROWS) {
-                const int64_t pr = pr0 + row;
-                const bool live = pr < P;
-                RowVals r = row_load(T + c0 * kLDA, tid);
-                if (live) {
-                    row_add_global(r, p.U + (int64_t)p.hi[pr] * kC, tid);
-                    row_add_global(r, p.V + (int64_t)p.wi[pr] * kC, tid);
-                }
-                row_gn(r, tid, p.gc, p.btc, p.eps);
-                row_relu(r);
-                if (live) row_store_global(p.m + pr * kC, tid, r);
-            }
-        }
-        lds_barrier();   // next tile rewrites A (read by the last gemm) and T (read just above)
-    }
-}
-
 // ------------------------------------------------------------ dispatch -----
 // CUs of the current device, asked per call: the library keeps no state, not even a cache (the query is a
 // table lookup in the runtime, ~0.1 us, against launches of >= 5 us).
@@ -840,20 +769,6 @@ int mapnet_input_bf(const InputParams &p, int mma, hipStream_t st) {
     }
 #undef LGCN_IN_RB
 #undef LGCN_IN
-    return launch_status();
-}
-
-int att_pairs_bf(const PairParams &p, int mma, hipStream_t st) {
-    // 32-pair tiles (RB = 2): ~43 KB of LDS, so 3 workgroups share a CU and cover each other's
-    // row phases (this kernel has no separate gather waves)
-    const int64_t tiles = (p.cap + 31) / 32;
-    const int64_t slots = (int64_t)cu_count() * 3;
-    const unsigned grid = (unsigned)(tiles < slots ? tiles : slots);
-    switch (fmt_of(mma)) {
-        case 0: hipLaunchKernelGGL((k_att_pairs_bf<2, 0>), dim3(grid), dim3(256), 0, st, p); break;
-        case 1: hipLaunchKernelGGL((k_att_pairs_bf<2, 1>), dim3(grid), dim3(256), 0, st, p); break;
-        default: hipLaunchKernelGGL((k_att_pairs_bf<2, 2>), dim3(grid), dim3(256), 0, st, p); break;
-    }
     return launch_status();
 }
 

@@ -124,7 +124,6 @@ int agg_mlp_bf(const lgcn_agg_mlp_t &p, bool lane_conv, hipStream_t st);
 int agg_mlp_pair_bf(const lgcn_agg_mlp_t &a, const lgcn_agg_mlp_t &b, hipStream_t st);
 int agg_mlp_multi_bf(const lgcn_agg_mlp_t *const *ps, int n, hipStream_t st);
 int mapnet_input_bf(const InputParams &p, int mma, hipStream_t st);
-int att_pairs_bf(const PairParams &p, int mma, hipStream_t st);
 int pack_weight_bf(const float *W, int ld, int mma, int transpose, void *out, hipStream_t st);
 int pack_weight_batch_bf(const lgcn_pack_job_t *jobs, int n_jobs, int mma, hipStream_t st);
 

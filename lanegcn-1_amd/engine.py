@@ -183,8 +183,6 @@ class HotPathEngine:
         # scenes/s) and a loss with four graphs in flight (61 k vs 90 k) -> off by default.
         self.branches = branches
         self._side = None
-        # the integer stage as lgcn_index_build (4 launches) instead of 12; False: the separate entry points
-        self.fused_index = os.environ.get("LGCN_INDEX", "fused") == "fused"
         self._cnt_capture = None      # counter buffer of the forward being captured (capture(); it lives with the graph)
         # Pair capacities (rows of hi / wi and of every [cap, 128] pair-row buffer of a forward).  "bound": sum_i t_i s_i,
         # can never overflow (265 MB of pair rows per A2M layer at S2, untouched but reserved).  "tight" (default):
@@ -237,7 +235,7 @@ class HotPathEngine:
         bufs = [ops.pairs_alloc(s[0].shape[0], fb.n_scenes, s[5], dev) for s in searches]   # on the main stream
         if side is not None:
             side.wait_stream(main)
-        if side is None and self.fused_index and ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
+        if side is None and ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
             # graph_gather (lanegcn.py:171-209) + CSR plan + the three pair searches: four launches in all
             flag = torch.empty(1, dtype=torch.int32, device=dev)       # the range guard's flag, cleared by the first launch
             plan, pairs = ops.index_build(fb.idx_local, fb.seg_off, fb.seg_base, fb.rel_slices, fb.n_nodes, searches,
@@ -340,7 +338,7 @@ class HotPathEngine:
             searches = ((fb.node_ctrs, fb.node_off, fb.actor_ctrs, fb.actor_off, cfg["actor2map_dist"], fb.cap_a2m),
                         (fb.actor_ctrs, fb.actor_off, fb.node_ctrs, fb.node_off, cfg["map2actor_dist"], fb.cap_a2m),
                         (fb.actor_ctrs, fb.actor_off, fb.actor_ctrs, fb.actor_off, cfg["actor2actor_dist"], fb.cap_a2a))
-            if self.fused_index and ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
+            if ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
                 cnt = st.get("_cnt")             # the stage's own counters (its captured graph is replayed alone)
                 if cnt is None:
                     cnt = st["_cnt"] = ops.index_counters(fb.n_nodes, len(fb.rel_slices), fb.node_ctrs.device)

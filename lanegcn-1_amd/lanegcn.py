@@ -331,7 +331,7 @@ class Att(nn.Module):
     P per pair set; the benchmark engine switches it off to run sync-free."""
     strict = True
     legacy_offsets = True   # zero-pair scenes do not advance hi/wi offsets (lanegcn.py:681-687)
-    fold = os.environ.get("LGCN_ATT_FOLD", "1") != "0"      # att_block: row-block launches folded across the Att layers
+    fold = True             # att_block: row-block launches folded across the Att layers
 
     def __init__(self, n_agt: int, n_ctx: int) -> None:
         super().__init__()
@@ -386,26 +386,10 @@ class Att(nn.Module):
     def run(self, agts: Tensor, ctx: Tensor, ps: ops.PairSet, side: Optional[torch.cuda.Stream] = None) -> Tensor:
         """The pair MLP + segment reduce + node epilogue for a given pair set (lanegcn.py:691-709).
         `side`: a second stream for V (independent of U) -- fork/join around it, buffers allocated here."""
-        T = agts.shape[0]
-        lin = self.linear
-        c0 = self.ctx[0]
-        if ops.att_impl() == "fused" and ops.get_mma() != "f32" and side is None and ctx.shape[0] > 0:
-            # one launch per tile of targets: query path, pair MLP, segment sum and epilogue (lgcn_att_fused); the
-            # per-context V = ctx W_c0[:,256:384]^T is its own small GEMM
-            V = ops.agg_mlp(ctx.shape[0], [ops.RelSpec(ctx, ops.packed(c0.linear.weight, 256, 128))], 0)
-            return ops.att_fused(agts, ps, V, ops.packed(self.query.linear.weight), _gn(self.query.norm),
-                                 ops.packed(c0.linear.weight, 128, 128), self.dist[0].weight, self.dist[0].bias,
-                                 ops.packed(self.dist[2].linear.weight), _gn(self.dist[2].norm),
-                                 ops.packed(c0.linear.weight, 0, 128), _gn(c0.norm), ops.packed(self.agt.weight),
-                                 ops.packed(self.ctx[1].weight), _gn(self.norm), ops.packed(lin.linear.weight),
-                                 _gn(lin.norm), eps=self.norm.eps)
         # row-wise Linears commute with the gathers agts[hi] / ctx[wi]: evaluate them per node.  U (per target:
         # query -> GN -> ReLU -> ctx.0[:,128:256]) and V (per context row: ctx.0[:,256:384]) are independent:
         # one dual-problem launch
-        u_kw = dict(n_rows=T, rels=[ops.RelSpec(agts, ops.packed(self.query.linear.weight))],
-                    flags=L.F_GN1 | L.F_RELU1 | L.F_GEMM2, gn1=_gn(self.query.norm),
-                    wp2=ops.packed(c0.linear.weight, 128, 128), eps=self.query.norm.eps)
-        v_kw = dict(n_rows=ctx.shape[0], rels=[ops.RelSpec(ctx, ops.packed(c0.linear.weight, 256, 128))], flags=0)
+        u_kw, v_kw = self.u_kw(agts), self.v_kw(ctx)
         if side is not None:
             main = torch.cuda.current_stream()
             V = torch.empty((ctx.shape[0], ops.C_FEAT), dtype=torch.float32, device=ctx.device)
@@ -416,21 +400,9 @@ class Att(nn.Module):
             main.wait_stream(side)
         else:
             U, V = ops.agg_mlp_pair(u_kw, v_kw)
-        # few targets with many pairs each (M2A, A2A: at least as many context rows as targets): the pair kernel
-        # sums the rows of a target inside every 16-aligned group, and the tail reads one row per piece
-        seg = 16 if ops.att_pairs_impl() in ("ws", "wi") and ctx.shape[0] >= T else 0
-        m = ops.att_pairs(ps, self.dist[0].weight, self.dist[0].bias, (self.dist[2].linear.weight, 0),
-                          _gn(self.dist[2].norm), (c0.linear.weight, 0), U, V, _gn(c0.norm),
-                          eps=c0.norm.eps, seg=seg)
-        # ctx.1 is linear: apply it to the per-target segment sum instead of every pair
-        rels = [ops.RelSpec(agts, ops.packed(self.agt.weight)),
-                ops.RelSpec(m, ops.packed(self.ctx[1].weight), L.REL_RANGE16 if seg else L.REL_RANGE)]
-        return ops.agg_mlp(T, rels, _FULL, rowptr=ps.rowptr, gn1=_gn(self.norm),
-                           wp2=ops.packed(lin.linear.weight), gn2=_gn(lin.norm), res=agts, eps=self.norm.eps,
-                           tag="att_post")
+        return self.pairs_tail(agts, ctx.shape[0], ps, U, V)
 
-
-    # ---- the pieces of run(), for att_block (launch folding across the Att layers of a fusion block)
+    # ---- the pieces of run(), also used by att_block (launch folding across the Att layers of a fusion block)
     def u_kw(self, agts: Tensor) -> dict:
         """U = ReLU(GN_q(agts W_q^T)) W_c0[:,128:256]^T per target row, as an agg_mlp problem."""
         return dict(n_rows=agts.shape[0], rels=[ops.RelSpec(agts, ops.packed(self.query.linear.weight))],
@@ -448,21 +420,23 @@ class Att(nn.Module):
     def chain_v(self):
         return ops.packed(self.ctx[0].linear.weight, 256, 128)
 
-    def pairs_tail(self, agts: Tensor, n_ctx: int, ps: ops.PairSet, U: Tensor, V: Tensor, chain_u=None, chain_v=None,
-                   tile_rb: int = 0):
+    def pairs_tail(self, agts: Tensor, n_ctx: int, ps: ops.PairSet, U: Tensor, V: Tensor, chain_u=None, chain_v=None):
         """Pair MLP + segment sum + node epilogue for given U / V (lanegcn.py:693-709); the tail's launch can emit the
         NEXT layer's U / V from its output rows (chain_u / chain_v).  Returns out or (out, U'[, V'])."""
         T = agts.shape[0]
         lin, c0 = self.linear, self.ctx[0]
+        # few targets with many pairs each (M2A, A2A: at least as many context rows as targets): the pair kernel
+        # sums the rows of a target inside every 16-aligned group, and the tail reads one row per piece
         seg = 16 if ops.att_pairs_impl() in ("ws", "wi") and n_ctx >= T else 0
         m = ops.att_pairs(ps, self.dist[0].weight, self.dist[0].bias, (self.dist[2].linear.weight, 0),
                           _gn(self.dist[2].norm), (c0.linear.weight, 0), U, V, _gn(c0.norm),
                           eps=c0.norm.eps, seg=seg)
+        # ctx.1 is linear: apply it to the per-target segment sum instead of every pair
         rels = [ops.RelSpec(agts, ops.packed(self.agt.weight)),
                 ops.RelSpec(m, ops.packed(self.ctx[1].weight), L.REL_RANGE16 if seg else L.REL_RANGE)]
         return ops.agg_mlp(T, rels, _FULL, rowptr=ps.rowptr, gn1=_gn(self.norm),
                            wp2=ops.packed(lin.linear.weight), gn2=_gn(lin.norm), res=agts, eps=self.norm.eps,
-                           tag="att_post", chain_u=chain_u, chain_v=chain_v, tile_rb=tile_rb)
+                           tag="att_post", chain_u=chain_u, chain_v=chain_v)
 
 
 def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: Optional[dict] = None, uv=None,
@@ -479,15 +453,12 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
     Returns (out, uv_next) -- uv_next is None without next_att."""
     n = len(atts)
     Vs = [None] * n
-    rows_t = head["n_rows"] if head is not None else agts.shape[0]
-    rb = _att_rb(rows_t)
     if uv is not None:
         U, Vs[0] = uv
     else:
         first = dict(head, chain_u=atts[0].chain_u()) if head is not None else atts[0].u_kw(agts)
         probs = [first] + [atts[i].v_kw(ctx) for i in range(1 if ctx_is_agts else n)]
-        rb_head = _att_rb(max(q["n_rows"] for q in probs))
-        res = ops.agg_mlp_multi([dict(q, tile_rb=rb_head) for q in probs], tag="att_head")
+        res = ops.agg_mlp_multi(probs, tag="att_head")
         if head is not None:
             agts, U = res[0]
         else:
@@ -504,7 +475,7 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
         want_v = nxt is not None and (ctx_is_agts if i + 1 < n else next_ctx_is_out)
         n_ctx = agts.shape[0] if ctx_is_agts else ctx.shape[0]
         res = att.pairs_tail(agts, n_ctx, ps, U, Vs[i], chain_u=nxt.chain_u() if nxt is not None else None,
-                             chain_v=nxt.chain_v() if want_v else None, tile_rb=rb)
+                             chain_v=nxt.chain_v() if want_v else None)
         if nxt is None:
             agts = res
         elif i + 1 < n:
@@ -516,18 +487,8 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
     return agts, uv_next
 
 
-def _att_rb(n_rows: int) -> int:
-    """Tile height (16-row blocks) of a fusion block's row-block launches; 0 = the library's pick.  These launches are
-    chains of up to five 128 x 128 passes whose weights every workgroup streams from L2: with enough rows to give
-    every CU a tile anyway, taller tiles halve the weight bytes a CU pulls."""
-    rb = int(os.environ.get("LGCN_ATT_RB", "-1"))
-    if rb >= 0:
-        return rb
-    return 0
-
-
 def _fold_ok(ctx: Tensor) -> bool:
-    return Att.fold and ops.att_impl() != "fused" and ctx.shape[0] > 0
+    return Att.fold and ctx.shape[0] > 0
 
 
 def _strict_check(ps: ops.PairSet):
@@ -749,12 +710,12 @@ class ActorNet(nn.Module):
         return ok and all(n in (5, 10, 20) for n in lens) and all(lens[i] == 2 * lens[i + 1] for i in range(len(lens) - 1)) and \
             all(c.in_channels <= 128 and c.out_channels in (32, 64, 128) and c.kernel_size[0] in (1, 3) and c.stride[0] in (1, 2) for c in convs)
 
-    # "hip": lgcn_conv1d_gn / lgcn_res1d_gn launches; "miopen": stock channels-last convolutions + lgcn_gn_cl (LGCN_ACTORNET)
-    impl = os.environ.get("LGCN_ACTORNET", "hip")
+    # "hip": lgcn_conv1d_gn / lgcn_res1d_gn launches; "miopen": stock channels-last convolutions + lgcn_gn_cl
+    impl = "hip"
     # a Res1d block (conv + GN + ReLU + conv + GN + shortcut + ReLU) in ONE launch (lgcn_res1d_gn) instead of two or three
-    fuse_blocks = os.environ.get("LGCN_ACTORNET_BLOCKS", "1") != "0"
+    fuse_blocks = True
     # the two Res1d blocks of a group in ONE launch (lgcn_res1d_pair_gn)
-    fuse_groups = os.environ.get("LGCN_ACTORNET_GROUPS", "1") != "0"
+    fuse_groups = True
 
     def _channels_last_ok(self, actors: Tensor) -> bool:
         mods = [b for g in self.groups for b in g] + [self.output]
@@ -832,7 +793,7 @@ class PredNet(nn.Module):
         self.att_dest = AttDest(n)
         self.cls = nn.Sequential(LinearRes(n, n, norm="GN", ng=1), nn.Linear(n, 1))
 
-    impl = os.environ.get("LGCN_PREDNET", "hip")      # "hip": the stock-op tail on lgcn_pred_reg / lgcn_pred_final (inference)
+    impl = "hip"      # "hip": the stock-op tail on lgcn_pred_reg / lgcn_pred_final (inference); "stock": ATen only
 
     def _hip_ok(self, actors: Tensor) -> bool:
         cfg = self.config
@@ -888,7 +849,7 @@ def _net_replay_or_run(self, eng, hfb, feats, rot, orig, sizes):
     is uploaded and run eagerly.  Net.graph_cache = False disables it."""
     m = hfb.meta
     sig = (m["n_nodes"], m["n_actors"], tuple(m["n_edges"]), tuple(sizes), m["cap_a2m"], m["cap_a2a"], ops.get_mma(),
-           ops.att_impl(), ops.att_pairs_impl(), ops.laneconv_impl(), Att.strict, ActorNet.impl, PredNet.impl,
+           ops.att_pairs_impl(), ops.laneconv_impl(), Att.strict, ActorNet.impl, PredNet.impl,
            sum(p._version for p in ops.module_params(self)))
     st = self.__dict__.setdefault("_graph_state", {"last": None, "sig": None, "graph": None})
     if Net.graph_cache and st["graph"] is not None and st["sig"] == sig:
@@ -1023,7 +984,7 @@ def _tree_cpu(x):
 class PredLoss(nn.Module):
     """Max-margin mode classification + SmoothL1 regression of the closest mode (reference lanegcn.py:740-807)."""
 
-    impl = os.environ.get("LGCN_PREDLOSS", "hip")      # "stock": the ATen composition below
+    impl = "hip"      # "stock": the ATen composition below
 
     def __init__(self, config):
         super().__init__()

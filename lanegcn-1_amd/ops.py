@@ -363,14 +363,6 @@ def index_build(idx_local: torch.Tensor, seg_off: torch.Tensor, seg_base: torch.
 
 
 # ------------------------------------------------------------------ ActorNet's convolution block (row f1)
-def conv_shape_ok(cin: int, cout: int, ks: int, stride: int, lin: int) -> bool:
-    """Shapes lgcn_conv1d_gn takes (ActorNet's all do)."""
-    if cin < 1 or cin > 128 or cout not in (32, 64, 128) or ks not in (1, 3) or stride not in (1, 2) or lin < 1:
-        return False
-    lout = (lin + 2 * ((ks - 1) // 2) - ks) // stride + 1
-    return lout in (5, 10, 20)      # 16 / 8 / 4 actors per 80-row workgroup
-
-
 def conv_packed(weight: torch.Tensor) -> torch.Tensor:
     """Packed image of a Conv1d weight [cout, cin, ks] for lgcn_conv1d_gn, cached on the parameter."""
     def make():
@@ -847,31 +839,8 @@ def cu_count(device) -> int:
     return _cu_cache[idx]
 
 
-_lc_groups_forced = int(os.environ.get("LGCN_LC_GROUPS", "0"))
-_lc_variant_forced = int(os.environ.get("LGCN_LC_VARIANT", "-1"))
-
-
-def set_lc_variant(v: int):
-    """Force the row-block shape of subsequently built LaneConv plans (0 shared, 1 tall, 2 short, -1 = pick by size)."""
-    global _lc_variant_forced
-    _lc_variant_forced = int(v)
-
-_lc_impl = os.environ.get("LGCN_LANECONV", "tiled")
-# Att layer for a given pair set: "split" (default) = U/V GEMMs + per-pair MLP (writes m [cap,128]) + segment-sum
-# tail, three wide launches; "fused" = lgcn_att_fused, one launch per tile of targets that keeps the pair rows on
-# the CU: no [cap,128] buffer (0.3-1.6 GB per call on large batches), measured 1.2-1.6x slower at S2.
-_att_impl = os.environ.get("LGCN_ATT", "split")
-
-
-def set_att_impl(name: str):
-    global _att_impl
-    if name not in ("fused", "split"):
-        raise L.LgcnError("att impl must be 'fused' or 'split'")
-    _att_impl = name
-
-
-def att_impl() -> str:
-    return _att_impl
+_lc_groups_forced = 0
+_lc_impl = "tiled"
 
 
 def set_laneconv_impl(name: str):
@@ -904,8 +873,6 @@ def lc_plan(lane: LanePlan, n_groups: Optional[int] = None, cap: Optional[int] =
         return None
     lib = L.load()
     if variant is None:
-        variant = _lc_variant_forced
-    if variant is None or variant < 0:
         cus = cu_count(lane.rowptr.device)
         m_tall, _ = lc_config(variant=1)
         m_short, _ = lc_config(variant=2)
@@ -951,28 +918,10 @@ def lc_part(lcp: LcPlan) -> Optional[torch.Tensor]:
     return torch.empty(n, dtype=torch.float32, device=lcp.plan.device)
 
 
-_lc_waves = int(os.environ.get("LGCN_LC_WAVES", "0"))      # 16: 16-wave workgroups for the short one-group shape
-
-
-def set_lc_waves(n: int):
-    """Waves per LaneConv workgroup of the short, one-group shape: 0 / 8 (default) or 16 (K split four ways: four waves
-    per SIMD from one workgroup -- for ONE forward at a time; with several forwards in flight two 8-wave workgroups of
-    different forwards share a CU instead)."""
-    global _lc_waves
-    if n not in (0, 8, 16):
-        raise L.LgcnError("LaneConv workgroups have 8 or 16 waves")
-    _lc_waves = n
-
-
-def lc_waves() -> int:
-    return _lc_waves
-
-
 def laneconv_fwd(x: torch.Tensor, lcp: LcPlan, wps: Sequence[Optional[torch.Tensor]], gn1, wp2, gn2, eps=EPS,
-                 part: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, tag="laneconv",
-                 waves: Optional[int] = None):
+                 part: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, tag="laneconv"):
     """One LaneConv layer (lgcn_laneconv_fwd): wps[u] = packed weight of unit u (ctr, then the plan's relations;
-    None for a relation without edges).  waves: None = the module setting (set_lc_waves) where the plan allows it."""
+    None for a relation without edges)."""
     lib = L.load()
     x = _dev(x, torch.float32, "x")
     if x.shape[0] != lcp.lane.n_nodes or len(wps) != lcp.n_units:
@@ -987,9 +936,6 @@ def laneconv_fwd(x: torch.Tensor, lcp: LcPlan, wps: Sequence[Optional[torch.Tens
         p.gstart[g] = v
     p.gn1_g, p.gn1_b, p.wp2, p.gn2_g, p.gn2_b = gn1[0].data_ptr(), gn1[1].data_ptr(), wp2.data_ptr(), gn2[0].data_ptr(), gn2[1].data_ptr()
     p.eps, p.mma = eps, _mma
-    short = lc_config(variant=2)
-    w = _lc_waves if waves is None else waves
-    p.waves = 16 if (w == 16 and short is not None and lcp.rows_per_block == short[0] and len(lcp.gstart) == 2) else 0
     if part is None:
         part = lc_part(lcp)
     if out is None:
@@ -1012,16 +958,17 @@ def mapnet_input(ctrs, feats, wa1, ba1, wpa2, gn_a, ws1, bs1, wps2, gn_s, eps=EP
     return out
 
 
-# Per-pair MLP of Att: "ws" (default in the 16-bit-plane modes) = lgcn_att_pairs_ws, both weights in registers;
-# "stream" = lgcn_att_pairs, weight fragments streamed per 32-pair tile (the only one in f32).
-# "wi" = lgcn_att_pairs_wi, wave-independent 16-pair blocks with both weights in LDS (f16x2 / bf16; the default there).
-_att_pairs_impl = os.environ.get("LGCN_ATT_PAIRS", "wi")
+# Per-pair MLP of Att in the 16-bit-plane modes: "wi" (default) = lgcn_att_pairs_wi, wave-independent 16-pair blocks
+# with both weights in LDS (f16x2 / bf16); "ws" = lgcn_att_pairs_ws, both weights in registers (bf16x3, whose three
+# planes do not fit the LDS).  f32 runs "stream" = lgcn_att_pairs, weight fragments streamed per 32-pair tile.
+_att_pairs_impl = "wi"
 
 
 def set_att_pairs_impl(name: str):
+    """"wi" (default) or "ws" where the mode has both (f16x2 / bf16)."""
     global _att_pairs_impl
-    if name not in ("wi", "ws", "stream"):
-        raise L.LgcnError("att pairs impl must be 'wi', 'ws' or 'stream'")
+    if name not in ("wi", "ws"):
+        raise L.LgcnError("att pairs impl must be 'wi' or 'ws'")
     _att_pairs_impl = name
 
 
@@ -1081,37 +1028,6 @@ def att_pairs(ps: PairSet, wd0, bd0, wpd2, gn_d, wpc0e, U, V, gn_c, m=None, eps=
             rc = lib.lgcn_att_pairs(*args, _ptr(m), _stream())
     L.check(rc, "lgcn_att_pairs")
     return m
-
-
-def att_targets_per_block(n_agt: int, device) -> int:
-    """Target rows per workgroup of att_fused: as many as still give the chip ~a workgroup per CU (8..32)."""
-    forced = int(os.environ.get("LGCN_ATT_TT", "0"))        # tests / tuning
-    if forced:
-        return forced
-    per = n_agt / max(1, cu_count(device))
-    return 32 if per >= 24 else 16 if per >= 12 else 8      # lgcn_att_fused also takes 4
-
-
-def att_fused(agts, ps: PairSet, V, wq, gn_q, wc0q, wd0, bd0, wd2, gn_d, wc0e, gn_c, wagt, wc1, gn_n, wlin, gn_l,
-              eps=EPS, targets_per_block: Optional[int] = None, tag="att_fused"):
-    """One Att layer for a given pair set (lgcn_att_fused): packed weights w*, (gamma, beta) pairs gn_*."""
-    lib = L.load()
-    agts = _dev(agts, torch.float32, "agts")
-    out = torch.empty_like(agts)
-    p = L.AttFused()
-    p.agts, p.n_agt, p.agt_ctrs, p.ctx_ctrs = agts.data_ptr(), agts.shape[0], ps.agt_ctrs.data_ptr(), ps.ctx_ctrs.data_ptr()
-    p.hi, p.wi, p.rowptr, p.cap = ps.hi.data_ptr(), ps.wi.data_ptr(), ps.rowptr.data_ptr(), ps.cap
-    p.wpq, p.gq, p.bq, p.wpc0q = wq.data_ptr(), gn_q[0].data_ptr(), gn_q[1].data_ptr(), wc0q.data_ptr()
-    p.wd0, p.bd0, p.wpd2, p.gd, p.btd = wd0.data_ptr(), bd0.data_ptr(), wd2.data_ptr(), gn_d[0].data_ptr(), gn_d[1].data_ptr()
-    p.wpc0e, p.V, p.gc, p.btc = wc0e.data_ptr(), V.data_ptr(), gn_c[0].data_ptr(), gn_c[1].data_ptr()
-    p.wpagt, p.wpc1, p.gn, p.bn = wagt.data_ptr(), wc1.data_ptr(), gn_n[0].data_ptr(), gn_n[1].data_ptr()
-    p.wplin, p.gl, p.bl = wlin.data_ptr(), gn_l[0].data_ptr(), gn_l[1].data_ptr()
-    p.eps, p.mma = eps, _mma
-    p.targets_per_block = targets_per_block or att_targets_per_block(agts.shape[0], agts.device)
-    p.out = out.data_ptr()
-    with _Timed(tag):
-        L.check(lib.lgcn_att_fused(C.byref(p), _stream()), "lgcn_att_fused")
-    return out
 
 
 def pred_loss_fwd(cls, reg, gt, has, cfg):

@@ -983,42 +983,23 @@ def test_gn_cl_channels_last_layout(hip, shape):
         assert float((got.cpu().double() - (up + ref)).abs().max()) <= 2e-5
 
 
-def test_att_fused_launch_vs_reference_captures(gcase, golden, hip, mma_mode):
-    """The memory-lean Att implementation (lgcn_att_fused: one launch per tile of targets, pair rows never written
-    to HBM) against the reference's stage captures, for every tile width; same 1e-4 bar as the default."""
-    M, ops = hip
-    if mma_mode == "f32":
-        pytest.skip("split-precision kernel")
-    scenes, _, mods = gcase
-    actors = torch.from_numpy(golden["actors_in"])
-    ops.set_att_impl("fused")
-    try:
-        for tt in (4, 8, 16, 32):
-            import os
-            os.environ["LGCN_ATT_TT"] = str(tt)
-            out, _ = run_hot_path(M, mods, scenes, actors)
-            for k in ("a2m", "m2m", "m2a", "a2a"):
-                err = float(np.abs(out[k] - golden[k]).max())
-                assert err <= FTOL, (tt, k, err)
-    finally:
-        os.environ.pop("LGCN_ATT_TT", None)
-        ops.set_att_impl("split")
-
-
-def test_att_pairs_weight_stationary_and_pieces(gcase, golden, hip, mma_mode):
+def test_att_pairs_ws_wi_agree_and_pieces(gcase, golden, hip, mma_mode):
     """lgcn_att_pairs_ws (weights in registers, 64-pair tiles) and lgcn_att_pairs_wi (weights in LDS, wave-independent
-    16-pair blocks): (1) seg = 0 writes the same pair rows as the streaming kernel; (2) seg = 16 writes exactly the
+    16-pair blocks): (1) seg = 0 writes the same pair rows as the other kernel of the mode (ws against wi in f16x2 /
+    bf16; in bf16x3, which has ws only, against the exact-f32 kernel lgcn_att_pairs); (2) seg = 16 writes exactly the
     per-target sums of the 16-aligned pieces, at the piece's first row, and touches no other row; (3) the whole hot path
-    with every pair kernel meets the reference captures."""
+    with every pair kernel of the mode meets the reference captures."""
     M, ops = hip
     if mma_mode == "f32":
         pytest.skip("split-precision kernel")
     scenes, _, mods = gcase
     actors = torch.from_numpy(golden["actors_in"])
-    # (3) both implementations end to end
+    # (3) every implementation of the mode end to end
     try:
-        for impl in ("stream", "ws", "wi"):
+        for impl in ("ws", "wi"):
             ops.set_att_pairs_impl(impl)
+            if ops.att_pairs_impl() != impl:
+                continue                      # wi: two- / one-plane modes only
             out, _ = run_hot_path(M, mods, scenes, actors)
             for k in ("a2m", "m2m", "m2a", "a2a"):
                 err = float(np.abs(out[k] - golden[k]).max())
@@ -1043,21 +1024,27 @@ def test_att_pairs_weight_stationary_and_pieces(gcase, golden, hip, mma_mode):
         V = ops.agg_mlp(n, [ops.RelSpec(x, ops.packed(c0.linear.weight, 256, 128))], 0)
         args = (ps, att.dist[0].weight, att.dist[0].bias, (att.dist[2].linear.weight, 0), M._gn(att.dist[2].norm),
                 (c0.linear.weight, 0), U, V, M._gn(c0.norm))
-        ops.set_att_pairs_impl("stream")
         try:
-            m_ref = ops.att_pairs(*args)[:P].cpu().numpy()
+            m = {}
+            for impl in ("ws", "wi"):
+                ops.set_att_pairs_impl(impl)
+                if ops.att_pairs_impl() == impl:      # wi: two- / one-plane modes only
+                    m[impl] = ops.att_pairs(*args)[:P].cpu().numpy()
+            if "wi" in m:
+                m_ref = m["wi"]
+            else:
+                with ops.mma_scope("f32"):            # lgcn_att_pairs on f32-packed images of the same weights
+                    m_ref = ops.att_pairs(*args)[:P].cpu().numpy()
+            err = float(np.abs(m["ws"] - m_ref).max()) / max(1.0, float(np.abs(m_ref).max()))
+            assert err <= 2e-5, err
             hi = ps.hi[:P].cpu().numpy()
             first = np.ones(P, bool)
             first[1:] = (hi[1:] != hi[:-1]) | (np.arange(1, P) % 16 == 0)
             starts = np.flatnonzero(first)
             untouched = np.ones(ps.cap, bool)
             untouched[starts] = False
-            for impl in ("ws", "wi"):
+            for impl, m_k in m.items():
                 ops.set_att_pairs_impl(impl)
-                if ops.att_pairs_impl() != impl:
-                    continue                      # wi: two- / one-plane modes only
-                m_k = ops.att_pairs(*args)[:P].cpu().numpy()
-                assert float(np.abs(m_k - m_ref).max()) <= 2e-5 * max(1.0, float(np.abs(m_ref).max())), impl
                 canary = torch.full((ps.cap, 128), 7777.0, device="cuda")
                 m_seg = ops.att_pairs(*args, m=canary, seg=16).cpu().numpy()
                 want = np.add.reduceat(m_k.astype(np.float64), starts, axis=0)

@@ -194,6 +194,8 @@ def test_unknown_flag_bits_and_laneconv_arguments(lib):
     # the weight-stationary pair kernel: split-precision modes only, seg in {0, 16}; RANGE16 relations likewise
     pa = [C.c_void_p(256)] * 5 + [64] + [C.c_void_p(256)] * 10 + [1e-5]
     assert l.lgcn_att_pairs_ws(*pa, mod.MMA_F32, 0, C.c_void_p(256), None) == ESHAPE
+    for mma in (mod.MMA_BF16X3, mod.MMA_F16X2, mod.MMA_BF16):                          # and the streaming one: f32 only
+        assert l.lgcn_att_pairs(*pa, mma, C.c_void_p(256), None) == ESHAPE
     assert l.lgcn_att_pairs_ws(*pa, mod.MMA_F16X2, 8, C.c_void_p(256), None) == EINVAL
     assert l.lgcn_att_pairs_ws(*pa, mod.MMA_F16X2, 16, C.c_void_p(260), None) == EALIGN
     pa[5] = 0

@@ -9,7 +9,7 @@ import numpy as np
 
 def short(n):
     n = n.replace("_ZN4lgcn", "")
-    for k in ("k_lc_tile", "k_lc_combine", "k_lc_plan", "k_att_pairs", "k_att_fused", "k_agg_mlp_bf2", "k_agg_mlp_bf", "k_agg_mlp",
+    for k in ("k_lc_tile", "k_lc_combine", "k_lc_plan", "k_att_pairs", "k_agg_mlp_bf2", "k_agg_mlp_bf", "k_agg_mlp",
               "k_pairs_rows", "k_pairs_scan", "k_csr_edges", "k_csr_sort", "k_scan", "k_graph_gather", "k_mapnet_input", "k_zero2",
               "k_widen"):
         if k in n:

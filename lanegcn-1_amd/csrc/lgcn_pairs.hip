@@ -9,10 +9,12 @@
 // (e0 planes -> GEMM -> fp32 tile -> GroupNorm rows -> planes -> GEMM -> tile -> rows -> piece sums): its phases add
 // up (stamps, round 2: ~19 k cycles per 64-pair tile against 3 k of MFMA work) instead of overlapping.
 //
-// Here ONE wave owns 16 pair rows from the centre offsets to the output and never meets another wave after the
-// prologue:
-//   * both weights live in LDS for the whole launch (2 x 64 KB of fp16 planes in the f16x2 mode: one workgroup of 16
-//     waves per CU), pre-arranged as MFMA fragments so that a fragment is one conflict-free ds_read_b128 per lane;
+// Here ONE wave owns 16 pair rows from the centre offsets to the output and meets the other waves of its workgroup only
+// at the weight copies:
+//   * ONE weight at a time lives in LDS (64 KB of fp16 planes in the f16x2 mode), pre-arranged as MFMA fragments so that
+//     a fragment is one conflict-free ds_read_b128 per lane: W_d2 for phase 1 (e0 -> W_d2 -> GN -> ReLU, e kept as
+//     operand planes in registers), then, after a barrier, W_c0e for phase 2.  69,120 B of LDS, 8 waves and <= 128
+//     VGPRs per workgroup: two workgroups share a CU, or one shares it with a LaneConv workgroup of another forward;
 //   * the GEMMs run "swapped" (D^T = W X^T: the weight is the A operand, the pair rows the B operand), so a lane ends up
 //     with 4 consecutive output channels of row lane & 15 for each of the 8 channel blocks -- 32 channels of ONE row;
 //   * with the K index of both weights permuted at pack time (lgcn_pack_weight_kperm: K-step s, lane group g, slot j
@@ -23,12 +25,9 @@
 //   * seg = 16: the rows of one target inside the block are summed by a segmented DPP scan over the 16 lanes of a row
 //     group (pairs are sorted by target) and only each piece's first row is written -- the same contract as
 //     lgcn_att_pairs_ws(seg = 16), read by the tail as an LGCN_REL_RANGE16 relation.
-// With 16 waves per CU in different phases the matrix pipe, the VALU and the LDS reads of different blocks overlap; the
-// LDS traffic per 16-pair block is 2 x 64 KB of weight fragments (256 B/clk/CU: 2 k cycles per 64 pairs, below the 3 k
-// of its MFMAs).
+// The LDS traffic per 16-pair block is 2 x 64 KB of weight fragments; the L2 -> LDS copies are 2 x 64 KB per 8 blocks.
 //
-// f16x2 (2 fp16 planes, 3 products) and bf16 (1 plane) only: three bf16 planes of two weights (192 KB) do not fit the
-// LDS; bf16x3 and f32 keep lgcn_att_pairs_ws / lgcn_att_pairs.
+// f16x2 (2 fp16 planes, 3 products) and bf16 (1 plane) only: bf16x3 and f32 keep lgcn_att_pairs_ws / lgcn_att_pairs.
 #include "lgcn_common.hpp"
 #include "lgcn_tile.hpp"
 #include "lgcn_mma_bf.hpp"
@@ -73,11 +72,20 @@ __device__ __forceinline__ int dpp_int_keep(int old, int x) {      // lanes with
     return __builtin_amdgcn_update_dpp(old, x, CTRL, 0xf, 0xf, false);
 }
 
+// Workgroups of 8 waves, one 16-pair block per wave per round, and ONE weight in LDS at a time: phase 1 (e0 -> W_d2 ->
+// GN -> ReLU) leaves e as operand planes in the wave's registers, a barrier, W_c0e overwrites the slice, phase 2 (U[h] +
+// W_c0e e + V[w] -> GN -> ReLU -> piece sums).  f16x2: 69,120 B of LDS and <= 128 VGPRs, so two workgroups share a CU,
+// or one shares it with a LaneConv workgroup (80,384 B, 8 waves) of another forward in flight.  bf16 (one plane, 36 KB)
+// needs ~160 VGPRs in this form and runs two waves per SIMD.
+constexpr int kPairWaves = 8;
+
 template <int F, bool SEG>
-__global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
+__global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu(F == 1 ? 4 : 2))) void k_att_pairs_wi(const PairParams p) {
     constexpr int NP = Fmt<F>::NP, NPROD = Fmt<F>::NPROD;
+    constexpr int NT = 64 * kPairWaves;
     constexpr int WFR = 8 * 4 * 64;                         // uint4 fragments of one plane of one weight
-    __shared__ __attribute__((aligned(16))) uint4 s_w[2 * NP * WFR];     // W_d2 planes | W_c0e planes
+    constexpr int NCP = NP * WFR / NT;                      // uint4 per thread to copy one weight
+    __shared__ __attribute__((aligned(16))) uint4 s_w[NP * WFR];         // W_d2 planes (phase 1) | W_c0e planes (phase 2)
     __shared__ __attribute__((aligned(16))) float s_par[7 * kC];         // wd0x | wd0y | bd0 | gd | btd | gc | btc
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: the block index and everything derived from it stay in SGPRs
@@ -85,19 +93,15 @@ __global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
     int P = *p.n_pairs;                                      // cap <= 0x7ffffff0 (host check): pair indices fit 32 bits
     if (P < 0 || (int64_t)P > p.cap) P = (int)p.cap;
     const int nblk = (P + 15) >> 4;
-    if ((int)blockIdx.x >= nblk) return;                    // (uniform per workgroup; grid <= blocks anyway)
+    const int first = (int)blockIdx.x * kPairWaves, rstride = (int)gridDim.x * kPairWaves;
+    if (first >= nblk) return;                              // (uniform per workgroup)
 
-    // this wave's first block: its pair indices travel while the weights are copied
-    int blk = (int)blockIdx.x + (int)gridDim.x * wave;
-    const int stride = (int)gridDim.x * 16;
     auto fetch_idx = [&](int b, int &h, int &w) {
         const bool live = b < nblk && b * 16 + r < P;
         const int32_t *hb = p.hi + (int64_t)b * 16, *wb = p.wi + (int64_t)b * 16;       // scalar bases, lane offset r
         h = live ? hb[r] : -1;
         w = live ? wb[r] : 0;
     };
-    int hi_c, wi_c;
-    fetch_idx(blk, hi_c, wi_c);
     auto fetch_d = [&](int h, int w, float &x, float &y) {      // centre offset of a pair (0 for a dead row)
         x = y = 0.f;
         if (h >= 0) {
@@ -106,36 +110,49 @@ __global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
             x = a.x - c.x; y = a.y - c.y;
         }
     };
-
-    float dx, dy;
-    {   // weights -> LDS (the packed images are already in fragment order), parameters -> LDS
-        const uint4 *B1 = reinterpret_cast<const uint4 *>(p.wpd2), *B2 = reinterpret_cast<const uint4 *>(p.wpc0e);
-        uint4 t[2 * NP * WFR / 1024];
-#pragma unroll
-        for (int i = 0; i < 2 * NP * WFR / 1024; ++i) {
-            const int e = tid + 1024 * i;
-            t[i] = e < NP * WFR ? B1[e] : B2[e - NP * WFR];
-        }
-        fetch_d(hi_c, wi_c, dx, dy);      // the first block's centres: requested behind the weight loads, land under the copy
-        if (tid < kC) {
-            s_par[tid] = p.wd0[2 * tid];
-            s_par[kC + tid] = p.wd0[2 * tid + 1];
-            s_par[2 * kC + tid] = p.bd0[tid];
-            s_par[3 * kC + tid] = p.gd[tid];
-            s_par[4 * kC + tid] = p.btd[tid];
-            s_par[5 * kC + tid] = p.gc[tid];
-            s_par[6 * kC + tid] = p.btc[tid];
-        }
-#pragma unroll
-        for (int i = 0; i < 2 * NP * WFR / 1024; ++i) s_w[tid + 1024 * i] = t[i];
+    // one weight image (already in fragment order) -> LDS.  The global loads are issued before `before_store`, which
+    // waits for the other waves to be done with the slice -- all of them, or (split: bounds the registers held while
+    // phase 1's operands are live) the first half, the second half following the first half's stores.
+    auto copy_weight = [&](const void *img, bool split, auto before_store) {
+        int o = tid;
+        asm volatile("" : "+v"(o));             // addresses formed here, not hoisted out of the round loop (registers)
+        const uint4 *B = reinterpret_cast<const uint4 *>(img) + o;
+        uint4 *S = s_w + o;
+        __builtin_amdgcn_sched_barrier(0);      // the copy's registers are not hoisted into phase 1
+        static_assert(NCP == 4 || NCP == 8, "copy in halves of 2 or 4");
+        constexpr int H = NCP / 2;
+        // named registers, not an array: an array held across the barrier is kept in scratch
+        uint4 a0 = B[0], a1 = B[NT], a2, a3, b0, b1, b2, b3;
+        if (H == 4) { a2 = B[2 * NT]; a3 = B[3 * NT]; }
+        auto load_b = [&] {
+            b0 = B[H * NT]; b1 = B[(H + 1) * NT];
+            if (H == 4) { b2 = B[(H + 2) * NT]; b3 = B[(H + 3) * NT]; }
+        };
+        if (!split) load_b();
+        before_store();
+        S[0] = a0; S[NT] = a1;
+        if (H == 4) { S[2 * NT] = a2; S[3 * NT] = a3; }
+        if (split) load_b();
+        S[H * NT] = b0; S[(H + 1) * NT] = b1;
+        if (H == 4) { S[(H + 2) * NT] = b2; S[(H + 3) * NT] = b3; }
+        lds_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    if (tid < kC) {
+        s_par[tid] = p.wd0[2 * tid];
+        s_par[kC + tid] = p.wd0[2 * tid + 1];
+        s_par[2 * kC + tid] = p.bd0[tid];
+        s_par[3 * kC + tid] = p.gd[tid];
+        s_par[4 * kC + tid] = p.btd[tid];
+        s_par[5 * kC + tid] = p.gc[tid];
+        s_par[6 * kC + tid] = p.btc[tid];
     }
-    __syncthreads();        // the only workgroup barrier of the kernel
 
     const float4 *l_wx = reinterpret_cast<const float4 *>(s_par) + g, *l_wy = reinterpret_cast<const float4 *>(s_par + kC) + g;
     const float4 *l_b0 = reinterpret_cast<const float4 *>(s_par + 2 * kC) + g;
     const float4 *l_gd = reinterpret_cast<const float4 *>(s_par + 3 * kC) + g, *l_bd = reinterpret_cast<const float4 *>(s_par + 4 * kC) + g;
     const float4 *l_gc = reinterpret_cast<const float4 *>(s_par + 5 * kC) + g, *l_bc = reinterpret_cast<const float4 *>(s_par + 6 * kC) + g;
-    const uint4 *w1 = s_w + lane, *w2 = s_w + NP * WFR + lane;
+    const uint4 *wl = s_w + lane;
 
     // one K = 128 pass: acc[cb] += W-fragments(cb, s) x X-planes(s); products smallest terms first.  The 32 (K-step,
     // channel block) steps run in order, each step's weight fragments requested two steps ahead (three fragment sets in
@@ -210,13 +227,22 @@ __global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
         rstd = 1.0f / sqrtf(q * (1.0f / kC) + p.eps);
     };
 
-    for (; blk < nblk; blk += stride) {
+    for (int base = first; base < nblk; base += rstride) {   // rounds of 8 blocks, uniform per workgroup
+        const int blk = base + wave;                        // scalar; a wave past the end still copies and meets the barriers
+        const bool act = blk < nblk;                        // (false only in the workgroup's last round)
+        int hi_c, wi_c;
+        fetch_idx(blk, hi_c, wi_c);
+        float dx, dy;
+        copy_weight(p.wpd2, false, [&] {
+            fetch_d(hi_c, wi_c, dx, dy);                    // requested behind the weight loads, land under the copy
+            if (base != first) lds_barrier();               // the previous round's phase 2 is done with W_c0e
+        });
         const bool live = hi_c >= 0;
         const int go = 4 * g, ro = r;
-        int hi_n, wi_n;
-        fetch_idx(blk + stride, hi_n, wi_n);                 // next block's indices: a block ahead
-        // ---- e0 = ReLU(W_d0 d + b_d0) for this lane's 32 channels -> operand planes
         uint4 x[NP][4];
+        f32x4 acc[8];
+        // (a wave past the end runs phase 1 on dead rows: uniform control flow up to the barrier)
+        // ---- e0 = ReLU(W_d0 d + b_d0) for this lane's 32 channels -> operand planes
 #pragma unroll
         for (int cb = 0; cb < 8; ++cb) {
             const float4 wx = l_wx[4 * cb], wy = l_wy[4 * cb], bb = l_b0[4 * cb];
@@ -228,14 +254,10 @@ __global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
             to_planes(x, cb, h);
         }
         // ---- e1 = W_d2 e0
-        f32x4 acc[8];
 #pragma unroll
         for (int cb = 0; cb < 8; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-        gemm(w1, x, acc, [](int) {});
-        fetch_d(hi_n, wi_n, dx, dy);                         // next block's centres (its indices have landed): under GN1 / the second GEMM
-        // ---- e = ReLU(GN_d(e1)) -> operand planes (registers only); an accumulator block that has been normalised is
-        // dead: U[h]'s block is requested into it (the second GEMM's accumulators start from U[h])
-        const float *up = p.U + (unsigned)((live ? hi_c : 0) * kC + go);      // scalar base + 32-bit lane offset (rows < 2^24)
+        gemm(wl, x, acc, [](int) {});
+        // ---- e = ReLU(GN_d(e1)) -> operand planes (registers only)
         {
             float rstd;
             row_stats(acc, rstd);
@@ -248,13 +270,21 @@ __global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
                 v[2] = relu_nan(fmaf(acc[cb][2] * rstd, gg.z, bb.z));
                 v[3] = relu_nan(fmaf(acc[cb][3] * rstd, gg.w, bb.w));
                 to_planes(x, cb, v);
-                acc[cb] = *reinterpret_cast<const f32x4 *>(up + 16 * cb);
             }
         }
+        // ---- W_c0e replaces W_d2 once every wave's first GEMM has read it; e stays in x[].  U[h] is requested into the
+        // accumulators (the second GEMM starts from U[h]) behind the first half of the copy, before the barrier
+        const float *up = p.U + (unsigned)((live ? hi_c : 0) * kC + go);      // scalar base + 32-bit lane offset (rows < 2^24)
+        copy_weight(p.wpc0e, true, [&] {
+#pragma unroll
+            for (int cb = 0; cb < 8; ++cb) acc[cb] = *reinterpret_cast<const f32x4 *>(up + 16 * cb);
+            lds_barrier();
+        });
+        if (!act) break;
         // ---- t = U[h] + W_c0e e + V[w]; V's blocks are requested as the K-steps release their operand registers
         f32x4 vv[8];
         const float *vp = p.V + (unsigned)((live ? wi_c : 0) * kC + go);
-        gemm(w2, x, acc, [&](int sk) {
+        gemm(wl, x, acc, [&](int sk) {
             vv[2 * sk] = *reinterpret_cast<const f32x4 *>(vp + 32 * sk);
             vv[2 * sk + 1] = *reinterpret_cast<const f32x4 *>(vp + 32 * sk + 16);
         });
@@ -303,7 +333,6 @@ __global__ __launch_bounds__(1024) void k_att_pairs_wi(const PairParams p) {
                 for (int cb = 0; cb < 8; ++cb) *reinterpret_cast<f32x4 *>(mp + 16 * cb) = acc[cb];
             }
         }
-        hi_c = hi_n; wi_c = wi_n;
     }
 }
 
@@ -339,15 +368,17 @@ extern "C" int lgcn_att_pairs_wi(const float *agt_ctrs, const float *ctx_ctrs, c
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
         cus = 256;
-    const int64_t blocks = (cap + 15) / 16;       // 16-pair blocks; one wave each, 16 waves per workgroup
-    const unsigned grid = (unsigned)(blocks < cus ? blocks : cus);
+    const int64_t blocks = (cap + 15) / 16;       // 16-pair blocks; one per wave and round, kPairWaves waves per workgroup
+    const int64_t wgs = (blocks + kPairWaves - 1) / kPairWaves;
+    const unsigned grid = (unsigned)(wgs < 2 * cus ? wgs : 2 * cus);     // two resident workgroups per CU; cap >> P is usual
+    const dim3 block(64 * kPairWaves);
     hipStream_t st = (hipStream_t)stream;
     if (mma == LGCN_MMA_F16X2) {
-        if (seg) hipLaunchKernelGGL((k_att_pairs_wi<1, true>), dim3(grid), dim3(1024), 0, st, p);
-        else hipLaunchKernelGGL((k_att_pairs_wi<1, false>), dim3(grid), dim3(1024), 0, st, p);
+        if (seg) hipLaunchKernelGGL((k_att_pairs_wi<1, true>), dim3(grid), block, 0, st, p);
+        else hipLaunchKernelGGL((k_att_pairs_wi<1, false>), dim3(grid), block, 0, st, p);
     } else {
-        if (seg) hipLaunchKernelGGL((k_att_pairs_wi<2, true>), dim3(grid), dim3(1024), 0, st, p);
-        else hipLaunchKernelGGL((k_att_pairs_wi<2, false>), dim3(grid), dim3(1024), 0, st, p);
+        if (seg) hipLaunchKernelGGL((k_att_pairs_wi<2, true>), dim3(grid), block, 0, st, p);
+        else hipLaunchKernelGGL((k_att_pairs_wi<2, false>), dim3(grid), block, 0, st, p);
     }
     return launch_status();
 }

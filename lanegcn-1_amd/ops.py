@@ -959,8 +959,8 @@ def mapnet_input(ctrs, feats, wa1, ba1, wpa2, gn_a, ws1, bs1, wps2, gn_s, eps=EP
 
 
 # Per-pair MLP of Att in the 16-bit-plane modes: "wi" (default) = lgcn_att_pairs_wi, wave-independent 16-pair blocks
-# with both weights in LDS (f16x2 / bf16); "ws" = lgcn_att_pairs_ws, both weights in registers (bf16x3, whose three
-# planes do not fit the LDS).  f32 runs "stream" = lgcn_att_pairs, weight fragments streamed per 32-pair tile.
+# with the weights in LDS one at a time (f16x2 / bf16); "ws" = lgcn_att_pairs_ws, both weights in registers (bf16x3,
+# which "wi" does not implement).  f32 runs "stream" = lgcn_att_pairs, weight fragments streamed per 32-pair tile.
 _att_pairs_impl = "wi"
 
 
@@ -973,8 +973,8 @@ def set_att_pairs_impl(name: str):
 
 
 def att_pairs_impl() -> str:
-    """The pair-MLP kernel of the current matrix mode: f32 has only "stream"; "wi" needs both weights in LDS (two or one
-    16-bit plane: f16x2 / bf16), bf16x3 falls back to "ws"."""
+    """The pair-MLP kernel of the current matrix mode: f32 has only "stream"; "wi" runs on two or one 16-bit weight
+    plane (f16x2 / bf16), bf16x3 falls back to "ws"."""
     if _mma == L.MMA_F32:
         return "stream"
     if _att_pairs_impl == "wi" and _mma not in (L.MMA_F16X2, L.MMA_BF16):

@@ -174,6 +174,40 @@ int lgcn_conv1d_gn(const float *x, int64_t n_act, int lin, int cin, const void *
                    float *out, void *stream);
 
 /*
+ * Training forward: lgcn_conv1d_gn that also stores the pre-norm convolution output y [A, lout, cout] (y = sum_t W_t x
+ * shifted, before the GroupNorm).  Same kernel, one extra store: `out` is bit-identical to lgcn_conv1d_gn's.  Same shape set,
+ * pointer and alignment checks; y must be non-null and 16-byte aligned.
+ */
+int lgcn_conv1d_gn_train(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
+                         const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
+                         float *out, float *y, void *stream);
+
+/*
+ * Backward of lgcn_conv1d_gn_train (reference layers.py:40-62, 142-190; lanegcn.py:212-263).  Given g = dL/dout [A, lout, cout]
+ * and the forward's x, y, out:
+ *   gm     = g masked by out > 0 (relu != 0; out may be NULL otherwise)
+ *   dres   = gm (res_mode 1, [A, lout, cout]), or for res_mode 2 the adjoint of the x2 upsampling of lgcn_gn_cl:
+ *            dres[h] = sum_l gm[l] (w0(l) [i0(l) == h] + w1(l) [i1(l) == h])  ([A, lout / 2, cout], edges clamped)
+ *   dy     = rstd (gm gamma - mean_a(gm gamma) - yhat mean_a(gm gamma yhat)),  yhat = (y - mean_a) rstd  (per actor, two-pass
+ *            statistics of y as the forward computed them)
+ *   dx     [A, lin, cin]:  dx[a, li, ci] = sum_{t, l: l stride + t - pad = li} sum_co dy[a, l, co] W[co, ci, t]
+ *   dW     [cout, cin, ks] (the parameter's layout):  dW[co, ci, t] = sum_{a, l} dy[a, l, co] x[a, l stride + t - pad, ci]
+ *   dgamma = sum_{a, l} gm yhat,  dbeta = sum_{a, l} gm     ([cout])
+ * dx, dres, dw, dgamma, dbeta may each be NULL (not computed); x is needed only for dw.  wt: lgcn_conv_pack_weight_t image of W
+ * (lgcn_conv_packed_t_bytes bytes: fp32 wt[t][ci][co], ci padded to a multiple of 16 with zeros).  ws: workspace of
+ * lgcn_conv1d_gn_bwd_ws_bytes(n_act, lin, cin, cout, ks, stride) bytes (dy, per-workgroup dgamma / dbeta partials, chunked dW
+ * partials), 16-byte aligned.  Shapes, res_mode and pointer checks as lgcn_conv1d_gn.  Three launches: the data backward
+ * (workgroups of whole actors as in the forward), the weight gradient in chunks, the fixed-order reduction of all
+ * partials.  Arithmetic: exact fp32 (v_mfma_f32_16x16x4_f32), no floating-point atomics: bitwise repeatable.
+ */
+int64_t lgcn_conv_packed_t_bytes(int cin, int cout, int ks);
+int lgcn_conv_pack_weight_t(const float *w, int cin, int cout, int ks, void *out, void *stream);
+int64_t lgcn_conv1d_gn_bwd_ws_bytes(int64_t n_act, int lin, int cin, int cout, int ks, int stride);
+int lgcn_conv1d_gn_bwd(const float *g, const float *x, const float *y, const float *out, int64_t n_act, int lin, int cin,
+                       const void *wt, int cout, int ks, int stride, const float *gamma, float eps, int res_mode, int relu,
+                       float *dx, float *dw, float *dgamma, float *dbeta, float *dres, void *ws, void *stream);
+
+/*
  * A whole layers.Res1d block (reference layers.py:142-190) in one launch, same layouts and shape limits as
  * lgcn_conv1d_gn:  out = relu( GN2(conv2( relu(GN1(conv1 x)) )) + r ),  conv1: k = 3, stride 1 / 2, cin -> c; conv2: k = 3,
  * stride 1, c -> c; r = x (wdp == NULL: needs cin == c, stride 1) or GN_d(conv_d x) with conv_d: k = 1, same stride

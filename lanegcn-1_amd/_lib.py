@@ -120,6 +120,11 @@ SIGNATURES = {
     "lgcn_conv_packed_bytes": (C.c_int64, [_I, _I, _I]),
     "lgcn_conv_pack_weight": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "lgcn_conv1d_gn": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P]),
+    "lgcn_conv1d_gn_train": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P, _P]),
+    "lgcn_conv_packed_t_bytes": (C.c_int64, [_I, _I, _I]),
+    "lgcn_conv_pack_weight_t": (C.c_int, [_P, _I, _I, _I, _P, _P]),
+    "lgcn_conv1d_gn_bwd_ws_bytes": (C.c_int64, [_L, _I, _I, _I, _I, _I]),
+    "lgcn_conv1d_gn_bwd": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P, _I, _I, _I, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "lgcn_res1d_gn": (C.c_int, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
     "lgcn_res1d_pair_gn": (C.c_int, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
     "lgcn_pred_reg": (C.c_int, [C.POINTER(PredReg), _P]),

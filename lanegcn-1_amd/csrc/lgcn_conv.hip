@@ -18,10 +18,10 @@
 #include "lgcn_common.hpp"
 #include "lgcn_tile.hpp"
 #include "lgcn_mma_bf.hpp"
+#include "lgcn_conv.hpp"
 
 namespace lgcn {
 
-constexpr int kConvRows = 80;          // output rows per workgroup (5 sub-blocks of 16)
 constexpr int kConvSub = kConvRows / 16;
 
 struct ConvParams {
@@ -35,9 +35,8 @@ struct ConvParams {
     int res_mode;                      // 0 none, 1 [A, lout, cout], 2 [A, lout / 2, cout] upsampled x2
     int relu;
     float *out;                        // [A, lout, cout]
+    float *y;                          // [A, lout, cout]: the pre-norm convolution output (training forward only)
 };
-
-__host__ __device__ inline int conv_kpad(int cin) { return (cin + 31) & ~31; }
 
 // Packed image: for tap t, K-chunk kc (32 input channels), channel block cb (16 outputs), plane pl: 64 x uint4, lane
 // (n = lane & 15, kq = lane >> 4) holds W[16 cb + n][32 kc + 8 kq + j][t], j = 0..7, as fp16 plane pl (hi, then the
@@ -71,17 +70,8 @@ __global__ __launch_bounds__(256) void k_conv_pack(const float *w, int cout, int
     out[base + 64 + lane] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 
-// F.interpolate(scale_factor = 2, mode = "linear", align_corners = False) of a length-n sequence at output position j:
-// source coordinate (j + 0.5) / 2 - 0.5, clamped at 0; weights 0.75 / 0.25 (and 1 / 0 at the two ends).
-__device__ __forceinline__ void up2_taps(int j, int n, int &i0, int &i1, float &w1) {
-    float src = (j + 0.5f) * 0.5f - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    i0 = (int)src;
-    i1 = i0 + 1 < n ? i0 + 1 : n - 1;
-    w1 = src - (float)i0;
-}
-
-template <int KS, int NKC>                                     // taps, 32-channel K chunks; KS == 0: both read from p (any shape)
+// SAVE: also store the pre-norm tile to p.y (the training forward); the arithmetic of `out` is the same either way.
+template <int KS, int NKC, bool SAVE>                          // taps, 32-channel K chunks; KS == 0: both read from p (any shape)
 __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -282,6 +272,7 @@ __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
                 }
                 if (p.relu) { y.x = relu_nan(y.x); y.y = relu_nan(y.y); y.z = relu_nan(y.z); y.w = relu_nan(y.w); }
                 *reinterpret_cast<float4 *>(p.out + (a * p.lout + l) * p.cout + c) = y;
+                if constexpr (SAVE) *reinterpret_cast<float4 *>(p.y + (a * p.lout + l) * p.cout + c) = v[k];
             }
         }
     }
@@ -569,15 +560,43 @@ __global__ __launch_bounds__(512) void k_res1d_gn(const Res1dParams p) {
 
 using namespace lgcn;
 
-extern "C" {
-
-static bool conv_shape_ok(int cin, int cout, int ks, int stride, int lin, int lout) {
-    if (cin < 1 || cin > 128 || (cout != 32 && cout != 64 && cout != 128)) return false;
-    if ((ks != 1 && ks != 3) || (stride != 1 && stride != 2) || lin < 1) return false;
+template <bool SAVE>
+static int conv1d_gn_launch(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
+                            const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
+                            float *out, float *y, void *stream) {
+    if (n_act < 0 || res_mode < 0 || res_mode > 2) return LGCN_EINVAL;
     const int pad = (ks - 1) / 2;
-    if (lout != (lin + 2 * pad - ks) / stride + 1) return false;
-    return lout == 5 || lout == 10 || lout == 20;             // 16 / 8 / 4 actors per workgroup: 512 / na threads each in the GroupNorm phase
+    const int lout = stride > 0 ? (lin + 2 * pad - ks) / stride + 1 : 0;
+    if (!conv_shape_ok(cin, cout, ks, stride, lin, lout)) return LGCN_ESHAPE;
+    if (res_mode == 2 && (lout & 1)) return LGCN_ESHAPE;
+    if (n_act == 0) return LGCN_OK;
+    if (n_act > 0x7fffffff / (kConvRows * 128)) return LGCN_ESHAPE;
+    const void *al[] = {x, wp, gamma, beta, out};
+    for (const void *v : al) { LGCN_CHECK_PTR(v); LGCN_CHECK_ALIGN16(v); }
+    if (res_mode != 0) { LGCN_CHECK_PTR(res); LGCN_CHECK_ALIGN16(res); }
+    if (SAVE) { LGCN_CHECK_PTR(y); LGCN_CHECK_ALIGN16(y); }
+    ConvParams p;
+    p.x = x; p.n_act = n_act; p.lin = lin; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.lout = lout;
+    p.wp = reinterpret_cast<const uint4 *>(wp); p.gamma = gamma; p.beta = beta; p.eps = eps;
+    p.res = res; p.res_mode = res_mode; p.relu = relu; p.out = out; p.y = y;
+    const int na = kConvRows / lout;
+    const size_t lds_planes = (size_t)2 * (na * lin + 1) * (conv_kpad(cin) + 8) * 2, lds_tile = (size_t)kConvRows * (cout + 4) * 4;
+    const size_t lds = lds_planes > lds_tile ? lds_planes : lds_tile;
+    if (lds > 159 * 1024) return LGCN_ESHAPE;                  // the kernel's static words share the 160 KB
+    void (*kern)(ConvParams) = k_conv_gn<0, 0, SAVE>;
+    const int nkc = conv_kpad(cin) >> 5;
+    if (ks == 1) kern = nkc == 1 ? k_conv_gn<1, 1, SAVE> : nkc == 2 ? k_conv_gn<1, 2, SAVE> : nkc == 4 ? k_conv_gn<1, 4, SAVE> : kern;
+    if (ks == 3) kern = nkc == 1 ? k_conv_gn<3, 1, SAVE> : nkc == 2 ? k_conv_gn<3, 2, SAVE> : nkc == 4 ? k_conv_gn<3, 4, SAVE> : kern;
+    if (lds > 64 * 1024) {             // above the default ceiling of dynamic LDS (a property set on the code object; idempotent)
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
+        if (e != hipSuccess) return (int)e;
+    }
+    const unsigned grid = (unsigned)((n_act + na - 1) / na);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, (hipStream_t)stream, p);
+    return launch_status();
 }
+
+extern "C" {
 
 int64_t lgcn_conv_packed_bytes(int cin, int cout, int ks) {
     if (cin < 1 || cin > 128 || (cout != 32 && cout != 64 && cout != 128) || (ks != 1 && ks != 3)) return LGCN_EINVAL;
@@ -596,35 +615,15 @@ int lgcn_conv_pack_weight(const float *w, int cin, int cout, int ks, void *out, 
 int lgcn_conv1d_gn(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
                    const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
                    float *out, void *stream) {
-    if (n_act < 0 || res_mode < 0 || res_mode > 2) return LGCN_EINVAL;
-    const int pad = (ks - 1) / 2;
-    const int lout = stride > 0 ? (lin + 2 * pad - ks) / stride + 1 : 0;
-    if (!conv_shape_ok(cin, cout, ks, stride, lin, lout)) return LGCN_ESHAPE;
-    if (res_mode == 2 && (lout & 1)) return LGCN_ESHAPE;
-    if (n_act == 0) return LGCN_OK;
-    if (n_act > 0x7fffffff / (kConvRows * 128)) return LGCN_ESHAPE;
-    const void *al[] = {x, wp, gamma, beta, out};
-    for (const void *v : al) { LGCN_CHECK_PTR(v); LGCN_CHECK_ALIGN16(v); }
-    if (res_mode != 0) { LGCN_CHECK_PTR(res); LGCN_CHECK_ALIGN16(res); }
-    ConvParams p;
-    p.x = x; p.n_act = n_act; p.lin = lin; p.cin = cin; p.cout = cout; p.ks = ks; p.stride = stride; p.lout = lout;
-    p.wp = reinterpret_cast<const uint4 *>(wp); p.gamma = gamma; p.beta = beta; p.eps = eps;
-    p.res = res; p.res_mode = res_mode; p.relu = relu; p.out = out;
-    const int na = kConvRows / lout;
-    const size_t lds_planes = (size_t)2 * (na * lin + 1) * (conv_kpad(cin) + 8) * 2, lds_tile = (size_t)kConvRows * (cout + 4) * 4;
-    const size_t lds = lds_planes > lds_tile ? lds_planes : lds_tile;
-    if (lds > 159 * 1024) return LGCN_ESHAPE;                  // the kernel's static words share the 160 KB
-    void (*kern)(ConvParams) = k_conv_gn<0, 0>;
-    const int nkc = conv_kpad(cin) >> 5;
-    if (ks == 1) kern = nkc == 1 ? k_conv_gn<1, 1> : nkc == 2 ? k_conv_gn<1, 2> : nkc == 4 ? k_conv_gn<1, 4> : kern;
-    if (ks == 3) kern = nkc == 1 ? k_conv_gn<3, 1> : nkc == 2 ? k_conv_gn<3, 2> : nkc == 4 ? k_conv_gn<3, 4> : kern;
-    if (lds > 64 * 1024) {             // above the default ceiling of dynamic LDS (a property set on the code object; idempotent)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-        if (e != hipSuccess) return (int)e;
-    }
-    const unsigned grid = (unsigned)((n_act + na - 1) / na);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, (hipStream_t)stream, p);
-    return launch_status();
+    return conv1d_gn_launch<false>(x, n_act, lin, cin, wp, cout, ks, stride, gamma, beta, eps, res, res_mode, relu, out,
+                                   nullptr, stream);
+}
+
+int lgcn_conv1d_gn_train(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
+                         const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
+                         float *out, float *y, void *stream) {
+    return conv1d_gn_launch<true>(x, n_act, lin, cin, wp, cout, ks, stride, gamma, beta, eps, res, res_mode, relu, out, y,
+                                  stream);
 }
 
 static int res1d_launch(const float *x, int64_t n_act, int lin, int cin, int c, int stride, const void *w1p, const float *g1,

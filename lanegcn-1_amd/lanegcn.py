@@ -656,13 +656,18 @@ class ActorNet(nn.Module):
         return res1d(self.output, out)[:, :, 0, -1]
 
     def _forward_hip(self, actors: Tensor) -> Tensor:
-        """Inference path on lgcn_conv1d_gn: every Conv1d + GroupNorm (+ residual, + x2 upsampling, + ReLU) of the FPN is
-        ONE launch on [A, L, C] tensors: 20 launches instead of 20 stock convolutions + 20 norm launches."""
+        """The FPN on lgcn_conv1d_gn: every Conv1d + GroupNorm (+ residual, + x2 upsampling, + ReLU) of the FPN is
+        ONE launch on [A, L, C] tensors: 20 launches instead of 20 stock convolutions + 20 norm launches.  Under autograd
+        the same 20 units run as Conv1dGNFn (lgcn_conv1d_gn_train forward, lgcn_conv1d_gn_bwd backward), unfused."""
+        train = ops.wants_grad(actors, *ops.module_params(self))
+
         def cg(conv: nn.Conv1d, norm: nn.GroupNorm, x: Tensor, **kw) -> Tensor:
+            if train:
+                return A.conv1d_gn(x, conv, norm, **kw)
             return ops.conv1d_gn(x, conv.weight, conv.stride[0], norm.weight, norm.bias, norm.eps, **kw)
 
         def fusable(b: Res1d) -> bool:
-            return ActorNet.fuse_blocks and b.act and b.conv1.kernel_size[0] == 3 and b.conv2.kernel_size[0] == 3 and \
+            return not train and ActorNet.fuse_blocks and b.act and b.conv1.kernel_size[0] == 3 and b.conv2.kernel_size[0] == 3 and \
                 b.conv2.stride[0] == 1 and b.bn1.eps == b.bn2.eps and \
                 (b.downsample is None or (b.downsample[0].kernel_size[0] == 1 and b.downsample[1].eps == b.bn1.eps))
 
@@ -697,7 +702,9 @@ class ActorNet(nn.Module):
         # lgcn_conv1d_gn / lgcn_res1d_gn take no matrix-mode argument: they always split operands into two fp16 planes.
         # In the exact-f32 and bf16x3 modes (and inside the range guard's bf16x3 re-run, which must cure an overflow that
         # starts in ActorNet too) the MIOpen channels-last path runs instead.
-        if ActorNet.impl != "hip" or ops.get_mma() != "f16x2" or not self._channels_last_ok(actors):
+        if ActorNet.impl != "hip" or ops.get_mma() != "f16x2" or not self._channels_last_shape_ok(actors):
+            return False
+        if not ActorNet.train_hip and ops.wants_grad(actors, *ops.module_params(self)):
             return False
         convs = [c for g in self.groups for b in g for c in ([b.conv1, b.conv2] + ([b.downsample[0]] if b.downsample is not None else []))]
         convs += [l.conv for l in self.lateral] + [self.output.conv1, self.output.conv2]
@@ -710,20 +717,28 @@ class ActorNet(nn.Module):
         return ok and all(n in (5, 10, 20) for n in lens) and all(lens[i] == 2 * lens[i + 1] for i in range(len(lens) - 1)) and \
             all(c.in_channels <= 128 and c.out_channels in (32, 64, 128) and c.kernel_size[0] in (1, 3) and c.stride[0] in (1, 2) for c in convs)
 
-    # "hip": lgcn_conv1d_gn / lgcn_res1d_gn launches; "miopen": stock channels-last convolutions + lgcn_gn_cl
+    # "hip": lgcn_conv1d_gn / lgcn_res1d_gn launches (training: Conv1dGNFn); "miopen": stock channels-last convolutions +
+    # lgcn_gn_cl for inference, the stock NCL path for training
     impl = "hip"
+    # training (autograd recording) on the HIP units too: Conv1dGNFn forward and backward instead of the stock NCL path.
+    # Off by default: the f16x2 forward moves the actor features by fp32 rounding, which is enough to change which
+    # knife-edge ReLUs of the graph hot path flip against the reference in the batch-32 training check.
+    train_hip = False
     # a Res1d block (conv + GN + ReLU + conv + GN + shortcut + ReLU) in ONE launch (lgcn_res1d_gn) instead of two or three
     fuse_blocks = True
     # the two Res1d blocks of a group in ONE launch (lgcn_res1d_pair_gn)
     fuse_groups = True
 
-    def _channels_last_ok(self, actors: Tensor) -> bool:
+    def _channels_last_shape_ok(self, actors: Tensor) -> bool:
         mods = [b for g in self.groups for b in g] + [self.output]
         norms = [m for b in mods for m in (b.bn1, b.bn2)] + [l.norm for l in self.lateral]
         return (actors.is_cuda and actors.dtype == torch.float32 and actors.dim() == 3 and actors.shape[0] > 0
-                and actors.shape[2] % 4 == 0 and not ops.wants_grad(actors, *ops.module_params(self))
+                and actors.shape[2] % 4 == 0
                 and all(isinstance(n, nn.GroupNorm) and n.num_groups == 1 for n in norms)
                 and not any(l.act for l in self.lateral[:-1]))
+
+    def _channels_last_ok(self, actors: Tensor) -> bool:
+        return self._channels_last_shape_ok(actors) and not ops.wants_grad(actors, *ops.module_params(self))
 
     def forward(self, actors: Tensor) -> Tensor:
         if self._hip_ok(actors):

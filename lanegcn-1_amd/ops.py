@@ -402,6 +402,80 @@ def conv1d_gn(x: torch.Tensor, weight: torch.Tensor, stride: int, gamma, beta, e
     return out
 
 
+def conv_packed_t(weight: torch.Tensor) -> torch.Tensor:
+    """fp32 image wt[t][ci][co] of a Conv1d weight [cout, cin, ks] (ci padded to 16) for the data backward of
+    lgcn_conv1d_gn_bwd, cached on the parameter like conv_packed (rebuilt once the parameter changes)."""
+    def make():
+        lib = L.load()
+        cout, cin, ks = weight.shape
+        nbytes = lib.lgcn_conv_packed_t_bytes(cin, cout, ks)
+        if nbytes < 0:
+            raise L.LgcnError("conv_packed_t: unsupported Conv1d weight shape %s" % (tuple(weight.shape),))
+        out = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
+        w = _dev(weight.detach(), torch.float32, "weight")
+        L.check(lib.lgcn_conv_pack_weight_t(_ptr(w), cin, cout, ks, _ptr(out), _stream()), "lgcn_conv_pack_weight_t")
+        return out
+    return _cached(weight, ("convT",), make)
+
+
+def conv1d_gn_train(x: torch.Tensor, weight: torch.Tensor, stride: int, gamma, beta, eps: float,
+                    res: Optional[torch.Tensor] = None, res_up2: bool = False, relu: bool = False):
+    """conv1d_gn that also returns the pre-norm convolution output: (out, y), both [A, Lout, Cout] (lgcn_conv1d_gn_train;
+    out is bit-identical to conv1d_gn's)."""
+    lib = L.load()
+    x = _dev(x, torch.float32, "x")
+    A_, lin, cin = x.shape
+    cout, cin_w, ks = weight.shape
+    if cin_w != cin:
+        raise L.LgcnError("conv1d_gn_train: weight does not match the input's channels")
+    lout = (lin + 2 * ((ks - 1) // 2) - ks) // stride + 1
+    out = torch.empty((A_, lout, cout), dtype=torch.float32, device=x.device)
+    y = torch.empty_like(out)
+    mode = 0
+    if res is not None:
+        res = _dev(res, torch.float32, "res")
+        mode = 2 if res_up2 else 1
+        if tuple(res.shape) != ((A_, lout // 2, cout) if res_up2 else (A_, lout, cout)):
+            raise L.LgcnError("conv1d_gn_train: residual of the wrong shape")
+    L.check(lib.lgcn_conv1d_gn_train(_ptr(x), A_, lin, cin, _ptr(conv_packed(weight)), cout, ks, stride,
+                                     _ptr(_dev(gamma.detach(), torch.float32, "gamma")),
+                                     _ptr(_dev(beta.detach(), torch.float32, "beta")), float(eps), _ptr(res), mode,
+                                     int(bool(relu)), _ptr(out), _ptr(y), _stream()), "lgcn_conv1d_gn_train")
+    return out, y
+
+
+def conv1d_gn_bwd(g: torch.Tensor, x: torch.Tensor, y: torch.Tensor, out: Optional[torch.Tensor], weight: torch.Tensor,
+                  stride: int, gamma, eps: float, res_mode: int = 0, relu: bool = False, want_dx: bool = True,
+                  want_dres: bool = True):
+    """Backward of conv1d_gn_train (lgcn_conv1d_gn_bwd): (dx | None, dW, dgamma, dbeta, dres | None).  out: the forward's
+    output (its ReLU mask; needed when relu); res_mode 0 none, 1 same-shape residual, 2 x2-upsampled residual."""
+    lib = L.load()
+    g, x, y = _dev(g, torch.float32, "g"), _dev(x, torch.float32, "x"), _dev(y, torch.float32, "y")
+    A_, lin, cin = x.shape
+    cout, _, ks = weight.shape
+    lout = y.shape[1]
+    if tuple(g.shape) != tuple(y.shape):
+        raise L.LgcnError("conv1d_gn_bwd: gradient of the wrong shape")
+    out = _dev(out, torch.float32, "out") if relu else None
+    dev = x.device
+    dx = torch.empty_like(x) if want_dx else None
+    dw = torch.empty((cout, cin, ks), dtype=torch.float32, device=dev)
+    dgamma = torch.empty(cout, dtype=torch.float32, device=dev)
+    dbeta = torch.empty_like(dgamma)
+    dres = None
+    if res_mode and want_dres:
+        dres = torch.empty((A_, lout // 2 if res_mode == 2 else lout, cout), dtype=torch.float32, device=dev)
+    nbytes = lib.lgcn_conv1d_gn_bwd_ws_bytes(A_, lin, cin, cout, ks, stride)
+    if nbytes < 0:
+        raise L.LgcnError("conv1d_gn_bwd: unsupported shape")
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+    L.check(lib.lgcn_conv1d_gn_bwd(_ptr(g), _ptr(x), _ptr(y), _ptr(out), A_, lin, cin, _ptr(conv_packed_t(weight)), cout, ks,
+                                   stride, _ptr(_dev(gamma.detach(), torch.float32, "gamma")), float(eps), int(res_mode),
+                                   int(bool(relu)), _ptr(dx), _ptr(dw), _ptr(dgamma), _ptr(dbeta), _ptr(dres), _ptr(ws),
+                                   _stream()), "lgcn_conv1d_gn_bwd")
+    return dx, dw, dgamma, dbeta, dres
+
+
 def res1d_gn(x: torch.Tensor, block, second=None) -> torch.Tensor:
     """A whole layers.Res1d block (conv1 k3 + GN + ReLU + conv2 k3 + GN + shortcut [identity | conv k1 + GN] + ReLU) on a
     channels-last tensor x [A, L, Cin] in one launch (lgcn_res1d_gn) -> [A, Lout, C]; with `second` (a Res1d with the

@@ -24,9 +24,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mma", default=None)
     ap.add_argument("--cpu-steps", type=int, default=2)
+    ap.add_argument("--actor-impl", default=None, choices=["hip", "miopen", "ab"],
+                    help="ActorNet.impl for the step; 'ab': both, alternating step by step after a warm-up of each")
     args = ap.parse_args()
     if args.mma:
         ops.set_mma(args.mma)
+    impls = ["hip", "miopen"] if args.actor_impl == "ab" else [args.actor_impl or M.ActorNet.impl]
+    M.ActorNet.impl = impls[0]
+    if args.actor_impl:
+        M.ActorNet.train_hip = True          # "hip": ActorNet's training units on Conv1dGNFn; "miopen": the stock path
     torch.manual_seed(0)
     torch.autograd.set_multithreading_enabled(False)      # what train_dp.py does for its loop
     net = M.Net(M.config).cuda().train()
@@ -52,18 +58,30 @@ def main():
                 stages.setdefault(k, []).append((b - a) * 1e3)
         return float(lo["loss"].detach())
 
-    losses = [step(i) for i in range(args.warmup)]
+    losses = []
+    for impl in impls:
+        M.ActorNet.impl = impl
+        losses += [step(i) for i in range(args.warmup)]
     torch.cuda.synchronize()
+    # per-step times (synchronised), the implementations interleaved step by step
+    per_step = {impl: [] for impl in impls}
     t0 = time.perf_counter()
     for i in range(args.steps):
-        losses.append(step(args.warmup + i))
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) / args.steps * 1e3
+        for impl in impls:
+            M.ActorNet.impl = impl
+            t1 = time.perf_counter()
+            losses.append(step(args.warmup + i))
+            torch.cuda.synchronize()
+            per_step[impl].append((time.perf_counter() - t1) * 1e3)
+    ms = (time.perf_counter() - t0) / (args.steps * len(impls)) * 1e3
+    M.ActorNet.impl = impls[0]
     for i in range(5):
         step(args.warmup + args.steps + i, timed=True)
     res = {"metric": "training step (forward + loss + backward + Adam), batch 32, S2", "mma": ops.get_mma(),
            "ms_per_step": ms, "scenes_per_s": 32e3 / ms, "loss_first": losses[0], "loss_last": losses[-1],
-           "stage_ms": {k: float(np.median(v)) for k, v in stages.items()}}
+           "stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
+           "actor_impl": impls[0] if len(impls) == 1 else "ab",
+           "median_step_ms": {k: float(np.median(v)) for k, v in per_step.items()}}
     print(json.dumps(res), flush=True)
 
 

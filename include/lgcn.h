@@ -670,6 +670,24 @@ int lgcn_gather_rows(const float *src, const int32_t *idx, const int32_t *n_dev,
  */
 int lgcn_check_finite(const float *a, int64_t na, const float *b, int64_t nb, int32_t *flag, int bit, void *stream);
 
+/*
+ * Exact-fp32 form of lgcn_conv1d_gn / lgcn_conv1d_gn_train (reference layers.py:40-62 Conv1d, 142-190 the halves of Res1d;
+ * ActorNet lanegcn.py:212-263): the same unit, shape set, residual modes, workgroups of whole actors and GroupNorm epilogue,
+ * with fp32 operands on v_mfma_f32_16x16x4_f32 instead of two fp16 planes.  No operand range limit; one fused
+ * multiply-add chain per output in a fixed order (taps outer, 32-channel chunks, 4 channels of each K quarter), no
+ * atomics: bitwise repeatable, and independent of any matrix mode.
+ * wp: lgcn_conv_pack_weight_f32 image of W [cout, cin, ks] (lgcn_conv_packed_f32_bytes bytes; per tap, 32-channel chunk
+ * and 16-output block two 64 x 16-byte fragments: lane (n, kq) holds W[16 cb + n][32 kc + 16 h + 4 kq + 0..3][t];
+ * channels beyond cin are zero).  y == NULL: inference; otherwise y [A, lout, cout] receives the pre-norm convolution
+ * output as lgcn_conv1d_gn_train stores it, which lgcn_conv1d_gn_bwd consumes unchanged (y must be 16-byte aligned).
+ * `out` is bit-identical with and without y.  Argument checks and error codes as lgcn_conv1d_gn.
+ */
+int64_t lgcn_conv_packed_f32_bytes(int cin, int cout, int ks);
+int lgcn_conv_pack_weight_f32(const float *w, int cin, int cout, int ks, void *out, void *stream);
+int lgcn_conv1d_gn_f32(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
+                       const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
+                       float *out, float *y /* NULL: inference */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,9 @@ SIGNATURES = {
     "lgcn_pack_weight_kperm": (C.c_int, [_P, _I, _I, _P, _P]),
     "lgcn_pred_loss_fwd": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _F, _F, _F, _F, _F, _P, _P, _P, _P]),
     "lgcn_pred_loss_bwd": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "lgcn_conv_packed_f32_bytes": (C.c_int64, [_I, _I, _I]),
+    "lgcn_conv_pack_weight_f32": (C.c_int, [_P, _I, _I, _I, _P, _P]),
+    "lgcn_conv1d_gn_f32": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P, _P]),
 }
 
 _lib = None

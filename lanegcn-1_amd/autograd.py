@@ -229,12 +229,13 @@ def gn_cl_act(x, gn, relu=False, res=None):
 class Conv1dGNFn(Function):
     """out = [ReLU](GroupNorm(1 group)(conv1d(x, weight)) [+ res | + up2(res)]) on channels-last tensors x [A, L, Cin] ->
     [A, Lout, Cout]: one unit of ActorNet (reference layers.py:40-62, 142-190).  Forward = lgcn_conv1d_gn_train (saving the
-    pre-norm y), backward = lgcn_conv1d_gn_bwd (dx, dW, dgamma, dbeta, dres; exact fp32)."""
+    pre-norm y), backward = lgcn_conv1d_gn_bwd (dx, dW, dgamma, dbeta, dres; exact fp32).  exact: the forward in exact fp32
+    too (lgcn_conv1d_gn_f32); the backward is the same."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, res, stride: int, res_mode: int, relu: bool, eps: float):
+    def forward(ctx, x, weight, gamma, beta, res, stride: int, res_mode: int, relu: bool, eps: float, exact: bool = False):
         out, y = ops.conv1d_gn_train(x, weight, stride, gamma, beta, eps, res=res if res_mode else None,
-                                     res_up2=res_mode == 2, relu=relu)
+                                     res_up2=res_mode == 2, relu=relu, exact=exact)
         ctx.stride, ctx.res_mode, ctx.relu, ctx.eps = stride, res_mode, relu, eps
         ctx.save_for_backward(x, y, out, weight, gamma)
         return out
@@ -247,13 +248,13 @@ class Conv1dGNFn(Function):
                                                  res_mode=ctx.res_mode, relu=ctx.relu, want_dx=ni[0],
                                                  want_dres=ctx.res_mode != 0 and ni[4])
         return (dx, dw if ni[1] else None, dg if ni[2] else None, db if ni[3] else None, dres,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
-def conv1d_gn(x, conv, gn, res=None, res_up2=False, relu=False):
+def conv1d_gn(x, conv, gn, res=None, res_up2=False, relu=False, exact=False):
     """Differentiable ops.conv1d_gn for an nn.Conv1d (no bias, padding (k - 1) / 2) and its nn.GroupNorm(1, C)."""
     mode = 0 if res is None else (2 if res_up2 else 1)
-    return Conv1dGNFn.apply(x, conv.weight, gn.weight, gn.bias, res, conv.stride[0], mode, bool(relu), gn.eps)
+    return Conv1dGNFn.apply(x, conv.weight, gn.weight, gn.bias, res, conv.stride[0], mode, bool(relu), gn.eps, bool(exact))
 
 
 class PairAddFn(Function):

@@ -70,17 +70,50 @@ __global__ __launch_bounds__(256) void k_conv_pack(const float *w, int cout, int
     out[base + 64 + lane] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 
+// Packed fp32 image (exact units): for tap t, K-chunk kc (32 input channels), channel block cb (16 outputs), half h:
+// 64 x float4, lane (n = lane & 15, kq = lane >> 4) holds W[16 cb + n][32 kc + 16 h + 4 kq + j][t], j = 0..3.  The same
+// bytes per K chunk as the two fp16 planes.  Input channels beyond cin are zero.
+__global__ __launch_bounds__(256) void k_conv_pack_f32(const float *w, int cout, int cin, int ks, float4 *out) {
+    const int nkc = conv_kpad(cin) / 32, ncb = cout / 16;
+    const int64_t total = (int64_t)ks * nkc * ncb * 128;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int lane = (int)(i & 63), h = (int)((i >> 6) & 1);
+    int64_t q = i >> 7;
+    const int cb = (int)(q % ncb); q /= ncb;
+    const int kc = (int)(q % nkc);
+    const int t = (int)(q / nkc);
+    const int n = lane & 15, kq = lane >> 4;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = 32 * kc + 16 * h + 4 * kq + j;
+        v[j] = c < cin ? w[((int64_t)(16 * cb + n) * cin + c) * ks + t] : 0.f;
+    }
+    out[i] = make_float4(v[0], v[1], v[2], v[3]);              // i = ((((t nkc + kc) ncb + cb) 2 + h) << 6) + lane
+}
+
 // SAVE: also store the pre-norm tile to p.y (the training forward); the arithmetic of `out` is the same either way.
-template <int KS, int NKC, bool SAVE>                          // taps, 32-channel K chunks; KS == 0: both read from p (any shape)
+//
+// F32: the exact-fp32 unit.  The rows are staged as fp32 and the convolution runs on v_mfma_f32_16x16x4_f32: a lane reads
+// 4 consecutive channels of its row (one ds_read_b128) and of its weight row (one 16-byte load, lgcn_conv_pack_weight_f32's
+// image) and feeds them to 4 MFMAs as K slot lane >> 4, so an output is ONE fused multiply-add chain in a fixed order.
+// Row stride in LDS: the 16 lanes that share an LDS cycle of a ds_read_b128 are 8 rows of one K quarter and the other 8
+// rows of the next quarter (4 dwords further on).  They cover the 64 banks once when consecutive rows are 2 (mod 4)
+// 16-byte slots apart -- even slots for one quarter, odd for the other: kpad + 8 floats for stride 1 (consecutive rows),
+// kpad + 4 for stride 2 (every other row).
+template <int KS, int NKC, bool SAVE, bool F32 = false>        // taps, 32-channel K chunks; KS == 0: both read from p (any shape)
 __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int na = kConvRows / p.lout;                        // actors per workgroup
     const int64_t a0 = (int64_t)blockIdx.x * na;
-    const int kpad = conv_kpad(p.cin), ldk = kpad + 8;         // fp16 elements per staged row (+ 16 B: bank spread)
+    const int kpad = conv_kpad(p.cin);
+    const int ldk = kpad + (F32 && p.stride == 2 ? 4 : 8);     // elements per staged row (fp16: + 16 B, bank spread; fp32: above)
     const int n_in = na * p.lin;                               // staged input rows; row n_in is all zero
     uint16_t *P0 = reinterpret_cast<uint16_t *>(smem);
     uint16_t *P1 = P0 + (n_in + 1) * ldk;
+    float *X = reinterpret_cast<float *>(smem);                // F32: the rows as they are
     const int ldt = p.cout + 4;
     float *T = reinterpret_cast<float *>(smem);                // the fp32 tile takes the planes' place once the GEMM is done
     const int pad = (p.ks - 1) >> 1;
@@ -104,6 +137,7 @@ __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
     }
 
     // ---- stage the actors' input rows as two fp16 planes (4 channels per thread and step, four row loads in flight)
+    // (F32: as one fp32 image)
     {
         const int c4n = kpad / 4, total = (n_in + 1) * c4n;
         for (int i0 = tid; i0 < total; i0 += 4 * 512) {
@@ -131,11 +165,15 @@ __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 if (i0 + u * 512 < total) {
-                    const uint32_t h0 = Fmt<1>::pack(v[u].x, v[u].y), h1 = Fmt<1>::pack(v[u].z, v[u].w);
-                    const f32x2 r0 = Fmt<1>::unpack(h0), r1 = Fmt<1>::unpack(h1);
-                    *reinterpret_cast<uint2 *>(P0 + rr[u] * ldk + cc[u]) = make_uint2(h0, h1);
-                    *reinterpret_cast<uint2 *>(P1 + rr[u] * ldk + cc[u]) =
-                        make_uint2(Fmt<1>::pack(v[u].x - r0.x, v[u].y - r0.y), Fmt<1>::pack(v[u].z - r1.x, v[u].w - r1.y));
+                    if constexpr (F32) {
+                        *reinterpret_cast<float4 *>(X + rr[u] * ldk + cc[u]) = v[u];
+                    } else {
+                        const uint32_t h0 = Fmt<1>::pack(v[u].x, v[u].y), h1 = Fmt<1>::pack(v[u].z, v[u].w);
+                        const f32x2 r0 = Fmt<1>::unpack(h0), r1 = Fmt<1>::unpack(h1);
+                        *reinterpret_cast<uint2 *>(P0 + rr[u] * ldk + cc[u]) = make_uint2(h0, h1);
+                        *reinterpret_cast<uint2 *>(P1 + rr[u] * ldk + cc[u]) =
+                            make_uint2(Fmt<1>::pack(v[u].x - r0.x, v[u].y - r0.y), Fmt<1>::pack(v[u].z - r1.x, v[u].w - r1.y));
+                    }
                 }
             }
         }
@@ -158,10 +196,29 @@ __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
 #pragma unroll
         for (int i = 0; i < kConvSub; ++i) {
             const int li = lpos[i] + t;
-            roff[i] = ((li >= 0 && li < p.lin) ? base[i] + li : n_in) * ldk + 8 * kq;
+            roff[i] = ((li >= 0 && li < p.lin) ? base[i] + li : n_in) * ldk + (F32 ? 4 : 8) * kq;
         }
     };
     auto kstep = [&](int kc, const uint4 b0, const uint4 b1) {
+        if constexpr (F32) {
+            // b0 / b1: the weights of channels 32 kc + 4 kq + j and 32 kc + 16 + 4 kq + j.  The sub-blocks' chains are
+            // independent: they are interleaved so that an MFMA does not wait for the one before it (40 cycles).
+            const f32x4 w[2] = {__builtin_bit_cast(f32x4, b0), __builtin_bit_cast(f32x4, b1)};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                f32x4 a[kConvSub];
+#pragma unroll
+                for (int i = 0; i < kConvSub; ++i)
+                    if (rb0 + i * nw < kConvSub) a[i] = *reinterpret_cast<const f32x4 *>(X + roff[i] + 32 * kc + 16 * h);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < kConvSub; ++i)
+                        if (rb0 + i * nw < kConvSub)           // wave-uniform
+                            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[h][j], a[i][j], acc[i], 0, 0, 0);
+            }
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < kConvSub; ++i) {
             if (rb0 + i * nw < kConvSub) {                     // wave-uniform
@@ -560,7 +617,7 @@ __global__ __launch_bounds__(512) void k_res1d_gn(const Res1dParams p) {
 
 using namespace lgcn;
 
-template <bool SAVE>
+template <bool SAVE, bool F32 = false>
 static int conv1d_gn_launch(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
                             const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
                             float *out, float *y, void *stream) {
@@ -580,13 +637,14 @@ static int conv1d_gn_launch(const float *x, int64_t n_act, int lin, int cin, con
     p.wp = reinterpret_cast<const uint4 *>(wp); p.gamma = gamma; p.beta = beta; p.eps = eps;
     p.res = res; p.res_mode = res_mode; p.relu = relu; p.out = out; p.y = y;
     const int na = kConvRows / lout;
+    // fp32 rows (F32) are at most as wide as the two fp16 planes
     const size_t lds_planes = (size_t)2 * (na * lin + 1) * (conv_kpad(cin) + 8) * 2, lds_tile = (size_t)kConvRows * (cout + 4) * 4;
     const size_t lds = lds_planes > lds_tile ? lds_planes : lds_tile;
     if (lds > 159 * 1024) return LGCN_ESHAPE;                  // the kernel's static words share the 160 KB
-    void (*kern)(ConvParams) = k_conv_gn<0, 0, SAVE>;
+    void (*kern)(ConvParams) = k_conv_gn<0, 0, SAVE, F32>;
     const int nkc = conv_kpad(cin) >> 5;
-    if (ks == 1) kern = nkc == 1 ? k_conv_gn<1, 1, SAVE> : nkc == 2 ? k_conv_gn<1, 2, SAVE> : nkc == 4 ? k_conv_gn<1, 4, SAVE> : kern;
-    if (ks == 3) kern = nkc == 1 ? k_conv_gn<3, 1, SAVE> : nkc == 2 ? k_conv_gn<3, 2, SAVE> : nkc == 4 ? k_conv_gn<3, 4, SAVE> : kern;
+    if (ks == 1) kern = nkc == 1 ? k_conv_gn<1, 1, SAVE, F32> : nkc == 2 ? k_conv_gn<1, 2, SAVE, F32> : nkc == 4 ? k_conv_gn<1, 4, SAVE, F32> : kern;
+    if (ks == 3) kern = nkc == 1 ? k_conv_gn<3, 1, SAVE, F32> : nkc == 2 ? k_conv_gn<3, 2, SAVE, F32> : nkc == 4 ? k_conv_gn<3, 4, SAVE, F32> : kern;
     if (lds > 64 * 1024) {             // above the default ceiling of dynamic LDS (a property set on the code object; idempotent)
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
         if (e != hipSuccess) return (int)e;
@@ -624,6 +682,32 @@ int lgcn_conv1d_gn_train(const float *x, int64_t n_act, int lin, int cin, const 
                          float *out, float *y, void *stream) {
     return conv1d_gn_launch<true>(x, n_act, lin, cin, wp, cout, ks, stride, gamma, beta, eps, res, res_mode, relu, out, y,
                                   stream);
+}
+
+// Exact-fp32 unit (reference layers.py:40-62 Conv1d, 142-190 Res1d's two halves; lanegcn.py:212-263): lgcn_conv1d_gn's
+// contract on v_mfma_f32_16x16x4_f32.
+int64_t lgcn_conv_packed_f32_bytes(int cin, int cout, int ks) {
+    if (cin < 1 || cin > 128 || (cout != 32 && cout != 64 && cout != 128) || (ks != 1 && ks != 3)) return LGCN_EINVAL;
+    return (int64_t)ks * (conv_kpad(cin) / 32) * (cout / 16) * 2 * 64 * 16;
+}
+
+int lgcn_conv_pack_weight_f32(const float *w, int cin, int cout, int ks, void *out, void *stream) {
+    if (lgcn_conv_packed_f32_bytes(cin, cout, ks) < 0) return LGCN_EINVAL;
+    LGCN_CHECK_PTR(w); LGCN_CHECK_PTR(out); LGCN_CHECK_ALIGN16(out);
+    const int64_t total = (int64_t)ks * (conv_kpad(cin) / 32) * (cout / 16) * 128;
+    hipLaunchKernelGGL(k_conv_pack_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
+                       ks, reinterpret_cast<float4 *>(out));
+    return launch_status();
+}
+
+int lgcn_conv1d_gn_f32(const float *x, int64_t n_act, int lin, int cin, const void *wp, int cout, int ks, int stride,
+                       const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
+                       float *out, float *y, void *stream) {
+    if (y != nullptr)
+        return conv1d_gn_launch<true, true>(x, n_act, lin, cin, wp, cout, ks, stride, gamma, beta, eps, res, res_mode, relu,
+                                            out, y, stream);
+    return conv1d_gn_launch<false, true>(x, n_act, lin, cin, wp, cout, ks, stride, gamma, beta, eps, res, res_mode, relu, out,
+                                         nullptr, stream);
 }
 
 static int res1d_launch(const float *x, int64_t n_act, int lin, int cin, int c, int stride, const void *w1p, const float *g1,

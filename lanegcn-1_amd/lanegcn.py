@@ -658,16 +658,20 @@ class ActorNet(nn.Module):
     def _forward_hip(self, actors: Tensor) -> Tensor:
         """The FPN on lgcn_conv1d_gn: every Conv1d + GroupNorm (+ residual, + x2 upsampling, + ReLU) of the FPN is
         ONE launch on [A, L, C] tensors: 20 launches instead of 20 stock convolutions + 20 norm launches.  Under autograd
-        the same 20 units run as Conv1dGNFn (lgcn_conv1d_gn_train forward, lgcn_conv1d_gn_bwd backward), unfused."""
+        the same 20 units run as Conv1dGNFn (lgcn_conv1d_gn_train forward, lgcn_conv1d_gn_bwd backward), unfused.  With
+        ActorNet.exact the 20 units are lgcn_conv1d_gn_f32 launches (fp32 operands), unfused in inference too."""
         train = ops.wants_grad(actors, *ops.module_params(self))
+        exact = ActorNet.exact
 
         def cg(conv: nn.Conv1d, norm: nn.GroupNorm, x: Tensor, **kw) -> Tensor:
+            if exact:
+                kw["exact"] = True
             if train:
                 return A.conv1d_gn(x, conv, norm, **kw)
             return ops.conv1d_gn(x, conv.weight, conv.stride[0], norm.weight, norm.bias, norm.eps, **kw)
 
         def fusable(b: Res1d) -> bool:
-            return not train and ActorNet.fuse_blocks and b.act and b.conv1.kernel_size[0] == 3 and b.conv2.kernel_size[0] == 3 and \
+            return not train and not exact and ActorNet.fuse_blocks and b.act and b.conv1.kernel_size[0] == 3 and b.conv2.kernel_size[0] == 3 and \
                 b.conv2.stride[0] == 1 and b.bn1.eps == b.bn2.eps and \
                 (b.downsample is None or (b.downsample[0].kernel_size[0] == 1 and b.downsample[1].eps == b.bn1.eps))
 
@@ -701,8 +705,9 @@ class ActorNet(nn.Module):
     def _hip_ok(self, actors: Tensor) -> bool:
         # lgcn_conv1d_gn / lgcn_res1d_gn take no matrix-mode argument: they always split operands into two fp16 planes.
         # In the exact-f32 and bf16x3 modes (and inside the range guard's bf16x3 re-run, which must cure an overflow that
-        # starts in ActorNet too) the MIOpen channels-last path runs instead.
-        if ActorNet.impl != "hip" or ops.get_mma() != "f16x2" or not self._channels_last_shape_ok(actors):
+        # starts in ActorNet too) the MIOpen channels-last path runs instead -- unless ActorNet.exact is set: the fp32
+        # units (lgcn_conv1d_gn_f32) have no operand range and serve every matrix mode.
+        if ActorNet.impl != "hip" or not (ActorNet.exact or ops.get_mma() == "f16x2") or not self._channels_last_shape_ok(actors):
             return False
         if not ActorNet.train_hip and ops.wants_grad(actors, *ops.module_params(self)):
             return False
@@ -724,6 +729,10 @@ class ActorNet(nn.Module):
     # Off by default: the f16x2 forward moves the actor features by fp32 rounding, which is enough to change which
     # knife-edge ReLUs of the graph hot path flip against the reference in the batch-32 training check.
     train_hip = False
+    # the units in exact fp32 (lgcn_conv1d_gn_f32: fp32 operands on v_mfma_f32_16x16x4_f32) in every matrix mode, one launch
+    # per unit (no fused Res1d blocks).  Off by default: the f16x2 units and their fused blocks stay the f16x2-mode path and
+    # MIOpen the path of the other modes.
+    exact = False
     # a Res1d block (conv + GN + ReLU + conv + GN + shortcut + ReLU) in ONE launch (lgcn_res1d_gn) instead of two or three
     fuse_blocks = True
     # the two Res1d blocks of a group in ONE launch (lgcn_res1d_pair_gn)
@@ -864,7 +873,7 @@ def _net_replay_or_run(self, eng, hfb, feats, rot, orig, sizes):
     is uploaded and run eagerly.  Net.graph_cache = False disables it."""
     m = hfb.meta
     sig = (m["n_nodes"], m["n_actors"], tuple(m["n_edges"]), tuple(sizes), m["cap_a2m"], m["cap_a2a"], ops.get_mma(),
-           ops.att_pairs_impl(), ops.laneconv_impl(), Att.strict, ActorNet.impl, PredNet.impl,
+           ops.att_pairs_impl(), ops.laneconv_impl(), Att.strict, ActorNet.impl, ActorNet.exact, PredNet.impl,
            sum(p._version for p in ops.module_params(self)))
     st = self.__dict__.setdefault("_graph_state", {"last": None, "sig": None, "graph": None})
     if Net.graph_cache and st["graph"] is not None and st["sig"] == sig:
@@ -977,8 +986,8 @@ class Net(nn.Module):
             dev = fb.node_ctrs.device
             with ops.mma_scope("bf16x3"):
                 out = eng.forward(fb, feats.to(dev), rot.to(dev), orig.to(dev), sizes, return_pairs=Att.strict)
-            # the re-run has fp32's exponent range in every stage (ActorNet takes the MIOpen path outside f16x2, see
-            # ActorNet._hip_ok): non-finite values that survive it were in the inputs or the weights, and are returned as
+            # the re-run has fp32's exponent range in every stage (outside f16x2 ActorNet runs its exact fp32 units when
+            # ActorNet.exact is set and the MIOpen path otherwise, see ActorNet._hip_ok): non-finite values that survive it were in the inputs or the weights, and are returned as
             # they are -- what the reference does with them
             host = [0] + torch.stack(out["n_pairs"]).flatten().tolist()
         if Att.strict and any(int(c) == 0 for c in host[1:]):

@@ -378,10 +378,27 @@ def conv_packed(weight: torch.Tensor) -> torch.Tensor:
     return _cached(weight, ("conv",), make)
 
 
+def conv_packed_f32(weight: torch.Tensor) -> torch.Tensor:
+    """fp32 fragment image of a Conv1d weight [cout, cin, ks] for lgcn_conv1d_gn_f32 (the exact units), cached on the
+    parameter under its own key like conv_packed (rebuilt once the parameter changes)."""
+    def make():
+        lib = L.load()
+        cout, cin, ks = weight.shape
+        nbytes = lib.lgcn_conv_packed_f32_bytes(cin, cout, ks)
+        if nbytes < 0:
+            raise L.LgcnError("conv_packed_f32: unsupported Conv1d weight shape %s" % (tuple(weight.shape),))
+        out = torch.empty(nbytes // 4, dtype=torch.float32, device=weight.device)
+        w = _dev(weight.detach(), torch.float32, "weight")
+        L.check(lib.lgcn_conv_pack_weight_f32(_ptr(w), cin, cout, ks, _ptr(out), _stream()), "lgcn_conv_pack_weight_f32")
+        return out
+    return _cached(weight, ("convF32",), make)
+
+
 def conv1d_gn(x: torch.Tensor, weight: torch.Tensor, stride: int, gamma, beta, eps: float, res: Optional[torch.Tensor] = None,
-              res_up2: bool = False, relu: bool = False) -> torch.Tensor:
+              res_up2: bool = False, relu: bool = False, exact: bool = False) -> torch.Tensor:
     """Conv1d (k = 1 / 3, padding (k - 1) / 2, no bias) + GroupNorm(1, C) + residual + ReLU on channels-last tensors in one
-    launch (lgcn_conv1d_gn): x [A, L, Cin] -> [A, Lout, Cout]; res [A, Lout, Cout], or [A, Lout / 2, Cout] with res_up2."""
+    launch (lgcn_conv1d_gn): x [A, L, Cin] -> [A, Lout, Cout]; res [A, Lout, Cout], or [A, Lout / 2, Cout] with res_up2.
+    exact: fp32 operands on the fp32-input MFMA (lgcn_conv1d_gn_f32) instead of two fp16 planes."""
     lib = L.load()
     x = _dev(x, torch.float32, "x")
     A_, lin, cin = x.shape
@@ -396,6 +413,12 @@ def conv1d_gn(x: torch.Tensor, weight: torch.Tensor, stride: int, gamma, beta, e
         mode = 2 if res_up2 else 1
         if tuple(res.shape) != ((A_, lout // 2, cout) if res_up2 else (A_, lout, cout)):
             raise L.LgcnError("conv1d_gn: residual of the wrong shape")
+    if exact:
+        L.check(lib.lgcn_conv1d_gn_f32(_ptr(x), A_, lin, cin, _ptr(conv_packed_f32(weight)), cout, ks, stride,
+                                       _ptr(_dev(gamma.detach(), torch.float32, "gamma")),
+                                       _ptr(_dev(beta.detach(), torch.float32, "beta")), float(eps), _ptr(res), mode,
+                                       int(bool(relu)), _ptr(out), None, _stream()), "lgcn_conv1d_gn_f32")
+        return out
     L.check(lib.lgcn_conv1d_gn(_ptr(x), A_, lin, cin, _ptr(conv_packed(weight)), cout, ks, stride,
                                _ptr(_dev(gamma.detach(), torch.float32, "gamma")), _ptr(_dev(beta.detach(), torch.float32, "beta")),
                                float(eps), _ptr(res), mode, int(bool(relu)), _ptr(out), _stream()), "lgcn_conv1d_gn")
@@ -419,9 +442,9 @@ def conv_packed_t(weight: torch.Tensor) -> torch.Tensor:
 
 
 def conv1d_gn_train(x: torch.Tensor, weight: torch.Tensor, stride: int, gamma, beta, eps: float,
-                    res: Optional[torch.Tensor] = None, res_up2: bool = False, relu: bool = False):
+                    res: Optional[torch.Tensor] = None, res_up2: bool = False, relu: bool = False, exact: bool = False):
     """conv1d_gn that also returns the pre-norm convolution output: (out, y), both [A, Lout, Cout] (lgcn_conv1d_gn_train;
-    out is bit-identical to conv1d_gn's)."""
+    out is bit-identical to conv1d_gn's).  exact: lgcn_conv1d_gn_f32 with y, as conv1d_gn(exact=True)."""
     lib = L.load()
     x = _dev(x, torch.float32, "x")
     A_, lin, cin = x.shape
@@ -437,6 +460,12 @@ def conv1d_gn_train(x: torch.Tensor, weight: torch.Tensor, stride: int, gamma, b
         mode = 2 if res_up2 else 1
         if tuple(res.shape) != ((A_, lout // 2, cout) if res_up2 else (A_, lout, cout)):
             raise L.LgcnError("conv1d_gn_train: residual of the wrong shape")
+    if exact:
+        L.check(lib.lgcn_conv1d_gn_f32(_ptr(x), A_, lin, cin, _ptr(conv_packed_f32(weight)), cout, ks, stride,
+                                       _ptr(_dev(gamma.detach(), torch.float32, "gamma")),
+                                       _ptr(_dev(beta.detach(), torch.float32, "beta")), float(eps), _ptr(res), mode,
+                                       int(bool(relu)), _ptr(out), _ptr(y), _stream()), "lgcn_conv1d_gn_f32")
+        return out, y
     L.check(lib.lgcn_conv1d_gn_train(_ptr(x), A_, lin, cin, _ptr(conv_packed(weight)), cout, ks, stride,
                                      _ptr(_dev(gamma.detach(), torch.float32, "gamma")),
                                      _ptr(_dev(beta.detach(), torch.float32, "beta")), float(eps), _ptr(res), mode,

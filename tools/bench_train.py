@@ -26,7 +26,10 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--actor-impl", default=None, choices=["hip", "miopen", "ab"],
                     help="ActorNet.impl for the step; 'ab': both, alternating step by step after a warm-up of each")
+    ap.add_argument("--actor-exact", action="store_true",
+                    help="ActorNet.exact: the 'hip' ActorNet on the exact-fp32 units (any --mma)")
     args = ap.parse_args()
+    M.ActorNet.exact = args.actor_exact
     if args.mma:
         ops.set_mma(args.mma)
     impls = ["hip", "miopen"] if args.actor_impl == "ab" else [args.actor_impl or M.ActorNet.impl]
@@ -80,7 +83,7 @@ def main():
     res = {"metric": "training step (forward + loss + backward + Adam), batch 32, S2", "mma": ops.get_mma(),
            "ms_per_step": ms, "scenes_per_s": 32e3 / ms, "loss_first": losses[0], "loss_last": losses[-1],
            "stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
-           "actor_impl": impls[0] if len(impls) == 1 else "ab",
+           "actor_impl": impls[0] if len(impls) == 1 else "ab", "actor_exact": M.ActorNet.exact,
            "median_step_ms": {k: float(np.median(v)) for k, v in per_step.items()}}
     print(json.dumps(res), flush=True)
 

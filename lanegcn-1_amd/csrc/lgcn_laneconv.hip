@@ -322,7 +322,6 @@ struct LcTileParams {
     float eps;
     float *out;
     unsigned long long *stamps;       // diagnostic build (-DLGCN_STAMPS) only: [workgroup][2][64] s_memtime stamps
-    int exp;                          // diagnostic build only: 1 = do not fetch the next unit's weight slice (WRONG results)
 };
 
 // Source rows in LDS: row s at s * NP * 256 B, plane p at + p * 256 B, 16-byte slot q of the plane row at
@@ -552,9 +551,6 @@ void k_lc_tile(const LcTileParams p) {
             const int un = more ? unit_at(k + 1) : 0;
             const float *wnext = more ? wptr(un) : p.wp2;
             if (DBUF) {
-#ifdef LGCN_STAMPS
-                if (p.exp & 1) wn = wc; else
-#endif
                 if (more || tail2) {
 #pragma unroll
                     for (int ks = 0; ks < KSW; ++ks) load_w_ks(wnext, wn, ks);
@@ -771,8 +767,6 @@ __global__ __launch_bounds__(256) void k_lc_combine(const LcCombParams p, int n_
     if (live_row) row_store_global(p.out + n * kC, tid, r);
 }
 
-static int fmt_of(int mma) { return mma == LGCN_MMA_BF16X3 ? 0 : mma == LGCN_MMA_F16X2 ? 1 : 2; }
-
 static bool lc_cfg(int mma, int variant, int *M, int *cap) {
     if (variant < 0 || variant > 2) return false;
 #define LGCN_CFG(F_) do { if (variant == 2) { *M = 16 * LcCfg<F_, 2>::RBN; *cap = LcCfg<F_, 2>::CAP; } else if (variant) { *M = 16 * LcCfg<F_, 1>::RBN; *cap = LcCfg<F_, 1>::CAP; } else { *M = 16 * LcCfg<F_, 0>::RBN; *cap = LcCfg<F_, 0>::CAP; } } while (0)
@@ -886,12 +880,8 @@ int lgcn_laneconv_fwd(const lgcn_laneconv_t *ph, void *stream) {
     t.part = q.part;
     t.wp2 = q.wp2; t.gn1_g = q.gn1_g; t.gn1_b = q.gn1_b; t.gn2_g = q.gn2_g; t.gn2_b = q.gn2_b; t.eps = q.eps; t.out = q.out;
     t.stamps = nullptr;
-    t.exp = 0;
 #ifdef LGCN_STAMPS
     t.stamps = g_lc_stamps;
-#endif
-#ifdef LGCN_TUNING
-    { const char *e = getenv("LGCN_EXP_LC"); t.exp = e ? atoi(e) : 0; }      // diagnostic build: work-skipping knobs
 #endif
     LcCombParams c{q.part, q.n_rows, M, q.n_groups, q.x, q.wp2, q.gn1_g, q.gn1_b, q.gn2_g, q.gn2_b, q.eps, q.out};
     const unsigned grid1 = (unsigned)(n_blocks * q.n_groups);

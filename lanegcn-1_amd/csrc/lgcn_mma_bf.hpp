@@ -57,6 +57,9 @@ template <> struct Fmt<2> : Fmt<0> {
     static constexpr int PA[1] = {0}, PB[1] = {0};
 };
 
+// LGCN_MMA_* -> format id of Fmt<>
+inline int fmt_of(int mma) { return mma == LGCN_MMA_BF16X3 ? 0 : mma == LGCN_MMA_F16X2 ? 1 : 2; }
+
 // Diagnostic build only (-DLGCN_STAMPS, tools/stamps.py): s_memtime stamps of the LaneConv phases go to
 // the buffer passed as out_pre (never to an output); the shipped library contains no stamp.
 #ifdef LGCN_STAMPS
@@ -131,21 +134,7 @@ __device__ __forceinline__ void kstep(const uint16_t *__restrict__ arow, int s, 
         }
 }
 
-// Weight-fragment ring: 4 sets = the 4 K-steps of a pass, prefetch distance 3 K-steps.  On entry
-// ring.b[0..2] hold K-steps 0..2 of Bw; step s first issues the load of the step 3 ahead (K-step 3 of
-// this pass for s = 0, K-step s-1 of Bw_next for s >= 1) and then runs its MFMAs, so a fragment has
-// three K-steps of MFMA time to arrive and the stream stays ahead across the per-relation barrier.
-template <int F>
-struct BRing { BFrag<F> b[4]; };
-
-template <int F>
-__device__ __forceinline__ void ring_prime(BRing<F> &r, const uint4 *__restrict__ Bw, int wave, int lane) {
-    load_b<F>(r.b[0], Bw, wave, lane, 0);
-    load_b<F>(r.b[1], Bw, wave, lane, 1);
-    load_b<F>(r.b[2], Bw, wave, lane, 2);
-}
-
-// Shallow variant: two fragment sets, prefetch distance 1 K-step (24 fewer VGPRs at NP = 3, which is
+// Weight-fragment ring, two fragment sets: prefetch distance 1 K-step (24 fewer VGPRs at NP = 3, which is
 // what lets two 8-wave workgroups share a CU; the latency is then hidden across workgroups instead).
 template <int F>
 struct BPair { BFrag<F> b[2]; };
@@ -195,24 +184,9 @@ __device__ __forceinline__ void gemm_pass(const uint16_t *__restrict__ A, const 
     kstep<RB, F>(arow, 3, r.b[1], acc);
 }
 
-template <int RB, int F>
-__device__ __forceinline__ void gemm_pass(const uint16_t *__restrict__ A, const uint4 *__restrict__ Bw,
-                                          const uint4 *__restrict__ Bw_next, BRing<F> &r, int wave, int lane,
-                                          f32x4 (&acc)[RB][2]) {
-    const uint16_t *arow = A + (lane & 15) * kLDB + 8 * (lane >> 4);
-    load_b<F>(r.b[3], Bw, wave, lane, 3);
-    kstep<RB, F>(arow, 0, r.b[0], acc);
-    if (Bw_next != nullptr) load_b<F>(r.b[0], Bw_next, wave, lane, 0);
-    kstep<RB, F>(arow, 1, r.b[1], acc);
-    if (Bw_next != nullptr) load_b<F>(r.b[1], Bw_next, wave, lane, 1);
-    kstep<RB, F>(arow, 2, r.b[2], acc);
-    if (Bw_next != nullptr) load_b<F>(r.b[2], Bw_next, wave, lane, 2);
-    kstep<RB, F>(arow, 3, r.b[3], acc);
-}
-
-// Second GEMM of a block (one pass over wp2).  On entry the ring holds K-step 0 (K-steps 0..2 for the deep
-// ring), prefetched by the last relation pass; gemm2_prefetch, called while the row phase runs on the other waves, adds the K-steps the
-// ring has room for, so that gemm2_pass starts with them landed.
+// Second GEMM of a block (one pass over wp2).  On entry the ring holds K-step 0, prefetched by the last relation
+// pass; gemm2_prefetch, called while the row phase runs on the other waves, adds the K-step the ring has room for,
+// so that gemm2_pass starts with it landed.
 template <int F>
 __device__ __forceinline__ void gemm2_prefetch(BPair<F> &r, const uint4 *__restrict__ Bw, int wave, int lane) {
     load_b<F>(r.b[1], Bw, wave, lane, 1);
@@ -224,10 +198,6 @@ __device__ __forceinline__ void gemm2_pass(const uint16_t *__restrict__ A, const
                                            int wave, int lane, f32x4 (&acc)[RB][2]) {
     gemm_pass<RB, F>(A, Bw, nullptr, r, wave, lane, acc);
 }
-template <int F>
-__device__ __forceinline__ void gemm2_prefetch(BRing<F> &r, const uint4 *__restrict__ Bw, int wave, int lane) {
-    load_b<F>(r.b[3], Bw, wave, lane, 3);   // K-steps 0..2 came with the last relation pass
-}
 template <int RB, int F>
 __device__ __forceinline__ void gemm2_pass(const uint16_t *__restrict__ A, const uint4 *__restrict__ Bw, BPair<F> &r,
                                            int wave, int lane, f32x4 (&acc)[RB][2]) {
@@ -238,15 +208,6 @@ __device__ __forceinline__ void gemm2_pass(const uint16_t *__restrict__ A, const
     load_b<F>(r.b[1], Bw, wave, lane, 3);
     kstep<RB, F>(arow, 2, r.b[0], acc);
     kstep<RB, F>(arow, 3, r.b[1], acc);
-}
-template <int RB, int F>
-__device__ __forceinline__ void gemm2_pass(const uint16_t *__restrict__ A, const uint4 *__restrict__, BRing<F> &r,
-                                           int wave, int lane, f32x4 (&acc)[RB][2]) {
-    const uint16_t *arow = A + (lane & 15) * kLDB + 8 * (lane >> 4);
-    kstep<RB, F>(arow, 0, r.b[0], acc);
-    kstep<RB, F>(arow, 1, r.b[1], acc);
-    kstep<RB, F>(arow, 2, r.b[2], acc);
-    kstep<RB, F>(arow, 3, r.b[3], acc);
 }
 
 // C/D layout of 16x16: col = lane & 15, row = 4 (lane >> 4) + reg

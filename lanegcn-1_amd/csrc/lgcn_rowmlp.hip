@@ -117,6 +117,29 @@ __device__ __forceinline__ void gather_rel(float *__restrict__ Abuf, const lgcn_
     }
 }
 
+// Does relation r have an edge into 32-row tile `tile`?  (A relation with none contributes an all-zero A tile: the
+// forward skips its gather and its MFMAs, the weight gradient the whole tile.)
+__device__ __forceinline__ bool rel_tile_active(const lgcn_agg_mlp_t &p, int r, int64_t tile) {
+    const int mode = p.rel[r].mode;
+    if (mode == LGCN_REL_CSR) {
+        const int64_t n_sub = (p.n_rows + 15) >> 4;
+        bool on = false;
+        for (int h = 0; h < 2; ++h) {
+            const int64_t sub = tile * 2 + h;
+            if (sub < n_sub) {
+                const int64_t k0 = (sub * p.n_rel_csr + p.rel[r].ridx) * 16;
+                on = on || p.rowptr[k0 + 16] > p.rowptr[k0];
+            }
+        }
+        return on;
+    }
+    if (mode == LGCN_REL_RANGE) {
+        const int64_t r0 = tile * kTM32, r1 = r0 + kTM32 < p.n_rows ? r0 + kTM32 : p.n_rows;
+        return p.rowptr[r1] > p.rowptr[r0];
+    }
+    return true;
+}
+
 // KIND only names the instantiation (1 = LaneConv layer: CSR relations; 0 = every other use) so
 // that profilers report the dominant kernel separately; the code is identical.
 template <int KIND>
@@ -129,28 +152,8 @@ __global__ __launch_bounds__(512) void k_agg_mlp(const lgcn_agg_mlp_t p, int n_t
     const int tile = xcd_chunk_remap(blockIdx.x, n_tiles);
     const int64_t row0 = (int64_t)tile * kTM32;
 
-    // active relations of this tile (a relation with no edge into the tile
-    // contributes an all-zero A tile: skip its gather and its MFMAs)
-    if (wave == 0) {
-        bool on = false;
-        if (lane < p.n_rel) {
-            const int mode = p.rel[lane].mode;
-            if (mode == LGCN_REL_CSR) {
-                const int64_t n_sub = (p.n_rows + 15) >> 4;
-                for (int h = 0; h < 2; ++h) {
-                    const int64_t sub = (int64_t)tile * 2 + h;
-                    if (sub < n_sub) {
-                        const int64_t k0 = (sub * p.n_rel_csr + p.rel[lane].ridx) * 16;
-                        on = on || p.rowptr[k0 + 16] > p.rowptr[k0];
-                    }
-                }
-            } else if (mode == LGCN_REL_RANGE) {
-                const int64_t r1 = row0 + kTM32 < p.n_rows ? row0 + kTM32 : p.n_rows;
-                on = p.rowptr[r1] > p.rowptr[row0];
-            } else {
-                on = true;
-            }
-        }
+    if (wave == 0) {     // active relations of this tile, in relation order
+        const bool on = lane < p.n_rel && rel_tile_active(p, lane, tile);
         const unsigned long long m = __ballot(on);
         if (on) act[__popcll(m & ((1ull << lane) - 1ull))] = lane;
         if (lane == 0) act[16] = __popcll(m);
@@ -357,27 +360,6 @@ __global__ __launch_bounds__(256) void k_att_pairs(const PairParams p) {
 // while waves 0-3 contract the current one over its rows on v_mfma_f32_32x32x2_f32 (K-step = 2 rows;
 // with lanes along the channel axis both operands are plain row reads, no transpose).  Wave w owns the
 // 64 x 64 block (w >> 1, w & 1) of the 128 x 128 result; partials per chunk are summed by k_wgrad_reduce.
-__device__ __forceinline__ bool wgrad_tile_active(const lgcn_agg_mlp_t &p, int r, int64_t tile) {
-    const int mode = p.rel[r].mode;
-    if (mode == LGCN_REL_CSR) {
-        const int64_t n_sub = (p.n_rows + 15) >> 4;
-        bool on = false;
-        for (int h = 0; h < 2; ++h) {
-            const int64_t sub = tile * 2 + h;
-            if (sub < n_sub) {
-                const int64_t k0 = (sub * p.n_rel_csr + p.rel[r].ridx) * 16;
-                on = on || p.rowptr[k0 + 16] > p.rowptr[k0];
-            }
-        }
-        return on;
-    }
-    if (mode == LGCN_REL_RANGE) {
-        const int64_t r0 = tile * kTM32, r1 = r0 + kTM32 < p.n_rows ? r0 + kTM32 : p.n_rows;
-        return p.rowptr[r1] > p.rowptr[r0];
-    }
-    return true;
-}
-
 __global__ __launch_bounds__(512) void k_wgrad(const lgcn_agg_mlp_t p, const float *__restrict__ dT,
                                                float *__restrict__ part, int n_tiles, int n_chunks) {
     __shared__ __attribute__((aligned(16))) float smem[4 * kTileFloats];
@@ -387,7 +369,7 @@ __global__ __launch_bounds__(512) void k_wgrad(const lgcn_agg_mlp_t p, const flo
     const int r = blockIdx.y, chunk = blockIdx.x;
 
     auto next_active = [&](int64_t t) -> int64_t {
-        while (t < n_tiles && !wgrad_tile_active(p, r, t)) t += n_chunks;
+        while (t < n_tiles && !rel_tile_active(p, r, t)) t += n_chunks;
         return t;
     };
     auto fill = [&](int b, int64_t t) {   // waves 4-7
@@ -510,28 +492,23 @@ int lgcn_pack_weight_batch(const lgcn_pack_job_t *jobs, int n_jobs, int mma, voi
 static_assert(sizeof(lgcn_agg_mlp_t) == 32 + LGCN_MAX_REL * 24 + 23 * 8 && LGCN_MAX_REL == 16,
               "lgcn_agg_mlp_t layout: keep lanegcn-1_amd/_lib.py (AggMlp) and tests/test_host_cabi.py in step");
 
-static int validate_agg(const lgcn_agg_mlp_t &p, bool *need_col_out) {
-    if (p.n_rows < 0 || p.n_rel < 1 || p.n_rel > LGCN_MAX_REL || !valid_mma(p.mma)) return LGCN_EINVAL;
-    constexpr int kKnownFlags = LGCN_F_GN1 | LGCN_F_RELU1 | LGCN_F_GEMM2 | LGCN_F_GN2 | LGCN_F_RES | LGCN_F_RELU2;
-#ifdef LGCN_ABLATE
-    if (p.flags & ~(kKnownFlags | (1 << 8) | (1 << 9))) return LGCN_EINVAL;
-#else
-    if (p.flags & ~kKnownFlags) return LGCN_EINVAL;      // unknown bits are an error, not a silent no-op
-#endif
-    if (p.n_rows == 0) return LGCN_OK;
-    if (p.n_rows > 0x7fffffff) return LGCN_ESHAPE;
-    LGCN_CHECK_PTR(p.out); LGCN_CHECK_ALIGN16(p.out);
+// The relation table of a launch: sources, modes and the index arrays they need.  fwd: a forward launch, which also
+// reads the packed weights and, in the split-precision modes, knows RANGE16; the weight gradient (fwd = false) does neither.
+static int validate_rels(const lgcn_agg_mlp_t &p, bool fwd, bool *need_col_out) {
     bool need_rowptr = false, need_col = false;
     for (int r = 0; r < p.n_rel; ++r) {
-        LGCN_CHECK_PTR(p.rel[r].src); LGCN_CHECK_PTR(p.rel[r].wp);
-        LGCN_CHECK_ALIGN16(p.rel[r].src); LGCN_CHECK_ALIGN16(p.rel[r].wp);
+        LGCN_CHECK_PTR(p.rel[r].src);
+        if (fwd) LGCN_CHECK_PTR(p.rel[r].wp);
+        LGCN_CHECK_ALIGN16(p.rel[r].src);
+        if (fwd) LGCN_CHECK_ALIGN16(p.rel[r].wp);
         switch (p.rel[r].mode) {
             case LGCN_REL_IDENT: break;
             case LGCN_REL_CSR:
                 if (p.rel[r].ridx < 0 || p.rel[r].ridx >= p.n_rel_csr) return LGCN_EINVAL;
                 need_rowptr = need_col = true; break;
             case LGCN_REL_RANGE: need_rowptr = true; break;
-            case LGCN_REL_RANGE16:          // split-precision kernels only
+            case LGCN_REL_RANGE16:          // split-precision forward kernels only
+                if (!fwd) return LGCN_EINVAL;
                 if (p.mma == LGCN_MMA_F32) return LGCN_ESHAPE;
                 need_rowptr = true; break;
             default: return LGCN_EINVAL;
@@ -539,6 +516,20 @@ static int validate_agg(const lgcn_agg_mlp_t &p, bool *need_col_out) {
     }
     if (need_rowptr) LGCN_CHECK_PTR(p.rowptr);
     if (need_col) LGCN_CHECK_PTR(p.col);
+    *need_col_out = need_col;
+    return LGCN_OK;
+}
+
+static int validate_agg(const lgcn_agg_mlp_t &p, bool *need_col_out) {
+    if (p.n_rows < 0 || p.n_rel < 1 || p.n_rel > LGCN_MAX_REL || !valid_mma(p.mma)) return LGCN_EINVAL;
+    constexpr int kKnownFlags = LGCN_F_GN1 | LGCN_F_RELU1 | LGCN_F_GEMM2 | LGCN_F_GN2 | LGCN_F_RES | LGCN_F_RELU2;
+    if (p.flags & ~kKnownFlags) return LGCN_EINVAL;      // unknown bits are an error, not a silent no-op
+    if (p.n_rows == 0) return LGCN_OK;
+    if (p.n_rows > 0x7fffffff) return LGCN_ESHAPE;
+    LGCN_CHECK_PTR(p.out); LGCN_CHECK_ALIGN16(p.out);
+    bool need_col = false;
+    const int rc = validate_rels(p, true, &need_col);
+    if (rc != LGCN_OK) return rc;
     if (need_col) {   // one rowptr per launch: a CSR plan and a RANGE prefix cannot be mixed
         for (int r = 0; r < p.n_rel; ++r)
             if (p.rel[r].mode == LGCN_REL_RANGE || p.rel[r].mode == LGCN_REL_RANGE16) return LGCN_EINVAL;
@@ -676,20 +667,9 @@ int lgcn_wgrad(const lgcn_agg_mlp_t *ph, const float *dT, float *dW, float *part
     if (p.n_rows < 0 || p.n_rel < 1 || p.n_rel > LGCN_MAX_REL || n_chunks < 1 || n_chunks > 1024) return LGCN_EINVAL;
     if (p.n_rows > 0x7fffffff) return LGCN_ESHAPE;
     LGCN_CHECK_ALIGN16(dT); LGCN_CHECK_ALIGN16(dW); LGCN_CHECK_ALIGN16(part);
-    bool need_rowptr = false, need_col = false;
-    for (int r = 0; r < p.n_rel; ++r) {
-        LGCN_CHECK_PTR(p.rel[r].src); LGCN_CHECK_ALIGN16(p.rel[r].src);
-        switch (p.rel[r].mode) {
-            case LGCN_REL_IDENT: break;
-            case LGCN_REL_CSR:
-                if (p.rel[r].ridx < 0 || p.rel[r].ridx >= p.n_rel_csr) return LGCN_EINVAL;
-                need_rowptr = need_col = true; break;
-            case LGCN_REL_RANGE: need_rowptr = true; break;
-            default: return LGCN_EINVAL;
-        }
-    }
-    if (need_rowptr) LGCN_CHECK_PTR(p.rowptr);
-    if (need_col) LGCN_CHECK_PTR(p.col);
+    bool need_col = false;
+    const int rc = validate_rels(p, false, &need_col);
+    if (rc != LGCN_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int n_tiles = (int)((p.n_rows + kTM32 - 1) / kTM32);
     hipLaunchKernelGGL(k_wgrad, dim3(n_chunks, p.n_rel), dim3(512), 0, st, p, dT, part, n_tiles, n_chunks);

@@ -12,15 +12,11 @@
 #include "lgcn_common.hpp"
 #include "lgcn_tile.hpp"
 #include "lgcn_mma_bf.hpp"
-#include <cstdlib>
 #include <type_traits>
-
-#ifndef LGCN_RB_ONE
-#define LGCN_RB_ONE 3      // tile height (in 16-row blocks) built with the one-set weight ring and held to 128 VGPRs
-#endif
 
 namespace lgcn {
 
+constexpr int LGCN_RB_ONE = 3;      // tile height (in 16-row blocks) built with the one-set weight ring and held to 128 VGPRs
 
 // ------------------------------------------------------------ packing -----
 template <int F>
@@ -226,7 +222,7 @@ __device__ __forceinline__ void gather_rel(uint16_t *__restrict__ Abuf, const lg
     else gather_mode<RB, F, LGCN_REL_RANGE, false>(Abuf, p, ri, tile, gt, ix, cadj, s, ring);
 }
 
-template <int RB, int F, int KIND, bool DEEP>
+template <int RB, int F, int KIND>
 __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, int bid, unsigned char *smem) {
     using TL = Tile<RB, F>;
     using IX = TileIdx<RB>;
@@ -255,7 +251,7 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
     const int flags = p.flags;
     const bool two = (flags & LGCN_F_GEMM2) != 0;
     const int gt = tid - 256;
-    typename std::conditional<DEEP, BRing<F>, typename std::conditional<RB == LGCN_RB_ONE && F != 0, BOne<F>, BPair<F>>::type>::type bfrag;
+    typename std::conditional<RB == LGCN_RB_ONE && F != 0, BOne<F>, BPair<F>>::type bfrag;
     f32x4 acc[RB][2];       // MFMA waves: accumulators; gather waves: the row sums of the relation in flight
     int cadj[RB];
 #pragma unroll
@@ -370,19 +366,10 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
         uint16_t *cur = (i & 1) ? buf1 : buf0;
         uint16_t *nxt = (i & 1) ? buf0 : buf1;
         if (wave < 4) {
-#ifdef LGCN_ABLATE   // diagnostic build only (make ablate, tools/bench_agg.py): flag bit 9 skips the MFMA passes
-            if (!(flags & (1 << 9)))
-#endif
-            {
             const float *wn = i + 1 < nact ? p.rel[rel_at(i + 1)].wp : (two ? p.wp2 : nullptr);
             gemm_pass<RB, F>(cur, reinterpret_cast<const uint4 *>(p.rel[rel_at(i)].wp),
-                              reinterpret_cast<const uint4 *>(wn), bfrag, wave, lane, acc);
-            }
-        } else if (i + 1 < nact
-#ifdef LGCN_ABLATE   // diagnostic build only: flag bit 8 skips the in-loop gathers
-                   && !(flags & (1 << 8))
-#endif
-        ) {
+                             reinterpret_cast<const uint4 *>(wn), bfrag, wave, lane, acc);
+        } else if (i + 1 < nact) {
             gather(nxt, rel_at(i + 1));
         }
         LGCN_STAMP(4 + 2 * i);       // own work of pass i done
@@ -531,23 +518,23 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
 // spilled registers: three-plane bf16x3 at RB = 2 runs 52 us held to 128 VGPRs, 74 us left free).
 // (Round 3: the three-plane kernels are no longer held to 128 VGPRs -- they spilled 10-170 registers to scratch there;
 // the library ships no kernel that uses scratch, tests/test_host_cabi.py.  bf16x3 row blocks run one workgroup per CU.)
-#define LGCN_WAVES_PER_SIMD(RB_, DEEP_, F_) \
-    __attribute__((amdgpu_waves_per_eu((F_) != 0 && ((RB_) <= 2 || (RB_) == LGCN_RB_ONE) && !(DEEP_) ? 4 : 2)))
+#define LGCN_WAVES_PER_SIMD(RB_, F_) __attribute__((amdgpu_waves_per_eu((F_) != 0 && ((RB_) <= 2 || (RB_) == LGCN_RB_ONE) ? 4 : 2)))
 
-template <int RB, int F, int KIND, bool DEEP>
-__global__ __launch_bounds__(512) LGCN_WAVES_PER_SIMD(RB, DEEP, F) void k_agg_mlp_bf(const lgcn_agg_mlp_t p, int n_tiles) {
+template <int RB, int F, int KIND>
+__global__ __launch_bounds__(512) LGCN_WAVES_PER_SIMD(RB, F) void k_agg_mlp_bf(const lgcn_agg_mlp_t p, int n_tiles) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[Tile<RB, F>::SMEM + 128 + TileIdx<RB>::INTS * 4 + 6 * kC * 4];
-    agg_body<RB, F, KIND, DEEP>(p, n_tiles, blockIdx.x, smem);
+    agg_body<RB, F, KIND>(p, n_tiles, blockIdx.x, smem);
 }
 
 // Two independent row blocks in one launch (Att's U and V: same shape of work, different inputs): blocks
 // [0, tiles_a) run problem a, the rest problem b.  One kernel boundary and one launch latency instead of two.
+// (The n = 2 case of k_agg_mlp_bfn below, kept because it measures faster: DESIGN.md section 3.5.)
 template <int RB, int F>
-__global__ __launch_bounds__(512) LGCN_WAVES_PER_SIMD(RB, false, F) void k_agg_mlp_bf2(const lgcn_agg_mlp_t pa, const lgcn_agg_mlp_t pb, int tiles_a,
-                                                     int tiles_b) {
+__global__ __launch_bounds__(512) LGCN_WAVES_PER_SIMD(RB, F) void k_agg_mlp_bf2(const lgcn_agg_mlp_t pa, const lgcn_agg_mlp_t pb, int tiles_a,
+                                                                                int tiles_b) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[Tile<RB, F>::SMEM + 128 + TileIdx<RB>::INTS * 4 + 6 * kC * 4];
-    if ((int)blockIdx.x < tiles_a) agg_body<RB, F, 0, false>(pa, tiles_a, blockIdx.x, smem);
-    else agg_body<RB, F, 0, false>(pb, tiles_b, blockIdx.x - tiles_a, smem);
+    if ((int)blockIdx.x < tiles_a) agg_body<RB, F, 0>(pa, tiles_a, blockIdx.x, smem);
+    else agg_body<RB, F, 0>(pb, tiles_b, blockIdx.x - tiles_a, smem);
 }
 
 // Up to LGCN_MAX_MULTI independent row blocks in one launch (lgcn_agg_mlp_multi): the problems' tiles follow each other
@@ -558,11 +545,11 @@ struct MultiArgs {
     int n;
 };
 template <int RB, int F>
-__global__ __launch_bounds__(512) LGCN_WAVES_PER_SIMD(RB, false, F) void k_agg_mlp_bfn(const MultiArgs m) {
+__global__ __launch_bounds__(512) LGCN_WAVES_PER_SIMD(RB, F) void k_agg_mlp_bfn(const MultiArgs m) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[Tile<RB, F>::SMEM + 128 + TileIdx<RB>::INTS * 4 + 6 * kC * 4];
     int b = blockIdx.x, i = 0;
     while (i + 1 < m.n && b >= m.tiles[i]) { b -= m.tiles[i]; ++i; }
-    agg_body<RB, F, 0, false>(m.p[i], m.tiles[i], b, smem);
+    agg_body<RB, F, 0>(m.p[i], m.tiles[i], b, smem);
 }
 
 template <int RB, int F>
@@ -655,62 +642,42 @@ static int pick_rb(int64_t n_rows, int fmt, bool lane_conv = false) {
     return best;
 }
 
-// Tuning knobs of the diagnostic builds (-DLGCN_TUNING: make stamps / ablate), read from the environment once:
-// LGCN_RB / LGCN_RB_LC force the tile height, LGCN_RING=3 the deep weight ring, LGCN_EXP_PAD_LDS pads the LaneConv
-// workgroups with dynamic LDS.  The shipped library reads no environment variable.
-static int env_int(const char *name, int dflt) {
-#ifdef LGCN_TUNING
-    const char *v = std::getenv(name);
-    return v && *v ? std::atoi(v) : dflt;
-#else
-    (void)name;
-    return dflt;
-#endif
-}
+// The kernels are instantiated per operand format F (Fmt<F>) and, the tiled ones, per tile height RB (16-row blocks):
+// with_fmt calls fn(integral_constant<int, F>) for the format of an LGCN_MMA_* mode, with_fmt_rb
+// fn(integral_constant<int, F>, integral_constant<int, RB>), rb = 1..4.  Both return the status of what fn launched.
+template <int N> using Int = std::integral_constant<int, N>;
 
-template <int F, bool DEEP>
-static void launch_agg(const lgcn_agg_mlp_t &p, int rb, bool lane_conv, hipStream_t st) {
-    const int rows = 16 * rb;
-    const int n_tiles = (int)((p.n_rows + rows - 1) / rows);
-    static const int pad_lds = env_int("LGCN_EXP_PAD_LDS", 0);     // experiment: extra dynamic LDS per workgroup
-#define LGCN_AGG(RB_)                                                                                                \
-    if (lane_conv) hipLaunchKernelGGL((k_agg_mlp_bf<RB_, F, 1, DEEP>), dim3(n_tiles), dim3(512), pad_lds, st, p, n_tiles); \
-    else hipLaunchKernelGGL((k_agg_mlp_bf<RB_, F, 0, DEEP>), dim3(n_tiles), dim3(512), 0, st, p, n_tiles)
-    switch (rb) {
-        case 1: LGCN_AGG(1); break;
-        case 2: LGCN_AGG(2); break;
-        case 3: LGCN_AGG(3); break;
-        default: LGCN_AGG(4); break;
-    }
-#undef LGCN_AGG
-}
-
-// LGCN_MMA_* -> format id of Fmt<>
-static int fmt_of(int mma) { return mma == LGCN_MMA_BF16X3 ? 0 : mma == LGCN_MMA_F16X2 ? 1 : 2; }
-
-int agg_mlp_bf(const lgcn_agg_mlp_t &p, bool lane_conv, hipStream_t st) {
-    static const int force_rb = env_int("LGCN_RB", 0), force_rb_lc = env_int("LGCN_RB_LC", 0), ring = env_int("LGCN_RING", 1);
-    int rb = p.tile_rb;
-    if (rb < 0 || rb > 4) return LGCN_EINVAL;
-    if (rb == 0 && lane_conv && force_rb_lc >= 1 && force_rb_lc <= 4) rb = force_rb_lc;
-    if (rb == 0) rb = force_rb >= 1 && force_rb <= 4 ? force_rb : pick_rb(p.n_rows, fmt_of(p.mma), lane_conv);
-#ifdef LGCN_TUNING      // the deep weight ring (measured: no gain, also for the small row blocks) exists in the tuning builds only
-    if (ring >= 3) {
-        switch (fmt_of(p.mma)) {
-            case 0: launch_agg<0, true>(p, rb, lane_conv, st); break;
-            case 1: launch_agg<1, true>(p, rb, lane_conv, st); break;
-            default: launch_agg<2, true>(p, rb, lane_conv, st); break;
-        }
-        return launch_status();
-    }
-#endif
-    (void)ring;
-    switch (fmt_of(p.mma)) {
-        case 0: launch_agg<0, false>(p, rb, lane_conv, st); break;
-        case 1: launch_agg<1, false>(p, rb, lane_conv, st); break;
-        default: launch_agg<2, false>(p, rb, lane_conv, st); break;
+template <class Fn>
+static int with_fmt(int mma, Fn fn) {
+    switch (fmt_of(mma)) {
+        case 0: fn(Int<0>{}); break;
+        case 1: fn(Int<1>{}); break;
+        default: fn(Int<2>{}); break;
     }
     return launch_status();
+}
+
+template <class Fn>
+static int with_fmt_rb(int mma, int rb, Fn fn) {
+    return with_fmt(mma, [&](auto f) {
+        switch (rb) {
+            case 1: fn(f, Int<1>{}); break;
+            case 2: fn(f, Int<2>{}); break;
+            case 3: fn(f, Int<3>{}); break;
+            default: fn(f, Int<4>{}); break;
+        }
+    });
+}
+
+int agg_mlp_bf(const lgcn_agg_mlp_t &p, bool lane_conv, hipStream_t st) {
+    if (p.tile_rb < 0 || p.tile_rb > 4) return LGCN_EINVAL;
+    const int rb = p.tile_rb ? p.tile_rb : pick_rb(p.n_rows, fmt_of(p.mma), lane_conv);
+    const int n_tiles = (int)((p.n_rows + 16 * rb - 1) / (16 * rb));
+    return with_fmt_rb(p.mma, rb, [&](auto f, auto r) {
+        constexpr int F = decltype(f)::value, RB = decltype(r)::value;
+        if (lane_conv) hipLaunchKernelGGL((k_agg_mlp_bf<RB, F, 1>), dim3(n_tiles), dim3(512), 0, st, p, n_tiles);
+        else hipLaunchKernelGGL((k_agg_mlp_bf<RB, F, 0>), dim3(n_tiles), dim3(512), 0, st, p, n_tiles);
+    });
 }
 
 int agg_mlp_pair_bf(const lgcn_agg_mlp_t &a, const lgcn_agg_mlp_t &b, hipStream_t st) {
@@ -718,16 +685,9 @@ int agg_mlp_pair_bf(const lgcn_agg_mlp_t &a, const lgcn_agg_mlp_t &b, hipStream_
     const int rb = pick_rb(a.n_rows > b.n_rows ? a.n_rows : b.n_rows, fmt_of(a.mma));
     const int rows = 16 * rb;
     const int ta = (int)((a.n_rows + rows - 1) / rows), tb = (int)((b.n_rows + rows - 1) / rows);
-#define LGCN_AGG2(RB_, F_) hipLaunchKernelGGL((k_agg_mlp_bf2<RB_, F_>), dim3(ta + tb), dim3(512), 0, st, a, b, ta, tb)
-#define LGCN_AGG2_RB(F_) switch (rb) { case 1: LGCN_AGG2(1, F_); break; case 2: LGCN_AGG2(2, F_); break; case 3: LGCN_AGG2(3, F_); break; default: LGCN_AGG2(4, F_); }
-    switch (fmt_of(a.mma)) {
-        case 0: LGCN_AGG2_RB(0); break;
-        case 1: LGCN_AGG2_RB(1); break;
-        default: LGCN_AGG2_RB(2); break;
-    }
-#undef LGCN_AGG2_RB
-#undef LGCN_AGG2
-    return launch_status();
+    return with_fmt_rb(a.mma, rb, [&](auto f, auto r) {
+        hipLaunchKernelGGL((k_agg_mlp_bf2<decltype(r)::value, decltype(f)::value>), dim3(ta + tb), dim3(512), 0, st, a, b, ta, tb);
+    });
 }
 
 int agg_mlp_multi_bf(const lgcn_agg_mlp_t *const *ps, int n, hipStream_t st) {
@@ -745,50 +705,30 @@ int agg_mlp_multi_bf(const lgcn_agg_mlp_t *const *ps, int n, hipStream_t st) {
         m.tiles[i] = (int)((ps[i]->n_rows + rows - 1) / rows);
         total += m.tiles[i];
     }
-#define LGCN_AGGN(RB_, F_) hipLaunchKernelGGL((k_agg_mlp_bfn<RB_, F_>), dim3(total), dim3(512), 0, st, m)
-#define LGCN_AGGN_RB(F_) switch (rb) { case 1: LGCN_AGGN(1, F_); break; case 2: LGCN_AGGN(2, F_); break; case 3: LGCN_AGGN(3, F_); break; default: LGCN_AGGN(4, F_); }
-    switch (fmt_of(ps[0]->mma)) {
-        case 0: LGCN_AGGN_RB(0); break;
-        case 1: LGCN_AGGN_RB(1); break;
-        default: LGCN_AGGN_RB(2); break;
-    }
-#undef LGCN_AGGN_RB
-#undef LGCN_AGGN
-    return launch_status();
+    return with_fmt_rb(ps[0]->mma, rb, [&](auto f, auto r) {
+        hipLaunchKernelGGL((k_agg_mlp_bfn<decltype(r)::value, decltype(f)::value>), dim3(total), dim3(512), 0, st, m);
+    });
 }
 
 int mapnet_input_bf(const InputParams &p, int mma, hipStream_t st) {
     const int rb = pick_rb(p.n_rows, fmt_of(mma));
     const int n_tiles = (int)((p.n_rows + 16 * rb - 1) / (16 * rb));
-#define LGCN_IN(RB_, F_) hipLaunchKernelGGL((k_mapnet_input_bf<RB_, F_>), dim3(n_tiles), dim3(256), 0, st, p, n_tiles)
-#define LGCN_IN_RB(F_) switch (rb) { case 1: LGCN_IN(1, F_); break; case 2: LGCN_IN(2, F_); break; case 3: LGCN_IN(3, F_); break; default: LGCN_IN(4, F_); }
-    switch (fmt_of(mma)) {
-        case 0: LGCN_IN_RB(0); break;
-        case 1: LGCN_IN_RB(1); break;
-        default: LGCN_IN_RB(2); break;
-    }
-#undef LGCN_IN_RB
-#undef LGCN_IN
-    return launch_status();
+    return with_fmt_rb(mma, rb, [&](auto f, auto r) {
+        hipLaunchKernelGGL((k_mapnet_input_bf<decltype(r)::value, decltype(f)::value>), dim3(n_tiles), dim3(256), 0, st, p, n_tiles);
+    });
 }
 
 int pack_weight_bf(const float *W, int ld, int mma, int transpose, void *out, hipStream_t st) {
     uint16_t *o = reinterpret_cast<uint16_t *>(out);
-    switch (fmt_of(mma)) {
-        case 0: hipLaunchKernelGGL((k_pack_weight_bf<0>), dim3(8), dim3(256), 0, st, W, ld, o, transpose); break;
-        case 1: hipLaunchKernelGGL((k_pack_weight_bf<1>), dim3(8), dim3(256), 0, st, W, ld, o, transpose); break;
-        default: hipLaunchKernelGGL((k_pack_weight_bf<2>), dim3(8), dim3(256), 0, st, W, ld, o, transpose); break;
-    }
-    return launch_status();
+    return with_fmt(mma, [&](auto f) {
+        hipLaunchKernelGGL((k_pack_weight_bf<decltype(f)::value>), dim3(8), dim3(256), 0, st, W, ld, o, transpose);
+    });
 }
 
 int pack_weight_batch_bf(const lgcn_pack_job_t *jobs, int n_jobs, int mma, hipStream_t st) {
-    switch (fmt_of(mma)) {
-        case 0: hipLaunchKernelGGL((k_pack_weight_batch_bf<0>), dim3(8, n_jobs), dim3(256), 0, st, jobs); break;
-        case 1: hipLaunchKernelGGL((k_pack_weight_batch_bf<1>), dim3(8, n_jobs), dim3(256), 0, st, jobs); break;
-        default: hipLaunchKernelGGL((k_pack_weight_batch_bf<2>), dim3(8, n_jobs), dim3(256), 0, st, jobs); break;
-    }
-    return launch_status();
+    return with_fmt(mma, [&](auto f) {
+        hipLaunchKernelGGL((k_pack_weight_batch_bf<decltype(f)::value>), dim3(8, n_jobs), dim3(256), 0, st, jobs);
+    });
 }
 
 }  // namespace lgcn

@@ -1174,6 +1174,23 @@ def test_chained_outputs_and_multi_launch_equal_separate_launches(hip):
                 assert all(torch.equal(a, b) for a, b in zip(o, want))
             else:
                 assert torch.equal(o, want)
+    # two two-stage + residual problems in one launch, as PredNet builds them for two heads (LinearRes.block_kw): the
+    # smallest row counts that put the boundary between the problems inside, at and past a 16-row sub-tile with a
+    # different tile count per problem; at the library's tile height and at every forced one
+    from lanegcn_amd.layers import LinearRes
+    heads = [LinearRes(128, 128, norm="GN", ng=1).cuda().eval() for _ in range(2)]
+    with torch.no_grad():
+        for h in heads:
+            for p in h.parameters():      # norm gains around 1, everything else around 0
+                p.copy_((1.0 if p.dim() == 1 else 0.0) + 0.09 * torch.randn(p.shape, generator=g))
+        for na, nb in ((1, 33), (17, 49), (250, 37)):
+            xa, xb = torch.randn(na, 128, generator=g).cuda(), torch.randn(nb, 128, generator=g).cuda()
+            for rb in (0, 1, 2, 3, 4):
+                probs = [dict(h.block_kw(x), tile_rb=rb) for h, x in zip(heads, (xa, xb))]
+                want = [ops.agg_mlp(**q) for q in probs]
+                for got in (ops.agg_mlp_multi(probs), ops.agg_mlp_pair(*probs)):      # (pair: one launch at rb = 0 only)
+                    for o, t in zip(got, want):
+                        assert torch.equal(o, t), (na, nb, rb)
 
 
 @pytest.mark.parametrize("rb", [1, 2, 3, 4])

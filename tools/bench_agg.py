@@ -1,4 +1,4 @@
-"""Ablation micro-benchmark of the fused LaneConv launch (lgcn_agg_mlp) on the S2 graph.
+"""Micro-benchmark of the fused LaneConv launch (lgcn_agg_mlp) on the S2 graph.
 Usage: python tools/bench_agg.py [mma ...]"""
 import os
 import sys
@@ -10,12 +10,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lanegcn_amd  # noqa: F401,E402
 from lanegcn_amd import _lib as L  # noqa: E402
-
-# the work-skipping flag bits (1 << 8: no in-loop gathers, 1 << 9: no MFMA passes) and the LGCN_RB* / LGCN_RING
-# environment knobs exist in the diagnostic library only (make -C lanegcn-1_amd/csrc ablate)
-_ABLATE = os.path.join(os.path.dirname(L.LIB_PATH), "liblgcn_ablate.so")
-if os.path.exists(_ABLATE):
-    L.LIB_PATH = _ABLATE
 from lanegcn_amd import data as gen  # noqa: E402
 from lanegcn_amd import lanegcn as M  # noqa: E402
 from lanegcn_amd import ops  # noqa: E402
@@ -93,12 +87,6 @@ def main():
             for n in (1, 2, 4, 8):
                 print("  %2d IDENT relation(s)    rb=auto: %7.1f us" % (n, run("ident", n)))
             print("  1 IDENT, no GEMM2/GN    rb=auto: %7.1f us" % run("ident", 1, flags=0))
-            if mode != "f32":
-                for rb in (2, 3):
-                    for kind in ("ident", "csr"):
-                        print("  ABLATION rb=%d 15 %s: full %6.1f | no in-loop gather %6.1f | no MFMA %6.1f | neither %6.1f us" % (
-                            rb, kind, run(kind, 15, rb=rb), run(kind, 15, flags=full | 256, rb=rb),
-                            run(kind, 15, flags=full | 512, rb=rb), run(kind, 15, flags=full | 768, rb=rb)))
             print("  8 CSR relations         rb=auto: %7.1f us" % run("csr", 8))
 
 

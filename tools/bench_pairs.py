@@ -1,5 +1,5 @@
 """Micro-benchmark of the pair MLP kernel (lgcn_att_pairs_ws) on the A2A / M2A / A2M pair sets of a synthetic S2 batch.
-Usage: python tools/bench_pairs.py [--lib stamps]   (--lib stamps: the diagnostic library, for its LGCN_EXP_* knobs)"""
+Usage: python tools/bench_pairs.py [--lib stamps]   (--lib NAME: liblgcn_NAME.so, a diagnostic library of the Makefile)"""
 import os
 import sys
 

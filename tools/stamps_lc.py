@@ -58,7 +58,7 @@ def main():
         med = lambda a: float(np.median(a))
         names = ["start->header", "header->rows stored", "barrier"] + ["unit %d" % k for k in range(nu)]
         print(" %s:" % name, " | ".join("%s %.0f" % (n, med(d[:, i])) for i, n in enumerate(names)))
-    if os.environ.get("LGCN_STAMPS_RAW"):      # every delta, in stamp order (for the LGCN_EXP_LC diagnostic knobs)
+    if os.environ.get("LGCN_STAMPS_RAW"):      # every delta, in stamp order
         for role, name in ((0, "wave 0"), (1, "wave 7")):
             d = np.diff(st[:, role, :], axis=1)
             cnt = int(np.median((st[:, role, :] > 0).sum(1)))

@@ -15,14 +15,9 @@
 // the packed image (lgcn_conv_pack_weight) once per K-step.  The 80 x Cout fp32 tile then goes through LDS to the
 // norm: 512 / NA threads per actor, two passes (mean, then variance about it, as ATen's GroupNorm), residual, ReLU, and
 // 512-byte coalesced stores.
-#include "lgcn_common.hpp"
-#include "lgcn_tile.hpp"
-#include "lgcn_mma_bf.hpp"
 #include "lgcn_conv.hpp"
 
 namespace lgcn {
-
-constexpr int kConvSub = kConvRows / 16;
 
 struct ConvParams {
     const float *x;                    // [A, lin, cin]
@@ -105,214 +100,64 @@ __global__ __launch_bounds__(256) void k_conv_pack_f32(const float *w, int cout,
 template <int KS, int NKC, bool SAVE, bool F32 = false>        // taps, 32-channel K chunks; KS == 0: both read from p (any shape)
 __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ float s_red[2][16];
+    const int tid = threadIdx.x;
     const int na = kConvRows / p.lout;                        // actors per workgroup
     const int64_t a0 = (int64_t)blockIdx.x * na;
     const int kpad = conv_kpad(p.cin);
     const int ldk = kpad + (F32 && p.stride == 2 ? 4 : 8);     // elements per staged row (fp16: + 16 B, bank spread; fp32: above)
     const int n_in = na * p.lin;                               // staged input rows; row n_in is all zero
-    uint16_t *P0 = reinterpret_cast<uint16_t *>(smem);
-    uint16_t *P1 = P0 + (n_in + 1) * ldk;
-    float *X = reinterpret_cast<float *>(smem);                // F32: the rows as they are
     const int ldt = p.cout + 4;
     float *T = reinterpret_cast<float *>(smem);                // the fp32 tile takes the planes' place once the GEMM is done
-    const int pad = (p.ks - 1) >> 1;
-
-    // wave -> channel block cb and the row sub-blocks rb0, rb0 + nw, ...
-    const int ncb = p.cout >> 4, nw = 8 / ncb, nkc = KS ? NKC : kpad >> 5;
-    const int cb = wave % ncb, rb0 = wave / ncb;
-    const int kq = lane >> 4;
-    auto wfrag = [&](int s_, uint4 &h, uint4 &l_) {               // packed weight fragments of K-step s_ = t * nkc + kc
-        const int64_t wb = (((int64_t)s_ * ncb + cb) * 2) << 6;
-        h = p.wp[wb + lane];
-        l_ = p.wp[wb + 64 + lane];
-    };
+    const ConvWave w(p.cout, tid);
     // An L2 round trip is several K-steps long (a K-step is <= 15 MFMAs): with the shape known the first kWd steps'
     // fragments are requested before the rows are staged and the ring is refilled kWd steps ahead.
     constexpr int NKS = KS * NKC, kWd = NKS < 6 ? (NKS ? NKS : 1) : 6;
     uint4 wh[kWd], wl[kWd];
     if constexpr (KS != 0) {
 #pragma unroll
-        for (int s_ = 0; s_ < kWd; ++s_) wfrag(s_, wh[s_], wl[s_]);
+        for (int s_ = 0; s_ < kWd; ++s_) w.wfrag(p.wp, s_, wh[s_], wl[s_]);
     }
 
-    // ---- stage the actors' input rows as two fp16 planes (4 channels per thread and step, four row loads in flight)
-    // (F32: as one fp32 image)
-    {
-        const int c4n = kpad / 4, total = (n_in + 1) * c4n;
-        for (int i0 = tid; i0 < total; i0 += 4 * 512) {
-            float4 v[4];
-            int rr[4], cc[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * 512;
-                const int r = i / c4n, c = 4 * (i - r * c4n);
-                rr[u] = r; cc[u] = c;
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int ar = r / p.lin;
-                const int64_t a = a0 + ar;
-                if (i < total && r < n_in && a < p.n_act) {
-                    const float *src = p.x + (a * p.lin + (r - ar * p.lin)) * p.cin + c;
-                    if (c + 3 < p.cin && (p.cin & 3) == 0) v[u] = *reinterpret_cast<const float4 *>(src);
-                    else {
-                        if (c < p.cin) v[u].x = src[0];
-                        if (c + 1 < p.cin) v[u].y = src[1];
-                        if (c + 2 < p.cin) v[u].z = src[2];
-                        if (c + 3 < p.cin) v[u].w = src[3];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (i0 + u * 512 < total) {
-                    if constexpr (F32) {
-                        *reinterpret_cast<float4 *>(X + rr[u] * ldk + cc[u]) = v[u];
-                    } else {
-                        const uint32_t h0 = Fmt<1>::pack(v[u].x, v[u].y), h1 = Fmt<1>::pack(v[u].z, v[u].w);
-                        const f32x2 r0 = Fmt<1>::unpack(h0), r1 = Fmt<1>::unpack(h1);
-                        *reinterpret_cast<uint2 *>(P0 + rr[u] * ldk + cc[u]) = make_uint2(h0, h1);
-                        *reinterpret_cast<uint2 *>(P1 + rr[u] * ldk + cc[u]) =
-                            make_uint2(Fmt<1>::pack(v[u].x - r0.x, v[u].y - r0.y), Fmt<1>::pack(v[u].z - r1.x, v[u].w - r1.y));
-                    }
-                }
-            }
-        }
-    }
+    conv_stage_rows<F32>(smem, p.x, a0, p.n_act, p.lin, p.cin, n_in, ldk, tid);
     lds_barrier();
 
     // ---- convolution
-    f32x4 acc[kConvSub];
-    int base[kConvSub], lpos[kConvSub];
-#pragma unroll
-    for (int i = 0; i < kConvSub; ++i) {
-        acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const int r = 16 * (rb0 + i * nw) + (lane & 15);       // output row of this lane in sub-block i (may be >= 80: unused)
-        const int a = r / p.lout, l = r - a * p.lout;
-        base[i] = a * p.lin;
-        lpos[i] = l * p.stride - pad;
-    }
-    int roff[kConvSub];                                         // LDS element offset of this lane's row under the current tap
-    auto tap = [&](int t) {
-#pragma unroll
-        for (int i = 0; i < kConvSub; ++i) {
-            const int li = lpos[i] + t;
-            roff[i] = ((li >= 0 && li < p.lin) ? base[i] + li : n_in) * ldk + (F32 ? 4 : 8) * kq;
-        }
-    };
-    auto kstep = [&](int kc, const uint4 b0, const uint4 b1) {
-        if constexpr (F32) {
-            // b0 / b1: the weights of channels 32 kc + 4 kq + j and 32 kc + 16 + 4 kq + j.  The sub-blocks' chains are
-            // independent: they are interleaved so that an MFMA does not wait for the one before it (40 cycles).
-            const f32x4 w[2] = {__builtin_bit_cast(f32x4, b0), __builtin_bit_cast(f32x4, b1)};
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                f32x4 a[kConvSub];
-#pragma unroll
-                for (int i = 0; i < kConvSub; ++i)
-                    if (rb0 + i * nw < kConvSub) a[i] = *reinterpret_cast<const f32x4 *>(X + roff[i] + 32 * kc + 16 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int i = 0; i < kConvSub; ++i)
-                        if (rb0 + i * nw < kConvSub)           // wave-uniform
-                            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[h][j], a[i][j], acc[i], 0, 0, 0);
-            }
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < kConvSub; ++i) {
-            if (rb0 + i * nw < kConvSub) {                     // wave-uniform
-                const int off = roff[i] + 32 * kc;
-                const uint4 a_hi = *reinterpret_cast<const uint4 *>(P0 + off);
-                const uint4 a_lo = *reinterpret_cast<const uint4 *>(P1 + off);
-                f32x4 c = acc[i];                               // smallest terms first; weights first: D^T, 4 channels per lane
-                c = Fmt<1>::mfma(b0, a_lo, c);
-                c = Fmt<1>::mfma(b1, a_hi, c);
-                c = Fmt<1>::mfma(b0, a_hi, c);
-                acc[i] = c;
-            }
-        }
-    };
+    const ConvRows<F32> rows(smem, (n_in + 1) * ldk, ldk, n_in, p.lin, p.stride, p.ks, p.lout, w);
+    ConvAcc acc;
     if constexpr (KS != 0) {
+        int roff[kConvSub];
+#pragma unroll
+        for (int i = 0; i < kConvSub; ++i) acc.v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int s_ = 0; s_ < NKS; ++s_) {
-            if (s_ % NKC == 0) tap(s_ / NKC);
+            if (s_ % NKC == 0) rows.tap(s_ / NKC, w.kq, roff);
             const uint4 b0 = wh[s_ % kWd], b1 = wl[s_ % kWd];
-            if (s_ + kWd < NKS) wfrag(s_ + kWd, wh[s_ % kWd], wl[s_ % kWd]);
-            kstep(s_ % NKC, b0, b1);
+            if (s_ + kWd < NKS) w.wfrag(p.wp, s_ + kWd, wh[s_ % kWd], wl[s_ % kWd]);
+            conv_kstep<F32>(w, rows, roff, s_ % NKC, b0, b1, acc);
         }
     } else {
-        const int nks = p.ks * nkc;                             // any shape: fragments one K-step ahead
-        uint4 nb0, nb1;
-        wfrag(0, nb0, nb1);
-        for (int t = 0; t < p.ks; ++t) {
-            tap(t);
-            for (int kc = 0; kc < nkc; ++kc) {
-                const uint4 b0 = nb0, b1 = nb1;
-                const int sn = t * nkc + kc + 1;
-                wfrag(sn < nks ? sn : nks - 1, nb0, nb1);
-                kstep(kc, b0, b1);
-            }
-        }
+        conv_taps<F32>(w, rows, kpad >> 5, p.wp, acc);          // any shape
     }
     lds_barrier();                                              // every wave is done reading the planes
-#pragma unroll
-    for (int i = 0; i < kConvSub; ++i)
-        if (rb0 + i * nw < kConvSub)
-            *reinterpret_cast<f32x4 *>(T + (16 * (rb0 + i * nw) + (lane & 15)) * ldt + 16 * cb + 4 * (lane >> 4)) = acc[i];
+    conv_acc_to_tile(w, T, ldt, acc);
     lds_barrier();
 
-    // ---- GroupNorm over (lout x cout) per actor, residual, ReLU.  All 512 threads: 512 / na threads per actor (128, 64
-    // or 32), each keeps its <= 5 float4 of the actor in registers (its channel quad is the same in every one of them:
-    // threads-per-actor is a multiple of cout / 4); the two statistics meet through 32-lane shuffles and one LDS word per
-    // half-wave.
-    __shared__ float s_red[2][16];
-    const int tpa = 512 / na, al = tid / tpa, j = tid - al * tpa;
-    const int c4 = p.cout >> 2, n4 = p.lout * c4;               // float4 columns per row, float4s per actor
-    const int64_t a = a0 + al;
-    const float *Ta = T + al * p.lout * ldt;
-    const int c = 4 * (j % c4);
+    // ---- GroupNorm over (lout x cout) per actor, residual, ReLU
+    const ConvGnMap m(p.lout, p.cout, tid);
+    const int64_t a = a0 + m.al;
+    const int c = m.c;
     float4 v[5];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int i = j + k * tpa;
-        v[k] = i < n4 ? *reinterpret_cast<const float4 *>(Ta + (i / c4) * ldt + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-    }
+    conv_tile_load(T, ldt, m, v);
     const float4 g = *reinterpret_cast<const float4 *>(p.gamma + c), bt = *reinterpret_cast<const float4 *>(p.beta + c);
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 31) == 0) s_red[0][tid >> 5] = s;
-    lds_barrier();
-    const int g0 = (al * tpa) >> 5, ng = tpa >> 5;              // this actor's half-waves
-    float mean = 0.f;
-    for (int k = 0; k < ng; ++k) mean += s_red[0][g0 + k];
-    const float per = (float)(p.lout * p.cout);
-    mean = mean / per;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        if (j + k * tpa < n4) {
-            const float d0 = v[k].x - mean, d1 = v[k].y - mean, d2 = v[k].z - mean, d3 = v[k].w - mean;
-            q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        }
-    }
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
-    if ((tid & 31) == 0) s_red[1][tid >> 5] = q;
-    lds_barrier();
-    float var = 0.f;
-    for (int k = 0; k < ng; ++k) var += s_red[1][g0 + k];
-    const float rstd = 1.0f / sqrtf(var / per + p.eps);
+    float mean, rstd;
+    conv_gn_stats(v, m, s_red, p.eps, mean, rstd);
     if (a < p.n_act) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
-            const int i = j + k * tpa;
-            if (i < n4) {
-                const int l = i / c4;
-                float4 y = make_float4((v[k].x - mean) * rstd * g.x + bt.x, (v[k].y - mean) * rstd * g.y + bt.y,
-                                       (v[k].z - mean) * rstd * g.z + bt.z, (v[k].w - mean) * rstd * g.w + bt.w);
+            if (m.has(k)) {
+                const int l = m.l(k);
+                float4 y = conv_gn_apply(v[k], mean, rstd, g, bt);
                 if (p.res_mode == 1) {
                     const float4 r = *reinterpret_cast<const float4 *>(p.res + (a * p.lout + l) * p.cout + c);
                     y.x += r.x; y.y += r.y; y.z += r.z; y.w += r.w;
@@ -357,7 +202,7 @@ struct Res1dParams {
 __global__ __launch_bounds__(512) void k_res1d_gn(const Res1dParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ float s_red[2][16];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int na = kConvRows / p.lout;
     const int64_t a0 = (int64_t)blockIdx.x * na;
     const int kpad = conv_kpad(p.cin), ldk = kpad + 8;
@@ -366,182 +211,54 @@ __global__ __launch_bounds__(512) void k_res1d_gn(const Res1dParams p) {
     // ONE region of LDS serves in turn as the input planes, every fp32 tile and every set of intermediate planes (80 rows
     // + a zero row): each is dead before the next is written -- a tile is consumed into registers by tile_gn (whose two
     // barriers every thread has passed when it returns), planes are done with at the barrier behind their convolution.
-    uint16_t *P0 = reinterpret_cast<uint16_t *>(smem), *P1 = P0 + (n_in + 1) * ldk;
     float *T = reinterpret_cast<float *>(smem);
     uint16_t *Y0 = reinterpret_cast<uint16_t *>(smem), *Y1 = Y0 + (kConvRows + 1) * ldy;
-    const bool chain = p.w1b != nullptr;
+    const bool chain = p.w1b != nullptr, down = p.wd != nullptr;
+    const ConvWave w(p.c, tid);
 
-    const int ncb = p.c >> 4, nw = 8 / ncb;
-    const int cb = wave % ncb, rb0 = wave / ncb, kq = lane >> 4;
-    const bool down = p.wd != nullptr;
-
-    // ---- stage x as two fp16 planes
-    {
-        const int c4n = kpad / 4, total = (n_in + 1) * c4n;
-        for (int i0 = tid; i0 < total; i0 += 4 * 512) {
-            float4 v[4];
-            int rr[4], cc[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int i = i0 + u * 512;
-                const int r = i / c4n, c = 4 * (i - r * c4n);
-                rr[u] = r; cc[u] = c;
-                v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                const int ar = r / p.lin;
-                const int64_t a = a0 + ar;
-                if (i < total && r < n_in && a < p.n_act) {
-                    const float *src = p.x + (a * p.lin + (r - ar * p.lin)) * p.cin + c;
-                    if (c + 3 < p.cin && (p.cin & 3) == 0) v[u] = *reinterpret_cast<const float4 *>(src);
-                    else {
-                        if (c < p.cin) v[u].x = src[0];
-                        if (c + 1 < p.cin) v[u].y = src[1];
-                        if (c + 2 < p.cin) v[u].z = src[2];
-                        if (c + 3 < p.cin) v[u].w = src[3];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (i0 + u * 512 < total) {
-                    const uint32_t h0 = Fmt<1>::pack(v[u].x, v[u].y), h1 = Fmt<1>::pack(v[u].z, v[u].w);
-                    const f32x2 q0 = Fmt<1>::unpack(h0), q1 = Fmt<1>::unpack(h1);
-                    *reinterpret_cast<uint2 *>(P0 + rr[u] * ldk + cc[u]) = make_uint2(h0, h1);
-                    *reinterpret_cast<uint2 *>(P1 + rr[u] * ldk + cc[u]) =
-                        make_uint2(Fmt<1>::pack(v[u].x - q0.x, v[u].y - q0.y), Fmt<1>::pack(v[u].z - q1.x, v[u].w - q1.y));
-                }
-            }
-        }
-    }
+    conv_stage_rows<false>(smem, p.x, a0, p.n_act, p.lin, p.cin, n_in, ldk, tid);
     lds_barrier();
 
-    // one convolution as shifted GEMMs over staged planes: out^T = W x^T, weight fragments one K-step ahead
-    f32x4 acc[kConvSub];
-    auto conv = [&](const uint16_t *Q0, const uint16_t *Q1, int ld, int zero_row, int lin_, int stride_, int ks_, int nkc_,
-                    const uint4 *wp) {
-        const int pad_ = (ks_ - 1) >> 1;
-        int base[kConvSub], lpos[kConvSub];
-#pragma unroll
-        for (int i = 0; i < kConvSub; ++i) {
-            acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const int r = 16 * (rb0 + i * nw) + (lane & 15);
-            const int a = r / p.lout, l = r - a * p.lout;
-            base[i] = a * lin_;
-            lpos[i] = l * stride_ - pad_;
-        }
-        auto wfrag = [&](int s_, uint4 &h, uint4 &l_) {
-            const int64_t wb = (((int64_t)s_ * ncb + cb) * 2) << 6;
-            h = wp[wb + lane];
-            l_ = wp[wb + 64 + lane];
-        };
-        const int nks = ks_ * nkc_;
-        uint4 nb0, nb1;
-        wfrag(0, nb0, nb1);
-        for (int t = 0; t < ks_; ++t) {
-            int roff[kConvSub];
-#pragma unroll
-            for (int i = 0; i < kConvSub; ++i) {
-                const int li = lpos[i] + t;
-                roff[i] = ((li >= 0 && li < lin_) ? base[i] + li : zero_row) * ld + 8 * kq;
-            }
-            for (int kc = 0; kc < nkc_; ++kc) {
-                const uint4 b0 = nb0, b1 = nb1;
-                const int sn = t * nkc_ + kc + 1;
-                wfrag(sn < nks ? sn : nks - 1, nb0, nb1);
-#pragma unroll
-                for (int i = 0; i < kConvSub; ++i) {
-                    if (rb0 + i * nw < kConvSub) {
-                        const int off = roff[i] + 32 * kc;
-                        const uint4 a_hi = *reinterpret_cast<const uint4 *>(Q0 + off);
-                        const uint4 a_lo = *reinterpret_cast<const uint4 *>(Q1 + off);
-                        f32x4 c = acc[i];
-                        c = Fmt<1>::mfma(b0, a_lo, c);
-                        c = Fmt<1>::mfma(b1, a_hi, c);
-                        c = Fmt<1>::mfma(b0, a_hi, c);
-                        acc[i] = c;
-                    }
-                }
-            }
-        }
+    ConvAcc acc;
+    auto conv_in = [&](int ks, const uint4 *wp) {               // on the staged input, stride s
+        const ConvRows<false> rows(smem, (n_in + 1) * ldk, ldk, n_in, p.lin, p.stride, ks, p.lout, w);
+        conv_taps<false>(w, rows, kpad >> 5, wp, acc);
     };
-    auto acc_to_tile = [&](const f32x4 (&q)[kConvSub]) {
-#pragma unroll
-        for (int i = 0; i < kConvSub; ++i)
-            if (rb0 + i * nw < kConvSub)
-                *reinterpret_cast<f32x4 *>(T + (16 * (rb0 + i * nw) + (lane & 15)) * ldt + 16 * cb + 4 * (lane >> 4)) = q[i];
+    auto conv_mid = [&](const uint4 *wp) {                      // 3 taps, stride 1 on the intermediate planes
+        const ConvRows<false> rows(smem, (kConvRows + 1) * ldy, ldy, kConvRows, p.lout, 1, 3, p.lout, w);
+        conv_taps<false>(w, rows, p.c >> 5, wp, acc);
     };
-    // GroupNorm of the tile per actor (512 / na threads each, <= 5 float4 per thread with the same channel quad)
-    const int tpa = 512 / na, al = tid / tpa, j = tid - al * tpa;
-    const int c4 = p.c >> 2, n4 = p.lout * c4;
-    const int64_t a = a0 + al;
-    const int c = 4 * (j % c4);
-    const float per = (float)(p.lout * p.c);
-    const int g0 = (al * tpa) >> 5, ng = tpa >> 5;
-    auto tile_gn = [&](float4 (&v)[5], const float *gamma, const float *beta) {     // contains two barriers
-        const float4 g = *reinterpret_cast<const float4 *>(gamma + c), bt = *reinterpret_cast<const float4 *>(beta + c);
-        const float *Ta = T + al * p.lout * ldt;
-        float s = 0.f;
+    const ConvGnMap m(p.lout, p.c, tid);
+    const int64_t a = a0 + m.al;
+    auto tile_gn = [&](float4 (&v)[5], const float *gamma, const float *beta) {     // GroupNorm of the tile; contains two barriers
+        const float4 g = *reinterpret_cast<const float4 *>(gamma + m.c), bt = *reinterpret_cast<const float4 *>(beta + m.c);
+        conv_tile_load(T, ldt, m, v);
+        float mean, rstd;
+        conv_gn_stats(v, m, s_red, p.eps, mean, rstd);
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int i = j + k * tpa;
-            v[k] = i < n4 ? *reinterpret_cast<const float4 *>(Ta + (i / c4) * ldt + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-            s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
-        }
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-        if ((tid & 31) == 0) s_red[0][tid >> 5] = s;
-        lds_barrier();
-        float mean = 0.f;
-        for (int k = 0; k < ng; ++k) mean += s_red[0][g0 + k];
-        mean = mean / per;
-        float q = 0.f;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            if (j + k * tpa < n4) {
-                const float d0 = v[k].x - mean, d1 = v[k].y - mean, d2 = v[k].z - mean, d3 = v[k].w - mean;
-                q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-            }
-        }
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
-        if ((tid & 31) == 0) s_red[1][tid >> 5] = q;
-        lds_barrier();
-        float var = 0.f;
-        for (int k = 0; k < ng; ++k) var += s_red[1][g0 + k];
-        const float rstd = 1.0f / sqrtf(var / per + p.eps);
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            v[k] = make_float4((v[k].x - mean) * rstd * g.x + bt.x, (v[k].y - mean) * rstd * g.y + bt.y,
-                               (v[k].z - mean) * rstd * g.z + bt.z, (v[k].w - mean) * rstd * g.w + bt.w);
+        for (int k = 0; k < 5; ++k) v[k] = conv_gn_apply(v[k], mean, rstd, g, bt);
     };
 
     // ---- conv1 (and the shortcut's 1 x 1 convolution) on the staged input
-    conv(P0, P1, ldk, n_in, p.lin, p.stride, 3, kpad >> 5, p.w1);
-    f32x4 acc1[kConvSub];
-#pragma unroll
-    for (int i = 0; i < kConvSub; ++i) acc1[i] = acc[i];
-    if (down) conv(P0, P1, ldk, n_in, p.lin, p.stride, 1, kpad >> 5, p.wd);
+    conv_in(3, p.w1);
+    const ConvAcc acc1 = acc;
+    if (down) conv_in(1, p.wd);
     lds_barrier();                                              // the input planes are done with
-    acc_to_tile(acc1);
+    conv_acc_to_tile(w, T, ldt, acc1);
     lds_barrier();
     float4 v[5], res[5];
     tile_gn(v, p.g1, p.b1);
     // a thread's normalised values -> operand planes (row = al * lout + l: the output row numbering)
-    auto to_planes = [&](uint16_t *U0, uint16_t *U1, const float4 (&y_)[5]) {
+    auto to_planes = [&](const float4 (&y_)[5]) {
         if (tid < ldy / 4) {                                    // the zero row the padding taps read
-            *reinterpret_cast<uint2 *>(U0 + kConvRows * ldy + 4 * tid) = make_uint2(0u, 0u);
-            *reinterpret_cast<uint2 *>(U1 + kConvRows * ldy + 4 * tid) = make_uint2(0u, 0u);
+            *reinterpret_cast<uint2 *>(Y0 + kConvRows * ldy + 4 * tid) = make_uint2(0u, 0u);
+            *reinterpret_cast<uint2 *>(Y1 + kConvRows * ldy + 4 * tid) = make_uint2(0u, 0u);
         }
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
-            const int i = j + k * tpa;
-            if (i < n4) {
-                const float4 y = y_[k];
-                const int row = al * p.lout + i / c4;
-                const uint32_t h0 = Fmt<1>::pack(y.x, y.y), h1 = Fmt<1>::pack(y.z, y.w);
-                const f32x2 q0 = Fmt<1>::unpack(h0), q1 = Fmt<1>::unpack(h1);
-                *reinterpret_cast<uint2 *>(U0 + row * ldy + c) = make_uint2(h0, h1);
-                *reinterpret_cast<uint2 *>(U1 + row * ldy + c) =
-                    make_uint2(Fmt<1>::pack(y.x - q0.x, y.y - q0.y), Fmt<1>::pack(y.z - q1.x, y.w - q1.y));
+            if (m.has(k)) {
+                const int off = m.row(k) * ldy + m.c;
+                conv_split_store(Y0 + off, Y1 + off, y_[k]);
             }
         }
     };
@@ -553,29 +270,27 @@ __global__ __launch_bounds__(512) void k_res1d_gn(const Res1dParams p) {
     relu5(v);
     // ---- the shortcut
     if (down) {
-        acc_to_tile(acc);                                       // the conv1 tile is in registers everywhere
+        conv_acc_to_tile(w, T, ldt, acc);                       // the conv1 tile is in registers everywhere
         lds_barrier();
         tile_gn(res, p.gd, p.bd);
     } else {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const int i = j + k * tpa;
-            res[k] = (a < p.n_act && i < n4) ? *reinterpret_cast<const float4 *>(p.x + (a * p.lout + i / c4) * p.c + c)
-                                             : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        for (int k = 0; k < 5; ++k)
+            res[k] = (a < p.n_act && m.has(k)) ? *reinterpret_cast<const float4 *>(p.x + (a * p.lout + m.l(k)) * p.c + m.c)
+                                               : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    to_planes(Y0, Y1, v);                                       // relu(GN1(conv1 x))
+    to_planes(v);                                               // relu(GN1(conv1 x))
     lds_barrier();
     // ---- conv2 on the intermediate, GN2, + shortcut, ReLU
-    conv(Y0, Y1, ldy, kConvRows, p.lout, 1, 3, p.c >> 5, p.w2);
+    conv_mid(p.w2);
     lds_barrier();                                              // the planes are done with: the tile takes their place
-    acc_to_tile(acc);
+    conv_acc_to_tile(w, T, ldt, acc);
     lds_barrier();
     tile_gn(v, p.g2, p.b2);
     auto add_res_relu = [&]() {
 #pragma unroll
         for (int k = 0; k < 5; ++k) {
-            const bool live = j + k * tpa < n4;
+            const bool live = m.has(k);
             v[k] = make_float4(live ? relu_nan(v[k].x + res[k].x) : 0.f, live ? relu_nan(v[k].y + res[k].y) : 0.f,
                                live ? relu_nan(v[k].z + res[k].z) : 0.f, live ? relu_nan(v[k].w + res[k].w) : 0.f);
         }
@@ -583,30 +298,28 @@ __global__ __launch_bounds__(512) void k_res1d_gn(const Res1dParams p) {
     auto store_out = [&]() {
         if (a < p.n_act) {
 #pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const int i = j + k * tpa;
-                if (i < n4) *reinterpret_cast<float4 *>(p.out + (a * p.lout + i / c4) * p.c + c) = v[k];
-            }
+            for (int k = 0; k < 5; ++k)
+                if (m.has(k)) *reinterpret_cast<float4 *>(p.out + (a * p.lout + m.l(k)) * p.c + m.c) = v[k];
         }
     };
     add_res_relu();
     if (!chain) { store_out(); return; }
     // ---- the chained block (identity shortcut = the values this thread holds)
-    to_planes(Y0, Y1, v);
+    to_planes(v);
 #pragma unroll
     for (int k = 0; k < 5; ++k) res[k] = v[k];
     lds_barrier();
-    conv(Y0, Y1, ldy, kConvRows, p.lout, 1, 3, p.c >> 5, p.w1b);
+    conv_mid(p.w1b);
     lds_barrier();
-    acc_to_tile(acc);
+    conv_acc_to_tile(w, T, ldt, acc);
     lds_barrier();
     tile_gn(v, p.g1b, p.b1b);
     relu5(v);
-    to_planes(Y0, Y1, v);
+    to_planes(v);
     lds_barrier();
-    conv(Y0, Y1, ldy, kConvRows, p.lout, 1, 3, p.c >> 5, p.w2b);
+    conv_mid(p.w2b);
     lds_barrier();
-    acc_to_tile(acc);
+    conv_acc_to_tile(w, T, ldt, acc);
     lds_barrier();
     tile_gn(v, p.g2b, p.b2b);
     add_res_relu();
@@ -637,34 +350,34 @@ static int conv1d_gn_launch(const float *x, int64_t n_act, int lin, int cin, con
     p.wp = reinterpret_cast<const uint4 *>(wp); p.gamma = gamma; p.beta = beta; p.eps = eps;
     p.res = res; p.res_mode = res_mode; p.relu = relu; p.out = out; p.y = y;
     const int na = kConvRows / lout;
-    // fp32 rows (F32) are at most as wide as the two fp16 planes
-    const size_t lds_planes = (size_t)2 * (na * lin + 1) * (conv_kpad(cin) + 8) * 2, lds_tile = (size_t)kConvRows * (cout + 4) * 4;
+    const size_t lds_planes = conv_lds_in_planes(na, lin, cin), lds_tile = conv_lds_tile(cout);
     const size_t lds = lds_planes > lds_tile ? lds_planes : lds_tile;
-    if (lds > 159 * 1024) return LGCN_ESHAPE;                  // the kernel's static words share the 160 KB
     void (*kern)(ConvParams) = k_conv_gn<0, 0, SAVE, F32>;
     const int nkc = conv_kpad(cin) >> 5;
     if (ks == 1) kern = nkc == 1 ? k_conv_gn<1, 1, SAVE, F32> : nkc == 2 ? k_conv_gn<1, 2, SAVE, F32> : nkc == 4 ? k_conv_gn<1, 4, SAVE, F32> : kern;
     if (ks == 3) kern = nkc == 1 ? k_conv_gn<3, 1, SAVE, F32> : nkc == 2 ? k_conv_gn<3, 2, SAVE, F32> : nkc == 4 ? k_conv_gn<3, 4, SAVE, F32> : kern;
-    if (lds > 64 * 1024) {             // above the default ceiling of dynamic LDS (a property set on the code object; idempotent)
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-        if (e != hipSuccess) return (int)e;
-    }
+    const int rc = set_lds(reinterpret_cast<const void *>(kern), lds);
+    if (rc != LGCN_OK) return rc;
     const unsigned grid = (unsigned)((n_act + na - 1) / na);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, (hipStream_t)stream, p);
     return launch_status();
 }
 
-extern "C" {
-
-int64_t lgcn_conv_packed_bytes(int cin, int cout, int ks) {
-    if (cin < 1 || cin > 128 || (cout != 32 && cout != 64 && cout != 128) || (ks != 1 && ks != 3)) return LGCN_EINVAL;
+// bytes of a packed image, fp16 planes or fp32 halves alike: per tap, K chunk and channel block 2 x 64 x 16
+static int64_t conv_packed_bytes(int cin, int cout, int ks) {
+    if (!conv_weight_ok(cin, cout, ks)) return LGCN_EINVAL;
     return (int64_t)ks * (conv_kpad(cin) / 32) * (cout / 16) * 2 * 64 * 16;
 }
 
+extern "C" {
+
+int64_t lgcn_conv_packed_bytes(int cin, int cout, int ks) { return conv_packed_bytes(cin, cout, ks); }
+
 int lgcn_conv_pack_weight(const float *w, int cin, int cout, int ks, void *out, void *stream) {
-    if (lgcn_conv_packed_bytes(cin, cout, ks) < 0) return LGCN_EINVAL;
+    const int64_t nbytes = conv_packed_bytes(cin, cout, ks);
+    if (nbytes < 0) return LGCN_EINVAL;
     LGCN_CHECK_PTR(w); LGCN_CHECK_PTR(out); LGCN_CHECK_ALIGN16(out);
-    const int64_t total = (int64_t)ks * (conv_kpad(cin) / 32) * (cout / 16) * 64;
+    const int64_t total = nbytes / 32;                          // one thread per lane: a uint4 of either plane
     hipLaunchKernelGGL(k_conv_pack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin, ks,
                        reinterpret_cast<uint4 *>(out));
     return launch_status();
@@ -686,15 +399,13 @@ int lgcn_conv1d_gn_train(const float *x, int64_t n_act, int lin, int cin, const 
 
 // Exact-fp32 unit (reference layers.py:40-62 Conv1d, 142-190 Res1d's two halves; lanegcn.py:212-263): lgcn_conv1d_gn's
 // contract on v_mfma_f32_16x16x4_f32.
-int64_t lgcn_conv_packed_f32_bytes(int cin, int cout, int ks) {
-    if (cin < 1 || cin > 128 || (cout != 32 && cout != 64 && cout != 128) || (ks != 1 && ks != 3)) return LGCN_EINVAL;
-    return (int64_t)ks * (conv_kpad(cin) / 32) * (cout / 16) * 2 * 64 * 16;
-}
+int64_t lgcn_conv_packed_f32_bytes(int cin, int cout, int ks) { return conv_packed_bytes(cin, cout, ks); }
 
 int lgcn_conv_pack_weight_f32(const float *w, int cin, int cout, int ks, void *out, void *stream) {
-    if (lgcn_conv_packed_f32_bytes(cin, cout, ks) < 0) return LGCN_EINVAL;
+    const int64_t nbytes = conv_packed_bytes(cin, cout, ks);
+    if (nbytes < 0) return LGCN_EINVAL;
     LGCN_CHECK_PTR(w); LGCN_CHECK_PTR(out); LGCN_CHECK_ALIGN16(out);
-    const int64_t total = (int64_t)ks * (conv_kpad(cin) / 32) * (cout / 16) * 128;
+    const int64_t total = nbytes / 16;                          // one thread per float4
     hipLaunchKernelGGL(k_conv_pack_f32, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, cout, cin,
                        ks, reinterpret_cast<float4 *>(out));
     return launch_status();
@@ -735,15 +446,11 @@ static int res1d_launch(const float *x, int64_t n_act, int lin, int cin, int c, 
         p.g2b = reinterpret_cast<const float *>(second[4]); p.b2b = reinterpret_cast<const float *>(second[5]);
     }
     const int na = kConvRows / lout;
-    const size_t in_planes = (size_t)2 * (na * lin + 1) * (conv_kpad(cin) + 8) * 2, tile = (size_t)kConvRows * (c + 4) * 4;
-    const size_t mid_planes = (size_t)2 * (kConvRows + 1) * (c + 8) * 2;
+    const size_t in_planes = conv_lds_in_planes(na, lin, cin), tile = conv_lds_tile(c), mid_planes = conv_lds_mid_planes(c);
     size_t lds = in_planes > tile ? in_planes : tile;          // one region, reused (see the kernel)
     lds = lds > mid_planes ? lds : mid_planes;
-    if (lds > 159 * 1024) return LGCN_ESHAPE;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_res1d_gn), hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-        if (e != hipSuccess) return (int)e;
-    }
+    const int rc = set_lds(reinterpret_cast<const void *>(k_res1d_gn), lds);
+    if (rc != LGCN_OK) return rc;
     hipLaunchKernelGGL(k_res1d_gn, dim3((unsigned)((n_act + na - 1) / na)), dim3(512), lds, (hipStream_t)stream, p);
     return launch_status();
 }

@@ -13,16 +13,9 @@
 //   k_conv_wgrad       dW[co, ci, t] = sum_{a, l} dy[a, l, co] x[a, l stride + t - pad, ci]: workgroup (chunk, t) walks
 //                      the actor groups chunk, chunk + n_chunks, ... and keeps a [cout, cin] partial in registers.
 //   k_conv_bwd_reduce  the chunk partials and the dgamma / dbeta partials summed in a fixed order.
-#include "lgcn_common.hpp"
 #include "lgcn_conv.hpp"
 
 namespace lgcn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 struct ConvBwdParams {
     const float *g, *y, *out;          // [A, lout, cout]: upstream gradient, pre-norm conv output, forward output (ReLU mask)
@@ -60,22 +53,16 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
     const int ldt = p.cout + 4;
     float *T0 = reinterpret_cast<float *>(smem), *T1 = T0 + (kConvRows + 1) * ldt;
 
-    // ---- the forward's GroupNorm mapping: 512 / na threads per actor, <= 5 float4 each with the same channel quad
-    const int tpa = 512 / na, al = tid / tpa, j = tid - al * tpa;
-    const int c4 = p.cout >> 2, n4 = p.lout * c4;
-    const int64_t a = a0 + al;
+    // ---- the forward's GroupNorm mapping and its statistics of y (the same code: conv_gn_stats)
+    const ConvGnMap m(p.lout, p.cout, tid);
+    const int64_t a = a0 + m.al;
     const bool live = a < p.n_act;
-    const int c = 4 * (j % c4);
-    const float per = (float)(p.lout * p.cout);
-    const int g0 = (al * tpa) >> 5, ng = tpa >> 5;
     float4 yv[5], gv[5];
-    float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const int i = j + k * tpa;
         yv[k] = gv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (live && i < n4) {
-            const int64_t off = (a * p.lout + i / c4) * p.cout + c;
+        if (live && m.has(k)) {
+            const int64_t off = (a * p.lout + m.l(k)) * p.cout + m.c;
             yv[k] = *reinterpret_cast<const float4 *>(p.y + off);
             gv[k] = *reinterpret_cast<const float4 *>(p.g + off);
             if (p.relu) {
@@ -85,33 +72,11 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
             }
             if (p.res_mode == 1 && p.dres) *reinterpret_cast<float4 *>(p.dres + off) = gv[k];
         }
-        s += (yv[k].x + yv[k].y) + (yv[k].z + yv[k].w);
     }
-    // statistics of y as the forward computed them (mean, then the variance about it)
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((tid & 31) == 0) s_red[0][tid >> 5] = s;
-    lds_barrier();
-    float mean = 0.f;
-    for (int k = 0; k < ng; ++k) mean += s_red[0][g0 + k];
-    mean = mean / per;
-    float q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        if (j + k * tpa < n4) {
-            const float d0 = yv[k].x - mean, d1 = yv[k].y - mean, d2 = yv[k].z - mean, d3 = yv[k].w - mean;
-            q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        }
-    }
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o, 64);
-    if ((tid & 31) == 0) s_red[1][tid >> 5] = q;
-    lds_barrier();
-    float var = 0.f;
-    for (int k = 0; k < ng; ++k) var += s_red[1][g0 + k];
-    const float rstd = 1.0f / sqrtf(var / per + p.eps);
+    float mean, rstd;
+    conv_gn_stats(yv, m, s_red, p.eps, mean, rstd);
     // GroupNorm backward: dy = rstd (g gamma - mean(g gamma) - xhat mean(g gamma xhat))
-    const float4 gm = *reinterpret_cast<const float4 *>(p.gamma + c);
+    const float4 gm = *reinterpret_cast<const float4 *>(p.gamma + m.c);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -120,26 +85,24 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
         s1 += (gg.x + gg.y) + (gg.z + gg.w);
         s2 += (gg.x * yv[k].x + gg.y * yv[k].y) + (gg.z * yv[k].z + gg.w * yv[k].w);
     }
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+    s1 = conv_half_sum(s1);
+    s2 = conv_half_sum(s2);
     if ((tid & 31) == 0) { s_red[2][tid >> 5] = s1; s_red[3][tid >> 5] = s2; }
     lds_barrier();
     float m1 = 0.f, m2 = 0.f;
-    for (int k = 0; k < ng; ++k) { m1 += s_red[2][g0 + k]; m2 += s_red[3][g0 + k]; }
-    m1 = m1 / per;
-    m2 = m2 / per;
+    for (int k = 0; k < m.ng; ++k) { m1 += s_red[2][m.g0 + k]; m2 += s_red[3][m.g0 + k]; }
+    m1 = m1 / m.per;
+    m2 = m2 / m.per;
     float4 dv[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const int i = j + k * tpa;
         dv[k] = make_float4(rstd * (gv[k].x * gm.x - m1 - yv[k].x * m2), rstd * (gv[k].y * gm.y - m1 - yv[k].y * m2),
                             rstd * (gv[k].z * gm.z - m1 - yv[k].z * m2), rstd * (gv[k].w * gm.w - m1 - yv[k].w * m2));
-        if (i < n4) {
+        if (m.has(k)) {
             if (!live) dv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            else *reinterpret_cast<float4 *>(p.dy + (a * p.lout + i / c4) * p.cout + c) = dv[k];
-            const int row = al * p.lout + i / c4;
-            *reinterpret_cast<float4 *>(T0 + row * ldt + c) = gv[k];
-            *reinterpret_cast<float4 *>(T1 + row * ldt + c) =
+            else *reinterpret_cast<float4 *>(p.dy + (a * p.lout + m.l(k)) * p.cout + m.c) = dv[k];
+            *reinterpret_cast<float4 *>(T0 + m.row(k) * ldt + m.c) = gv[k];
+            *reinterpret_cast<float4 *>(T1 + m.row(k) * ldt + m.c) =
                 make_float4(gv[k].x * yv[k].x, gv[k].y * yv[k].y, gv[k].z * yv[k].z, gv[k].w * yv[k].w);
         }
     }
@@ -154,7 +117,7 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
     }
     // ---- dres of the x2-upsampled residual: res'[l] = w0(l) r[i0(l)] + w1(l) r[i1(l)]  ->  dr[h] = sum_l g[l] w(l -> h)
     if (p.res_mode == 2 && p.dres) {
-        const int half = p.lout >> 1, per_a = half * c4;
+        const int half = p.lout >> 1, c4 = m.c4, per_a = half * c4;
         for (int e = tid; e < na * per_a; e += 512) {
             const int ah = e / per_a, rem = e - ah * per_a, h = rem / c4, cq = 4 * (rem - (rem / c4) * c4);
             if (a0 + ah >= p.n_act) continue;
@@ -176,11 +139,9 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
     if (p.dx == nullptr) return;                                // block-uniform
     lds_barrier();                                              // T0 / T1 are done with: dy takes T0's place
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int i = j + k * tpa;
-        if (i < n4) *reinterpret_cast<float4 *>(T0 + (al * p.lout + i / c4) * ldt + c) = dv[k];
-    }
-    if (tid < c4) *reinterpret_cast<float4 *>(T0 + kConvRows * ldt + 4 * tid) = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < 5; ++k)
+        if (m.has(k)) *reinterpret_cast<float4 *>(T0 + m.row(k) * ldt + m.c) = dv[k];
+    if (tid < m.c4) *reinterpret_cast<float4 *>(T0 + kConvRows * ldt + 4 * tid) = make_float4(0.f, 0.f, 0.f, 0.f);
     lds_barrier();
 
     // ---- dx[r_in, ci] = sum_t sum_co dy[row(r_in, t), co] W[co, ci, t]: row(r_in, t) = the output row whose tap t reads
@@ -373,15 +334,6 @@ static bool conv_bwd_layout(int64_t n_act, int lin, int cin, int cout, int ks, i
     return true;
 }
 
-static int set_lds(const void *kern, size_t lds) {
-    if (lds > 159 * 1024) return LGCN_ESHAPE;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024);
-        if (e != hipSuccess) return (int)e;
-    }
-    return LGCN_OK;
-}
-
 }  // namespace lgcn
 
 using namespace lgcn;
@@ -389,7 +341,7 @@ using namespace lgcn;
 extern "C" {
 
 int64_t lgcn_conv_packed_t_bytes(int cin, int cout, int ks) {
-    if (cin < 1 || cin > 128 || (cout != 32 && cout != 64 && cout != 128) || (ks != 1 && ks != 3)) return LGCN_EINVAL;
+    if (!conv_weight_ok(cin, cout, ks)) return LGCN_EINVAL;
     return (int64_t)ks * ((cin + 15) & ~15) * cout * 4;
 }
 
@@ -443,7 +395,7 @@ int lgcn_conv1d_gn_bwd(const float *g, const float *x, const float *y, const flo
         q.dy = wsf + L.dy; q.x = x; q.n_act = n_act;
         q.lin = lin; q.cin = cin; q.cout = cout; q.ks = ks; q.stride = stride; q.lout = L.lout;
         q.n_groups = L.n_wg; q.n_chunks = L.n_chunks; q.part = wsf + L.wpart;
-        const size_t lds_w = ((size_t)kConvRows * (cout + 4) + (size_t)(L.na * lin + 1) * (((cin + 15) & ~15) + 4)) * 4;
+        const size_t lds_w = conv_lds_tile(cout) + (size_t)(L.na * lin + 1) * (((cin + 15) & ~15) + 4) * 4;
         rc = set_lds(reinterpret_cast<const void *>(k_conv_wgrad), lds_w);
         if (rc != LGCN_OK) return rc;
         hipLaunchKernelGGL(k_conv_wgrad, dim3((unsigned)L.n_chunks, (unsigned)ks), dim3(512), lds_w, st, q);

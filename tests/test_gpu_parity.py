@@ -773,7 +773,9 @@ def test_actor_net_channels_last_path_equals_stock_path(hip):
 def test_actor_net_hip_conv_path(hip, mma_mode):
     """ActorNet on lgcn_conv1d_gn (conv + GroupNorm + residual / x2-upsampled residual + ReLU in one launch) against the
     CPU fp32 run of the same module and the channels-last stock path, actor counts that are not a multiple of the
-    workgroup's 4 / 8 / 16 actors included; and the single op against torch for every shape ActorNet uses.
+    workgroup's 4 / 8 / 16 actors included; and the single op against torch for every shape ActorNet uses.  Bit for bit:
+    a fused Res1d launch against its composition of single units, and (f16x2 mode, where the HIP path runs) the whole
+    net with fuse_blocks / fuse_groups on against off.
     The HIP convolutions always split their operands into two fp16 planes, so they are the path of the f16x2 mode only:
     in the exact-f32 and bf16x3 modes (and inside the range guard's bf16x3 re-run) ActorNet takes the MIOpen path."""
     M, ops = hip
@@ -803,8 +805,12 @@ def test_actor_net_hip_conv_path(hip, mma_mode):
         assert got.shape == (n, 128)
         assert float((got.cpu() - want).abs().max()) <= 1e-4, n
         assert float((got - other).abs().max()) <= 2e-4, n
-    # whole Res1d blocks in one launch (lgcn_res1d_gn) against the same module on the CPU, and the two HIP paths against each other
+    # whole Res1d blocks in one launch (lgcn_res1d_gn) against the same module on the CPU, and bit for bit against its
+    # composition of single units (one definition of staging, tap GEMM and GroupNorm serves both kernels)
     from lanegcn_amd.layers import Res1d
+
+    def unit(conv, norm, x, **kw):
+        return ops.conv1d_gn(x, conv.weight, conv.stride[0], norm.weight, norm.bias, norm.eps, **kw)
     for cin, c, stride, lin in ((3, 32, 1, 20), (32, 32, 1, 20), (32, 64, 2, 20), (64, 64, 1, 10), (64, 128, 2, 10),
                                 (128, 128, 1, 5), (128, 128, 1, 20), (96, 128, 2, 20)):
         torch.manual_seed(cin + c)
@@ -818,11 +824,15 @@ def test_actor_net_hip_conv_path(hip, mma_mode):
             with torch.no_grad():
                 want = blk(x)
             blk = blk.cuda()
-            got = ops.res1d_gn(x.transpose(1, 2).contiguous().cuda(), blk)
+            xg = x.transpose(1, 2).contiguous().cuda()
+            got = ops.res1d_gn(xg, blk)
+            skip = xg if blk.downsample is None else unit(blk.downsample[0], blk.downsample[1], xg)
+            units = unit(blk.conv2, blk.bn2, unit(blk.conv1, blk.bn1, xg, relu=True), res=skip, relu=True)
             blk = blk.cpu()
             assert got.shape == (A_, want.shape[2], c)
             err = float((got.cpu().transpose(1, 2) - want).abs().max())
             assert err <= 1e-4, (cin, c, stride, lin, A_, err)
+            assert torch.equal(got, units), (cin, c, stride, lin, A_, float((got - units).abs().max()))
     # two blocks of a group in one launch (lgcn_res1d_pair_gn) against the CPU modules
     for cin, c, stride, lin in ((3, 32, 1, 20), (32, 64, 2, 20), (64, 128, 2, 10), (64, 64, 1, 10)):
         torch.manual_seed(7 * cin + c)
@@ -855,6 +865,8 @@ def test_actor_net_hip_conv_path(hip, mma_mode):
         M.ActorNet.fuse_blocks, M.ActorNet.fuse_groups = prev
     net = net.cpu()
     assert float((y1 - y0).abs().max()) <= 1e-4 and float((y2 - y0).abs().max()) <= 1e-4
+    if mma_mode == "f16x2":             # the HIP path (elsewhere the switches select nothing: three MIOpen runs)
+        assert torch.equal(y1, y0) and torch.equal(y2, y0), (float((y1 - y0).abs().max()), float((y2 - y0).abs().max()))
     # the op alone
     gen = torch.Generator().manual_seed(3)
     for cin, cout, ks, stride, lin, mode in ((3, 32, 3, 1, 20, 0), (3, 32, 1, 1, 20, 0), (32, 32, 3, 1, 20, 1), (32, 64, 3, 2, 20, 0),

@@ -261,6 +261,62 @@ int lgcn_pred_reg(const lgcn_pred_reg_t *q, void *stream);
 int lgcn_pred_final(const float *f, const float *wc, const float *bc, const float *reg, const float *rot, const float *orig,
                     int64_t n_act, int n_mod, int n_pred, float *cls, float *out, void *stream);
 
+/*
+ * Training forward of the final launch (reference lanegcn.py:614-625): lgcn_pred_final without rot / orig that also
+ * stores order [A, n_mod] int32, order[a, j] = the mode whose score took rank j (cls[a, j] = s[a, order[a, j]],
+ * out[a, j] = reg[a, order[a, j]]).  Same kernel, one extra store: cls / out are bit-identical to lgcn_pred_final's.
+ * np2 = 2 * num_preds, even, 2..64 (the shape set of lgcn_pred_reg, which serves the training forward unchanged).
+ */
+int lgcn_pred_final_train(const float *f, const float *wc, const float *bc, const float *reg, int64_t n_act, int n_mod,
+                          int np2, float *cls, float *out, int32_t *order, void *stream);
+
+/*
+ * Backward of lgcn_pred_final_train (the sort and gather of lanegcn.py:618-622, the score nn.Linear(128, 1) of :599).
+ * Given g_cls [A, n_mod] and g_out [A, n_mod, np2] (either may be NULL: taken as zeros), the forward's order, f and wc:
+ *   g_s[a, order[a, j]] = g_cls[a, j],   g_reg[a, order[a, j], :] = g_out[a, j, :]        (g_reg [A, n_mod, np2])
+ *   d_f[a n_mod + m, :] = g_s[a, m] wc                                                     (d_f [A n_mod, 128])
+ *   d_wc[c] = sum_rows g_s f[row, c],  d_bc = sum g_s                                      ([128], [1])
+ * Every element of g_reg and d_f is written (no memset needed); g_reg / d_f may be NULL (not computed).  part: workspace
+ * of lgcn_pred_final_bwd_ws_elems(n_act) floats.  Two launches: the per-actor pass with per-workgroup partials of
+ * d_wc / d_bc, and their reduction in a fixed order.  Plain fp32, no floating-point atomics: bitwise repeatable.
+ * g_out, f, wc, g_reg, d_f 8-byte aligned.
+ */
+int64_t lgcn_pred_final_bwd_ws_elems(int64_t n_act);
+int lgcn_pred_final_bwd(const float *g_cls, const float *g_out, const int32_t *order, const float *f, const float *wc,
+                        int64_t n_act, int n_mod, int np2, float *g_reg, float *d_f, float *d_wc, float *d_bc, float *part,
+                        void *stream);
+
+/*
+ * Backward of lgcn_pred_reg (the heads' nn.Linear(128, 2 T) and the centre add of lanegcn.py:601-612, AttDest.dist[0] of
+ * :725-729).  The reference detaches the destination before AttDest (:614), so hd carries gradient to wd / bd only.
+ * Given g_reg [A, n_mod, np2], g_hd [A n_mod, 128] (may be NULL: taken as zeros) and the forward's h, w, hd, reg, ctrs:
+ *   d_h[m][a, :] = sum_o g_reg[a, m, o] w[m][o, :]
+ *   d_w[m][o, :] = sum_a g_reg[a, m, o] h[m][a, :],   d_b[m][o] = sum_a g_reg[a, m, o]
+ *   p = g_hd (hd > 0),  d = ctr[a] - reg[a, m, np2 - 2 : np2]:
+ *   d_wd[c, :] = sum_rows p[row, c] d[row, :],        d_bd[c] = sum_rows p[row, c]
+ * Every output pointer may be NULL: that gradient is not computed (all d_h NULL skips the data gradient, all d_w / d_b
+ * NULL the contraction over actors, d_wd and d_bd NULL the AttDest part).  part: workspace of
+ * lgcn_pred_reg_bwd_ws_elems(n_act, n_mod, np2) floats, 16-byte aligned, as are h, w and d_h.  Two launches: workgroups
+ * of (chunk of actors, mode) that write d_h and one partial record per chunk, and the reduction of the records in chunk
+ * order.  Plain fp32 FMA chains, no floating-point atomics: bitwise repeatable.
+ */
+typedef struct lgcn_pred_reg_bwd {
+    const float *g_reg;
+    const float *g_hd;
+    const float *h[8];
+    const float *w[8];
+    const float *hd, *reg, *ctrs;
+    float *d_h[8];
+    float *d_w[8];
+    float *d_b[8];
+    float *d_wd, *d_bd;
+    float *part;
+    int64_t n_act;
+    int32_t n_mod, np2;
+} lgcn_pred_reg_bwd_t;
+int64_t lgcn_pred_reg_bwd_ws_elems(int64_t n_act, int n_mod, int np2);
+int lgcn_pred_reg_bwd(const lgcn_pred_reg_bwd_t *q, void *stream);
+
 /* ------------------------------------------------------------------ */
 /* Graph construction on the device       */
 /* ------------------------------------------------------------------ */

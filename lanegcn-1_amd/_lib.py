@@ -50,6 +50,16 @@ class PredReg(C.Structure):       # lgcn_pred_reg_t
     ]
 
 
+class PredRegBwd(C.Structure):    # lgcn_pred_reg_bwd_t
+    _fields_ = [
+        ("g_reg", C.c_void_p), ("g_hd", C.c_void_p), ("h", C.c_void_p * 8), ("w", C.c_void_p * 8),
+        ("hd", C.c_void_p), ("reg", C.c_void_p), ("ctrs", C.c_void_p),
+        ("d_h", C.c_void_p * 8), ("d_w", C.c_void_p * 8), ("d_b", C.c_void_p * 8),
+        ("d_wd", C.c_void_p), ("d_bd", C.c_void_p), ("part", C.c_void_p),
+        ("n_act", C.c_int64), ("n_mod", C.c_int32), ("np2", C.c_int32),
+    ]
+
+
 class AggMlp(C.Structure):
     _fields_ = [
         ("n_rows", C.c_int64), ("n_rel", C.c_int32), ("n_rel_csr", C.c_int32),
@@ -129,6 +139,11 @@ SIGNATURES = {
     "lgcn_res1d_pair_gn": (C.c_int, [_P, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P]),
     "lgcn_pred_reg": (C.c_int, [C.POINTER(PredReg), _P]),
     "lgcn_pred_final": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
+    "lgcn_pred_final_train": (C.c_int, [_P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P]),
+    "lgcn_pred_final_bwd_ws_elems": (C.c_int64, [_L]),
+    "lgcn_pred_final_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "lgcn_pred_reg_bwd_ws_elems": (C.c_int64, [_L, _I, _I]),
+    "lgcn_pred_reg_bwd": (C.c_int, [C.POINTER(PredRegBwd), _P]),
     "lgcn_scan_ws_elems": (C.c_int64, [_L]),
     "lgcn_bool_square_bound": (C.c_int, [_P, _P, _L, _P, _P, _P]),
     "lgcn_bool_square": (C.c_int, [_P, _P, _L, _P, _P, _P, _P, _P]),

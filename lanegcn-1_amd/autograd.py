@@ -6,6 +6,8 @@ kernels on transposed plans / transposed weights plus three backward kernels:
                                  gather-by-destination is a gather-by-source on the transposed plan)
   GroupNorm / ReLU backward  -> lgcn_gn_bwd   (deterministic dgamma / dbeta)
   weight gradients           -> lgcn_wgrad    (dW_r = dT^T (G_r src_r), fp32-input MFMA)
+PredNet's tail (the heads' nn.Linear(128, 2 T), AttDest's first layer, the score Linear, the sort and the gather) has
+its own pair: PredRegFn / PredFinalFn on lgcn_pred_reg / lgcn_pred_final_train and their backward entries.
 Only the K = 2 / K = 4 input Linears (nn.Linear(2,128) of the stems, the 4 meta columns) stay on stock
 ATen ops in the training path: they are [N,2]-shaped, not 128-d contractions.
 """
@@ -255,6 +257,66 @@ def conv1d_gn(x, conv, gn, res=None, res_up2=False, relu=False, exact=False):
     """Differentiable ops.conv1d_gn for an nn.Conv1d (no bias, padding (k - 1) / 2) and its nn.GroupNorm(1, C)."""
     mode = 0 if res is None else (2 if res_up2 else 1)
     return Conv1dGNFn.apply(x, conv.weight, gn.weight, gn.bias, res, conv.stride[0], mode, bool(relu), gn.eps, bool(exact))
+
+
+class PredRegFn(Function):
+    """(reg [A, M, T, 2], hd [A M, 128]) = lgcn_pred_reg of (h_0 .. h_{M-1}, W_0 .., b_0 .., ctrs, wd, bd): the M heads'
+    nn.Linear(128, 2 T) + centre and AttDest's first layer on the detached destinations (reference lanegcn.py:601-614,
+    725-729).  Backward = lgcn_pred_reg_bwd.  hd carries gradient to wd / bd only (the reference detaches the destination);
+    ctrs gets none and must not ask for one."""
+
+    @staticmethod
+    def forward(ctx, *tensors):
+        M = (len(tensors) - 3) // 3
+        if M < 1 or len(tensors) != 3 * M + 3:
+            raise L.LgcnError("PredRegFn: expected (h_0 .., W_0 .., b_0 .., ctrs, wd, bd)")
+        if ctx.needs_input_grad[3 * M]:
+            raise L.LgcnError("PredRegFn: no gradient with respect to ctrs")
+        h = [t.contiguous() for t in tensors[:M]]
+        w, b = tensors[M:2 * M], tensors[2 * M:3 * M]
+        ctrs, wd, bd = tensors[3 * M:]
+        reg, hd = ops.pred_reg(h, w, b, ctrs, wd, bd)
+        ctx.n_mod = M
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*h, *w, ctrs, reg, hd)
+        return reg, hd
+
+    @staticmethod
+    def backward(ctx, g_reg, g_hd):
+        M, ni = ctx.n_mod, ctx.needs_input_grad
+        saved = ctx.saved_tensors
+        h, w = saved[:M], saved[M:2 * M]
+        ctrs, reg, hd = saved[2 * M:]
+        if g_reg is None:
+            g_reg = torch.zeros_like(reg)
+        want_w, want_d = any(ni[M:3 * M]), ni[3 * M + 1] or ni[3 * M + 2]
+        d_h, d_w, d_b, d_wd, d_bd = ops.pred_reg_bwd(g_reg, g_hd, h, w, hd, reg, ctrs, want_h=ni[:M], want_w=want_w,
+                                                     want_d=want_d)
+        return (*d_h, *(d_w[m] if ni[M + m] else None for m in range(M)),
+                *(d_b[m] if ni[2 * M + m] else None for m in range(M)), None,
+                d_wd if ni[3 * M + 1] else None, d_bd if ni[3 * M + 2] else None)
+
+
+class PredFinalFn(Function):
+    """(cls [A, M] descending, out [A, M, T, 2] in that order) = lgcn_pred_final_train of (f, wc, bc, reg): the score
+    nn.Linear(128, 1), the sort and the gather of reference lanegcn.py:616-622.  The order is saved, not returned; backward
+    = lgcn_pred_final_bwd."""
+
+    @staticmethod
+    def forward(ctx, f, wc, bc, reg):
+        f, reg = f.contiguous(), reg.contiguous()
+        cls, out, order = ops.pred_final_train(f, wc, bc, reg)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(f, wc, order)
+        ctx.n_pred = reg.shape[2]
+        return cls, out
+
+    @staticmethod
+    def backward(ctx, g_cls, g_out):
+        f, wc, order = ctx.saved_tensors
+        ni = ctx.needs_input_grad
+        g_reg, d_f, d_wc, d_bc = ops.pred_final_bwd(g_cls, g_out, order, f, wc, ctx.n_pred, want_reg=ni[3], want_f=ni[0])
+        return d_f, d_wc.view_as(wc) if ni[1] else None, d_bc if ni[2] else None, g_reg
 
 
 class PairAddFn(Function):

@@ -818,12 +818,31 @@ class PredNet(nn.Module):
         self.cls = nn.Sequential(LinearRes(n, n, norm="GN", ng=1), nn.Linear(n, 1))
 
     impl = "hip"      # "hip": the stock-op tail on lgcn_pred_reg / lgcn_pred_final (inference); "stock": ATen only
+    # training (autograd recording) on the HIP tail too: PredRegFn / PredFinalFn forward and backward instead of the stock
+    # GEMM, sort and index ops.  Opt-in, like ActorNet.train_hip: the default training path stays the stock one.
+    train_hip = False
 
-    def _hip_ok(self, actors: Tensor) -> bool:
+    def _shape_ok(self, actors: Tensor) -> bool:
         cfg = self.config
         return (PredNet.impl == "hip" and actors.is_cuda and actors.dtype == torch.float32 and actors.shape[0] > 0
-                and cfg["n_actor"] == ops.C_FEAT and cfg["num_mods"] <= 8 and 2 * cfg["num_preds"] <= 64
-                and not ops.wants_grad(actors, *ops.module_params(self)))
+                and cfg["n_actor"] == ops.C_FEAT and cfg["num_mods"] <= 8 and 2 * cfg["num_preds"] <= 64)
+
+    def _hip_ok(self, actors: Tensor) -> bool:
+        return self._shape_ok(actors) and not ops.wants_grad(actors, *ops.module_params(self))
+
+    def _train_hip_ok(self, actors: Tensor, actor_ctrs: List[Tensor]) -> bool:
+        return (PredNet.train_hip and self._shape_ok(actors) and ops.wants_grad(actors, *ops.module_params(self))
+                and not any(c.requires_grad for c in actor_ctrs))
+
+    def forward_flat_train(self, actors: Tensor, ctrs: Tensor):
+        """forward_flat (without rot / orig) recorded by autograd, on the same kernels: the heads' LinearRes (LaneConvFn),
+        PredRegFn, AttDest's two row blocks, the score head's LinearRes, PredFinalFn."""
+        actors = actors.contiguous()
+        h = [head[0](actors) for head in self.pred]
+        reg, hd = A.PredRegFn.apply(*h, *[head[1].weight for head in self.pred], *[head[1].bias for head in self.pred],
+                                    ctrs, self.att_dest.dist[0].weight, self.att_dest.dist[0].bias)
+        f = self.cls[0](self.att_dest.from_dist(actors, hd, len(self.pred)))
+        return A.PredFinalFn.apply(f, self.cls[1].weight, self.cls[1].bias, reg)
 
     def forward_flat(self, actors: Tensor, ctrs: Tensor, rot: Optional[Tensor] = None, orig: Optional[Tensor] = None):
         """Inference on the HIP tail: (cls [A, M] descending, reg [A, M, T, 2] in that order) for all actors of the batch;
@@ -845,6 +864,9 @@ class PredNet(nn.Module):
     def forward(self, actors: Tensor, actor_idcs: List[Tensor], actor_ctrs: List[Tensor]) -> Dict[str, List[Tensor]]:
         if self._hip_ok(actors):
             cls, reg = self.forward_flat(actors, torch.cat(actor_ctrs, 0))
+            return {"cls": [cls[i] for i in actor_idcs], "reg": [reg[i] for i in actor_idcs]}
+        if self._train_hip_ok(actors, actor_ctrs):
+            cls, reg = self.forward_flat_train(actors, torch.cat(actor_ctrs, 0))
             return {"cls": [cls[i] for i in actor_idcs], "reg": [reg[i] for i in actor_idcs]}
         reg = torch.stack([head(actors) for head in self.pred], 1)
         reg = reg.view(reg.size(0), reg.size(1), -1, 2)

@@ -587,6 +587,100 @@ def pred_final(f: torch.Tensor, wc: torch.Tensor, bc: torch.Tensor, reg: torch.T
     return cls, out
 
 
+def pred_final_train(f: torch.Tensor, wc: torch.Tensor, bc: torch.Tensor, reg: torch.Tensor):
+    """lgcn_pred_final_train: pred_final without rot / orig that also returns order [A, M] int32 (the mode that took each
+    rank), which pred_final_bwd scatters back through.  cls / out are bit-identical to pred_final's."""
+    lib = L.load()
+    A_, M, npred, _ = reg.shape
+    f, reg = _dev(f, torch.float32, "f"), _dev(reg, torch.float32, "reg")
+    wc, bc = _dev(wc.detach().reshape(-1), torch.float32, "wc"), _dev(bc.detach(), torch.float32, "bc")
+    if tuple(f.shape) != (A_ * M, C_FEAT) or wc.numel() != C_FEAT or bc.numel() != 1:
+        raise L.LgcnError("pred_final_train: score head of the wrong shape")
+    cls = torch.empty((A_, M), dtype=torch.float32, device=reg.device)
+    out = torch.empty_like(reg)
+    order = torch.empty((A_, M), dtype=torch.int32, device=reg.device)
+    L.check(lib.lgcn_pred_final_train(_ptr(f), _ptr(wc), _ptr(bc), _ptr(reg), A_, M, 2 * npred, _ptr(cls), _ptr(out),
+                                      _ptr(order), _stream()), "lgcn_pred_final_train")
+    return cls, out, order
+
+
+def pred_final_bwd(g_cls: Optional[torch.Tensor], g_out: Optional[torch.Tensor], order: torch.Tensor, f: torch.Tensor,
+                   wc: torch.Tensor, n_pred: int, want_reg: bool = True, want_f: bool = True):
+    """lgcn_pred_final_bwd: (g_reg [A, M, T, 2] | None, d_f [A M, 128] | None, d_wc [128], d_bc [1]) from the gradients of
+    pred_final_train's cls [A, M] and out [A, M, T, 2], T = n_pred; either may be None (zeros)."""
+    lib = L.load()
+    order, f = _dev(order, torch.int32, "order"), _dev(f, torch.float32, "f")
+    A_, M = order.shape
+    wc = _dev(wc.detach().reshape(-1), torch.float32, "wc")
+    if f.shape[0] != A_ * M or f.shape[1] != C_FEAT or wc.numel() != C_FEAT:
+        raise L.LgcnError("pred_final_bwd: score head of the wrong shape")
+    if g_cls is not None:
+        g_cls = _dev(g_cls, torch.float32, "g_cls")
+        if tuple(g_cls.shape) != (A_, M):
+            raise L.LgcnError("pred_final_bwd: g_cls of the wrong shape")
+    if g_out is not None:
+        g_out = _dev(g_out, torch.float32, "g_out")
+        if tuple(g_out.shape) != (A_, M, n_pred, 2):
+            raise L.LgcnError("pred_final_bwd: g_out of the wrong shape")
+    dev = f.device
+    g_reg = torch.empty((A_, M, n_pred, 2), dtype=torch.float32, device=dev) if want_reg else None
+    d_f = torch.empty_like(f) if want_f else None
+    d_wc = torch.empty(C_FEAT, dtype=torch.float32, device=dev)
+    d_bc = torch.empty(1, dtype=torch.float32, device=dev)
+    n = lib.lgcn_pred_final_bwd_ws_elems(A_)
+    if n < 0:
+        raise L.LgcnError("pred_final_bwd: unsupported shape")
+    part = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
+    L.check(lib.lgcn_pred_final_bwd(_ptr(g_cls), _ptr(g_out), _ptr(order), _ptr(f), _ptr(wc), A_, M, 2 * n_pred, _ptr(g_reg),
+                                    _ptr(d_f), _ptr(d_wc), _ptr(d_bc), _ptr(part), _stream()), "lgcn_pred_final_bwd")
+    return g_reg, d_f, d_wc, d_bc
+
+
+def pred_reg_bwd(g_reg: torch.Tensor, g_hd: Optional[torch.Tensor], h: Sequence[torch.Tensor], w: Sequence[torch.Tensor],
+                 hd: torch.Tensor, reg: torch.Tensor, ctrs: torch.Tensor, want_h: Sequence[bool], want_w: bool = True,
+                 want_d: bool = True):
+    """lgcn_pred_reg_bwd: (d_h list (None where want_h is False), d_w list, d_b list, d_wd [128, 2], d_bd [128]) from the
+    gradients of pred_reg's reg [A, M, T, 2] and hd [A M, 128] (g_hd may be None: zeros).  want_w False: d_w / d_b are
+    None; want_d False: d_wd / d_bd are None."""
+    lib = L.load()
+    M, A_ = len(h), h[0].shape[0]
+    np2 = w[0].shape[0]
+    g_reg, hd = _dev(g_reg, torch.float32, "g_reg"), _dev(hd, torch.float32, "hd")
+    reg, ctrs = _dev(reg, torch.float32, "reg"), _dev(ctrs, torch.float32, "ctrs")
+    if g_reg.numel() != A_ * M * np2 or reg.numel() != A_ * M * np2 or tuple(hd.shape) != (A_ * M, C_FEAT) \
+            or tuple(ctrs.shape) != (A_, 2):
+        raise L.LgcnError("pred_reg_bwd: gradient / saved tensors of the wrong shape")
+    if g_hd is not None:
+        g_hd = _dev(g_hd, torch.float32, "g_hd")
+        if tuple(g_hd.shape) != (A_ * M, C_FEAT):
+            raise L.LgcnError("pred_reg_bwd: g_hd of the wrong shape")
+    dev = ctrs.device
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    q = L.PredRegBwd()
+    keep, d_h, d_w, d_b = [], [], [], []
+    for m in range(M):
+        hm, wm = _dev(h[m], torch.float32, "h"), _dev(w[m].detach(), torch.float32, "w")
+        if tuple(hm.shape) != (A_, C_FEAT) or tuple(wm.shape) != (np2, C_FEAT):
+            raise L.LgcnError("pred_reg_bwd: head %d has the wrong shape" % m)
+        keep += [hm, wm]
+        d_h.append(new(A_, C_FEAT) if want_h[m] else None)
+        d_w.append(new(np2, C_FEAT) if want_w else None)
+        d_b.append(new(np2) if want_w else None)
+        q.h[m], q.w[m] = hm.data_ptr(), wm.data_ptr()
+        q.d_h[m], q.d_w[m], q.d_b[m] = (None if t is None else t.data_ptr() for t in (d_h[m], d_w[m], d_b[m]))
+    d_wd, d_bd = (new(C_FEAT, 2), new(C_FEAT)) if want_d else (None, None)
+    n = lib.lgcn_pred_reg_bwd_ws_elems(A_, M, np2)
+    if n < 0:
+        raise L.LgcnError("pred_reg_bwd: unsupported shape")
+    part = new(max(n, 4))
+    q.g_reg, q.hd, q.reg, q.ctrs, q.part = (t.data_ptr() for t in (g_reg, hd, reg, ctrs, part))
+    q.g_hd = None if g_hd is None else g_hd.data_ptr()
+    q.d_wd, q.d_bd = (None, None) if not want_d else (d_wd.data_ptr(), d_bd.data_ptr())
+    q.n_act, q.n_mod, q.np2 = A_, M, np2
+    L.check(lib.lgcn_pred_reg_bwd(C.byref(q), _stream()), "lgcn_pred_reg_bwd")
+    return d_h, d_w, d_b, d_wd, d_bd
+
+
 # ------------------------------------------------------------------ graph construction (row f3)
 def dilated_nbrs(u: torch.Tensor, v: torch.Tensor, num_nodes: int, num_scales: int):
     """Scales 1 .. num_scales - 1 of a relation on the device (reference data.dilated_nbrs, data.py:520-534): the

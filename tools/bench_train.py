@@ -26,14 +26,27 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--actor-impl", default=None, choices=["hip", "miopen", "ab"],
                     help="ActorNet.impl for the step; 'ab': both, alternating step by step after a warm-up of each")
+    ap.add_argument("--pred-impl", default=None, choices=["hip", "stock", "ab"],
+                    help="PredNet's training tail: 'hip' sets PredNet.train_hip, 'stock' leaves the ATen tail; 'ab': both, "
+                         "alternating step by step after a warm-up of each")
     ap.add_argument("--actor-exact", action="store_true",
                     help="ActorNet.exact: the 'hip' ActorNet on the exact-fp32 units (any --mma)")
     args = ap.parse_args()
     M.ActorNet.exact = args.actor_exact
     if args.mma:
         ops.set_mma(args.mma)
-    impls = ["hip", "miopen"] if args.actor_impl == "ab" else [args.actor_impl or M.ActorNet.impl]
-    M.ActorNet.impl = impls[0]
+    if args.actor_impl == "ab" and args.pred_impl == "ab":
+        ap.error("one of --actor-impl / --pred-impl can alternate at a time")
+    actor_impls = ["hip", "miopen"] if args.actor_impl == "ab" else [args.actor_impl or M.ActorNet.impl]
+    pred_impls = ["hip", "stock"] if args.pred_impl == "ab" else [args.pred_impl or "stock"]
+    # a variant of the step: (ActorNet.impl, PredNet's training tail); its name is the side that alternates
+    impls = [(a, p) for a in actor_impls for p in pred_impls]
+    name = lambda v: v[1] if args.pred_impl == "ab" else v[0]
+
+    def select(v):
+        M.ActorNet.impl, M.PredNet.train_hip = v[0], v[1] == "hip"
+
+    select(impls[0])
     if args.actor_impl:
         M.ActorNet.train_hip = True          # "hip": ActorNet's training units on Conv1dGNFn; "miopen": the stock path
     torch.manual_seed(0)
@@ -63,27 +76,28 @@ def main():
 
     losses = []
     for impl in impls:
-        M.ActorNet.impl = impl
+        select(impl)
         losses += [step(i) for i in range(args.warmup)]
     torch.cuda.synchronize()
     # per-step times (synchronised), the implementations interleaved step by step
-    per_step = {impl: [] for impl in impls}
+    per_step = {name(impl): [] for impl in impls}
     t0 = time.perf_counter()
     for i in range(args.steps):
         for impl in impls:
-            M.ActorNet.impl = impl
+            select(impl)
             t1 = time.perf_counter()
             losses.append(step(args.warmup + i))
             torch.cuda.synchronize()
-            per_step[impl].append((time.perf_counter() - t1) * 1e3)
+            per_step[name(impl)].append((time.perf_counter() - t1) * 1e3)
     ms = (time.perf_counter() - t0) / (args.steps * len(impls)) * 1e3
-    M.ActorNet.impl = impls[0]
+    select(impls[0])
     for i in range(5):
         step(args.warmup + args.steps + i, timed=True)
     res = {"metric": "training step (forward + loss + backward + Adam), batch 32, S2", "mma": ops.get_mma(),
            "ms_per_step": ms, "scenes_per_s": 32e3 / ms, "loss_first": losses[0], "loss_last": losses[-1],
            "stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
-           "actor_impl": impls[0] if len(impls) == 1 else "ab", "actor_exact": M.ActorNet.exact,
+           "actor_impl": actor_impls[0] if len(actor_impls) == 1 else "ab", "actor_exact": M.ActorNet.exact,
+           "pred_impl": pred_impls[0] if len(pred_impls) == 1 else "ab",
            "median_step_ms": {k: float(np.median(v)) for k, v in per_step.items()}}
     print(json.dumps(res), flush=True)
 

@@ -617,6 +617,61 @@ int lgcn_att_pairs_wi(const float *agt_ctrs, const float *ctx_ctrs,
                       float eps, int mma, int seg, float *m, void *stream);
 
 /*
+ * Training of the pair stage of Att (reference lanegcn.py:691-703), exact fp32 whatever the matrix mode of the rest
+ * of the network.  Per pair p < *n_pairs (clamped to cap), h = hi[p], w = wi[p]:
+ *   d  = agt_ctrs[h] - ctx_ctrs[w]
+ *   z0 = W_d0 d + b_d0;                    h1 = ReLU(z0)         mask0 = z0 > 0
+ *   t1 = W_d2 h1;                          e  = ReLU(GN_d(t1))   mask1 = e  > 0
+ *   c  = W_c0[:, 0:128] e + U[h] + V[w];   m  = ReLU(GN_c(c))    mask2 = m  > 0
+ * and S[t] = sum of m_p over the pairs of target t (lgcn_gather_sum over the pair search's rowptr).
+ *
+ * lgcn_att_pairs_train: lgcn_att_pairs (LGCN_MMA_F32 images wpd2, wpc0e) with one more output, the three masks as bits;
+ * m is bit for bit what lgcn_att_pairs writes.
+ *   masks: [cap, 3, 4] uint32, rows < *n_pairs written: masks[p][k][j] bit b = mask k of channel 32 j + b.
+ *
+ * lgcn_att_pairs_bwd, for dS [T,128] (one main launch + one fixed-order reduction launch; no atomics, no host read):
+ *   g2 = dS[h] * mask2;  dgamma_c += g2 * chat;  dbeta_c += g2;  dc = GN_c backward of g2 (formula of lgcn_gn_bwd)
+ *   dW_c0[:, 0:128] += dc (x) e;  de = dc W_c0[:, 0:128]
+ *   g1 = de * mask1;  dgamma_d += g1 * t1hat;  dbeta_d += g1;  dt1 = GN_d backward of g1
+ *   dW_d2 += dt1 (x) h1;  dh1 = dt1 W_d2;  dz0 = dh1 * mask0;  dW_d0 += dz0 (x) d;  db_d0 += dz0
+ * h1, t1, e, c and the GroupNorm statistics are recomputed per 32-pair tile with the forward's device functions; the
+ * masks are read, not re-derived.  dU[h] += dc and dV[w] += dc are lgcn_gather_sum launches over dc (by the pair
+ * search's rowptr, and by a CSR of the pairs by context row).
+ *   wptd2, wptc0e: lgcn_pack_weight_t images (LGCN_MMA_F32) of W_d2 and of W_c0[:, 0:128]
+ *   dc:     [cap,128], rows < *n_pairs written -- the only per-pair tensor that reaches memory; may be NULL
+ *   d_*:    gradient outputs, each may be NULL and its work is then skipped: d_wd2, d_wc0e [128,128] (d_wc0e is the
+ *           dense [128,128] block of columns 0:128), d_wd0 [128,2], d_bd0, d_gd, d_btd, d_gc, d_btc [128]
+ *   n_chunks: 1..1024 workgroups (never more than ceil(cap / 32) are launched): workgroup k owns the tiles k,
+ *           k + n_chunks, ... and writes one record of 2 * 128 * 128 + 7 * 128 floats -- dW_d2, dW_c0e, dgamma_c,
+ *           dbeta_c, dgamma_d, dbeta_d, db_d0, dW_d0[:,0], dW_d0[:,1]; the second launch sums the records in chunk order.
+ *   ws:     lgcn_att_pairs_bwd_ws_elems(cap, n_chunks) floats (negative: LGCN_EINVAL for cap < 0, cap too large or
+ *           n_chunks outside 1..1024); needed when any d_* is given.
+ */
+typedef struct {
+    const float *agt_ctrs, *ctx_ctrs;
+    const int32_t *hi, *wi, *n_pairs;
+    int64_t cap;
+    const float *wd0, *bd0, *wpd2, *gd, *btd, *wpc0e, *U, *V, *gc, *btc;
+    const float *wptd2, *wptc0e;
+    const uint32_t *masks;
+    const float *dS;
+    float *dc, *d_wd2, *d_wc0e, *d_wd0, *d_bd0, *d_gd, *d_btd, *d_gc, *d_btc, *ws;
+    float eps;
+    int32_t n_chunks;
+} lgcn_att_pairs_bwd_t;
+
+int lgcn_att_pairs_train(const float *agt_ctrs, const float *ctx_ctrs,
+                         const int32_t *hi, const int32_t *wi,
+                         const int32_t *n_pairs, int64_t cap,
+                         const float *wd0, const float *bd0, const float *wpd2,
+                         const float *gd, const float *btd,
+                         const float *wpc0e, const float *U, const float *V,
+                         const float *gc, const float *btc,
+                         float eps, float *m, uint32_t *masks, void *stream);
+int64_t lgcn_att_pairs_bwd_ws_elems(int64_t cap, int n_chunks);
+int lgcn_att_pairs_bwd(const lgcn_att_pairs_bwd_t *p_host, void *stream);
+
+/*
  * PredLoss (reference lanegcn.py:740-807), forward and backward, one launch each.
  *   cls [A, M], reg [A, M, T, 2], gt [A, T, 2] fp32; has [A, T] bytes (torch.bool); M <= 8, T <= 64.
  * Per actor: last = argmax_t(has[t] + 0.1 t / T), kept iff that maximum > 1.0; dist_j = |reg[j, last] - gt[last]|;

@@ -60,6 +60,19 @@ class PredRegBwd(C.Structure):    # lgcn_pred_reg_bwd_t
     ]
 
 
+class AttPairsBwd(C.Structure):   # lgcn_att_pairs_bwd_t
+    _fields_ = [
+        ("agt_ctrs", C.c_void_p), ("ctx_ctrs", C.c_void_p), ("hi", C.c_void_p), ("wi", C.c_void_p), ("n_pairs", C.c_void_p),
+        ("cap", C.c_int64),
+        ("wd0", C.c_void_p), ("bd0", C.c_void_p), ("wpd2", C.c_void_p), ("gd", C.c_void_p), ("btd", C.c_void_p),
+        ("wpc0e", C.c_void_p), ("U", C.c_void_p), ("V", C.c_void_p), ("gc", C.c_void_p), ("btc", C.c_void_p),
+        ("wptd2", C.c_void_p), ("wptc0e", C.c_void_p), ("masks", C.c_void_p), ("dS", C.c_void_p),
+        ("dc", C.c_void_p), ("d_wd2", C.c_void_p), ("d_wc0e", C.c_void_p), ("d_wd0", C.c_void_p), ("d_bd0", C.c_void_p),
+        ("d_gd", C.c_void_p), ("d_btd", C.c_void_p), ("d_gc", C.c_void_p), ("d_btc", C.c_void_p), ("ws", C.c_void_p),
+        ("eps", C.c_float), ("n_chunks", C.c_int32),
+    ]
+
+
 class AggMlp(C.Structure):
     _fields_ = [
         ("n_rows", C.c_int64), ("n_rel", C.c_int32), ("n_rel_csr", C.c_int32),
@@ -127,6 +140,9 @@ SIGNATURES = {
     "lgcn_check_finite": (C.c_int, [_P, _L, _P, _L, _P, _I, _P]),
     "lgcn_mapnet_input": (C.c_int, [_P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
+    "lgcn_att_pairs_train": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _P, _P, _P]),
+    "lgcn_att_pairs_bwd_ws_elems": (C.c_int64, [_L, _I]),
+    "lgcn_att_pairs_bwd": (C.c_int, [C.POINTER(AttPairsBwd), _P]),
     "lgcn_conv_packed_bytes": (C.c_int64, [_I, _I, _I]),
     "lgcn_conv_pack_weight": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "lgcn_conv1d_gn": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P]),

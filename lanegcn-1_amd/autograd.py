@@ -6,6 +6,7 @@ kernels on transposed plans / transposed weights plus three backward kernels:
                                  gather-by-destination is a gather-by-source on the transposed plan)
   GroupNorm / ReLU backward  -> lgcn_gn_bwd   (deterministic dgamma / dbeta)
   weight gradients           -> lgcn_wgrad    (dW_r = dT^T (G_r src_r), fp32-input MFMA)
+Att's pair stage has a fused pair of its own (Att.train_hip): AttPairsFn on lgcn_att_pairs_train / lgcn_att_pairs_bwd.
 PredNet's tail (the heads' nn.Linear(128, 2 T), AttDest's first layer, the score Linear, the sort and the gather) has
 its own pair: PredRegFn / PredFinalFn on lgcn_pred_reg / lgcn_pred_final_train and their backward entries.
 Only the K = 2 / K = 4 input Linears (nn.Linear(2,128) of the stems, the 4 meta columns) stay on stock
@@ -339,6 +340,47 @@ class PairAddFn(Function):
             rp, col = ps.csr_by_wi(ctx.n_v)
             dV = ops.gather_sum(g, rp, col, ctx.n_v)
         return g, dU, dV, None
+
+
+class AttPairsFn(Function):
+    """S [T,128] = per-target sum of the pair MLP of Att (reference lanegcn.py:691-703; formulas: include/lgcn.h,
+    lgcn_att_pairs_train) of (pairs, dist.0 weight / bias, dist.2 weight, dist.2 norm weight / bias, ctx.0 weight
+    [128,384], U, V, ctx.0 norm weight / bias).  Exact fp32 in every matrix mode.  Forward = lgcn_att_pairs_train + the
+    segment sum; only the inputs and the ReLU masks (48 B per pair) are saved -- m is not.  Backward =
+    lgcn_att_pairs_bwd, then dU / dV as segment sums of dc.  The gradient of ctx.0's weight fills columns 0:128 of a zero
+    [128,384]; the U / V row blocks add their own column blocks.  The centres of `pairs` get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pairs, wd0, bd0, w_d2, gd_w, gd_b, w_c0, U, V, gc_w, gc_b, eps: float = ops.EPS):
+        U, V = U.contiguous(), V.contiguous()
+        m, masks = ops.att_pairs_train(pairs, wd0, bd0, w_d2, (gd_w, gd_b), w_c0, U, V, (gc_w, gc_b), eps=eps)
+        ctx.pairs, ctx.eps = pairs, eps
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(wd0, bd0, w_d2, gd_w, gd_b, w_c0, U, V, gc_w, gc_b, masks)
+        return ops.gather_sum(m, pairs.rowptr, None, U.shape[0])
+
+    @staticmethod
+    def backward(ctx, dS):
+        if dS is None:
+            return (None,) * 12
+        wd0, bd0, w_d2, gd_w, gd_b, w_c0, U, V, gc_w, gc_b, masks = ctx.saved_tensors
+        ps, ni = ctx.pairs, ctx.needs_input_grad
+        names = {1: "d_wd0", 2: "d_bd0", 3: "d_wd2", 4: "d_gd", 5: "d_btd", 6: "d_wc0e", 9: "d_gc", 10: "d_btc"}
+        want = [n for i, n in names.items() if ni[i]]
+        g = ops.att_pairs_bwd(ps, dS.contiguous(), masks, wd0, bd0, w_d2, (gd_w, gd_b), w_c0, U, V, (gc_w, gc_b), want=want,
+                              want_dc=ni[7] or ni[8], eps=ctx.eps)
+        out = [None] * 12
+        for i, n in names.items():
+            out[i] = g.get(n)
+        if ni[6]:
+            out[6] = torch.zeros_like(w_c0)
+            out[6][:, :C_FEAT] = g["d_wc0e"]
+        if ni[7]:
+            out[7] = ops.gather_sum(g["dc"], ps.rowptr, None, U.shape[0])          # sorted by hi
+        if ni[8]:
+            rp, col = ps.csr_by_wi(V.shape[0])
+            out[8] = ops.gather_sum(g["dc"], rp, col, V.shape[0])
+        return tuple(out)
 
 
 class GatherSumFn(Function):

@@ -299,7 +299,47 @@ __global__ __launch_bounds__(256) void k_mapnet_input(const InputParams p, int n
 }
 
 // ---------------------------------------------------------- att pairs -----
-__global__ __launch_bounds__(256) void k_att_pairs(const PairParams p) {
+// ReLU masks of a pair row as bits (the training forward saves them instead of any [P,128] tensor): word j of a row's four
+// holds channels 32 j .. 32 j + 31, bit b = channel 32 j + b is set where the value is > 0.  A thread owns bits
+// 4 sub .. 4 sub + 3 of every word; the 8 threads of a row OR theirs together (the butterfly of sum8).
+template <int CTRL>
+__device__ __forceinline__ uint32_t dpp_mov_u(uint32_t x) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
+
+__device__ __forceinline__ uint4 row_mask_words(const RowVals &r, int t) {
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t b = (r.v[j].x > 0.f ? 1u : 0u) | (r.v[j].y > 0.f ? 2u : 0u) | (r.v[j].z > 0.f ? 4u : 0u) |
+                     (r.v[j].w > 0.f ? 8u : 0u);
+        b <<= 4 * (t & 7);
+        b |= dpp_mov_u<0xB1>(b);
+        b |= dpp_mov_u<0x4E>(b);
+        b |= dpp_mov_u<0x141>(b);
+        w[j] = b;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// g = 0 where the thread's bit of the row's mask words is clear
+__device__ __forceinline__ float4 mask4(float4 g, uint32_t b) {
+    return make_float4((b & 1u) ? g.x : 0.f, (b & 2u) ? g.y : 0.f, (b & 4u) ? g.z : 0.f, (b & 8u) ? g.w : 0.f);
+}
+
+// mw = the row's four words of one mask, or nullptr for a row past the count (no gradient)
+__device__ __forceinline__ void row_apply_mask(RowVals &g, const uint4 *__restrict__ mw, int t) {
+    uint32_t w0 = 0u, w1 = 0u, w2 = 0u, w3 = 0u;
+    if (mw != nullptr) { const uint4 m = *mw; w0 = m.x; w1 = m.y; w2 = m.z; w3 = m.w; }
+    const int sh = 4 * (t & 7);
+    g.v[0] = mask4(g.v[0], w0 >> sh); g.v[1] = mask4(g.v[1], w1 >> sh);
+    g.v[2] = mask4(g.v[2], w2 >> sh); g.v[3] = mask4(g.v[3], w3 >> sh);
+}
+
+// MASKS: the training forward (lgcn_att_pairs_train).  masks[p][k] = the four words of mask k of pair p, k = 0: W_d0 d +
+// b_d0 > 0, 1: e > 0, 2: m > 0; the arithmetic of m is the inference kernel's.
+template <bool MASKS>
+__global__ __launch_bounds__(256) void k_att_pairs(const PairParams p, uint4 *__restrict__ masks) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTileFloats];
     float *T1 = smem, *T2 = smem + kTileFloats;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -320,6 +360,10 @@ __global__ __launch_bounds__(256) void k_att_pairs(const PairParams p) {
             dx = a.x - c.x; dy = a.y - c.y;
         }
         lin2_relu_to_lds(T1, tid, dx, dy, p.wd0, p.bd0);
+        if constexpr (MASKS) {      // ReLU(z) > 0 <=> z > 0; the thread reads back its own elements
+            const uint4 mw = row_mask_words(row_load(T1, tid), tid);
+            if (live && (tid & 7) == 0) masks[pr * 3] = mw;
+        }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -331,6 +375,10 @@ __global__ __launch_bounds__(256) void k_att_pairs(const PairParams p) {
             row_gn(r, tid, p.gd, p.btd, p.eps);
             row_relu(r);
             row_store_lds(T2, tid, r);
+            if constexpr (MASKS) {
+                const uint4 mw = row_mask_words(r, tid);
+                if (live && (tid & 7) == 0) masks[pr * 3 + 1] = mw;
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -347,6 +395,10 @@ __global__ __launch_bounds__(256) void k_att_pairs(const PairParams p) {
             row_gn(r, tid, p.gc, p.btc, p.eps);
             row_relu(r);
             if (live) row_store_global(p.m + pr * kC, tid, r);
+            if constexpr (MASKS) {
+                const uint4 mw = row_mask_words(r, tid);
+                if (live && (tid & 7) == 0) masks[pr * 3 + 2] = mw;
+            }
         }
         // next iteration's first write to T1 is by the same thread that just
         // read those elements; T2 is rewritten only after the next barrier.
@@ -355,6 +407,35 @@ __global__ __launch_bounds__(256) void k_att_pairs(const PairParams p) {
 
 
 // ------------------------------------------------------------- wgrad ------
+// One 32-row tile of dW += D^T S for the 64 x 64 block (q >> 1, q & 1) of the 128 x 128 result: D (the dT rows) and S (the
+// source rows) are LDS tiles, the contraction runs over their rows, two per MFMA; a?? = the block's four 32 x 32 quadrants.
+__device__ __forceinline__ void wgrad_tile(const float *__restrict__ D, const float *__restrict__ S, f32x16 &a00, f32x16 &a01,
+                                           f32x16 &a10, f32x16 &a11, int q, int lane) {
+    const float *Dp = D + (lane >> 5) * kLDA + 64 * (q >> 1) + (lane & 31);
+    const float *Sp = S + (lane >> 5) * kLDA + 64 * (q & 1) + (lane & 31);
+#pragma unroll 4
+    for (int s = 0; s < 16; ++s) {
+        const float a0 = Dp[2 * s * kLDA], a1 = Dp[2 * s * kLDA + 32];
+        const float b0 = Sp[2 * s * kLDA], b1 = Sp[2 * s * kLDA + 32];
+        a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, a00, 0, 0, 0);
+        a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, a01, 0, 0, 0);
+        a10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, a10, 0, 0, 0);
+        a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, a11, 0, 0, 0);
+    }
+}
+
+// The block's four quadrants to a row-major [128,128] image
+__device__ __forceinline__ void wgrad_store(float *__restrict__ o, const f32x16 &a00, const f32x16 &a01, const f32x16 &a10,
+                                            const f32x16 &a11, int q, int lane) {
+    float *p = o + (64 * (q >> 1)) * kC + 64 * (q & 1) + (lane & 31);
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+        const int r = acc_row(g, lane);
+        p[r * kC] = a00[g]; p[r * kC + 32] = a01[g];
+        p[(32 + r) * kC] = a10[g]; p[(32 + r) * kC + 32] = a11[g];
+    }
+}
+
 // dW[r] = dT^T (G_r src_r): block (chunk, r) walks the 32-row tiles chunk, chunk + n_chunks, ... that
 // relation r touches; waves 4-7 stage the gathered source rows and the dT rows of the next tile in LDS
 // while waves 0-3 contract the current one over its rows on v_mfma_f32_32x32x2_f32 (K-step = 2 rows;
@@ -398,21 +479,10 @@ __global__ __launch_bounds__(512) void k_wgrad(const lgcn_agg_mlp_t p, const flo
     if (wave >= 4 && t < n_tiles) fill(0, t);
     __syncthreads();
     int b = 0;
-    const int wj = wave >> 1, wk = wave & 1, i = lane & 31, kk = lane >> 5;
     while (t < n_tiles) {
         const int64_t tn = next_active(t + n_chunks);
         if (wave < 4) {
-            const float *D = bufD(b) + kk * kLDA + 64 * wj + i;
-            const float *A = bufA(b) + kk * kLDA + 64 * wk + i;
-#pragma unroll 4
-            for (int s = 0; s < 16; ++s) {
-                const float a0 = D[2 * s * kLDA], a1 = D[2 * s * kLDA + 32];
-                const float b0 = A[2 * s * kLDA], b1 = A[2 * s * kLDA + 32];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
+            wgrad_tile(bufD(b), bufA(b), acc[0][0], acc[0][1], acc[1][0], acc[1][1], wave, lane);
         } else if (tn < n_tiles) {
             fill(b ^ 1, tn);
         }
@@ -420,16 +490,8 @@ __global__ __launch_bounds__(512) void k_wgrad(const lgcn_agg_mlp_t p, const flo
         t = tn;
         b ^= 1;
     }
-    if (wave < 4) {
-        float *o = part + ((int64_t)r * n_chunks + chunk) * (kC * kC);
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb)
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int g = 0; g < 16; ++g)
-                    o[(64 * wj + 32 * jb + acc_row(g, lane)) * kC + 64 * wk + 32 * kb + i] = acc[jb][kb][g];
-    }
+    if (wave < 4)
+        wgrad_store(part + ((int64_t)r * n_chunks + chunk) * (kC * kC), acc[0][0], acc[0][1], acc[1][0], acc[1][1], wave, lane);
 }
 
 __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ part, int n_chunks, float *__restrict__ dW) {
@@ -439,6 +501,216 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float *__restrict__ 
     float s = 0.f;
     for (int c = 0; c < n_chunks; ++c) s += p[(int64_t)c * (kC * kC)];
     dW[(int64_t)r * (kC * kC) + e] = s;
+}
+
+// ------------------------------------------------------ att pairs bwd -----
+// Backward of the pair stage for dS [T,128] (include/lgcn.h, lgcn_att_pairs_bwd).  Workgroup `chunk` walks the 32-pair
+// tiles chunk, chunk + n_chunks, ...  Per tile, waves 0-3 recompute h1, t1, e, c and the GroupNorm statistics with the
+// forward's device functions (their 256 threads are the row phase, their 4 waves the 32 x 128 x 128 tile GEMMs), apply the
+// stored masks, run both GroupNorm backwards in registers and the two dx GEMMs on the transposed images.  Waves 4-7 own
+// everything that is summed over pairs, in registers across the workgroup's tiles: the two 128 x 128 weight gradients
+// (wave 4 + q: block q of both, A[0..7]) contracted over the tile's rows, and the seven [128] vectors as column sums of
+// tiles the row phase leaves in LDS (thread (which, c) of the 2 x 128: one column of one tile), all while waves 0-3 run
+// the next GEMM.  That split instead of "waves 0-3 dW_d2, waves 4-7 dW_c0e": waves 0-3 already issue four tile GEMMs
+// (256 MFMAs) per tile against 128 MFMAs for both weight gradients, and 64 more accumulator registers beside the row
+// phase's working set did not fit without scratch.
+// LDS: H (h1), E (e), X (GEMM output), G (dc, then dt1, then dz0 * dy), XD (xhat of GN_d), P1 / P2 (g * xhat / g of a
+// GroupNorm backward, then dz0 / dz0 * dx): 7 x 16.5 KiB.
+constexpr int kPairRecTail = 7 * kC;
+constexpr int kPairRec = 2 * kC * kC + kPairRecTail;      // floats per chunk record
+
+__device__ __forceinline__ RowVals row_mul(const RowVals &a, const RowVals &b) {
+    RowVals r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.v[j] = make_float4(a.v[j].x * b.v[j].x, a.v[j].y * b.v[j].y, a.v[j].z * b.v[j].z, a.v[j].w * b.v[j].w);
+    return r;
+}
+
+__device__ __forceinline__ RowVals row_scale(const RowVals &a, float s) {
+    RowVals r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.v[j] = make_float4(a.v[j].x * s, a.v[j].y * s, a.v[j].z * s, a.v[j].w * s);
+    return r;
+}
+
+// sum over the 32 rows of column c of a tile, in row order
+__device__ __forceinline__ float tile_colsum(const float *T, int c) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) s += T[r * kLDA + c];
+    return s;
+}
+
+__global__ __launch_bounds__(512) void k_att_pairs_bwd(const PairBwdParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[7 * kTileFloats];
+    float *H = smem, *E = smem + kTileFloats, *X = smem + 2 * kTileFloats, *G = smem + 3 * kTileFloats;
+    float *XD = smem + 4 * kTileFloats, *P1 = smem + 5 * kTileFloats, *P2 = smem + 6 * kTileFloats;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool rowt = tid < 256;
+    const int which = (tid >> 7) & 1, col = tid & 127;       // waves 4-7: column sums
+    const PairParams &f = p.f;
+    int64_t P = *f.n_pairs;
+    if (P < 0 || P > f.cap) P = f.cap;
+    const int64_t n_tiles = (P + kTM32 - 1) / kTM32;
+    const bool want_rec = p.rec != nullptr, want_d = p.want_d != 0, want_wc = p.want_wc != 0;
+
+    f32x16 A[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) A[k][i] = 0.f;
+    float s_c = 0.f, s_d = 0.f, s_0a = 0.f, s_0b = 0.f;      // which = 0: dgamma_c, dgamma_d, db_d0, dW_d0[:,0]; 1: dbeta_c, dbeta_d, dW_d0[:,1]
+    bool pend = false;           // those three tiles are waiting
+    f32x16 acc;
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t pr = tile * kTM32 + (tid >> 3);
+        const bool live = rowt && pr < P;
+        const uint4 *mk = live ? p.masks + pr * 3 : nullptr;              // rows past the count: no gradient
+        int h = 0, w = 0;
+        float dx = 0.f, dy = 0.f;
+        if (live) {
+            h = f.hi[pr]; w = f.wi[pr];
+            const float2 a = reinterpret_cast<const float2 *>(f.agt_ctrs)[h];
+            const float2 c = reinterpret_cast<const float2 *>(f.ctx_ctrs)[w];
+            dx = a.x - c.x; dy = a.y - c.y;
+        }
+        // ---- forward again: h1 -> H, t1 -> X, e -> E, c -> X
+        if (rowt) lin2_relu_to_lds(H, tid, dx, dy, f.wd0, f.bd0);
+        __syncthreads();
+        if (wave < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            tile_gemm(H, reinterpret_cast<const float4 *>(f.wpd2) + wave * (16 * 64), acc, lane, 16);
+            acc_to_lds(X, acc, lane, wave);
+        } else if (pend) {      // what the last row phase of the tile before left: P1 = dz0, P2 = dz0 * dx, G = dz0 * dy
+            s_0a += tile_colsum(which ? G : P1, col);     // (they are next written three barriers from here)
+            if (which == 0) s_0b += tile_colsum(P2, col);
+        }
+        pend = false;
+        __syncthreads();
+        float rstd_d = 0.f;
+        if (rowt) {
+            RowVals xd = row_load(X, tid);
+            rstd_d = row_gn_hat(xd, f.eps);
+            row_store_lds(XD, tid, xd);     // read back by this thread alone
+            RowVals e = row_affine(xd, tid, f.gd, f.btd);
+            row_relu(e);
+            row_store_lds(E, tid, e);
+        }
+        __syncthreads();
+        if (wave < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            tile_gemm(E, reinterpret_cast<const float4 *>(f.wpc0e) + wave * (16 * 64), acc, lane, 16);
+            acc_to_lds(X, acc, lane, wave);
+        }
+        __syncthreads();
+        // ---- m = ReLU(GN_c(c)): g2 = dS[h] * mask2 (P1 = g2 * chat, P2 = g2), dc -> G and global
+        if (rowt) {
+            RowVals c = row_load(X, tid);
+            RowVals g;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g.v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live) {
+                row_add_global(c, f.U + (int64_t)h * kC, tid);
+                row_add_global(c, f.V + (int64_t)w * kC, tid);
+                row_add_global(g, p.dS + (int64_t)h * kC, tid);
+            }
+            const float rstd_c = row_gn_hat(c, f.eps);
+            row_apply_mask(g, mk ? mk + 2 : mk, tid);
+            if (want_rec) { row_store_lds(P1, tid, row_mul(g, c)); row_store_lds(P2, tid, g); }
+            row_gn_bwd(g, c, rstd_c, tid, f.gc);
+            row_store_lds(G, tid, g);
+            if (live && p.dc) row_store_global(p.dc + pr * kC, tid, g);
+        }
+        if (!want_rec) continue;                // uniform; X is next written two barriers from here
+        __syncthreads();
+        // ---- c = W_c0e e + ..: de = dc W_c0e -> X (waves 0-3); dW_c0e += dc^T e, dgamma_c, dbeta_c (waves 4-7)
+        if (wave < 4) {
+            if (want_d) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                tile_gemm(G, reinterpret_cast<const float4 *>(p.wptc0e) + wave * (16 * 64), acc, lane, 16);
+                acc_to_lds(X, acc, lane, wave);
+            }
+        } else {
+            if (want_wc) wgrad_tile(G, E, A[4], A[5], A[6], A[7], wave - 4, lane);
+            s_c += tile_colsum(which ? P2 : P1, col);
+        }
+        if (!want_d) continue;                  // uniform; E, G, P1 and P2 are next written at least two barriers from here
+        __syncthreads();
+        // ---- e = ReLU(GN_d(t1)): g1 = de * mask1 (P1 = g1 * t1hat, P2 = g1), dt1 -> G
+        if (rowt) {
+            RowVals g = row_load(X, tid);
+            const RowVals xd = row_load(XD, tid);
+            row_apply_mask(g, mk ? mk + 1 : mk, tid);
+            row_store_lds(P1, tid, row_mul(g, xd));
+            row_store_lds(P2, tid, g);
+            row_gn_bwd(g, xd, rstd_d, tid, f.gd);
+            row_store_lds(G, tid, g);
+        }
+        __syncthreads();
+        // ---- t1 = W_d2 h1: dh1 = dt1 W_d2 -> X (waves 0-3); dW_d2 += dt1^T h1, dgamma_d, dbeta_d (waves 4-7)
+        if (wave < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            tile_gemm(G, reinterpret_cast<const float4 *>(p.wptd2) + wave * (16 * 64), acc, lane, 16);
+            acc_to_lds(X, acc, lane, wave);
+        } else {
+            wgrad_tile(G, H, A[0], A[1], A[2], A[3], wave - 4, lane);
+            s_d += tile_colsum(which ? P2 : P1, col);
+        }
+        __syncthreads();
+        // ---- h1 = ReLU(W_d0 d + b_d0): dz0 = dh1 * mask0 -> P1, dz0 * dx -> P2, dz0 * dy -> G; waves 4-7 sum them
+        // behind the next barrier (the next tile's first, or the one after the loop)
+        if (rowt) {
+            RowVals g = row_load(X, tid);
+            row_apply_mask(g, mk, tid);
+            row_store_lds(P1, tid, g);
+            row_store_lds(P2, tid, row_scale(g, dx));
+            row_store_lds(G, tid, row_scale(g, dy));
+        }
+        pend = true;
+    }
+
+    if (!want_rec) return;
+    if (pend) {
+        __syncthreads();
+        if (wave >= 4) {
+            s_0a += tile_colsum(which ? G : P1, col);
+            if (which == 0) s_0b += tile_colsum(P2, col);
+        }
+    }
+    if (wave >= 4) {
+        float *rec = p.rec + (int64_t)blockIdx.x * kPairRec;
+        wgrad_store(rec, A[0], A[1], A[2], A[3], wave - 4, lane);
+        wgrad_store(rec + kC * kC, A[4], A[5], A[6], A[7], wave - 4, lane);
+        float *tail = rec + 2 * kC * kC;
+        tail[which * kC + col] = s_c;
+        tail[(2 + which) * kC + col] = s_d;
+        tail[(which ? 6 : 4) * kC + col] = s_0a;
+        if (which == 0) tail[5 * kC + col] = s_0b;
+    }
+}
+
+// out = sum over the chunk records, in chunk order.  Record: dW_d2 [128,128], dW_c0e [128,128], then seven [128] vectors:
+// dgamma_c, dbeta_c, dgamma_d, dbeta_d, db_d0, dW_d0[:,0], dW_d0[:,1].
+__global__ __launch_bounds__(256) void k_att_pairs_bwd_reduce(const float *__restrict__ rec, int n_rec, const PairBwdOut o) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kPairRec) return;
+    float *dst = nullptr;
+    if (e < kC * kC) dst = o.dwd2 ? o.dwd2 + e : nullptr;
+    else if (e < 2 * kC * kC) dst = o.dwc0e ? o.dwc0e + (e - kC * kC) : nullptr;
+    else {
+        const int v = (e - 2 * kC * kC) >> 7, c = e & 127;
+        float *const vec = v == 0 ? o.dgc : v == 1 ? o.dbc : v == 2 ? o.dgd : v == 3 ? o.dbd : v == 4 ? o.dbd0 : o.dwd0;
+        if (vec != nullptr) dst = v < 5 ? vec + c : vec + 2 * c + (v - 5);
+    }
+    if (dst == nullptr) return;
+    float s = 0.f;
+    for (int k = 0; k < n_rec; ++k) s += rec[(int64_t)k * kPairRec + e];
+    *dst = s;
 }
 
 }  // namespace lgcn
@@ -657,7 +929,73 @@ int lgcn_att_pairs(const float *agt_ctrs, const float *ctx_ctrs, const int32_t *
     PairParams p{agt_ctrs, ctx_ctrs, hi, wi, n_pairs, cap, wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, eps, m};
     int64_t tiles = (cap + kTM32 - 1) / kTM32;
     const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
-    hipLaunchKernelGGL(k_att_pairs, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_att_pairs<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, (uint4 *)nullptr);
+    return launch_status();
+}
+
+int lgcn_att_pairs_train(const float *agt_ctrs, const float *ctx_ctrs, const int32_t *hi, const int32_t *wi,
+                         const int32_t *n_pairs, int64_t cap, const float *wd0, const float *bd0, const float *wpd2,
+                         const float *gd, const float *btd, const float *wpc0e, const float *U, const float *V,
+                         const float *gc, const float *btc, float eps, float *m, uint32_t *masks, void *stream) {
+    if (cap < 0) return LGCN_EINVAL;
+    if (cap == 0) return LGCN_OK;
+    if (cap > 0x7ffffff0) return LGCN_ESHAPE;
+    const void *ptrs[] = {agt_ctrs, ctx_ctrs, hi, wi, n_pairs, wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, m, masks};
+    for (const void *q : ptrs) LGCN_CHECK_PTR(q);
+    const void *al[] = {wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, m, masks};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);
+    PairParams p{agt_ctrs, ctx_ctrs, hi, wi, n_pairs, cap, wd0, bd0, wpd2, gd, btd, wpc0e, U, V, gc, btc, eps, m};
+    const int64_t tiles = (cap + kTM32 - 1) / kTM32;
+    const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
+    hipLaunchKernelGGL(k_att_pairs<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, reinterpret_cast<uint4 *>(masks));
+    return launch_status();
+}
+
+static_assert(sizeof(lgcn_att_pairs_bwd_t) == 31 * 8,
+              "lgcn_att_pairs_bwd_t layout: keep lanegcn-1_amd/_lib.py (AttPairsBwd) and tests/test_host_att_train_cabi.py in step");
+
+// workgroups of a backward launch: never more than the tiles that cap allows
+static int64_t pair_bwd_chunks(int64_t cap, int n_chunks) {
+    const int64_t tiles = (cap + kTM32 - 1) / kTM32;
+    return tiles < n_chunks ? tiles : n_chunks;
+}
+
+int64_t lgcn_att_pairs_bwd_ws_elems(int64_t cap, int n_chunks) {
+    if (cap < 0 || cap > 0x7ffffff0 || n_chunks < 1 || n_chunks > 1024) return LGCN_EINVAL;
+    return pair_bwd_chunks(cap, n_chunks) * kPairRec;
+}
+
+int lgcn_att_pairs_bwd(const lgcn_att_pairs_bwd_t *ph, void *stream) {
+    LGCN_CHECK_PTR(ph);
+    const lgcn_att_pairs_bwd_t &a = *ph;
+    if (a.cap < 0 || a.n_chunks < 1 || a.n_chunks > 1024) return LGCN_EINVAL;
+    if (a.cap == 0) return LGCN_OK;
+    if (a.cap > 0x7ffffff0) return LGCN_ESHAPE;
+    const bool want_d = a.d_wd2 || a.d_wd0 || a.d_bd0 || a.d_gd || a.d_btd;
+    const bool want_rec = want_d || a.d_wc0e || a.d_gc || a.d_btc;
+    const void *ptrs[] = {a.agt_ctrs, a.ctx_ctrs, a.hi, a.wi, a.n_pairs, a.wd0, a.bd0, a.wpd2, a.gd, a.btd, a.wpc0e, a.U, a.V,
+                          a.gc, a.btc, a.masks, a.dS};
+    for (const void *q : ptrs) LGCN_CHECK_PTR(q);
+    if (want_d) { LGCN_CHECK_PTR(a.wptd2); LGCN_CHECK_PTR(a.wptc0e); }
+    if (want_rec) LGCN_CHECK_PTR(a.ws);
+    const void *al[] = {a.wd0, a.bd0, a.wpd2, a.gd, a.btd, a.wpc0e, a.U, a.V, a.gc, a.btc, a.masks, a.dS, a.wptd2, a.wptc0e,
+                        a.dc, a.ws, a.d_wd2, a.d_wc0e, a.d_wd0, a.d_bd0, a.d_gd, a.d_btd, a.d_gc, a.d_btc};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);      // absent (null) ones pass
+    if (!want_rec && a.dc == nullptr) return LGCN_OK;
+    PairBwdParams p{};
+    p.f = PairParams{a.agt_ctrs, a.ctx_ctrs, a.hi, a.wi, a.n_pairs, a.cap, a.wd0, a.bd0, a.wpd2, a.gd, a.btd, a.wpc0e, a.U, a.V,
+                     a.gc, a.btc, a.eps, nullptr};
+    p.wptd2 = a.wptd2; p.wptc0e = a.wptc0e;
+    p.masks = reinterpret_cast<const uint4 *>(a.masks);
+    p.dS = a.dS; p.dc = a.dc; p.rec = want_rec ? a.ws : nullptr;
+    p.want_d = want_d; p.want_wc = a.d_wc0e != nullptr;
+    const int n_rec = (int)pair_bwd_chunks(a.cap, a.n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_att_pairs_bwd, dim3(n_rec), dim3(512), 0, st, p);
+    if (want_rec) {
+        const PairBwdOut o{a.d_wd2, a.d_wc0e, a.d_gc, a.d_btc, a.d_gd, a.d_btd, a.d_bd0, a.d_wd0};
+        hipLaunchKernelGGL(k_att_pairs_bwd_reduce, dim3((kPairRec + 255) / 256), dim3(256), 0, st, a.ws, n_rec, o);
+    }
     return launch_status();
 }
 

@@ -67,6 +67,63 @@ __device__ __forceinline__ void row_gn(RowVals &r, int t, const float *__restric
     }
 }
 
+// The two halves of row_gn for a backward that recomputes the forward: r becomes xhat = (x - mean) * rstd (returns rstd),
+// and row_affine(xhat) = xhat * g + b restates row_gn's output with the same source operations in the same order (the
+// library is built with -ffp-contract=off).  Nothing downstream needs the two to agree to the bit: the backward takes its
+// ReLU decisions from the stored masks.
+__device__ __forceinline__ float row_gn_hat(RowVals &r, float eps) {
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += (r.v[j].x + r.v[j].y) + (r.v[j].z + r.v[j].w);
+    const float mean = sum8(s) * (1.0f / kC);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = r.v[j].x - mean, bb = r.v[j].y - mean, c = r.v[j].z - mean, d = r.v[j].w - mean;
+        q += (a * a + bb * bb) + (c * c + d * d);
+    }
+    const float rstd = 1.0f / sqrtf(sum8(q) * (1.0f / kC) + eps);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        r.v[j].x = (r.v[j].x - mean) * rstd; r.v[j].y = (r.v[j].y - mean) * rstd;
+        r.v[j].z = (r.v[j].z - mean) * rstd; r.v[j].w = (r.v[j].w - mean) * rstd;
+    }
+    return rstd;
+}
+
+__device__ __forceinline__ RowVals row_affine(const RowVals &xh, int t, const float *__restrict__ g, const float *__restrict__ b) {
+    RowVals r;
+    const int c0 = 4 * (t & 7);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 gg = *reinterpret_cast<const float4 *>(g + c0 + 32 * j);
+        const float4 bb = *reinterpret_cast<const float4 *>(b + c0 + 32 * j);
+        r.v[j] = make_float4(xh.v[j].x * gg.x + bb.x, xh.v[j].y * gg.y + bb.y, xh.v[j].z * gg.z + bb.z, xh.v[j].w * gg.w + bb.w);
+    }
+    return r;
+}
+
+// GroupNorm backward of one row in registers (the formula of k_gn_bwd): g = dy (already masked) becomes
+// dx = rstd * (g gamma - mean(g gamma) - xhat * mean(g gamma xhat)).
+__device__ __forceinline__ void row_gn_bwd(RowVals &g, const RowVals &xh, float rstd, int t, const float *__restrict__ gamma) {
+    const int c0 = 4 * (t & 7);
+    float m1 = 0.f, m2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 gm = *reinterpret_cast<const float4 *>(gamma + c0 + 32 * j);
+        g.v[j] = make_float4(g.v[j].x * gm.x, g.v[j].y * gm.y, g.v[j].z * gm.z, g.v[j].w * gm.w);
+        m1 += (g.v[j].x + g.v[j].y) + (g.v[j].z + g.v[j].w);
+        m2 += (g.v[j].x * xh.v[j].x + g.v[j].y * xh.v[j].y) + (g.v[j].z * xh.v[j].z + g.v[j].w * xh.v[j].w);
+    }
+    m1 = sum8(m1) * (1.0f / kC);
+    m2 = sum8(m2) * (1.0f / kC);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        g.v[j].x = rstd * (g.v[j].x - m1 - xh.v[j].x * m2); g.v[j].y = rstd * (g.v[j].y - m1 - xh.v[j].y * m2);
+        g.v[j].z = rstd * (g.v[j].z - m1 - xh.v[j].z * m2); g.v[j].w = rstd * (g.v[j].w - m1 - xh.v[j].w * m2);
+    }
+}
+
 __device__ __forceinline__ void row_relu(RowVals &r) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -118,6 +175,18 @@ struct PairParams {
     float eps;
     float *m;
 };
+
+// lgcn_att_pairs_bwd: the forward's inputs, what it saved and the gradient outputs (see include/lgcn.h)
+struct PairBwdParams {
+    PairParams f;
+    const float *wptd2, *wptc0e;      // transposed images of W_d2 and W_c0[:, 0:128]
+    const uint4 *masks;
+    const float *dS;
+    float *dc, *rec;
+    int want_d, want_wc;              // anything upstream of e (the dist parameters) / dW_c0e
+};
+
+struct PairBwdOut { float *dwd2, *dwc0e, *dgc, *dbc, *dgd, *dbd, *dbd0, *dwd0; };
 
 // split-bf16 implementations (lgcn_rowmlp_bf.hip)
 int agg_mlp_bf(const lgcn_agg_mlp_t &p, bool lane_conv, hipStream_t st);

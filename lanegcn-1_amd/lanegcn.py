@@ -332,6 +332,10 @@ class Att(nn.Module):
     strict = True
     legacy_offsets = True   # zero-pair scenes do not advance hi/wi offsets (lanegcn.py:681-687)
     fold = True             # att_block: row-block launches folded across the Att layers
+    # Train the pair stage (lanegcn.py:691-703) on the fused exact-fp32 pair of autograd.AttPairsFn (lgcn_att_pairs_train /
+    # lgcn_att_pairs_bwd) instead of the composition of row blocks below: no [P,128] tensor is saved, one is written in the
+    # backward.  Opt-in, like ActorNet.train_hip / PredNet.train_hip: the default training path stays the composed one.
+    train_hip = False
 
     def __init__(self, n_agt: int, n_ctx: int) -> None:
         super().__init__()
@@ -364,9 +368,31 @@ class Att(nn.Module):
             raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
         return self.run_train(agts, ctx, ps) if train else ops.guarded(lambda: self.run(agts, ctx, ps))
 
+    def _train_hip_ok(self, agts: Tensor, ctx: Tensor, ps: ops.PairSet) -> bool:
+        rows_ok = max(agts.shape[0], ctx.shape[0]) < (1 << 23)
+        return (Att.train_hip and agts.is_cuda and agts.dtype == torch.float32 and ctx.dtype == torch.float32
+                and agts.shape[1] == ops.C_FEAT and ctx.shape[1] == ops.C_FEAT and self.agt.weight.shape[0] == ops.C_FEAT
+                and rows_ok and ps.count() > 0 and not (ps.agt_ctrs.requires_grad or ps.ctx_ctrs.requires_grad))
+
+    def run_train_hip(self, agts: Tensor, ctx: Tensor, ps: ops.PairSet) -> Tensor:
+        """run_train with the pair stage on AttPairsFn: U, V and the node epilogue are the same row blocks; the segment
+        sum S comes out of the pair stage, and ctx.1 (linear) is applied to it as in pairs_tail."""
+        T = agts.shape[0]
+        lin, c0, d = self.linear, self.ctx[0], self.dist
+        q = A.linear_gn(agts, self.query.linear.weight, gn=self.query.norm, relu=True)
+        U = A.linear_gn(q, c0.linear.weight, col0=128)
+        V = A.linear_gn(ctx, c0.linear.weight, col0=256)
+        S = A.AttPairsFn.apply(ps, d[0].weight, d[0].bias, d[2].linear.weight, d[2].norm.weight, d[2].norm.bias,
+                               c0.linear.weight, U, V, c0.norm.weight, c0.norm.bias, c0.norm.eps)
+        y = A.row_block([agts, S], [self.agt.weight, self.ctx[1].weight], [A.Rel(0, 0, L.REL_IDENT), A.Rel(1, 1, L.REL_IDENT)],
+                        T, gn=self.norm, relu=True, tag="att_post")
+        return A.linear_gn(y, lin.linear.weight, gn=lin.norm, relu=True, res=agts)
+
     def run_train(self, agts: Tensor, ctx: Tensor, ps: ops.PairSet) -> Tensor:
         """Differentiable composition of the same arithmetic as run() (lanegcn.py:691-709): per-pair tensors are
         sized by the exact pair count (one host read per pair set, already paid by the emptiness check)."""
+        if self._train_hip_ok(agts, ctx, ps):
+            return self.run_train_hip(agts, ctx, ps)
         P, T = ps.count(), agts.shape[0]
         lin, c0 = self.linear, self.ctx[0]
         hi, wi = ps.hi[:P].long(), ps.wi[:P].long()

@@ -68,6 +68,14 @@ class mma_scope:
         _mma = self.prev
 
 
+def exact_mma() -> mma_scope:
+    """``with ops.exact_mma():`` -- exact fp32 (LGCN_MMA_F32) for the launches and the weight images inside the block,
+    whatever set_mma() says: the training pair stage of Att (att_pairs_train / att_pairs_bwd) runs in it like
+    ActorNet.exact's conv units.  The images are cached per mode and registered like every other one, so
+    refresh_packed() rebuilds them too."""
+    return mma_scope("f32")
+
+
 # What happens when a forward in the range-restricted default mode (f16x2: operands below 65504) comes back with
 # non-finite features: "reroute" (default) runs it again in bf16x3 (fp32's exponent range, same fp32-grade
 # accuracy), "raise" raises LgcnError, "off" returns it as it is.
@@ -1225,6 +1233,89 @@ def att_pairs(ps: PairSet, wd0, bd0, wpd2, gn_d, wpc0e, U, V, gn_c, m=None, eps=
             rc = lib.lgcn_att_pairs(*args, _ptr(m), _stream())
     L.check(rc, "lgcn_att_pairs")
     return m
+
+
+# ------------------------------------------------------------------ Att's pair stage, training (exact fp32)
+PAIR_MASK_WORDS = 12       # per pair: 3 masks x 4 words of 32 channels
+
+
+def att_pairs_train(ps: PairSet, wd0, bd0, w_d2, gn_d, w_c0, U, V, gn_c, m=None, masks=None, eps=EPS, tag="att_pairs_train"):
+    """(m [cap,128], masks [cap,12] int32) of lgcn_att_pairs_train: the pair MLP of lgcn_att_pairs in exact fp32 plus its
+    three ReLU masks as bits (att_pair_masks decodes them).  w_d2 [128,128] and w_c0 [128,384] are the parameters; their
+    F32 images are made here.  Rows >= *n_pairs of m / masks are not written."""
+    lib = L.load()
+    U, V = _dev(U, torch.float32, "U"), _dev(V, torch.float32, "V")
+    with exact_mma():
+        wpd2, wpc0e = packed(w_d2, 0, C_FEAT), packed(w_c0, 0, C_FEAT)
+    rows = max(ps.cap, 1)
+    if m is None:
+        m = torch.empty((rows, C_FEAT), dtype=torch.float32, device=U.device)
+    if masks is None:
+        masks = torch.empty((rows, PAIR_MASK_WORDS), dtype=torch.int32, device=U.device)
+    with _Timed(tag):
+        rc = lib.lgcn_att_pairs_train(_ptr(ps.agt_ctrs), _ptr(ps.ctx_ctrs), _ptr(ps.hi), _ptr(ps.wi), _ptr(ps.n_pairs), ps.cap,
+                                      _ptr(wd0), _ptr(bd0), _ptr(wpd2), _ptr(gn_d[0]), _ptr(gn_d[1]), _ptr(wpc0e), _ptr(U),
+                                      _ptr(V), _ptr(gn_c[0]), _ptr(gn_c[1]), eps, _ptr(m), _ptr(masks), _stream())
+    L.check(rc, "lgcn_att_pairs_train")
+    return m, masks
+
+
+def att_pair_masks(masks: torch.Tensor, P: int) -> torch.Tensor:
+    """bool [P,3,128] of the first P rows of att_pairs_train's masks: [p, k, c] = mask k of channel c of pair p, k = 0:
+    W_d0 d + b_d0 > 0, 1: e > 0, 2: m > 0.  Layout: word 4 k + j of a row holds channels 32 j .. 32 j + 31, bit b =
+    channel 32 j + b."""
+    w = masks[:P].reshape(P, 3, 4, 1).to(torch.int64) & 0xFFFFFFFF
+    bits = (w >> torch.arange(32, device=masks.device)) & 1
+    return bits.reshape(P, 3, C_FEAT).bool()
+
+
+PAIR_BWD_OUTS = ("d_wd2", "d_wc0e", "d_wd0", "d_bd0", "d_gd", "d_btd", "d_gc", "d_btc")
+
+
+def att_pairs_bwd(ps: PairSet, dS, masks, wd0, bd0, w_d2, gn_d, w_c0, U, V, gn_c, want=PAIR_BWD_OUTS, want_dc=True, dc=None,
+                  eps=EPS, n_chunks: Optional[int] = None, tag="att_pairs_bwd"):
+    """lgcn_att_pairs_bwd for dS [T,128]: dict with "dc" ([cap,128], rows < P written; None unless want_dc) and the
+    gradients named in `want` -- d_wd2 [128,128], d_wc0e [128,128] (the columns 0:128 of ctx.0's weight), d_wd0 [128,2],
+    d_bd0, d_gd, d_btd (dist.2's norm), d_gc, d_btc (ctx.0's norm) [128].  n_chunks: workgroups, each with one partial
+    record of 134,656 B that the reduction launch reads back (default: one per CU, never more than a quarter of the
+    32-pair tiles of the pair count when the host already knows it -- a workgroup then walks at least four tiles --
+    else of the capacity)."""
+    lib = L.load()
+    dS, U, V = _dev(dS, torch.float32, "dS"), _dev(U, torch.float32, "U"), _dev(V, torch.float32, "V")
+    dev, want = dS.device, tuple(want)
+    with exact_mma():
+        wpd2, wpc0e = packed(w_d2, 0, C_FEAT), packed(w_c0, 0, C_FEAT)
+        wptd2, wptc0e = packed_t(w_d2, 0), packed_t(w_c0, 0)
+    if n_chunks is None:
+        rows = ps.cap if ps._p_host is None else ps._p_host
+        n_chunks = min(cu_count(dev), (rows + 127) // 128)
+    n_chunks = max(1, min(int(n_chunks), (ps.cap + 31) // 32, 1024))
+    out = {"dc": None}
+    q = L.AttPairsBwd()
+    q.agt_ctrs, q.ctx_ctrs, q.hi, q.wi, q.n_pairs = (t.data_ptr() for t in (ps.agt_ctrs, ps.ctx_ctrs, ps.hi, ps.wi, ps.n_pairs))
+    q.cap = ps.cap
+    q.wd0, q.bd0, q.wpd2, q.gd, q.btd = (t.data_ptr() for t in (wd0, bd0, wpd2, gn_d[0], gn_d[1]))
+    q.wpc0e, q.U, q.V, q.gc, q.btc = (t.data_ptr() for t in (wpc0e, U, V, gn_c[0], gn_c[1]))
+    q.wptd2, q.wptc0e, q.masks, q.dS = wptd2.data_ptr(), wptc0e.data_ptr(), masks.data_ptr(), dS.data_ptr()
+    if want_dc:
+        out["dc"] = dc if dc is not None else torch.empty((max(ps.cap, 1), C_FEAT), dtype=torch.float32, device=dev)
+        q.dc = out["dc"].data_ptr()
+    shapes = {"d_wd2": (C_FEAT, C_FEAT), "d_wc0e": (C_FEAT, C_FEAT), "d_wd0": (C_FEAT, 2)}
+    for name in want:
+        out[name] = torch.empty(shapes.get(name, (C_FEAT,)), dtype=torch.float32, device=dev)
+        setattr(q, name, out[name].data_ptr())
+    ws = None
+    if want:
+        n_ws = lib.lgcn_att_pairs_bwd_ws_elems(ps.cap, n_chunks)
+        if n_ws < 0:
+            raise L.LgcnError("att_pairs_bwd: cap = %d / n_chunks = %d not supported" % (ps.cap, n_chunks))
+        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        q.ws = ws.data_ptr()
+    q.eps, q.n_chunks = eps, n_chunks
+    with _Timed(tag):
+        rc = lib.lgcn_att_pairs_bwd(C.byref(q), _stream())
+    L.check(rc, "lgcn_att_pairs_bwd")
+    return out
 
 
 def pred_loss_fwd(cls, reg, gt, has, cfg):

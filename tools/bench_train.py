@@ -29,22 +29,26 @@ def main():
     ap.add_argument("--pred-impl", default=None, choices=["hip", "stock", "ab"],
                     help="PredNet's training tail: 'hip' sets PredNet.train_hip, 'stock' leaves the ATen tail; 'ab': both, "
                          "alternating step by step after a warm-up of each")
+    ap.add_argument("--att-impl", default=None, choices=["hip", "stock", "ab"],
+                    help="Att's training pair stage: 'hip' sets Att.train_hip (AttPairsFn), 'stock' leaves the composed row "
+                         "blocks; 'ab': both, alternating step by step after a warm-up of each")
     ap.add_argument("--actor-exact", action="store_true",
                     help="ActorNet.exact: the 'hip' ActorNet on the exact-fp32 units (any --mma)")
     args = ap.parse_args()
     M.ActorNet.exact = args.actor_exact
     if args.mma:
         ops.set_mma(args.mma)
-    if args.actor_impl == "ab" and args.pred_impl == "ab":
-        ap.error("one of --actor-impl / --pred-impl can alternate at a time")
+    if [args.actor_impl, args.pred_impl, args.att_impl].count("ab") > 1:
+        ap.error("one of --actor-impl / --pred-impl / --att-impl can alternate at a time")
     actor_impls = ["hip", "miopen"] if args.actor_impl == "ab" else [args.actor_impl or M.ActorNet.impl]
     pred_impls = ["hip", "stock"] if args.pred_impl == "ab" else [args.pred_impl or "stock"]
-    # a variant of the step: (ActorNet.impl, PredNet's training tail); its name is the side that alternates
-    impls = [(a, p) for a in actor_impls for p in pred_impls]
-    name = lambda v: v[1] if args.pred_impl == "ab" else v[0]
+    att_impls = ["hip", "stock"] if args.att_impl == "ab" else [args.att_impl or "stock"]
+    # a variant of the step: (ActorNet.impl, PredNet's training tail, Att's pair stage); its name is the side that alternates
+    impls = [(a, p, t) for a in actor_impls for p in pred_impls for t in att_impls]
+    name = lambda v: v[2] if args.att_impl == "ab" else v[1] if args.pred_impl == "ab" else v[0]
 
     def select(v):
-        M.ActorNet.impl, M.PredNet.train_hip = v[0], v[1] == "hip"
+        M.ActorNet.impl, M.PredNet.train_hip, M.Att.train_hip = v[0], v[1] == "hip", v[2] == "hip"
 
     select(impls[0])
     if args.actor_impl:
@@ -98,6 +102,8 @@ def main():
            "stage_ms": {k: float(np.median(v)) for k, v in stages.items()},
            "actor_impl": actor_impls[0] if len(actor_impls) == 1 else "ab", "actor_exact": M.ActorNet.exact,
            "pred_impl": pred_impls[0] if len(pred_impls) == 1 else "ab",
+           "att_impl": att_impls[0] if len(att_impls) == 1 else "ab",
+           "spread_step_ms": {k: [float(np.percentile(v, 25)), float(np.percentile(v, 75))] for k, v in per_step.items()},
            "median_step_ms": {k: float(np.median(v)) for k, v in per_step.items()}}
     print(json.dumps(res), flush=True)
 

@@ -721,6 +721,48 @@ int lgcn_wgrad(const lgcn_agg_mlp_t *p_host, const float *dT, float *dW, float *
                int n_chunks, void *stream);
 
 /*
+ * Backward of one LaneConv / LinearRes block (reference lanegcn.py:331-362, layers.py:193-238) below its aggregate stage,
+ * exact fp32 whatever the matrix mode of the rest of the network.  The forward (lgcn_agg_mlp with every epilogue flag and
+ * out_pre = T, out_mid = Y, out_pre2 = Z) computed, per row,
+ *   T = sum_r (G_r X) W_r^T;   Y = ReLU(GN1(T));   Z = Y W2^T;   out = ReLU(GN2(Z) + X)
+ * lgcn_laneconv_bwd, for d_out [n_rows,128] (one main launch + one fixed-order reduction launch; no atomics, no host read):
+ *   g2 = d_out * (out > 0);  dgamma2 += g2 * zhat;  dbeta2 += g2;  dZ = GN2 backward of g2 (formula of lgcn_gn_bwd)
+ *   dW2 += dZ (x) Y;  dY = dZ W2
+ *   g1 = dY * (Y > 0);  dgamma1 += g1 * that;  dbeta1 += g1;  dT = GN1 backward of g1
+ * zhat, that and the GroupNorm statistics are recomputed per 32-row tile from the saved Z and T.
+ * ident1 == 0 (any relations): dT and g2 are written, rows < n_rows only; the caller finishes with the launches it already
+ *   has: dX = sum_r G_r^T dT W_r + g2 (lgcn_agg_mlp on the transposed plan, LGCN_F_RES with res = g2) and dW_r (lgcn_wgrad).
+ * ident1 == 1 (T = X W1^T, one IDENT relation): the entry finishes the block,
+ *   dX = dT W1 + g2;  dW1 += dT (x) X
+ *   and neither dT nor g2 reaches memory.
+ *   d_out, out, Z, Y, T: [n_rows,128]; X: [n_rows,128], ident1 only;  gamma1, gamma2: the GroupNorm weights [128]
+ *   wpt2, wpt1: lgcn_pack_weight_t images (LGCN_MMA_F32) of W2 and, ident1 only, of W1
+ *   dT, g2: [n_rows,128] outputs of ident1 == 0, each may be NULL (no g2: no dX is wanted)
+ *   dX:     [n_rows,128] output of ident1 == 1, may be NULL (its GEMM is then skipped)
+ *   d_*:    gradient outputs, each may be NULL and its work is then skipped: d_w2 [128,128], d_w1 [128,128] (ident1 only),
+ *           d_g2, d_b2, d_g1, d_b1 [128].  An output of the other variant (dX / d_w1 with ident1 == 0, dT / g2 with
+ *           ident1 == 1) is LGCN_EINVAL.
+ *   n_chunks: 1..1024 workgroups (never more than ceil(n_rows / 32) are launched): workgroup k owns the tiles k,
+ *           k + n_chunks, ... and writes one record of (1 + ident1) * 128 * 128 + 4 * 128 floats -- dW2, dW1 (ident1 only),
+ *           dgamma2, dbeta2, dgamma1, dbeta1; the second launch sums the records in chunk order.
+ *   ws:     lgcn_laneconv_bwd_ws_elems(n_rows, n_chunks, ident1) floats (negative: LGCN_EINVAL for n_rows < 0 or above
+ *           0x7fffffff, n_chunks outside 1..1024 or ident1 outside 0..1); needed when any d_* is given.
+ * n_rows == 0, or every output NULL: LGCN_OK without a launch.
+ */
+typedef struct {
+    const float *d_out, *out, *Z, *Y, *T, *X;
+    const float *gamma1, *gamma2, *wpt2, *wpt1;
+    float *dT, *g2, *dX;
+    float *d_w2, *d_w1, *d_g2, *d_b2, *d_g1, *d_b1, *ws;
+    int64_t n_rows;
+    float eps;
+    int32_t n_chunks, ident1, pad_;
+} lgcn_laneconv_bwd_t;
+
+int64_t lgcn_laneconv_bwd_ws_elems(int64_t n_rows, int n_chunks, int ident1);
+int lgcn_laneconv_bwd(const lgcn_laneconv_bwd_t *p_host, void *stream);
+
+/*
  * Forward of  out = [ReLU]( GroupNorm(1,128)(x) [+ res] )  as a stand-alone row kernel (the fused
  * kernels do this in their epilogues; the differentiable per-pair composition needs it alone).
  * gamma == NULL: no normalisation.  relu != 0 applies the ReLU.

@@ -73,6 +73,17 @@ class AttPairsBwd(C.Structure):   # lgcn_att_pairs_bwd_t
     ]
 
 
+class LaneConvBwd(C.Structure):   # lgcn_laneconv_bwd_t
+    _fields_ = [
+        ("d_out", C.c_void_p), ("out", C.c_void_p), ("Z", C.c_void_p), ("Y", C.c_void_p), ("T", C.c_void_p), ("X", C.c_void_p),
+        ("gamma1", C.c_void_p), ("gamma2", C.c_void_p), ("wpt2", C.c_void_p), ("wpt1", C.c_void_p),
+        ("dT", C.c_void_p), ("g2", C.c_void_p), ("dX", C.c_void_p),
+        ("d_w2", C.c_void_p), ("d_w1", C.c_void_p), ("d_g2", C.c_void_p), ("d_b2", C.c_void_p), ("d_g1", C.c_void_p),
+        ("d_b1", C.c_void_p), ("ws", C.c_void_p),
+        ("n_rows", C.c_int64), ("eps", C.c_float), ("n_chunks", C.c_int32), ("ident1", C.c_int32), ("pad_", C.c_int32),
+    ]
+
+
 class AggMlp(C.Structure):
     _fields_ = [
         ("n_rows", C.c_int64), ("n_rel", C.c_int32), ("n_rel_csr", C.c_int32),
@@ -143,6 +154,8 @@ SIGNATURES = {
     "lgcn_att_pairs_train": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _P, _P, _P]),
     "lgcn_att_pairs_bwd_ws_elems": (C.c_int64, [_L, _I]),
     "lgcn_att_pairs_bwd": (C.c_int, [C.POINTER(AttPairsBwd), _P]),
+    "lgcn_laneconv_bwd_ws_elems": (C.c_int64, [_L, _I, _I]),
+    "lgcn_laneconv_bwd": (C.c_int, [C.POINTER(LaneConvBwd), _P]),
     "lgcn_conv_packed_bytes": (C.c_int64, [_I, _I, _I]),
     "lgcn_conv_pack_weight": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "lgcn_conv1d_gn": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P]),

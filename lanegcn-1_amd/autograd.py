@@ -49,6 +49,7 @@ class BlockSpec:
     seg_ids: Optional[torch.Tensor] = None     # RANGE relation: segment id of every source row (int32)
     n_seg_rows: Optional[torch.Tensor] = None  # device count of valid source rows (int32 [1])
     tag: Optional[str] = None
+    fused_bwd: bool = False                    # LaneConvFn: backward on lgcn_laneconv_bwd (exact fp32) instead of the composed one
 
 
 def _fwd_rels(spec: BlockSpec, srcs, weights):
@@ -153,7 +154,8 @@ class RowBlockFn(Function):
 
 class LaneConvFn(Function):
     """One fused LaneConv layer (lanegcn.py:331-362): X' = ReLU(GN2(ReLU(GN1(sum_r (G_r X) W_r^T)) W2^T) + X).
-    Forward is the single fused launch of inference (saving T, Y, Z); backward is composed."""
+    Forward is the single fused launch of inference (saving T, Y, Z); backward is composed, or with spec.fused_bwd
+    the fused lgcn_laneconv_bwd."""
 
     @staticmethod
     def forward(ctx, spec: BlockSpec, feat, gn1_w, gn1_b, w2, gn2_w, gn2_b, *weights):
@@ -173,6 +175,9 @@ class LaneConvFn(Function):
         feat, gn1_w, w2, gn2_w, T, Y, Z, out, *weights = ctx.saved_tensors
         ni = ctx.needs_input_grad
         N = spec.n_rows
+        if (spec.fused_bwd and d_out.is_cuda and d_out.dtype == torch.float32 and N > 0
+                and all(tuple(w.shape) == (C_FEAT, C_FEAT) for w in (w2, *weights))):
+            return LaneConvFn._backward_fused(spec, ni, d_out, feat, gn1_w, w2, gn2_w, T, Y, Z, out, weights)
         # out = ReLU(GN2(Z) + X)
         dZ, g2, d_g2w, d_g2b = ops.gn_bwd(d_out.contiguous(), Z, out, gn2_w, eps=spec.eps, want_g=True)
         # Z = Y W2^T
@@ -186,6 +191,25 @@ class LaneConvFn(Function):
         with ops.backward_mma():
             d_srcs, d_ws = _stage_backward(spec, [feat], list(weights), dT, [ni[1]], need_w, res_grad=g2)
         return (None, d_srcs[0], d_g1w, d_g1b, d_w2, d_g2w, d_g2b, *d_ws)
+
+    @staticmethod
+    def _backward_fused(spec, ni, d_out, feat, gn1_w, w2, gn2_w, T, Y, Z, out, weights):
+        """BlockSpec.fused_bwd: everything below the relation stage in one launch pair (lgcn_laneconv_bwd); with one IDENT
+        relation (LinearRes) that is the whole backward, otherwise dX and dW_r stay the two launches of _stage_backward."""
+        names = {2: "d_g1", 3: "d_b1", 4: "d_w2", 5: "d_g2", 6: "d_b2"}
+        want = [n for i, n in names.items() if ni[i]]
+        need_w = [ni[7 + i] for i in range(len(weights))]
+        r0 = spec.rels[0]
+        if len(spec.rels) == 1 and r0.mode == L.REL_IDENT and r0.col0 == 0:
+            g = ops.laneconv_bwd(d_out, out, Z, Y, T, gn1_w, w2, gn2_w, x=feat, w1=weights[0],
+                                 want=want + (["d_w1"] if need_w[0] else []), want_dx=ni[1], eps=spec.eps)
+            d_x, d_ws = g["dX"], [g.get("d_w1")]
+        else:
+            g = ops.laneconv_bwd(d_out, out, Z, Y, T, gn1_w, w2, gn2_w, want=want, want_dx=ni[1], eps=spec.eps)
+            with ops.backward_mma():
+                d_srcs, d_ws = _stage_backward(spec, [feat], list(weights), g["dT"], [ni[1]], need_w, res_grad=g["g2"])
+            d_x = d_srcs[0]
+        return (None, d_x, g.get("d_g1"), g.get("d_b1"), g.get("d_w2"), g.get("d_g2"), g.get("d_b2"), *d_ws)
 
 
 class GNActFn(Function):

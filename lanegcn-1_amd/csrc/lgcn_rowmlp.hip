@@ -713,6 +713,184 @@ __global__ __launch_bounds__(256) void k_att_pairs_bwd_reduce(const float *__res
     *dst = s;
 }
 
+// --------------------------------------------------- LaneConv block bwd ----
+// Backward of out = ReLU(GN2(ReLU(GN1(T)) W2^T) + X) from d_out down to dT (include/lgcn.h, lgcn_laneconv_bwd), shaped like
+// k_att_pairs_bwd: workgroup `chunk` walks the 32-row tiles chunk, chunk + n_chunks, ...; waves 0-3 are the row phase (8
+// threads per row) and the tile GEMMs, waves 4-7 stage the saved Y (and X) rows and own everything summed over rows, in
+// registers across the workgroup's tiles: dW2 (and dW1) on wgrad_tile, wave 4 + q holding block q, and the four GroupNorm
+// vectors as column sums of the tiles P1 / P2 the row phase leaves in LDS.  IDENT1 (T = X W1^T, a LinearRes) finishes the
+// block: dX = dT W1 + g2 with g2 kept in the row threads' registers, dW1 += dT^T X; neither dT nor g2 reaches memory.
+// LDS: YT (Y rows), D (dZ, then dT), P1 / P2 (g * xhat / g of a GroupNorm backward), G (GEMM output), and XT (X rows) for
+// IDENT1: 5 or 6 x 16.5 KiB.  Four barriers per tile.
+struct LcBwdParams {
+    const float *d_out, *out, *Z, *Y, *T, *X;
+    const float *gamma1, *gamma2, *wpt2, *wpt1;
+    float *dT, *g2, *dX, *rec;
+    int64_t n_rows;
+    float eps;
+    int want_w2, want_w1;
+};
+
+struct LcBwdOut { float *dw2, *dw1, *dg2, *db2, *dg1, *db1; };
+
+__host__ __device__ constexpr int lc_rec_floats(bool ident1) { return (ident1 ? 2 : 1) * kC * kC + 4 * kC; }
+
+__device__ __forceinline__ RowVals row_load_global(const float *__restrict__ rowp, int t) {
+    RowVals r;
+    const float *p = rowp + 4 * (t & 7);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.v[j] = *reinterpret_cast<const float4 *>(p + 32 * j);
+    return r;
+}
+
+__device__ __forceinline__ RowVals row_zero() {
+    RowVals r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    return r;
+}
+
+// g where post > 0, else 0 (the mask of k_gn_bwd)
+__device__ __forceinline__ void row_mask_pos(RowVals &g, const RowVals &post) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        g.v[j].x = post.v[j].x > 0.f ? g.v[j].x : 0.f; g.v[j].y = post.v[j].y > 0.f ? g.v[j].y : 0.f;
+        g.v[j].z = post.v[j].z > 0.f ? g.v[j].z : 0.f; g.v[j].w = post.v[j].w > 0.f ? g.v[j].w : 0.f;
+    }
+}
+
+// rows [32 tile, 32 tile + 32) of a [n_rows,128] tensor into an LDS tile, zeros past n_rows (gt = 0..255 of waves 4-7)
+__device__ __forceinline__ void stage_rows(float *__restrict__ dst, const float *__restrict__ src, int64_t tile, int64_t n_rows,
+                                           int gt) {
+    const int hw = gt >> 5, l = gt & 31;
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int row = it * 8 + hw;
+        const int64_t n = tile * kTM32 + row;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (n < n_rows) v = reinterpret_cast<const float4 *>(src)[n * 32 + l];
+        *reinterpret_cast<float4 *>(dst + row * kLDA + 4 * l) = v;
+    }
+}
+
+template <bool IDENT1>
+__global__ __launch_bounds__(512) void k_lc_bwd_rows(const LcBwdParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[(IDENT1 ? 6 : 5) * kTileFloats];
+    float *YT = smem, *D = smem + kTileFloats, *P1 = smem + 2 * kTileFloats, *P2 = smem + 3 * kTileFloats;
+    float *G = smem + 4 * kTileFloats, *XT = smem + (IDENT1 ? 5 : 0) * kTileFloats;      // XT: IDENT1 only
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool rowt = tid < 256;
+    const int which = (tid >> 7) & 1, col = tid & 127;       // waves 4-7: column sums
+    const int64_t n_tiles = (p.n_rows + kTM32 - 1) / kTM32;
+    const bool want_rec = p.rec != nullptr, want_w2 = p.want_w2 != 0, want_w1 = IDENT1 && p.want_w1 != 0;
+    const bool want_dx = IDENT1 && p.dX != nullptr;
+
+    f32x16 A[IDENT1 ? 8 : 4];
+#pragma unroll
+    for (int k = 0; k < (IDENT1 ? 8 : 4); ++k)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) A[k][i] = 0.f;
+    float s2 = 0.f, s1 = 0.f;      // which = 0: dgamma2, dgamma1; 1: dbeta2, dbeta1
+    f32x16 acc;
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t n = tile * kTM32 + (tid >> 3);
+        const bool live = rowt && n < p.n_rows;
+        RowVals g2 = row_zero();
+        // ---- out = ReLU(GN2(Z) + X): g2 = d_out * (out > 0) (P1 = g2 * zhat, P2 = g2), dZ -> D; waves 4-7 stage Y (and X)
+        if (rowt) {
+            RowVals z = row_zero();
+            if (live) {
+                g2 = row_load_global(p.d_out + n * kC, tid);
+                row_mask_pos(g2, row_load_global(p.out + n * kC, tid));
+                z = row_load_global(p.Z + n * kC, tid);
+                if (!IDENT1 && p.g2) row_store_global(p.g2 + n * kC, tid, g2);
+            }
+            const float rstd2 = row_gn_hat(z, p.eps);
+            if (want_rec) { row_store_lds(P1, tid, row_mul(g2, z)); row_store_lds(P2, tid, g2); }
+            RowVals dz = g2;
+            row_gn_bwd(dz, z, rstd2, tid, p.gamma2);
+            row_store_lds(D, tid, dz);
+        } else {
+            stage_rows(YT, p.Y, tile, p.n_rows, tid - 256);
+            if (want_w1) stage_rows(XT, p.X, tile, p.n_rows, tid - 256);
+        }
+        __syncthreads();
+        // ---- Z = Y W2^T: dY = dZ W2 -> G (waves 0-3); dW2 += dZ^T Y, dgamma2, dbeta2 (waves 4-7)
+        if (wave < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            tile_gemm(D, reinterpret_cast<const float4 *>(p.wpt2) + wave * (16 * 64), acc, lane, 16);
+            acc_to_lds(G, acc, lane, wave);
+        } else if (want_rec) {
+            if (want_w2) wgrad_tile(D, YT, A[0], A[1], A[2], A[3], wave - 4, lane);
+            s2 += tile_colsum(which ? P2 : P1, col);
+        }
+        __syncthreads();
+        // ---- Y = ReLU(GN1(T)): g1 = dY * (Y > 0) (P1 = g1 * that, P2 = g1), dT -> memory, or -> D for IDENT1
+        if (rowt) {
+            RowVals g = row_load(G, tid);
+            row_mask_pos(g, row_load(YT, tid));
+            RowVals t = row_zero();
+            if (live) t = row_load_global(p.T + n * kC, tid);
+            const float rstd1 = row_gn_hat(t, p.eps);
+            if (want_rec) { row_store_lds(P1, tid, row_mul(g, t)); row_store_lds(P2, tid, g); }
+            row_gn_bwd(g, t, rstd1, tid, p.gamma1);
+            if (IDENT1) row_store_lds(D, tid, g);
+            else if (live && p.dT) row_store_global(p.dT + n * kC, tid, g);
+        }
+        __syncthreads();
+        // ---- T = X W1^T (IDENT1): dX = dT W1 -> G (waves 0-3); dW1 += dT^T X, and dgamma1, dbeta1 for both (waves 4-7)
+        if (wave < 4) {
+            if (want_dx) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                tile_gemm(D, reinterpret_cast<const float4 *>(p.wpt1) + wave * (16 * 64), acc, lane, 16);
+                acc_to_lds(G, acc, lane, wave);
+            }
+        } else if (want_rec) {
+            if constexpr (IDENT1) {
+                if (want_w1) wgrad_tile(D, XT, A[4], A[5], A[6], A[7], wave - 4, lane);
+            }
+            s1 += tile_colsum(which ? P2 : P1, col);
+        }
+        __syncthreads();      // every tile is next written behind this barrier, G two barriers from here
+        if (want_dx && live) {
+            RowVals dx = row_load(G, tid);
+            row_add(dx, g2);
+            row_store_global(p.dX + n * kC, tid, dx);
+        }
+    }
+
+    if (!want_rec || wave < 4) return;
+    float *rec = p.rec + (int64_t)blockIdx.x * lc_rec_floats(IDENT1);
+    wgrad_store(rec, A[0], A[1], A[2], A[3], wave - 4, lane);
+    if constexpr (IDENT1) wgrad_store(rec + kC * kC, A[4], A[5], A[6], A[7], wave - 4, lane);
+    float *tail = rec + (IDENT1 ? 2 : 1) * kC * kC;
+    tail[which * kC + col] = s2;
+    tail[(2 + which) * kC + col] = s1;
+}
+
+// out = sum over the chunk records, in chunk order.  Record: dW2 [128,128], dW1 [128,128] (ident1 only), then four [128]
+// vectors: dgamma2, dbeta2, dgamma1, dbeta1.
+__global__ __launch_bounds__(256) void k_lc_bwd_reduce(const float *__restrict__ rec, int n_rec, int ident1, const LcBwdOut o) {
+    const int n_w = (ident1 ? 2 : 1) * kC * kC, n_e = n_w + 4 * kC;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_e) return;
+    float *dst = nullptr;
+    if (e < kC * kC) dst = o.dw2 ? o.dw2 + e : nullptr;
+    else if (e < n_w) dst = o.dw1 ? o.dw1 + (e - kC * kC) : nullptr;
+    else {
+        const int v = (e - n_w) >> 7, c = e & 127;
+        float *const vec = v == 0 ? o.dg2 : v == 1 ? o.db2 : v == 2 ? o.dg1 : o.db1;
+        if (vec != nullptr) dst = vec + c;
+    }
+    if (dst == nullptr) return;
+    float s = 0.f;
+    for (int k = 0; k < n_rec; ++k) s += rec[(int64_t)k * n_e + e];
+    *dst = s;
+}
+
 }  // namespace lgcn
 
 using namespace lgcn;
@@ -995,6 +1173,52 @@ int lgcn_att_pairs_bwd(const lgcn_att_pairs_bwd_t *ph, void *stream) {
     if (want_rec) {
         const PairBwdOut o{a.d_wd2, a.d_wc0e, a.d_gc, a.d_btc, a.d_gd, a.d_btd, a.d_bd0, a.d_wd0};
         hipLaunchKernelGGL(k_att_pairs_bwd_reduce, dim3((kPairRec + 255) / 256), dim3(256), 0, st, a.ws, n_rec, o);
+    }
+    return launch_status();
+}
+
+static_assert(sizeof(lgcn_laneconv_bwd_t) == 23 * 8,
+              "lgcn_laneconv_bwd_t layout: keep lanegcn-1_amd/_lib.py (LaneConvBwd) and tests/test_host_laneconv_bwd_cabi.py in step");
+
+// workgroups of a backward launch: never more than the 32-row tiles
+static int64_t lc_bwd_chunks(int64_t n_rows, int n_chunks) {
+    const int64_t tiles = (n_rows + kTM32 - 1) / kTM32;
+    return tiles < n_chunks ? tiles : n_chunks;
+}
+
+int64_t lgcn_laneconv_bwd_ws_elems(int64_t n_rows, int n_chunks, int ident1) {
+    if (n_rows < 0 || n_rows > 0x7fffffff || n_chunks < 1 || n_chunks > 1024 || (ident1 != 0 && ident1 != 1)) return LGCN_EINVAL;
+    return lc_bwd_chunks(n_rows, n_chunks) * lc_rec_floats(ident1 != 0);
+}
+
+int lgcn_laneconv_bwd(const lgcn_laneconv_bwd_t *ph, void *stream) {
+    LGCN_CHECK_PTR(ph);
+    const lgcn_laneconv_bwd_t &a = *ph;
+    if (a.n_rows < 0 || a.n_chunks < 1 || a.n_chunks > 1024 || (a.ident1 != 0 && a.ident1 != 1)) return LGCN_EINVAL;
+    if (a.n_rows == 0) return LGCN_OK;
+    if (a.n_rows > 0x7fffffff) return LGCN_ESHAPE;
+    const bool ident1 = a.ident1 != 0;
+    // outputs of the other variant are an error, not a silent no-op
+    if (ident1 ? (a.dT || a.g2) : (a.dX || a.d_w1)) return LGCN_EINVAL;
+    const bool want_rec = a.d_w2 || a.d_w1 || a.d_g2 || a.d_b2 || a.d_g1 || a.d_b1;
+    const void *ptrs[] = {a.d_out, a.out, a.Z, a.Y, a.T, a.gamma1, a.gamma2, a.wpt2};
+    for (const void *q : ptrs) LGCN_CHECK_PTR(q);
+    if (ident1) { LGCN_CHECK_PTR(a.X); LGCN_CHECK_PTR(a.wpt1); }
+    if (want_rec) LGCN_CHECK_PTR(a.ws);
+    const void *al[] = {a.d_out, a.out, a.Z, a.Y, a.T, a.X, a.gamma1, a.gamma2, a.wpt2, a.wpt1, a.dT, a.g2, a.dX,
+                        a.d_w2, a.d_w1, a.d_g2, a.d_b2, a.d_g1, a.d_b1, a.ws};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);      // absent (null) ones pass
+    if (!want_rec && !(ident1 ? a.dX != nullptr : (a.dT || a.g2))) return LGCN_OK;
+    LcBwdParams p{a.d_out, a.out, a.Z, a.Y, a.T, a.X, a.gamma1, a.gamma2, a.wpt2, a.wpt1, a.dT, a.g2, a.dX,
+                  want_rec ? a.ws : nullptr, a.n_rows, a.eps, a.d_w2 != nullptr, a.d_w1 != nullptr};
+    const int n_rec = (int)lc_bwd_chunks(a.n_rows, a.n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    if (ident1) hipLaunchKernelGGL(k_lc_bwd_rows<true>, dim3(n_rec), dim3(512), 0, st, p);
+    else hipLaunchKernelGGL(k_lc_bwd_rows<false>, dim3(n_rec), dim3(512), 0, st, p);
+    if (want_rec) {
+        const LcBwdOut o{a.d_w2, a.d_w1, a.d_g2, a.d_b2, a.d_g1, a.d_b1};
+        hipLaunchKernelGGL(k_lc_bwd_reduce, dim3((lc_rec_floats(ident1) + 255) / 256), dim3(256), 0, st, a.ws, n_rec,
+                           (int)ident1, o);
     }
     return launch_status();
 }

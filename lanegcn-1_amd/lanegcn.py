@@ -188,8 +188,9 @@ def lane_plan_t(graph: Dict) -> ops.LanePlan:
 
 
 def lane_conv_train(fuse: nn.ModuleDict, feat: Tensor, plan: ops.LanePlan, plan_t: ops.LanePlan,
-                    num_scales: int) -> Tensor:
-    """lane_conv with autograd (LaneConvFn: fused forward launch, composed HIP backward)."""
+                    num_scales: int, fused_bwd: bool = False) -> Tensor:
+    """lane_conv with autograd (LaneConvFn: fused forward launch, composed HIP backward; fused_bwd: lgcn_laneconv_bwd
+    for everything below the relation stage)."""
     keys = rel_keys(num_scales)
     for i in range(len(fuse["ctr"])):
         rels, weights = [A.Rel(0, 0, L.REL_IDENT)], [fuse["ctr"][i].weight]
@@ -198,7 +199,7 @@ def lane_conv_train(fuse: nn.ModuleDict, feat: Tensor, plan: ops.LanePlan, plan_
                 rels.append(A.Rel(0, len(weights), L.REL_CSR, r))
                 weights.append(fuse[key][i].weight)
         spec = A.BlockSpec(n_rows=feat.shape[0], rels=rels, gn=True, relu=True, has_res=True, eps=fuse["norm"][i].eps,
-                           plan=plan, plan_t=plan_t)
+                           plan=plan, plan_t=plan_t, fused_bwd=fused_bwd)
         c2 = fuse["ctr2"][i]
         feat = A.LaneConvFn.apply(spec, feat, fuse["norm"][i].weight, fuse["norm"][i].bias, c2.linear.weight,
                                   c2.norm.weight, c2.norm.bias, *weights)
@@ -256,6 +257,9 @@ def lane_conv(fuse: nn.ModuleDict, feat: Tensor, plan: ops.LanePlan, num_scales:
 
 class MapNet(nn.Module):
     """Map Graph feature extractor with LaneGraphCNN (reference lanegcn.py:266-363)."""
+    # Train the 4 LaneConv layers with the fused exact-fp32 backward (autograd.BlockSpec.fused_bwd: lgcn_laneconv_bwd, then
+    # the relation stage's two launches) instead of the ten composed launches per layer.  Opt-in, like Att.train_hip.
+    train_hip = False
 
     def __init__(self, config):
         super().__init__()
@@ -286,7 +290,8 @@ class MapNet(nn.Module):
             a, s = self.input, self.seg      # the two nn.Linear(2,128) are [N,2]-shaped: stock ops
             fa = A.linear_gn(F.relu(a[0](ctrs)), a[2].linear.weight, gn=a[2].norm)
             fs = A.linear_gn(F.relu(s[0](graph["feats"])), s[2].linear.weight, gn=s[2].norm)
-            feat = lane_conv_train(self.fuse, F.relu(fa + fs), lane_plan(graph), lane_plan_t(graph), len(graph["pre"]))
+            feat = lane_conv_train(self.fuse, F.relu(fa + fs), lane_plan(graph), lane_plan_t(graph), len(graph["pre"]),
+                                   fused_bwd=MapNet.train_hip)
             return feat, graph["idcs"], graph["ctrs"]
         feat = ops.guarded(lambda: lane_conv(self.fuse, self.stem(ctrs, graph["feats"]), lane_plan(graph), len(graph["pre"])))
         return feat, graph["idcs"], graph["ctrs"]
@@ -294,6 +299,7 @@ class MapNet(nn.Module):
 
 class M2M(nn.Module):
     """Lane to lane block: 4 more LaneConv layers (reference lanegcn.py:410-480)."""
+    train_hip = False       # as MapNet.train_hip
 
     def __init__(self, config):
         super().__init__()
@@ -303,7 +309,8 @@ class M2M(nn.Module):
 
     def forward(self, feat: Tensor, graph: Dict) -> Tensor:
         if _hot_guard(feat, *ops.module_params(self)):
-            return lane_conv_train(self.fuse, feat, lane_plan(graph), lane_plan_t(graph), len(graph["pre"]))
+            return lane_conv_train(self.fuse, feat, lane_plan(graph), lane_plan_t(graph), len(graph["pre"]),
+                                   fused_bwd=M2M.train_hip)
         return ops.guarded(lambda: lane_conv(self.fuse, feat, lane_plan(graph), len(graph["pre"])))
 
 

@@ -130,6 +130,9 @@ class Res1d(nn.Module):
 
 class LinearRes(nn.Module):
     """Two-layer residual MLP (reference layers.py:193-238); PredNet only."""
+    # Train the 128 -> 128 block with the fused exact-fp32 backward (autograd.BlockSpec.fused_bwd: one lgcn_laneconv_bwd
+    # call, ident1) instead of the ten composed launches.  Opt-in, like PredNet.train_hip.
+    train_hip = False
 
     def __init__(self, n_in, n_out, norm="GN", ng=32):
         super().__init__()
@@ -162,7 +165,7 @@ class LinearRes(nn.Module):
             x = x.contiguous()
             if ops.wants_grad(x, *ops.module_params(self)):
                 spec = A.BlockSpec(n_rows=x.shape[0], rels=[A.Rel(0, 0, L.REL_IDENT)], gn=True, relu=True, has_res=True,
-                                   eps=self.norm1.eps)
+                                   eps=self.norm1.eps, fused_bwd=LinearRes.train_hip)
                 return A.LaneConvFn.apply(spec, x, self.norm1.weight, self.norm1.bias, self.linear2.weight,
                                           self.norm2.weight, self.norm2.bias, self.linear1.weight)
             return ops.agg_mlp(**self.block_kw(x))

@@ -1453,6 +1453,68 @@ def wgrad(n_rows: int, rels: Sequence[RelSpec], dT: torch.Tensor, *, rowptr=None
     return dW
 
 
+LC_BWD_OUTS = ("d_w2", "d_g2", "d_b2", "d_g1", "d_b1")      # with x / w1 (one IDENT relation) also "d_w1"
+
+
+def laneconv_bwd(d_out, out, Z, Y, T, gn1_w, w2, gn2_w, *, x=None, w1=None, want=None, want_dx=True, dT=None, g2=None,
+                 n_chunks: Optional[int] = None, eps=EPS, tag="laneconv_bwd"):
+    """lgcn_laneconv_bwd for d_out [N,128] and the tensors LaneConvFn's forward saved (exact fp32 in every matrix mode):
+    dict with the gradients named in `want` -- d_w2 [128,128], d_g2, d_b2 (the second norm), d_g1, d_b1 (the first) [128]
+    -- and
+      without x / w1: "dT" [N,128] and "g2" [N,128] (None unless want_dx), the inputs of the relation stage's backward;
+      with x and w1 (T = x w1^T, a LinearRes): "dX" [N,128] (None unless want_dx) and, when wanted, d_w1 [128,128].
+    w2 / w1 are the parameters; their transposed F32 images are made here.  dT / g2: preallocated outputs, at least N rows.
+    n_chunks: workgroups, each with one partial record that the reduction launch reads back (default: one per CU, never
+    more than a quarter of the 32-row tiles -- a workgroup then walks at least four)."""
+    lib = L.load()
+    ident1 = x is not None
+    if ident1 != (w1 is not None):
+        raise L.LgcnError("laneconv_bwd: x and w1 come together")
+    d_out = _dev(d_out, torch.float32, "d_out")
+    out, Z, Y, T = (_dev(t, torch.float32, n) for t, n in ((out, "out"), (Z, "Z"), (Y, "Y"), (T, "T")))
+    N, dev = d_out.shape[0], d_out.device
+    want = (LC_BWD_OUTS + (("d_w1",) if ident1 else ())) if want is None else tuple(want)
+    if not ident1 and "d_w1" in want:
+        raise L.LgcnError("laneconv_bwd: d_w1 needs x and w1")
+    q = L.LaneConvBwd()
+    q.d_out, q.out, q.Z, q.Y, q.T = (t.data_ptr() for t in (d_out, out, Z, Y, T))
+    q.gamma1, q.gamma2 = gn1_w.data_ptr(), gn2_w.data_ptr()
+    with exact_mma():
+        wpt2 = packed_t(w2)
+        wpt1 = packed_t(w1) if ident1 else None
+    q.wpt2 = wpt2.data_ptr()
+    res = {}
+    if ident1:
+        x = _dev(x, torch.float32, "x")
+        q.X, q.wpt1 = x.data_ptr(), wpt1.data_ptr()
+        res["dX"] = torch.empty((N, C_FEAT), dtype=torch.float32, device=dev) if want_dx else None
+        q.dX = 0 if res["dX"] is None else res["dX"].data_ptr()
+    else:
+        for name, buf, on in (("dT", dT, True), ("g2", g2, want_dx)):
+            if on and buf is not None and (buf.shape[0] < N or not buf.is_contiguous() or buf.dtype != torch.float32):
+                raise L.LgcnError("laneconv_bwd: %s must be a contiguous float32 [>= %d, 128]" % (name, N))
+            res[name] = None if not on else buf if buf is not None else torch.empty((N, C_FEAT), dtype=torch.float32, device=dev)
+            setattr(q, name, 0 if res[name] is None else res[name].data_ptr())
+    for name in want:
+        res[name] = torch.empty((C_FEAT, C_FEAT) if name in ("d_w2", "d_w1") else (C_FEAT,), dtype=torch.float32, device=dev)
+        setattr(q, name, res[name].data_ptr())
+    if n_chunks is None:
+        n_chunks = min(cu_count(dev), (N + 127) // 128)
+    n_chunks = max(1, min(int(n_chunks), (N + 31) // 32, 1024))
+    ws = None
+    if want:
+        n_ws = lib.lgcn_laneconv_bwd_ws_elems(N, n_chunks, int(ident1))
+        if n_ws < 0:
+            raise L.LgcnError("laneconv_bwd: n_rows = %d / n_chunks = %d not supported" % (N, n_chunks))
+        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        q.ws = ws.data_ptr()
+    q.n_rows, q.eps, q.n_chunks, q.ident1 = N, eps, n_chunks, int(ident1)
+    with _Timed(tag):
+        rc = lib.lgcn_laneconv_bwd(C.byref(q), _stream())
+    L.check(rc, "lgcn_laneconv_bwd")
+    return res
+
+
 def gather_rows(src, idx, n_dev, cap):
     lib = L.load()
     src = _dev(src, torch.float32, "src")

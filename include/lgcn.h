@@ -763,6 +763,51 @@ int64_t lgcn_laneconv_bwd_ws_elems(int64_t n_rows, int n_chunks, int ident1);
 int lgcn_laneconv_bwd(const lgcn_laneconv_bwd_t *p_host, void *stream);
 
 /*
+ * Backward of one row block with IDENT relations only,
+ *   out = [ReLU]( [GN]( sum_{r < n_rel} src_r W_r^T ) [+ res] )       (lgcn_agg_mlp with out_pre = `pre`),
+ * exact fp32 whatever the matrix mode of the rest of the network: the backward of layers.Linear, the input stems' second
+ * layers, A2M's meta layer, AttDest and the node side of Att.  For d_out [n_rows,128] (one main launch + one fixed-order
+ * reduction launch; no atomics, no host read):
+ *   g     = d_out * (out > 0)         when out != NULL (the block had a ReLU), else d_out
+ *   d_res = g                         written only when d_res != NULL (a caller asks only when there was a ReLU and a residual;
+ *                                     without a ReLU the gradient of the residual is d_out itself)
+ *   no GN (pre == gamma == NULL):  dT = g
+ *   GN:   xhat, rstd recomputed per 32-row tile from the saved `pre`;  dT = GN backward of g (formula of lgcn_gn_bwd);
+ *         dgamma += g * xhat;  dbeta += g
+ *   for r < n_rel (1 or 2):   d_src[r] = dT W_r        (on wpt[r], the lgcn_pack_weight_t LGCN_MMA_F32 image of the 128 x 128 block)
+ *                             d_w[r]  += dT (x) src_r  (v_mfma_f32_32x32x2_f32), written with row stride ld_w[r]
+ *   d_out, out, pre, src[r], d_src[r], d_res: [n_rows,128];  gamma, d_gamma, d_beta: [128]
+ *   src[r], wpt[r]: required for r < n_rel;  pre and gamma: both or neither;  d_gamma / d_beta without them: LGCN_EINVAL
+ *   d_src[r], d_w[r], d_res, d_gamma, d_beta: each may be NULL and its work is then skipped.  Rows >= n_rows of d_src[r] /
+ *           d_res are never written.
+ *   d_w[r]: the [128,128] block at columns col0 .. col0 + 128 of a row-major [128,K] gradient: the pointer to element
+ *           (0, col0), ld_w[r] = K floats (>= 128, a multiple of 4; 16-byte alignment asks the same of col0).  Only the
+ *           block is written; two relations may name two blocks of one gradient.
+ *   n_chunks: 1..1024 workgroups (never more than ceil(n_rows / 32) are launched): workgroup k owns the tiles k,
+ *           k + n_chunks, ... and writes one record of n_rel * 128 * 128 + 2 * 128 floats -- dW_0, dW_1 (two relations
+ *           only), dgamma, dbeta; the second launch sums the records in chunk order into the outputs asked for.
+ *   ws:     lgcn_rowblock_bwd_ws_elems(n_rows, n_chunks, n_rel) floats (negative: LGCN_EINVAL for n_rows < 0 or above
+ *           0x7fffffff, n_chunks outside 1..1024 or n_rel outside 1..2); needed when any of d_w[r], d_gamma, d_beta is
+ *           given.  Without one of them there is no record and no second launch.
+ * Checked before anything is launched, in this order: the struct, n_rows (negative: LGCN_EINVAL, above 0x7fffffff:
+ * LGCN_ESHAPE), n_rel, n_chunks, the required pointers, ld_w, then 16-byte alignment of every pointer (LGCN_EALIGN; those of
+ * an unused second relation included).  n_rows == 0, or every output NULL: LGCN_OK without a launch.
+ */
+typedef struct {
+    const float *d_out, *out, *pre, *gamma;
+    const float *src[2], *wpt[2];
+    float *d_src[2], *d_w[2];
+    float *d_res, *d_gamma, *d_beta, *ws;
+    int64_t n_rows;
+    int32_t ld_w[2];
+    float eps;
+    int32_t n_rel, n_chunks, pad_;
+} lgcn_rowblock_bwd_t;
+
+int64_t lgcn_rowblock_bwd_ws_elems(int64_t n_rows, int n_chunks, int n_rel);
+int lgcn_rowblock_bwd(const lgcn_rowblock_bwd_t *p_host, void *stream);
+
+/*
  * Forward of  out = [ReLU]( GroupNorm(1,128)(x) [+ res] )  as a stand-alone row kernel (the fused
  * kernels do this in their epilogues; the differentiable per-pair composition needs it alone).
  * gamma == NULL: no normalisation.  relu != 0 applies the ReLU.

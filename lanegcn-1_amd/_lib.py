@@ -84,6 +84,16 @@ class LaneConvBwd(C.Structure):   # lgcn_laneconv_bwd_t
     ]
 
 
+class RowBlockBwd(C.Structure):   # lgcn_rowblock_bwd_t
+    _fields_ = [
+        ("d_out", C.c_void_p), ("out", C.c_void_p), ("pre", C.c_void_p), ("gamma", C.c_void_p),
+        ("src", C.c_void_p * 2), ("wpt", C.c_void_p * 2), ("d_src", C.c_void_p * 2), ("d_w", C.c_void_p * 2),
+        ("d_res", C.c_void_p), ("d_gamma", C.c_void_p), ("d_beta", C.c_void_p), ("ws", C.c_void_p),
+        ("n_rows", C.c_int64), ("ld_w", C.c_int32 * 2), ("eps", C.c_float), ("n_rel", C.c_int32), ("n_chunks", C.c_int32),
+        ("pad_", C.c_int32),
+    ]
+
+
 class AggMlp(C.Structure):
     _fields_ = [
         ("n_rows", C.c_int64), ("n_rel", C.c_int32), ("n_rel_csr", C.c_int32),
@@ -156,6 +166,8 @@ SIGNATURES = {
     "lgcn_att_pairs_bwd": (C.c_int, [C.POINTER(AttPairsBwd), _P]),
     "lgcn_laneconv_bwd_ws_elems": (C.c_int64, [_L, _I, _I]),
     "lgcn_laneconv_bwd": (C.c_int, [C.POINTER(LaneConvBwd), _P]),
+    "lgcn_rowblock_bwd_ws_elems": (C.c_int64, [_L, _I, _I]),
+    "lgcn_rowblock_bwd": (C.c_int, [C.POINTER(RowBlockBwd), _P]),
     "lgcn_conv_packed_bytes": (C.c_int64, [_I, _I, _I]),
     "lgcn_conv_pack_weight": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "lgcn_conv1d_gn": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P]),

@@ -6,6 +6,9 @@ kernels on transposed plans / transposed weights plus three backward kernels:
                                  gather-by-destination is a gather-by-source on the transposed plan)
   GroupNorm / ReLU backward  -> lgcn_gn_bwd   (deterministic dgamma / dbeta)
   weight gradients           -> lgcn_wgrad    (dW_r = dT^T (G_r src_r), fp32-input MFMA)
+Every Function also has a fused exact-fp32 backward, opt-in: RowBlockFn with RowBlockFn.train_hip (one or two IDENT
+relations: lgcn_rowblock_bwd does the whole backward in one launch pair; blocks with a RANGE or CSR relation keep the
+composition above) and LaneConvFn with BlockSpec.fused_bwd (lgcn_laneconv_bwd).
 Att's pair stage has a fused pair of its own (Att.train_hip): AttPairsFn on lgcn_att_pairs_train / lgcn_att_pairs_bwd.
 PredNet's tail (the heads' nn.Linear(128, 2 T), AttDest's first layer, the score Linear, the sort and the gather) has
 its own pair: PredRegFn / PredFinalFn on lgcn_pred_reg / lgcn_pred_final_train and their backward entries.
@@ -49,7 +52,8 @@ class BlockSpec:
     seg_ids: Optional[torch.Tensor] = None     # RANGE relation: segment id of every source row (int32)
     n_seg_rows: Optional[torch.Tensor] = None  # device count of valid source rows (int32 [1])
     tag: Optional[str] = None
-    fused_bwd: bool = False                    # LaneConvFn: backward on lgcn_laneconv_bwd (exact fp32) instead of the composed one
+    fused_bwd: bool = False                    # backward on lgcn_laneconv_bwd (LaneConvFn) / lgcn_rowblock_bwd (RowBlockFn), exact
+                                               # fp32, instead of the composed one
 
 
 def _fwd_rels(spec: BlockSpec, srcs, weights):
@@ -109,7 +113,11 @@ def _stage_backward(spec: BlockSpec, srcs, weights, dT, need_src, need_w, res_gr
 
 class RowBlockFn(Function):
     """out = [ReLU]( [GN]( sum_r (G_r src_r) W_r^T ) [+ res] )  -- layers.Linear, Att.query / agt+ctx.1 tail,
-    the pure Linear stages (gn = relu = False)."""
+    the pure Linear stages (gn = relu = False).  Backward is composed, or with spec.fused_bwd, for the blocks that
+    _fused_ok() accepts, the fused lgcn_rowblock_bwd."""
+    # Default of BlockSpec.fused_bwd for the blocks built by row_block(): one switch for every module behind it
+    # (layers.Linear, the input stems, A2M.meta, AttDest, the node side of Att, lanercnn.py).  Opt-in, like Att.train_hip.
+    train_hip = False
 
     @staticmethod
     def forward(ctx, spec: BlockSpec, n_src: int, n_w: int, *tensors):
@@ -139,6 +147,8 @@ class RowBlockFn(Function):
         ni = ctx.needs_input_grad          # (spec, n_src, n_w, *tensors)
         need_src = [ni[3 + i] for i in range(n_src)]
         need_w = [ni[3 + n_src + i] for i in range(n_w)]
+        if spec.fused_bwd and RowBlockFn._fused_ok(spec, d_out, weights):
+            return RowBlockFn._backward_fused(spec, ni, d_out, srcs, weights, gn_w, pre, out)
         d_gw = d_gb = d_res = None
         if spec.gn or spec.relu:
             dT, g, d_gw, d_gb = ops.gn_bwd(d_out, pre, out if spec.relu else None, gn_w if spec.gn else None,
@@ -150,6 +160,45 @@ class RowBlockFn(Function):
         with ops.backward_mma():
             d_srcs, d_ws = _stage_backward(spec, srcs, weights, dT, need_src, need_w)
         return (None, None, None, *d_srcs, *d_ws, d_gw, d_gb, d_res)
+
+    @staticmethod
+    def _fused_ok(spec, d_out, weights):
+        """What lgcn_rowblock_bwd covers: CUDA fp32 rows, one or two IDENT relations on distinct sources and distinct
+        128-column blocks ([128, K] weights, K and col0 multiples of 4: the block's gradient is written in place)."""
+        rels = spec.rels
+        if not (d_out.is_cuda and d_out.dtype == torch.float32 and spec.n_rows > 0 and 1 <= len(rels) <= 2):
+            return False
+        if any(r.mode != L.REL_IDENT for r in rels) or len({r.src for r in rels}) != len(rels):
+            return False
+        if len(rels) == 2 and rels[0].w == rels[1].w and abs(rels[0].col0 - rels[1].col0) < C_FEAT:
+            return False                      # the same (or an overlapping) block twice: its gradient is a sum
+        if len(rels) == 2 and rels[0].w != rels[1].w and weights[rels[0].w].data_ptr() == weights[rels[1].w].data_ptr():
+            return False                      # one parameter passed as two weight arguments: autograd adds their gradients
+        for r in rels:
+            w = weights[r.w]
+            if w.dim() != 2 or w.shape[0] != C_FEAT or r.col0 < 0 or r.col0 + C_FEAT > w.shape[1] or w.shape[1] % 4 or r.col0 % 4:
+                return False
+        return True
+
+    @staticmethod
+    def _backward_fused(spec, ni, d_out, srcs, weights, gn_w, pre, out):
+        """BlockSpec.fused_bwd: the whole backward in one launch pair (lgcn_rowblock_bwd); inputs that need no gradient
+        cost nothing."""
+        n_src, n_w = len(srcs), len(weights)
+        i_gn = 3 + n_src + n_w
+        need_w = [ni[3 + n_src + i] for i in range(n_w)]
+        want_res = spec.has_res and spec.relu and ni[i_gn + 2]
+        g = ops.rowblock_bwd(d_out, out if spec.relu else None, pre if spec.gn else None, gn_w if spec.gn else None,
+                             [(srcs[r.src], weights[r.w], r.col0) for r in spec.rels],
+                             want_src=[ni[3 + r.src] for r in spec.rels], want_w=[need_w[r.w] for r in spec.rels],
+                             want_gn=spec.gn and (ni[i_gn] or ni[i_gn + 1]), want_res=want_res, eps=spec.eps)
+        d_srcs: List[Optional[torch.Tensor]] = [None] * n_src
+        d_ws: List[Optional[torch.Tensor]] = [None] * n_w
+        for i, r in enumerate(spec.rels):
+            d_srcs[r.src] = g["d_src"][i]
+            d_ws[r.w] = g["d_w"][g["w_index"][i]]
+        d_res = g["d_res"] if spec.relu else (d_out if spec.has_res else None)
+        return (None, None, None, *d_srcs, *d_ws, g["d_gamma"], g["d_beta"], d_res)
 
 
 class LaneConvFn(Function):
@@ -424,7 +473,8 @@ class GatherSumFn(Function):
 
 # ------------------------------------------------------------------ convenience wrappers
 def row_block(srcs, weights, rels, n_rows, gn=None, relu=False, res=None, **kw):
-    """Differentiable row block.  gn: nn.GroupNorm or None."""
+    """Differentiable row block.  gn: nn.GroupNorm or None.  fused_bwd (default: RowBlockFn.train_hip): see BlockSpec."""
+    kw.setdefault("fused_bwd", RowBlockFn.train_hip)
     spec = BlockSpec(n_rows=n_rows, rels=rels, gn=gn is not None, relu=relu, has_res=res is not None,
                      eps=gn.eps if gn is not None else ops.EPS, **kw)
     gw, gb = (gn.weight, gn.bias) if gn is not None else (None, None)

@@ -891,6 +891,130 @@ __global__ __launch_bounds__(256) void k_lc_bwd_reduce(const float *__restrict__
     *dst = s;
 }
 
+// ------------------------------------------------------ row block bwd -----
+// Backward of one row block out = [ReLU]([GN](sum_r src_r W_r^T) [+ res]) with NREL = 1 or 2 IDENT relations
+// (include/lgcn.h, lgcn_rowblock_bwd): the lower half of k_lc_bwd_rows<true> as a kernel of its own.  Workgroup `chunk`
+// walks the 32-row tiles chunk, chunk + n_chunks, ...  Waves 0-3 are the row phase (8 threads per row: g = d_out masked by
+// out > 0, d_res = g, and with GN the tiles P1 = g * xhat, P2 = g and dT = GroupNorm backward of g; without GN dT = g, so
+// that a plain Linear stages d_out straight into D) and then the NREL tile GEMMs dT W_r -> G_r, which the row threads store
+// behind the barrier.  Waves 4-7 stage the src_r rows and own everything summed over rows, in registers across the
+// workgroup's tiles: dW_r on wgrad_tile (wave 4 + q: block q of every relation) and, with GN, dgamma / dbeta as column sums
+// of P1 / P2.  LDS: D, G_r, S_r (src_r rows) and, with GN, P1 / P2: 3 + 2 (NREL - 1) + 2 GN tiles of 16.5 KiB, seven at
+// the most.  Two barriers per tile.
+struct RbBwdParams {
+    const float *d_out, *out, *pre, *gamma;
+    const float *src[2], *wpt[2];
+    float *d_src[2], *d_res, *rec;
+    int64_t n_rows;
+    float eps;
+    int want_w[2], want_gn;
+};
+
+struct RbBwdOut { float *dw[2], *dg, *db; int ld[2]; };
+
+__host__ __device__ constexpr int rb_rec_floats(int n_rel) { return n_rel * kC * kC + 2 * kC; }
+
+template <int NREL, bool GN>
+__global__ __launch_bounds__(512) void k_rb_bwd_rows(const RbBwdParams p) {
+    constexpr int kTiles = 1 + 2 * NREL + (GN ? 2 : 0);
+    __shared__ __attribute__((aligned(16))) float smem[kTiles * kTileFloats];
+    float *D = smem, *G = smem + kTileFloats, *S = smem + (1 + NREL) * kTileFloats;      // G, S: NREL tiles each
+    float *P1 = smem + (GN ? 1 + 2 * NREL : 0) * kTileFloats, *P2 = smem + (GN ? 2 + 2 * NREL : 0) * kTileFloats;   // GN only
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool rowt = tid < 256;
+    const int which = (tid >> 7) & 1, col = tid & 127;       // waves 4-7: column sums
+    const int64_t n_tiles = (p.n_rows + kTM32 - 1) / kTM32;
+    const bool want_rec = p.rec != nullptr, want_gn = GN && p.want_gn != 0;
+
+    f32x16 A[4 * NREL];
+#pragma unroll
+    for (int k = 0; k < 4 * NREL; ++k)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) A[k][i] = 0.f;
+    float s = 0.f;      // which = 0: dgamma; 1: dbeta
+    f32x16 acc;
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t n = tile * kTM32 + (tid >> 3);
+        const bool live = rowt && n < p.n_rows;
+        // ---- g = d_out * (out > 0) -> d_res; GN: P1 = g * xhat, P2 = g, dT = GN backward of g; dT -> D.  Waves 4-7 stage src_r
+        if (rowt) {
+            RowVals g = row_zero();
+            if (live) {
+                g = row_load_global(p.d_out + n * kC, tid);
+                if (p.out) row_mask_pos(g, row_load_global(p.out + n * kC, tid));
+                if (p.d_res) row_store_global(p.d_res + n * kC, tid, g);
+            }
+            if constexpr (GN) {
+                RowVals x = row_zero();
+                if (live) x = row_load_global(p.pre + n * kC, tid);
+                const float rstd = row_gn_hat(x, p.eps);
+                if (want_gn) { row_store_lds(P1, tid, row_mul(g, x)); row_store_lds(P2, tid, g); }
+                row_gn_bwd(g, x, rstd, tid, p.gamma);
+            }
+            row_store_lds(D, tid, g);
+        } else {
+#pragma unroll
+            for (int r = 0; r < NREL; ++r)
+                if (p.want_w[r]) stage_rows(S + r * kTileFloats, p.src[r], tile, p.n_rows, tid - 256);
+        }
+        __syncthreads();
+        // ---- d_src_r = dT W_r -> G_r (waves 0-3); dW_r += dT^T src_r, dgamma, dbeta (waves 4-7)
+        if (wave < 4) {
+#pragma unroll
+            for (int r = 0; r < NREL; ++r) {
+                if (p.d_src[r] == nullptr) continue;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                tile_gemm(D, reinterpret_cast<const float4 *>(p.wpt[r]) + wave * (16 * 64), acc, lane, 16);
+                acc_to_lds(G + r * kTileFloats, acc, lane, wave);
+            }
+        } else if (want_rec) {
+#pragma unroll
+            for (int r = 0; r < NREL; ++r)
+                if (p.want_w[r]) wgrad_tile(D, S + r * kTileFloats, A[4 * r], A[4 * r + 1], A[4 * r + 2], A[4 * r + 3], wave - 4, lane);
+            if constexpr (GN) {
+                if (want_gn) s += tile_colsum(which ? P2 : P1, col);
+            }
+        }
+        __syncthreads();      // D, P1, P2 and S_r are next written behind this barrier, G_r behind the next one
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < NREL; ++r)
+                if (p.d_src[r]) row_store_global(p.d_src[r] + n * kC, tid, row_load(G + r * kTileFloats, tid));
+        }
+    }
+
+    if (!want_rec || wave < 4) return;
+    float *rec = p.rec + (int64_t)blockIdx.x * rb_rec_floats(NREL);
+#pragma unroll
+    for (int r = 0; r < NREL; ++r)
+        if (p.want_w[r]) wgrad_store(rec + r * kC * kC, A[4 * r], A[4 * r + 1], A[4 * r + 2], A[4 * r + 3], wave - 4, lane);
+    if constexpr (GN) {
+        if (want_gn) rec[NREL * kC * kC + which * kC + col] = s;
+    }
+}
+
+// out = sum over the chunk records, in chunk order.  Record: dW_0 [128,128], dW_1 [128,128] (two relations only), then
+// dgamma, dbeta [128]; dW_r goes out with row stride ld[r] (a 128-column block of a wider weight gradient).
+__global__ __launch_bounds__(256) void k_rb_bwd_reduce(const float *__restrict__ rec, int n_rec, int n_rel, const RbBwdOut o) {
+    const int n_w = n_rel * kC * kC, n_e = n_w + 2 * kC;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_e) return;
+    float *dst = nullptr;
+    if (e < n_w) {
+        const int r = e >> 14, row = (e >> 7) & 127, c = e & 127;
+        if (o.dw[r] != nullptr) dst = o.dw[r] + (int64_t)row * o.ld[r] + c;
+    } else {
+        float *const vec = (e - n_w) < kC ? o.dg : o.db;
+        if (vec != nullptr) dst = vec + (e & 127);
+    }
+    if (dst == nullptr) return;
+    float s = 0.f;
+    for (int k = 0; k < n_rec; ++k) s += rec[(int64_t)k * n_e + e];
+    *dst = s;
+}
+
 }  // namespace lgcn
 
 using namespace lgcn;
@@ -1220,6 +1344,63 @@ int lgcn_laneconv_bwd(const lgcn_laneconv_bwd_t *ph, void *stream) {
         hipLaunchKernelGGL(k_lc_bwd_reduce, dim3((lc_rec_floats(ident1) + 255) / 256), dim3(256), 0, st, a.ws, n_rec,
                            (int)ident1, o);
     }
+    return launch_status();
+}
+
+static_assert(sizeof(lgcn_rowblock_bwd_t) == 20 * 8,
+              "lgcn_rowblock_bwd_t layout: keep lanegcn-1_amd/_lib.py (RowBlockBwd) and tests/test_host_rowblock_bwd_cabi.py in step");
+
+int64_t lgcn_rowblock_bwd_ws_elems(int64_t n_rows, int n_chunks, int n_rel) {
+    if (n_rows < 0 || n_rows > 0x7fffffff || n_chunks < 1 || n_chunks > 1024 || n_rel < 1 || n_rel > 2) return LGCN_EINVAL;
+    return lc_bwd_chunks(n_rows, n_chunks) * rb_rec_floats(n_rel);
+}
+
+int lgcn_rowblock_bwd(const lgcn_rowblock_bwd_t *ph, void *stream) {
+    LGCN_CHECK_PTR(ph);
+    const lgcn_rowblock_bwd_t &a = *ph;
+    if (a.n_rows < 0) return LGCN_EINVAL;
+    if (a.n_rows > 0x7fffffff) return LGCN_ESHAPE;
+    if (a.n_rel < 1 || a.n_rel > 2 || a.n_chunks < 1 || a.n_chunks > 1024) return LGCN_EINVAL;
+    if (a.n_rows == 0) return LGCN_OK;
+    const int n_rel = a.n_rel;
+    const bool gn = a.pre != nullptr;
+    LGCN_CHECK_PTR(a.d_out);
+    if (gn != (a.gamma != nullptr)) return LGCN_EINVAL;
+    if (!gn && (a.d_gamma || a.d_beta)) return LGCN_EINVAL;
+    bool want_rec = a.d_gamma || a.d_beta, want_rows = a.d_res != nullptr;
+    for (int r = 0; r < n_rel; ++r) {
+        LGCN_CHECK_PTR(a.src[r]); LGCN_CHECK_PTR(a.wpt[r]);
+        want_rec = want_rec || a.d_w[r];
+        want_rows = want_rows || a.d_src[r];
+    }
+    if (want_rec) LGCN_CHECK_PTR(a.ws);
+    for (int r = 0; r < n_rel; ++r)
+        if (a.d_w[r] && (a.ld_w[r] < kC || (a.ld_w[r] & 3) != 0)) return LGCN_EINVAL;
+    const void *al[] = {a.d_out, a.out, a.pre, a.gamma, a.src[0], a.src[1], a.wpt[0], a.wpt[1], a.d_src[0], a.d_src[1],
+                        a.d_w[0], a.d_w[1], a.d_res, a.d_gamma, a.d_beta, a.ws};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);      // absent (null) ones pass
+    if (!want_rec && !want_rows) return LGCN_OK;
+    RbBwdParams p{};
+    p.d_out = a.d_out; p.out = a.out; p.pre = a.pre; p.gamma = a.gamma;
+    RbBwdOut o{};
+    for (int r = 0; r < n_rel; ++r) {
+        p.src[r] = a.src[r]; p.wpt[r] = a.wpt[r]; p.d_src[r] = a.d_src[r]; p.want_w[r] = a.d_w[r] != nullptr;
+        o.dw[r] = a.d_w[r]; o.ld[r] = a.ld_w[r];
+    }
+    p.d_res = a.d_res; p.rec = want_rec ? a.ws : nullptr;
+    p.n_rows = a.n_rows; p.eps = a.eps; p.want_gn = a.d_gamma || a.d_beta;
+    o.dg = a.d_gamma; o.db = a.d_beta;
+    const int n_rec = (int)lc_bwd_chunks(a.n_rows, a.n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rel == 2) {
+        if (gn) hipLaunchKernelGGL((k_rb_bwd_rows<2, true>), dim3(n_rec), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((k_rb_bwd_rows<2, false>), dim3(n_rec), dim3(512), 0, st, p);
+    } else {
+        if (gn) hipLaunchKernelGGL((k_rb_bwd_rows<1, true>), dim3(n_rec), dim3(512), 0, st, p);
+        else hipLaunchKernelGGL((k_rb_bwd_rows<1, false>), dim3(n_rec), dim3(512), 0, st, p);
+    }
+    if (want_rec)
+        hipLaunchKernelGGL(k_rb_bwd_reduce, dim3((rb_rec_floats(n_rel) + 255) / 256), dim3(256), 0, st, a.ws, n_rec, n_rel, o);
     return launch_status();
 }
 

@@ -1515,6 +1515,107 @@ def laneconv_bwd(d_out, out, Z, Y, T, gn1_w, w2, gn2_w, *, x=None, w1=None, want
     return res
 
 
+def rowblock_bwd(d_out, out, pre, gn_w, rels, *, want_src=None, want_w=None, want_gn=True, want_res=False, d_src=None,
+                 d_res=None, n_chunks: Optional[int] = None, eps=EPS, tag="rowblock_bwd"):
+    """lgcn_rowblock_bwd: the whole backward of out = [ReLU]([GN](sum_r src_r W_r[:, col0_r:col0_r+128]^T) [+ res]) with
+    one or two IDENT relations, for d_out [N,128], in one launch pair (exact fp32 in every matrix mode).
+      out:  the block's output when it had a ReLU, else None;  pre / gn_w: the saved pre-normalisation tensor and the
+            GroupNorm weight when it had a norm, else both None
+      rels: [(src [N,128], weight [128,K], col0)], K and col0 multiples of 4; the weights are the parameters, their
+            transposed F32 images are made here
+      want_src / want_w: one flag per relation (default: all); want_gn: dgamma / dbeta (ignored without a norm);
+      want_res: g = d_out * (out > 0) as the gradient of the residual
+      d_src / d_res: preallocated outputs (a list with None for the absent ones / a tensor), at least N rows
+    Returns a dict: "d_src" (list per relation, None where not wanted), "d_w" (list per distinct weight, in order of first
+    appearance in rels: a tensor shaped like the weight, zero outside the relations' column blocks, or None when none of
+    its relations wants it), "w_index" (per relation: its weight's place in "d_w"), "d_gamma", "d_beta", "d_res".
+    n_chunks: workgroups, each with one partial record that the reduction launch reads back (default as laneconv_bwd)."""
+    lib = L.load()
+    n_rel = len(rels)
+    if n_rel < 1 or n_rel > 2:
+        raise L.LgcnError("rowblock_bwd: one or two relations, got %d" % n_rel)
+    if (pre is None) != (gn_w is None):
+        raise L.LgcnError("rowblock_bwd: pre and gn_w come together")
+    d_out = _dev(d_out, torch.float32, "d_out")
+    N, dev = d_out.shape[0], d_out.device
+    want_src = [True] * n_rel if want_src is None else [bool(f) for f in want_src]
+    want_w = [True] * n_rel if want_w is None else [bool(f) for f in want_w]
+    want_gn = bool(want_gn) and pre is not None
+    q = L.RowBlockBwd()
+    q.d_out = d_out.data_ptr()
+    keep = [d_out]
+    if out is not None:
+        out = _dev(out, torch.float32, "out")
+        q.out = out.data_ptr()
+    if pre is not None:
+        pre = _dev(pre, torch.float32, "pre")
+        q.pre, q.gamma = pre.data_ptr(), gn_w.data_ptr()
+    ws_of, w_index = [], []           # distinct weights, by identity
+    for r, (src, w, col0) in enumerate(rels):
+        if w.dim() != 2 or w.shape[0] != C_FEAT or col0 < 0 or col0 + C_FEAT > w.shape[1] or w.shape[1] % 4 or col0 % 4:
+            raise L.LgcnError("rowblock_bwd: relation %d needs a [128, K] weight with col0 + 128 <= K, K and col0 multiples of 4" % r)
+        src = _dev(src, torch.float32, "src")
+        keep.append(src)
+        with exact_mma():
+            wpt = packed_t(w, col0)
+        keep.append(wpt)
+        q.src[r], q.wpt[r] = src.data_ptr(), wpt.data_ptr()
+        k = next((i for i, t in enumerate(ws_of) if t is w), None)
+        if k is None:
+            k = len(ws_of)
+            ws_of.append(w)
+        w_index.append(k)
+    res = {"d_src": [None] * n_rel, "d_w": [None] * len(ws_of), "w_index": w_index, "d_gamma": None, "d_beta": None,
+           "d_res": None}
+    rows = lambda: torch.empty((N, C_FEAT), dtype=torch.float32, device=dev)
+
+    def given(buf, name):
+        if buf.shape[0] < N or not buf.is_contiguous() or buf.dtype != torch.float32 or not buf.is_cuda:
+            raise L.LgcnError("rowblock_bwd: %s must be a contiguous float32 [>= %d, 128]" % (name, N))
+        return buf
+
+    for r in range(n_rel):
+        if want_src[r]:
+            buf = None if d_src is None else d_src[r]
+            res["d_src"][r] = rows() if buf is None else given(buf, "d_src[%d]" % r)
+            q.d_src[r] = res["d_src"][r].data_ptr()
+    if want_res:
+        res["d_res"] = rows() if d_res is None else given(d_res, "d_res")
+        q.d_res = res["d_res"].data_ptr()
+    for k, w in enumerate(ws_of):
+        cols = sorted(rels[r][2] for r in range(n_rel) if w_index[r] == k and want_w[r])
+        if not cols:
+            continue
+        if len(cols) == 2 and cols[1] - cols[0] < C_FEAT:
+            raise L.LgcnError("rowblock_bwd: two relations on overlapping column blocks of one weight")
+        K = w.shape[1]
+        full = cols[0] == 0 and all(b - a == C_FEAT for a, b in zip(cols, cols[1:])) and cols[-1] + C_FEAT == K
+        res["d_w"][k] = (torch.empty if full else torch.zeros)((C_FEAT, K), dtype=torch.float32, device=dev)
+    for r in range(n_rel):
+        if want_w[r]:
+            g = res["d_w"][w_index[r]]
+            q.d_w[r], q.ld_w[r] = g.data_ptr() + 4 * rels[r][2], g.shape[1]
+    if want_gn:
+        res["d_gamma"] = torch.empty(C_FEAT, dtype=torch.float32, device=dev)
+        res["d_beta"] = torch.empty(C_FEAT, dtype=torch.float32, device=dev)
+        q.d_gamma, q.d_beta = res["d_gamma"].data_ptr(), res["d_beta"].data_ptr()
+    if n_chunks is None:
+        n_chunks = min(cu_count(dev), (N + 127) // 128)
+    n_chunks = max(1, min(int(n_chunks), (N + 31) // 32, 1024))
+    if want_gn or any(want_w):
+        n_ws = lib.lgcn_rowblock_bwd_ws_elems(N, n_chunks, n_rel)
+        if n_ws < 0:
+            raise L.LgcnError("rowblock_bwd: n_rows = %d / n_chunks = %d not supported" % (N, n_chunks))
+        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        keep.append(ws)
+        q.ws = ws.data_ptr()
+    q.n_rows, q.eps, q.n_rel, q.n_chunks = N, eps, n_rel, n_chunks
+    with _Timed(tag):
+        rc = lib.lgcn_rowblock_bwd(C.byref(q), _stream())
+    L.check(rc, "lgcn_rowblock_bwd")
+    return res
+
+
 def gather_rows(src, idx, n_dev, cap):
     lib = L.load()
     src = _dev(src, torch.float32, "src")

@@ -13,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import lanegcn_amd  # noqa: E402,F401
+from lanegcn_amd import autograd as A  # noqa: E402
 from lanegcn_amd import data as gen  # noqa: E402
 from lanegcn_amd import lanegcn as M  # noqa: E402
 from lanegcn_amd import layers  # noqa: E402
@@ -37,26 +38,33 @@ def main():
                     help="LaneConv / LinearRes backward: 'hip' sets MapNet.train_hip, M2M.train_hip and LinearRes.train_hip "
                          "(lgcn_laneconv_bwd), 'stock' leaves the composed launches; 'ab': both, alternating step by step after "
                          "a warm-up of each")
+    ap.add_argument("--rb-impl", default=None, choices=["hip", "stock", "ab"],
+                    help="Row-block backward (layers.Linear, the input stems, A2M.meta, AttDest, the node side of Att): 'hip' sets "
+                         "autograd.RowBlockFn.train_hip (lgcn_rowblock_bwd), 'stock' leaves the composed launches; 'ab': both, "
+                         "alternating step by step after a warm-up of each")
     ap.add_argument("--actor-exact", action="store_true",
                     help="ActorNet.exact: the 'hip' ActorNet on the exact-fp32 units (any --mma)")
     args = ap.parse_args()
     M.ActorNet.exact = args.actor_exact
     if args.mma:
         ops.set_mma(args.mma)
-    if [args.actor_impl, args.pred_impl, args.att_impl, args.lc_impl].count("ab") > 1:
-        ap.error("one of --actor-impl / --pred-impl / --att-impl / --lc-impl can alternate at a time")
+    if [args.actor_impl, args.pred_impl, args.att_impl, args.lc_impl, args.rb_impl].count("ab") > 1:
+        ap.error("one of --actor-impl / --pred-impl / --att-impl / --lc-impl / --rb-impl can alternate at a time")
     actor_impls = ["hip", "miopen"] if args.actor_impl == "ab" else [args.actor_impl or M.ActorNet.impl]
     pred_impls = ["hip", "stock"] if args.pred_impl == "ab" else [args.pred_impl or "stock"]
     att_impls = ["hip", "stock"] if args.att_impl == "ab" else [args.att_impl or "stock"]
     lc_impls = ["hip", "stock"] if args.lc_impl == "ab" else [args.lc_impl or "stock"]
-    # a variant of the step: (ActorNet.impl, PredNet's training tail, Att's pair stage, the LaneConv / LinearRes backward);
-    # its name is the side that alternates
-    impls = [(a, p, t, c) for a in actor_impls for p in pred_impls for t in att_impls for c in lc_impls]
-    name = lambda v: v[3] if args.lc_impl == "ab" else v[2] if args.att_impl == "ab" else v[1] if args.pred_impl == "ab" else v[0]
+    rb_impls = ["hip", "stock"] if args.rb_impl == "ab" else [args.rb_impl or "stock"]
+    # a variant of the step: (ActorNet.impl, PredNet's training tail, Att's pair stage, the LaneConv / LinearRes backward, the
+    # row-block backward); its name is the side that alternates
+    impls = [(a, p, t, c, r) for a in actor_impls for p in pred_impls for t in att_impls for c in lc_impls for r in rb_impls]
+    name = lambda v: (v[4] if args.rb_impl == "ab" else v[3] if args.lc_impl == "ab" else v[2] if args.att_impl == "ab"
+                      else v[1] if args.pred_impl == "ab" else v[0])
 
     def select(v):
         M.ActorNet.impl, M.PredNet.train_hip, M.Att.train_hip = v[0], v[1] == "hip", v[2] == "hip"
         M.MapNet.train_hip = M.M2M.train_hip = layers.LinearRes.train_hip = v[3] == "hip"
+        A.RowBlockFn.train_hip = v[4] == "hip"
 
     select(impls[0])
     if args.actor_impl:
@@ -112,6 +120,7 @@ def main():
            "pred_impl": pred_impls[0] if len(pred_impls) == 1 else "ab",
            "att_impl": att_impls[0] if len(att_impls) == 1 else "ab",
            "lc_impl": lc_impls[0] if len(lc_impls) == 1 else "ab",
+           "rb_impl": rb_impls[0] if len(rb_impls) == 1 else "ab",
            "spread_step_ms": {k: [float(np.percentile(v, 25)), float(np.percentile(v, 75))] for k, v in per_step.items()},
            "median_step_ms": {k: float(np.median(v)) for k, v in per_step.items()}}
     print(json.dumps(res), flush=True)

@@ -886,6 +886,50 @@ int lgcn_conv1d_gn_f32(const float *x, int64_t n_act, int lin, int cin, const vo
                        const float *gamma, const float *beta, float eps, const float *res, int res_mode, int relu,
                        float *out, float *y /* NULL: inference */, void *stream);
 
+/*
+ * Optimizer step (reference utils.py:98-162: Optimizer.step = clip, then torch.optim's Adam / AdamW / SGD): the gradient
+ * clamp and the update of many fp32 tensors, in place, in ONE launch.  Exact fp32, every operation rounded on its own
+ * (no fused multiply-add), in the order of torch.optim's single-tensor path; one thread per element, no atomics, no
+ * LDS, no scratch: bitwise repeatable.
+ *
+ * tensors : DEVICE array of n_tensors lgcn_opt_tensor_t.  p, g: parameter and gradient, n contiguous floats each.
+ *           m: exp_avg (Adam / AdamW) or the momentum buffer (SGD; unused and may be NULL when momentum == 0).
+ *           v: exp_avg_sq (NULL for SGD).  Any alignment of 4 bytes is accepted: a chunk whose four pointers are all
+ *           16-byte aligned moves 16 bytes per access, any other chunk 4 bytes.  n == 0 is allowed.
+ * chunks  : DEVICE array int32 [n_chunks][2] of (tensor id, first element); a chunk covers elements
+ *           [first, min(first + lgcn_opt_chunk_elems(), n)) of its tensor, first % lgcn_opt_chunk_elems() == 0 (the
+ *           chunk length is a multiple of 4).  The caller lists every chunk of every tensor it wants updated exactly
+ *           once.  Workgroups of 256 threads grid-stride over the chunks (at most 2048 workgroups).  A row whose tensor
+ *           id or first element lies outside its table, or whose tensor lacks a pointer the kind needs, is skipped.
+ * One launch = one (parameter group, step count) segment: lr and the step count t are scalars of the launch.
+ *
+ * Per element, with the host's double hyper-parameters rounded to float once (w1 = 1 - beta1, w2 = 1 - beta2,
+ * s = lr / bc1, r = sqrt(bc2), d = 1 - lr * wd), bc1 = 1 - beta1^t and bc2 = 1 - beta2^t computed by the caller in
+ * double as torch.optim computes them:
+ *   clip_on          : g = g < clip_low ? clip_low : g > clip_high ? clip_high : g, STORED to g (the reference clamps
+ *                      p.grad in place); a NaN stays NaN, like clamp_.  Nothing else is written to g.
+ *   LGCN_OPT_ADAM    : if wd: g' = g + wd * p (a temporary)      m = m + w1 * (g' - m)   [w1 >= 0.5: g' - (g' - m) * (1 - w1)]
+ *                      v = v * beta2 + w2 * (g' * g')             p = p + (-s) * (m / (sqrt(v) / r + eps))
+ *   LGCN_OPT_ADAMW   : if wd: p = p * d; then LGCN_OPT_ADAM with wd = 0.
+ *   LGCN_OPT_SGD     : if wd: g' = g + wd * p.  momentum != 0: m = first_step ? g' : m * momentum + g'; g' = m.
+ *                      p = p + (-lr) * g'.  (dampening 0, no Nesterov; momentum == 0: no buffer is read or written)
+ * amsgrad and maximize are not implemented.  first_step is read by LGCN_OPT_SGD only (m is not read on it); beta1,
+ * beta2, eps, bc1, bc2 by the Adam kinds only; momentum by LGCN_OPT_SGD only.
+ *
+ * Returns LGCN_EINVAL, launching nothing, for an unknown kind, n_chunks < 0, n_tensors < 0, a non-finite lr,
+ * clip_on with clip_low > clip_high (or a NaN bound), an Adam kind with bc1 <= 0 or bc2 <= 0, and for n_chunks > 0
+ * with a NULL table or n_tensors == 0.  n_chunks == 0 with valid scalars returns LGCN_OK without launching.
+ */
+enum { LGCN_OPT_ADAM = 0, LGCN_OPT_ADAMW = 1, LGCN_OPT_SGD = 2 };
+typedef struct {
+    float *p, *g, *m, *v;
+    int64_t n;
+} lgcn_opt_tensor_t;
+int lgcn_opt_chunk_elems(void);
+int lgcn_opt_step(const lgcn_opt_tensor_t *tensors, int n_tensors, const int32_t *chunks, int n_chunks, int kind,
+                  double lr, double beta1, double beta2, double eps, double weight_decay, double momentum, int first_step,
+                  double bc1, double bc2, int clip_on, float clip_low, float clip_high, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,7 +124,14 @@ class LaneConv(C.Structure):      # lgcn_laneconv_t
     ]
 
 
-_P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
+class OptTensor(C.Structure):     # lgcn_opt_tensor_t
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
+
+
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
+OPT_KINDS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}
+
+_P, _I, _L, _F, _D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol include/lgcn.h declares
 SIGNATURES = {
@@ -201,6 +208,8 @@ SIGNATURES = {
     "lgcn_conv_packed_f32_bytes": (C.c_int64, [_I, _I, _I]),
     "lgcn_conv_pack_weight_f32": (C.c_int, [_P, _I, _I, _I, _P, _P]),
     "lgcn_conv1d_gn_f32": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P, _P]),
+    "lgcn_opt_chunk_elems": (C.c_int, []),
+    "lgcn_opt_step": (C.c_int, [_P, _I, _P, _I, _I, _D, _D, _D, _D, _D, _D, _I, _D, _D, _I, _F, _F, _P]),
 }
 
 _lib = None

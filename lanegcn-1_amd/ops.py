@@ -773,9 +773,12 @@ def _register_pack(weight, key, out, col0, transpose, mma):
     _pack_jobs.append([weakref.ref(weight), key, out, col0, transpose, mma])
 
 
-def refresh_packed() -> int:
+def refresh_packed(force: bool = False) -> int:
     """Re-pack, in place, every registered image whose parameter changed since it was packed (optimizer step:
-    reference train.py:190).  One launch per matrix-core mode in use.  Returns the number of images rebuilt."""
+    reference train.py:190).  One launch per matrix-core mode in use.  Returns the number of images rebuilt.
+    force: every live registered image of a CUDA weight is rebuilt and restamped without looking at its stamp -- for a
+    writer that goes through raw pointers (optim_hip.FusedOptim), after which (data_ptr, _version) says nothing; the
+    device table of the last such call is reused while the job list is unchanged."""
     if not _pack_jobs:
         return 0
     lib = L.load()
@@ -789,7 +792,7 @@ def refresh_packed() -> int:
         if entry is None or entry[1] is not job[2] or not w.is_cuda:
             continue                     # cache entry dropped or replaced: nothing to refresh
         alive.append(job)
-        if entry[0] != (w.data_ptr(), w._version, w.device):
+        if force or entry[0] != (w.data_ptr(), w._version, w.device):
             stale.setdefault(job[5], []).append((job, w))
     _pack_jobs[:] = alive
     n = 0

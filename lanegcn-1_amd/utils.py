@@ -39,7 +39,11 @@ class StepLR:
 
 
 class Optimizer(object):
-    """torch.optim wrapper whose step(epoch) sets lr = lr_func(epoch) * coef first (reference utils.py:98-162)."""
+    """torch.optim wrapper whose step(epoch) sets lr = lr_func(epoch) * coef first (reference utils.py:98-162).
+    train_hip (class switch, read at construction, off by default): clip and update run in one HIP launch
+    (optim_hip.FusedOptim, lgcn_opt_step) when every parameter is a CUDA fp32 tensor; same state_dict format."""
+
+    train_hip = False
 
     def __init__(self, params, config, coef=None):
         if not isinstance(params, (list, tuple)):
@@ -54,7 +58,16 @@ class Optimizer(object):
         groups = [{"params": p, "lr": 0} for p in params]
         kind = config["opt"]
         assert kind in ("sgd", "adam", "adamw")
-        if kind == "sgd":
+        self.fused = False
+        if self.train_hip:
+            from . import optim_hip
+            groups = [{"params": [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"]), "lr": 0} for g in groups]
+            self.fused = optim_hip.eligible([p for g in groups for p in g["params"]])
+        if self.fused:
+            hyper = (dict(momentum=config["momentum"], weight_decay=config["wd"]) if kind == "sgd" else dict(weight_decay=0)
+                     if kind == "adam" else dict(weight_decay=config.get("weight_decay", 0.01)))      # the stock lines' arguments
+            self.opt = optim_hip.FusedOptim(groups, kind, **hyper)
+        elif kind == "sgd":
             self.opt = optim.SGD(groups, momentum=config["momentum"], weight_decay=config["wd"])
         elif kind == "adam":
             self.opt = optim.Adam(groups, weight_decay=0)
@@ -69,13 +82,17 @@ class Optimizer(object):
         self.opt.zero_grad()
 
     def step(self, epoch):
-        if self.clip_grads:
+        if self.clip_grads and not self.fused:
             self.clip()
         lr = self.lr_func(epoch)
         for c, g in zip(self.coef, self.opt.param_groups):
             g["lr"] = lr * c
-        self.opt.step()
         from . import ops
+        if self.fused:
+            self.opt.step(clip=(self.clip_low, self.clip_high) if self.clip_grads else None)      # the clamp is in the launch
+            ops.refresh_packed(force=True)     # written through raw pointers: every registered image, whatever its stamp
+            return lr
+        self.opt.step()
         ops.refresh_packed()     # the MFMA images of the weights, rebuilt in one launch (else: one per weight on first use)
         return lr
 

@@ -18,6 +18,7 @@ from lanegcn_amd import data as gen  # noqa: E402
 from lanegcn_amd import lanegcn as M  # noqa: E402
 from lanegcn_amd import layers  # noqa: E402
 from lanegcn_amd import ops  # noqa: E402
+from lanegcn_amd import utils  # noqa: E402
 
 
 def main():
@@ -42,6 +43,9 @@ def main():
                     help="Row-block backward (layers.Linear, the input stems, A2M.meta, AttDest, the node side of Att): 'hip' sets "
                          "autograd.RowBlockFn.train_hip (lgcn_rowblock_bwd), 'stock' leaves the composed launches; 'ab': both, "
                          "alternating step by step after a warm-up of each")
+    ap.add_argument("--opt-impl", default="stock", choices=["hip", "stock"],
+                    help="the optimizer step: 'hip' sets utils.Optimizer.train_hip (lgcn_opt_step), 'stock' leaves torch.optim.  A "
+                         "choice for the whole process, not 'ab': the optimizer's state makes interleaved steps meaningless")
     ap.add_argument("--actor-exact", action="store_true",
                     help="ActorNet.exact: the 'hip' ActorNet on the exact-fp32 units (any --mma)")
     args = ap.parse_args()
@@ -73,7 +77,10 @@ def main():
     torch.autograd.set_multithreading_enabled(False)      # what train_dp.py does for its loop
     net = M.Net(M.config).cuda().train()
     loss_fn = M.Loss(M.config).cuda()
+    utils.Optimizer.train_hip = args.opt_impl == "hip"
     opt = M.Optimizer(net.parameters(), M.config)
+    assert opt.fused == (args.opt_impl == "hip")
+    opt_host, opt_dev = [], []           # of opt.step alone: host time to enqueue it (no sync), device time between two events
     batch = gen.collate_fn(gen.synth_batch("S2", seed=5))
     stages = {}
 
@@ -87,9 +94,16 @@ def main():
         lo["loss"].backward()
         if timed:
             torch.cuda.synchronize(); marks.append(time.perf_counter())
+        if timed:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+            t_opt = time.perf_counter()
         opt.step(i / 6436.0)
         if timed:
+            opt_host.append((time.perf_counter() - t_opt) * 1e3)
+            ev[1].record()
             torch.cuda.synchronize(); marks.append(time.perf_counter())
+            opt_dev.append(ev[0].elapsed_time(ev[1]))
             for k, a, b in zip(("forward", "loss+backward", "adam"), marks[:-1], marks[1:]):
                 stages.setdefault(k, []).append((b - a) * 1e3)
         return float(lo["loss"].detach())
@@ -111,7 +125,7 @@ def main():
             per_step[name(impl)].append((time.perf_counter() - t1) * 1e3)
     ms = (time.perf_counter() - t0) / (args.steps * len(impls)) * 1e3
     select(impls[0])
-    for i in range(5):
+    for i in range(max(5, args.steps)):
         step(args.warmup + args.steps + i, timed=True)
     res = {"metric": "training step (forward + loss + backward + Adam), batch 32, S2", "mma": ops.get_mma(),
            "ms_per_step": ms, "scenes_per_s": 32e3 / ms, "loss_first": losses[0], "loss_last": losses[-1],
@@ -121,6 +135,11 @@ def main():
            "att_impl": att_impls[0] if len(att_impls) == 1 else "ab",
            "lc_impl": lc_impls[0] if len(lc_impls) == 1 else "ab",
            "rb_impl": rb_impls[0] if len(rb_impls) == 1 else "ab",
+           "opt_impl": args.opt_impl,
+           "opt_step_host_ms": {"median": float(np.median(opt_host)), "p25": float(np.percentile(opt_host, 25)),
+                                "p75": float(np.percentile(opt_host, 75))},
+           "opt_step_device_ms": {"median": float(np.median(opt_dev)), "p25": float(np.percentile(opt_dev, 25)),
+                                  "p75": float(np.percentile(opt_dev, 75))},
            "spread_step_ms": {k: [float(np.percentile(v, 25)), float(np.percentile(v, 75))] for k, v in per_step.items()},
            "median_step_ms": {k: float(np.median(v)) for k, v in per_step.items()}}
     print(json.dumps(res), flush=True)

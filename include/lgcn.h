@@ -165,7 +165,7 @@ int lgcn_index_build(const lgcn_index_t *p_host, void *stream);
  * anything else: LGCN_ESHAPE.  wp: lgcn_conv_pack_weight image of W [cout, cin, ks] (lgcn_conv_packed_bytes bytes).
  * res_mode 0: no residual; 1: res [A, lout, cout]; 2: res [A, lout / 2, cout], upsampled x2 as
  * F.interpolate(mode = "linear", align_corners = False) (the FPN's top-down step, lanegcn.py:256-260).  relu != 0: ReLU last.
- * Arithmetic: fp16 operand planes (2 planes, 3 products, fp32 accumulate: fp32-grade, |x|, |W| < 65504).
+ * Arithmetic: fp16 operand planes (2 planes, 3 products, fp32 accumulate: fp32-grade inside LGCN_MMA_F16X2's operand window, see below).
  */
 int64_t lgcn_conv_packed_bytes(int cin, int cout, int ks);
 int lgcn_conv_pack_weight(const float *w, int cin, int cout, int ks, void *out, void *stream);
@@ -376,8 +376,12 @@ int lgcn_widen_i32(const int32_t *in, const int32_t *n_dev, int64_t cap,
  *                   3 products hi*hi, hi*lo, lo*hi on v_mfma_f32_16x16x32_f16, fp32 accumulation:
  *                   fp32-grade (dropped terms <= 2^-22 relative; measured equal to fp32's own
  *                   reordering noise on this path) with 2/3 of the weight bytes and half the
- *                   MFMAs of BF16X3.  Operands must stay inside fp16's range (|x| < 65504): true
- *                   behind this network's GroupNorms; use BF16X3 or F32 for unbounded inputs.
+ *                   MFMAs of BF16X3.  Operand window: |x| < 65520 (the first fp32 value that rounds to
+ *                   fp16's infinity), and, because the planes' quantum stops shrinking below fp16's normal
+ *                   range, within 1e-4 of the output's scale only while max |W| of a weight block >= 2^-9
+ *                   (2e-3) and max |x| >= 2^-10 with the other operand O(1) (1e-3 at max |W| = 2^-13, 1e-2 at
+ *                   2^-17; subnormal planes are kept).  True behind this network's GroupNorms with weights of
+ *                   ordinary size; use BF16X3 or F32 for unbounded inputs or small weight blocks.
  */
 enum { LGCN_MMA_F32 = 0, LGCN_MMA_BF16X3 = 1, LGCN_MMA_BF16 = 2, LGCN_MMA_F16X2 = 3 };
 
@@ -859,8 +863,8 @@ int lgcn_gather_rows(const float *src, const int32_t *idx, const int32_t *n_dev,
                      float *out, void *stream);
 
 /*
- * Range check of the 16-bit-plane matrix modes.  LGCN_MMA_F16X2 operands must stay below fp16's 65504 (BF16X3 / BF16:
- * bf16's 3.4e38); an operand beyond that becomes +-inf planes, whose products cancel to NaN, and every ReLU of this
+ * Range check of the 16-bit-plane matrix modes.  LGCN_MMA_F16X2 operands must stay below 65520, the first value that rounds
+ * to fp16's infinity (BF16X3 / BF16: bf16's 3.4e38); an operand from there on becomes +-inf planes, whose products cancel to NaN, and every ReLU of this
  * library keeps a NaN a NaN (like ATen's), so the row it belongs to -- and every row fed by it -- reaches the stage
  * output as NaN rather than as plausible numbers.  lgcn_check_finite looks for that on the device:
  *   flag[0] |= bit  if any of a[0..na) or b[0..nb) is not finite   (a, b 16-byte aligned; flag zeroed by the caller).

@@ -20,8 +20,15 @@ constexpr int kLDB = kC + 8;  // 16-bit elements per LDS plane row (272 B)
 // (x = p0 + p1 (+ p2), each plane the rounding of the residual left by the previous ones);
 // PROD lists the plane pairs (A plane, B plane) that are multiplied, smallest terms first.
 //   F = 0  LGCN_MMA_BF16X3: 3 bf16 planes (3 x 8 bits), 6 products, dropped terms <= 2^-24
-//   F = 1  LGCN_MMA_F16X2 : 2 fp16 planes (2 x 11 bits), 3 products, dropped terms <= 2^-22
-//          (operands must stay below fp16's 65504: true behind the GroupNorms of this network)
+//   F = 1  LGCN_MMA_F16X2 : 2 fp16 planes (2 x 11 bits), 3 products, dropped terms <= 2^-22 WHILE BOTH PLANES ARE
+//          NORMAL fp16 NUMBERS.  The format has a window (DESIGN.md "Operand scale", measured on MI355X):
+//            above: |x| < 65520 (65520 is the first fp32 value that rounds to fp16's infinity: NaN rows);
+//            below: the second plane's quantum stops shrinking at 2^-24, the first plane's below 6.1e-5, so the
+//                   error against fp32 grows as the operand shrinks -- within 1e-4 of the output's scale while
+//                   max |W| >= 2^-9 (2e-3) and max |x| >= 2^-10 (1e-3) with the other operand O(1); 5e-4 .. 1e-3 at
+//                   max |W| = 2^-13, 1e-2 at 2^-17.  Subnormal planes are kept, not flushed (pack kernels, split_store
+//                   and the MFMA alike).
+//          True behind the GroupNorms of this network with weights of ordinary size; BF16X3 has fp32's exponent range.
 //   F = 2  LGCN_MMA_BF16  : 1 bf16 plane, 1 product
 template <int F> struct Fmt;
 template <> struct Fmt<0> {

@@ -40,8 +40,29 @@ __device__ __forceinline__ float sum8(float x) {
     return x;
 }
 
+// 1 / sqrt(var + eps) of a row whose fp32 sum of squares overflowed (centred values beyond ~2^60: var = inf, rstd = 0,
+// and the row would come out as beta): the same sum over the centred values scaled by 2^-68 (exact), rstd scaled back.
+// Rare path behind one compare; a row that holds a NaN or an inf takes it too and comes out NaN as before.  The eight
+// lanes of a row share var, so they take the branch together and sum8 finds its partners.
+// row_gn compiles it in with WIDE (the default): the f32 kernels and the split kernels of the range-safe three-plane
+// mode (Fmt<0>) do.  The fp16-plane kernels pass WIDE = false: their GEMM outputs cannot pass 128 * 15 * 65520^2 < 2^50,
+// whose squares fit (what else reaches a GroupNorm there -- U + V of the pair stage, the rank-4 meta update -- are such
+// outputs or O(1) inputs in this network), and they keep the register budget that lets two workgroups share a CU.  (row_gn_hat, the backward's
+// recomputation, is left as it was: gradients of rows that large leave fp32's range on their own.)
+__device__ __forceinline__ float row_rstd_wide(const RowVals &r, float mean, float eps) {
+    constexpr float k = 0x1p-68f;
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float a = (r.v[j].x - mean) * k, bb = (r.v[j].y - mean) * k, c = (r.v[j].z - mean) * k, d = (r.v[j].w - mean) * k;
+        q += (a * a + bb * bb) + (c * c + d * d);
+    }
+    return k / sqrtf(sum8(q) * (1.0f / kC) + eps * (k * k));
+}
+
 // GroupNorm(1, 128): per-row mean / biased variance over the 128 channels
 // (layers.py:73, gcd(1, n_out) = 1 group), two-pass in registers.
+template <bool WIDE = true>
 __device__ __forceinline__ void row_gn(RowVals &r, int t, const float *__restrict__ g,
                                        const float *__restrict__ b, float eps) {
     float s = 0.f;
@@ -54,7 +75,10 @@ __device__ __forceinline__ void row_gn(RowVals &r, int t, const float *__restric
         const float a = r.v[j].x - mean, bb = r.v[j].y - mean, c = r.v[j].z - mean, d = r.v[j].w - mean;
         q += (a * a + bb * bb) + (c * c + d * d);
     }
-    const float rstd = 1.0f / sqrtf(sum8(q) * (1.0f / kC) + eps);
+    const float var = sum8(q) * (1.0f / kC);
+    float rstd = 1.0f / sqrtf(var + eps);
+    if constexpr (WIDE)
+        if (__builtin_expect(!(var <= 3.4028234e38f), 0)) rstd = row_rstd_wide(r, mean, eps);
     const int c0 = 4 * (t & 7);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

@@ -323,7 +323,7 @@ class HotPathEngine:
         if ops.get_guard() == "off" or ops.get_mma() != "f16x2" or int(out["nonfinite"].item()) == 0:
             return out
         if ops.get_guard() == "raise":
-            raise ops.L.LgcnError("non-finite features in f16x2 mode: an operand left fp16's range (|x| >= 65504)")
+            raise ops.L.LgcnError("non-finite features in f16x2 mode: an operand left fp16's range (|x| >= 65520)")
         with ops.mma_scope("bf16x3"):
             return self.forward(fb, actors, **kw)
 

@@ -1037,7 +1037,7 @@ class Net(nn.Module):
         if ops.get_guard() != "off" and ops.get_mma() == "f16x2" and host[0] != 0:
             # an operand left fp16's range: the forward comes back with NaN rows; policy = re-run in bf16x3 or raise
             if ops.get_guard() == "raise":
-                raise L.LgcnError("non-finite outputs in f16x2 mode: an operand left fp16's range (|x| >= 65504)")
+                raise L.LgcnError("non-finite outputs in f16x2 mode: an operand left fp16's range (|x| >= 65520)")
             dev = fb.node_ctrs.device
             with ops.mma_scope("bf16x3"):
                 out = eng.forward(fb, feats.to(dev), rot.to(dev), orig.to(dev), sizes, return_pairs=Att.strict)

@@ -18,8 +18,11 @@ EPS = 1e-5
 
 # How the 128-d contractions run on the matrix cores (include/lgcn.h, LGCN_MMA_*):
 #   "f32"    exact fp32 fma chain (v_mfma_f32_32x32x2_f32)
-#   "bf16x3" 3-way bf16 split, 6 products, fp32 accumulate: fp32-grade, 2.67x the f32 MFMA rate
-#   "f16x2"  2-way fp16 split, 3 products, fp32 accumulate: fp32-grade (operands < 65504), 5.3x the f32 rate
+#   "bf16x3" 3-way bf16 split, 6 products, fp32 accumulate: fp32-grade over fp32's exponent range, 2.67x the f32 MFMA rate
+#   "f16x2"  2-way fp16 split, 3 products, fp32 accumulate, 5.3x the f32 rate: fp32-grade inside a window -- operands
+#            below 65520 (the first value that rounds to fp16's infinity), and within 1e-4 while a block's max |W| >= 2^-9
+#            (2e-3) and max |x| >= 2^-10 with the other operand O(1); below it the fp16 planes run out of bits (1e-3 at
+#            max |W| = 2^-13, 1e-2 at 2^-17: DESIGN.md "Operand scale"; tools/check_weight_scale.py lists such blocks)
 #   "bf16"   single bf16 product (BASELINE config "bf16"; not within 1e-4)
 _mma = L.MMA_NAMES[os.environ.get("LGCN_MMA", "f16x2")]
 
@@ -76,7 +79,7 @@ def exact_mma() -> mma_scope:
     return mma_scope("f32")
 
 
-# What happens when a forward in the range-restricted default mode (f16x2: operands below 65504) comes back with
+# What happens when a forward in the range-restricted default mode (f16x2: operands below 65520) comes back with
 # non-finite features: "reroute" (default) runs it again in bf16x3 (fp32's exponent range, same fp32-grade
 # accuracy), "raise" raises LgcnError, "off" returns it as it is.
 _guard = os.environ.get("LGCN_GUARD", "reroute")
@@ -118,7 +121,7 @@ def guarded(run, tensors_of=lambda out: (out,)):
     if int(flag.item()) == 0:
         return out
     if _guard == "raise":
-        raise L.LgcnError("non-finite features in f16x2 mode: an operand left fp16's range (|x| >= 65504); "
+        raise L.LgcnError("non-finite features in f16x2 mode: an operand left fp16's range (|x| >= 65520); "
                           "use ops.set_mma('bf16x3') or ops.set_guard('reroute')")
     with mma_scope("bf16x3"):
         return run()

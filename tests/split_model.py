@@ -1,0 +1,192 @@
+"""Float64 model of the split-precision operand formats (csrc/lgcn_mma_bf.hpp: Fmt<>, split_store) and float64
+restatements of the forward kernels built on them.
+
+Test infrastructure, like lc_plan_ref.py.  A kernel in a split mode does not compute the fp32 product: it rounds both
+operands to 16-bit planes and multiplies a subset of the plane pairs.  The model does exactly that and nothing else --
+RNE planes with the residual taken in fp32, subnormals kept, the products of Fmt<>'s PA / PB lists, everything behind
+the rounding in float64 -- so model - fp64 is the error the FORMAT commits on a given input, and a kernel that stays
+within a small factor of it is implementing its format and no worse.  Every restatement takes model=False and then
+returns the exact float64 value of the same formulas on the fp32 inputs (the reference).
+
+Inputs are numpy arrays or torch tensors; outputs are float64 numpy arrays."""
+import numpy as np
+
+C = 128
+EPS = 1e-5
+
+# mode -> (16-bit type, planes, PA, PB): the product list of Fmt<F> (A plane, B plane)
+FORMATS = {
+    "bf16x3": ("bf16", 3, (2, 0, 1, 1, 0, 0), (0, 2, 1, 0, 1, 0)),
+    "f16x2": ("f16", 2, (1, 0, 0), (0, 1, 0)),
+}
+MODES = ("f32", "bf16x3", "f16x2")
+
+
+def arr(a, dtype=None):
+    if hasattr(a, "detach"):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    return a if dtype is None else a.astype(dtype)
+
+
+def f32(a):
+    """Round to fp32 (where a kernel holds a value in a float register)."""
+    return arr(a).astype(np.float32)
+
+
+def round16(v, kind):
+    """fp32 -> fp16 / bf16 -> fp32, round to nearest even, subnormals kept, overflow to inf (v_cvt_pk_*_f32)."""
+    v = np.ascontiguousarray(v, np.float32)
+    if kind == "f16":
+        with np.errstate(over="ignore"):
+            return v.astype(np.float16).astype(np.float32)
+    u = v.view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    out = (r & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
+    return np.where(np.isnan(v), v, out)
+
+
+def planes(a, mode):
+    """The planes of an fp32 array as split_store forms them: plane p = round16(residual), residual -= plane in fp32."""
+    kind, n_planes = FORMATS[mode][:2]
+    v = f32(a).copy()
+    out = []
+    for p in range(n_planes):
+        q = round16(v, kind)
+        out.append(q.astype(np.float64))
+        if p + 1 < n_planes:
+            with np.errstate(invalid="ignore"):
+                v = (v - q).astype(np.float32)
+    return out
+
+
+def mm(a, w, mode):
+    """a [n, K] x w [c, K]^T -> [n, c]: the mode's plane products summed in float64; "f32": the float64 product."""
+    if mode == "f32":
+        return arr(a, np.float32).astype(np.float64) @ arr(w, np.float32).astype(np.float64).T
+    pa, pb = planes(a, mode), planes(w, mode)
+    out = 0.0
+    with np.errstate(invalid="ignore"):
+        for i, j in zip(*FORMATS[mode][2:]):
+            out = out + pa[i] @ pb[j].T
+    return out
+
+
+def rel_err(got, ref):
+    got, ref = arr(got, np.float64), arr(ref, np.float64)
+    return float(np.abs(got - ref).max() / np.abs(ref).max())
+
+
+def gn(x, gamma, beta, eps=EPS):
+    """GroupNorm(1, C) over the last axis (row_gn: biased variance)."""
+    mu = x.mean(-1, keepdims=True)
+    var = ((x - mu) ** 2).mean(-1, keepdims=True)
+    return (x - mu) / np.sqrt(var + eps) * arr(gamma, np.float64) + arr(beta, np.float64)
+
+
+def gather_sum(x, edges, n_rows, model=True):
+    """A[n] = sum_{e: u[e] = n} x[v[e]], sources in ascending order of v, duplicates kept (LGCN_REL_CSR).  The kernels
+    form the sum in fp32 and split the sum; model=False: the float64 sum."""
+    if edges is None:
+        return arr(x, np.float32)[:n_rows]
+    u, v = (arr(t, np.int64) for t in edges)
+    order = np.lexsort((v, u))
+    u, v = u[order], v[order]
+    dt = np.float32 if model else np.float64
+    out = np.zeros((n_rows, arr(x).shape[1]), dt)
+    np.add.at(out, u, arr(x, np.float32).astype(dt)[v])       # unbuffered: one addition per edge, in order
+    return out
+
+
+def _mm(a, w, mode, model):
+    if model:
+        return mm(f32(a), w, mode)
+    return arr(a, np.float64) @ arr(w, np.float32).astype(np.float64).T
+
+
+def _hold(a, model):
+    """A value the kernel holds in fp32 before it splits it again."""
+    return f32(a) if model else a
+
+
+def row_block(n_rows, rels, mode, gn1=None, relu1=False, w2=None, gn2=None, res=None, relu2=False, eps=EPS, model=True):
+    """lgcn_agg_mlp.  rels: (x, w [128, 128], edges (u, v) | None = IDENT).  Returns dict(pre = T, mid = Y, out):
+    T = sum_r gather_r(x_r) w_r^T;  Y = act(GN1(T));  out = act(GN2(Y w2^T) + res) (one stage without w2: out = Y + res)."""
+    T = 0.0
+    for x, w, edges in rels:
+        T = T + _mm(gather_sum(x, edges, n_rows, model), w, mode, model)
+    y = gn(T, *gn1, eps) if gn1 is not None else T
+    if w2 is None and res is not None:
+        y = y + arr(res, np.float64)
+    if relu1:
+        y = np.maximum(y, 0.0)
+    if w2 is None:
+        return dict(pre=T, mid=y, out=y)
+    z = _mm(_hold(y, model), w2, mode, model)
+    if gn2 is not None:
+        z = gn(z, *gn2, eps)
+    if res is not None:
+        z = z + arr(res, np.float64)
+    if relu2:
+        z = np.maximum(z, 0.0)
+    return dict(pre=T, mid=y, out=z)
+
+
+def lane_conv(x, units, gn1, w2, gn2, mode, eps=EPS, model=True):
+    """One LaneConv layer (lgcn_laneconv_fwd == lgcn_agg_mlp with every flag): units = (w, edges | None for ctr)."""
+    n = arr(x).shape[0]
+    return row_block(n, [(x, w, e) for w, e in units], mode, gn1=gn1, relu1=True, w2=w2, gn2=gn2, res=x, relu2=True,
+                     eps=eps, model=model)["out"]
+
+
+def lin2_relu(xy, w1, b1, model):
+    """ReLU(w1 xy + b1) of an [n, 2] input, held in fp32."""
+    h = arr(xy, np.float32).astype(np.float64) @ arr(w1, np.float32).astype(np.float64).T + arr(b1, np.float64)
+    return _hold(np.maximum(h, 0.0), model)
+
+
+def att_pairs(agt_ctrs, ctx_ctrs, hi, wi, wd0, bd0, w_d2, gn_d, w_c0e, U, V, gn_c, mode, eps=EPS, model=True):
+    """m [P, 128] of lgcn_att_pairs / _ws / _wi (include/lgcn.h); w_c0e = columns 0:128 of ctx.0's weight."""
+    hi, wi = arr(hi, np.int64), arr(wi, np.int64)
+    d = arr(agt_ctrs, np.float32)[hi] - arr(ctx_ctrs, np.float32)[wi]                 # fp32, as the kernels form it
+    h1 = lin2_relu(d, wd0, bd0, model)
+    e = np.maximum(gn(_mm(h1, w_d2, mode, model), *gn_d, eps), 0.0)
+    c = _mm(_hold(e, model), w_c0e, mode, model) + arr(U, np.float64)[hi] + arr(V, np.float64)[wi]
+    return np.maximum(gn(c, *gn_c, eps), 0.0)
+
+
+def mapnet_input(ctrs, feats, wa1, ba1, wa2, gn_a, ws1, bs1, ws2, gn_s, mode, eps=EPS, model=True):
+    """lgcn_mapnet_input: ReLU(GN_a(W_a2 ReLU(W_a1 ctr + b_a1)) + GN_s(W_s2 ReLU(W_s1 seg + b_s1)))."""
+    a = gn(_mm(lin2_relu(ctrs, wa1, ba1, model), wa2, mode, model), *gn_a, eps)
+    s = gn(_mm(lin2_relu(feats, ws1, bs1, model), ws2, mode, model), *gn_s, eps)
+    return np.maximum(a + s, 0.0)
+
+
+def conv1d_unit(x, w, stride, gamma, beta, mode, eps=EPS, relu=False, model=True):
+    """lgcn_conv1d_gn_train on channels-last x [A, L, cin], w [cout, cin, ks] (ks 1 / 3, padding (ks - 1) / 2, no bias):
+    (out, y), y the convolution, out = act(GN(y)) with the statistics over an actor's lout x cout values.
+    mode "f16x2": the two-plane units; "f32": the exact units."""
+    x, w = arr(x, np.float32), arr(w, np.float32)
+    A_, lin, cin = x.shape
+    cout, _, ks = w.shape
+    pad = (ks - 1) // 2
+    lout = (lin + 2 * pad - ks) // stride + 1
+    xp = np.zeros((A_, lin + 2 * pad, cin), np.float32)
+    xp[:, pad:pad + lin] = x
+    y = np.zeros((A_ * lout, cout))
+    for t in range(ks):
+        rows = xp[:, t:t + (lout - 1) * stride + 1:stride].reshape(A_ * lout, cin)
+        y = y + _mm(rows, w[:, :, t], mode, model)
+    y = y.reshape(A_, lout, cout)
+    mu = y.mean((1, 2), keepdims=True)
+    var = ((y - mu) ** 2).mean((1, 2), keepdims=True)
+    out = (y - mu) / np.sqrt(var + eps) * arr(gamma, np.float64) + arr(beta, np.float64)
+    return (np.maximum(out, 0.0) if relu else out), y
+
+
+def bar(e_model):
+    """What a kernel may show against float64 where its format's model shows e_model: twice the model, never below
+    1e-6 (fp32's own reordering noise on a 128-term sum), and inside the window -- where the model stays under 5e-5 --
+    never above the project's 1e-4."""
+    b = max(2.0 * e_model, 1e-6)
+    return min(b, 1e-4) if e_model <= 5e-5 else b

@@ -73,6 +73,9 @@ def main(argv=None):
         if args.resume:
             config["epoch"] = ckpt["epoch"]
             opt.load_state_dict(ckpt["opt_state"])
+        if rank == 0 and (args.weight or args.eval):               # loaded weights run inference in the default f16x2 mode
+            from tools.check_weight_scale import warn_small_blocks
+            warn_small_blocks(ckpt["state_dict"])
     D.broadcast_parameters(net.state_dict().values(), 0)
 
     kw = {"length": args.dataset_len} if args.dataset_len else {}

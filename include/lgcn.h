@@ -934,6 +934,63 @@ int lgcn_opt_step(const lgcn_opt_tensor_t *tensors, int n_tensors, const int32_t
                   double lr, double beta1, double beta2, double eps, double weight_decay, double momentum, int first_step,
                   double bc1, double bc2, int clip_on, float clip_low, float clip_high, void *stream);
 
+/*
+ * Goal decoder of the fork model (reference lanercnn.py:683-924): segmented greedy NMS, goal decoding and trajectory
+ * refinement.  All three are exact fp32 with every operation rounded on its own (no fused multiply-add) in the
+ * reference's order, asynchronous on `stream`, without workspace, floating-point atomics or host reads: bitwise repeatable.
+ *
+ * lgcn_nms_select -- nms_select (:687-708) for n_seg segments (RoIs) in one launch, one workgroup per segment.
+ *   xys [n, 2], logits [n]; seg_off [n_seg + 1] int32, segment s = rows seg_off[s] .. seg_off[s + 1].
+ *   The list of a segment:
+ *     1. the survivors of greedy NMS in descending logit order: a node is dropped when
+ *        sqrt(dx * dx + dy * dy) < threshold (strict; correctly rounded sqrt, compared as a distance, not as squares) for
+ *        an already kept node;
+ *     2. with fewer than min_len survivors, the highest-logit nodes not yet listed follow in descending logit order until
+ *        the list has min_len entries or the segment is exhausted;
+ *     3. the list is cut to max_keep entries (max_keep <= 0: no limit).
+ *   Order of the logits, where torch.sort leaves it open: equal logits -- the lower index comes first; a NaN logit ranks
+ *   above every number (as torch.sort(descending=True) ranks it), among NaNs the lower index comes first.
+ *   idx [n] int32, segment-local: idx[seg_off[s] + j] = j-th entry of the list for j < count[s], -1 beyond; count [n_seg].
+ *   A segment whose offsets do not lie in [0, n] in ascending order gets count 0 and its idx rows are not touched.
+ *   LGCN_EINVAL: n < 0, n_seg < 0, min_len < 0, NaN threshold, NULL seg_off, or with work to do a NULL tensor;
+ *   LGCN_ESHAPE: n > 2^28.  n_seg == 0: LGCN_OK without a launch.
+ *
+ * lgcn_goal_decode -- Decode.forward :802-865 for all n_agt interest agents in one launch, one workgroup per agent.
+ *   pred [n, 5]: the goal head's rows of the interest RoIs, concatenated; pred_off [n_agt + 1] their spans (pred_off[0] = 0).
+ *   anc_ctrs, anc_dirs [n_anc, 2]: the anchors of every RoI; anc_off [n_agt]: first anchor row of each interest RoI.
+ *   pred_off_host / anc_off_host: the same two tables in HOST memory, read for the argument check only.
+ *   agt_ctrs [n_agt, 2]; agt_dir_last [n_agt, 2] raw: d = dir / |dir|, and d = 0 where |dir| < 1e-6 (:845-848);
+ *   agt_vel [n_agt]; k = num_mods (1..8).  Per agent, node i of its RoI:
+ *     logit = pred[i, 0]    xy = anchor_ctr[i] + pred[i, 1:3]    theta = atan2(dir.y, dir.x) + atan(pred[i, 3] / pred[i, 4])
+ *     top_idx = the lgcn_nms_select list of (xy, logit) with min_len = max_keep = k
+ *   and per mode m with goal g = xy[top_idx[m]], p = (cos theta, sin theta), agent centre c (:710-723):
+ *     a1 = (2 g.x d.x + 2 c.x d.x) / (2 + d.x - p.x)    a0 = g.x - c.x - a1    a2 = c.x       (b0, b1, b2: the same in y)
+ *     L  = sum_j |P(j / 30) - P((j - 1) / 30)|, j = 1..30,  P(s) = (a0 s^2 + a1 s + a2, b0 s^2 + b1 s + b2)   (:851-855)
+ *     acc = 2 (L - 3 vel) / 9    v_j = max(vel + acc * 0.1 j, 0)    s_samples[j - 1] = (v_0 + v_j) * 0.1 j / 2      (:856-861)
+ *   (1.0 / 30 and 0.1 are rounded to fp32 before they multiply, as ATen rounds Python scalars.)
+ *   Outputs: top_idx [n_agt, k] int32 RoI-local, goals [n_agt, k, 2], logits [n_agt, k], coef [n_agt, k, 6] =
+ *   (a0, a1, a2, b0, b1, b2), s_samples [n_agt, k, 30] NOT normalised by its maximum (:900 adds to it as it is).
+ *   LGCN_EINVAL: a negative size, k outside 1..8, NaN threshold, NULL host tables, pred_off_host[0] != 0, an interest
+ *   RoI with fewer than k nodes (the reference fails there too, in torch.cat) or a span outside pred / the anchors,
+ *   or with n_agt > 0 a NULL tensor.  n_agt == 0: LGCN_OK without a launch.
+ *
+ * lgcn_goal_refine -- Decode.forward :899-919, one wave per (agent, mode) row; n_rows = n_agt * k.
+ *   s = s_samples[r] + traj_delta[r, :, 0];  s = s / max_t s (a NaN wins the maximum, as in torch.max);  exact zeros -> 1
+ *   P = sample_trajectory(s) as above;  T = (2 a0 s + a1, 2 b0 s + b1) (sample_d1_trajectory);
+ *   pred_trajs[r, t] = P + [[0, -1], [1, 0]] T * traj_delta[r, t, 1].
+ *   s_samples [n_rows, 30], coef [n_rows, 6], traj_delta and pred_trajs [n_rows, 30, 2].
+ *   LGCN_EINVAL: n_rows < 0 or with n_rows > 0 a NULL tensor.
+ */
+int lgcn_nms_select(const float *xys, const float *logits, const int32_t *seg_off, int64_t n, int n_seg,
+                    float threshold, int min_len, int max_keep, int32_t *idx, int32_t *count, void *stream);
+int lgcn_goal_decode(const float *pred, const int32_t *pred_off, const int32_t *pred_off_host, int64_t n,
+                     const float *anc_ctrs, const float *anc_dirs, int64_t n_anc, const int32_t *anc_off,
+                     const int32_t *anc_off_host, const float *agt_ctrs, const float *agt_dir_last,
+                     const float *agt_vel, int n_agt, int k, float threshold, int32_t *top_idx, float *goals,
+                     float *logits, float *coef, float *s_samples, void *stream);
+int lgcn_goal_refine(const float *s_samples, const float *coef, const float *traj_delta, int64_t n_rows,
+                     float *pred_trajs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

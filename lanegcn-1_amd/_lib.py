@@ -210,6 +210,9 @@ SIGNATURES = {
     "lgcn_conv1d_gn_f32": (C.c_int, [_P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _P, _P, _P]),
     "lgcn_opt_chunk_elems": (C.c_int, []),
     "lgcn_opt_step": (C.c_int, [_P, _I, _P, _I, _I, _D, _D, _D, _D, _D, _D, _I, _D, _D, _I, _F, _F, _P]),
+    "lgcn_nms_select": (C.c_int, [_P, _P, _P, _L, _I, _F, _I, _I, _P, _P, _P]),
+    "lgcn_goal_decode": (C.c_int, [_P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
+    "lgcn_goal_refine": (C.c_int, [_P, _P, _P, _L, _P, _P]),
 }
 
 _lib = None

@@ -7,13 +7,17 @@ Same class names, constructor arguments, forward signatures and state_dict names
   GlobalGraphNet lanercnn.py:517-600  4 LaneConv layers on a given feature
   LanePooling    lanercnn.py:433-514  distance-gated pooling between two lane graphs: the Att pattern with a 4-d
                                       relative pose instead of the 2-d offset and without a query term
+  Interactor     lanercnn.py:603-642  stem (MapNet's input form) -> LanePooling -> GlobalGraphNet -> LanePooling
+  Decode         lanercnn.py:740-924  goal head, NMS + trajectory coefficients (lgcn_goal_decode), pooling of the agent's
+                                      motion into its RoI, refinement head, refined trajectories (lgcn_goal_refine)
+and the module-level nms_select / compute_coefficent / sample_trajectory / sample_d1_trajectory (:687-737).
 
 Inference (no_grad) runs on the HIP kernels; under autograd LaneRoI / GlobalGraphNet train through the LaneConv
 autograd path of lanegcn.py, LanePooling and LaneInput through the row-block / pair / gather Functions of autograd.py
 (the same composition as Att.run_train): every 128-d contraction of the backward is a HIP launch as well.
 """
 from math import gcd
-from typing import Dict, List
+from typing import Dict, List, Tuple
 
 import numpy as np
 import torch
@@ -171,3 +175,216 @@ class LanePooling(nn.Module):
                         wp2=ops.packed(m0.linear.weight), gn2=_gn(m0.norm), eps=self.norm.eps)
         return ops.agg_mlp(T, [ops.RelSpec(y, ops.packed(m1.linear.weight))], L.F_GN1 | L.F_RES | L.F_RELU1,
                            gn1=_gn(m1.norm), res=target_feat, eps=m1.norm.eps)
+
+
+def _stem(a: nn.Sequential, s: nn.Sequential, xa: Tensor, xs: Tensor) -> Tensor:
+    """ReLU(a(xa) + s(xs)) for two Linear(2,128) -> ReLU -> Linear(128,128,GN) branches: MapNet's stem form
+    (lgcn_mapnet_input, one launch); under autograd composed as MapNet.forward composes it."""
+    xa, xs = xa.contiguous(), xs.contiguous()
+    if ops.wants_grad(xa, xs, *ops.module_params(a), *ops.module_params(s)):
+        fa = A.linear_gn(F.relu(a[0](xa)), a[2].linear.weight, gn=a[2].norm)
+        fs = A.linear_gn(F.relu(s[0](xs)), s[2].linear.weight, gn=s[2].norm)
+        return F.relu(fa + fs)
+    return ops.mapnet_input(xa, xs, a[0].weight, a[0].bias, ops.packed(a[2].linear.weight), _gn(a[2].norm),
+                            s[0].weight, s[0].bias, ops.packed(s[2].linear.weight), _gn(s[2].norm), eps=a[2].norm.eps)
+
+
+def _stem_branch(n: int) -> nn.Sequential:
+    return nn.Sequential(nn.Linear(2, n), nn.ReLU(inplace=True), Linear(n, n, norm="GN", ng=1, act=False))
+
+
+class Interactor(nn.Module):
+    """Exchange between the lane RoIs and the global lane graph (reference lanercnn.py:603-642): the RoI features are
+    pooled into the graph's stem features, run through GlobalGraphNet and pooled back into the RoIs."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        n_map = config["n_map"]
+        self.input = _stem_branch(n_map)
+        self.seg = _stem_branch(n_map)
+        self.relu = nn.ReLU(inplace=True)
+        self.roi2graph = LanePooling(in_dim=128, out_dim=128)
+        self.global_graph_net = GlobalGraphNet(config)
+        self.graph2roi = LanePooling(in_dim=128, out_dim=128)
+
+    def graph_input(self, graph: Dict) -> Tensor:
+        return _stem(self.input, self.seg, torch.cat(graph["ctrs"], 0), graph["feats"])
+
+    def forward(self, graph: Dict, subgraph: Dict, roi_feat: Tensor) -> Tensor:
+        _need_cuda(roi_feat, graph["feats"])
+        graph_feat = self.roi2graph(roi_feat, subgraph, self.graph_input(graph), graph)
+        graph_feat = self.global_graph_net(graph_feat, graph)
+        return self.graph2roi(graph_feat, graph, roi_feat, subgraph)
+
+
+# ------------------------------------------------------------------ goal decoding (reference lanercnn.py:683-924)
+def nms_select(xys: Tensor, logits: Tensor, threshold: float = 2.0, min_len: int = 6) -> Tensor:
+    """The full list of the reference's nms_select (:687-708) for one RoI: greedy survivors in descending logit order,
+    padded with the best dropped nodes up to min_len.  One launch (lgcn_nms_select); the length is read from the
+    device (this function returns a list of data-dependent length; Decode does not use it)."""
+    _need_cuda(xys, logits)
+    n = logits.shape[0]
+    idx, count = ops.nms_select_segments(xys.detach().float(), logits.detach().float(), [0, n], threshold, min_len, 0)
+    return idx[:int(count.item())].long()
+
+
+def compute_coefficent(agt_ctrs: Tensor, agt_dirs: Tensor, pred_ctrs: Tensor, pred_dirs: Tensor):
+    """Coefficients of the quadratic x(s) = a0 s^2 + a1 s + a2, y(s) = b0 s^2 + b1 s + b2 from the agent's centre and
+    unit direction to each goal with its unit direction (:710-723).  pred_*: [A, k, 2]; returns six [A, k, 1]."""
+    c, d = agt_ctrs.view(-1, 1, 2), agt_dirs.view(-1, 1, 2)
+    out = []
+    for ax in (0, 1):
+        g, p = pred_ctrs[:, :, ax], pred_dirs[:, :, ax]
+        c_, d_ = c[:, :, ax], d[:, :, ax]
+        q1 = (2 * g * d_ + 2 * c_ * d_) / (2 + d_ - p)
+        q0 = g - c_ - q1
+        q2 = c_.expand_as(g)
+        out += [q0.unsqueeze(2), q1.unsqueeze(2), q2.unsqueeze(2)]
+    return tuple(out)
+
+
+def sample_trajectory(s_samples: Tensor, a0, a1, a2, b0, b1, b2) -> Tensor:
+    """Points of the quadratic at s_samples: [..., S] -> [..., S, 2] (:728-732)."""
+    x = a0 * s_samples ** 2 + a1 * s_samples + a2
+    y = b0 * s_samples ** 2 + b1 * s_samples + b2
+    return torch.stack([x, y], -1)
+
+
+def sample_d1_trajectory(s_samples: Tensor, a0, a1, a2, b0, b1, b2) -> Tensor:
+    """First derivative of the quadratic at s_samples (:734-737)."""
+    return torch.stack([2 * a0 * s_samples + a1, 2 * b0 * s_samples + b1], -1)
+
+
+class Decode(nn.Module):
+    """Goal decoder (reference lanercnn.py:740-924).  Inference: goal head (row block + Linear(128, 5)), one
+    lgcn_goal_decode launch for NMS, goals, coefficients and arc-length samples of all interest agents, the agent's
+    observed motion (stem form) pooled into its RoI, the refinement head on the k gathered rows and one
+    lgcn_goal_refine launch -- no device -> host read besides the pair count inside LanePooling.  Under autograd the
+    indices still come from lgcn_nms_select (the reference does not propagate through the selection either) and
+    everything else runs on differentiable ops.
+
+    The reference hands the motion graph's centres to LanePooling as [1, 20, 2] tensors, whose len() is 1, so its
+    context row offset grows by 1 per scene, not by 20: scene b pools rows b .. b + 19 of the concatenated [A * 20]
+    motion features and poses (distances still come from scene b's own trajectory).  That numbering is reproduced
+    here: the stem and pose rows are gathered in that order before LanePooling sees [20, 2] centres."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        n_actor = config["n_actor"]
+        self.pred = nn.Sequential(Linear(n_actor, n_actor, norm="GN", ng=1), nn.Linear(n_actor, 5))
+        self.agt_layer1 = _stem_branch(n_actor)
+        self.agt_layer2 = _stem_branch(n_actor)
+        self.relu = nn.ReLU(inplace=True)
+        self.lane_pool = LanePooling(n_actor, n_actor)
+        self.refinement = nn.Sequential(Linear(n_actor, n_actor, norm="GN", ng=1), nn.Linear(n_actor, 30 * 2))
+
+    @staticmethod
+    def _interest(subgraph: Dict) -> Tuple[List[int], List[Tuple[int, int]]]:
+        ids = subgraph["interest_roi"]
+        ids = [int(i) for i in (ids.tolist() if torch.is_tensor(ids) or isinstance(ids, np.ndarray) else ids)]
+        spans = [(int(subgraph["roi_spans"][i][0]), int(subgraph["roi_spans"][i][1])) for i in ids]
+        return ids, spans
+
+    def forward(self, roi_feat: Tensor, subgraph: Dict, data: Dict):
+        out = self.decode(roi_feat, subgraph, data)
+        return out["logits"], out["goals"], out["pred_trajs"]
+
+    def decode(self, roi_feat: Tensor, subgraph: Dict, data: Dict) -> Dict[str, Tensor]:
+        """forward() with its intermediates: pred [n, 5], top_idx [A, k] (RoI-local), goals, logits, s_samples
+        (un-normalised), pooled [n, 128], traj_delta [A, k, 30, 2] and pred_trajs."""
+        _need_cuda(roi_feat)
+        k, dev = self.config["num_mods"], roi_feat.device
+        if self.config["num_preds"] != ops.GOAL_STEPS:
+            raise L.LgcnError("Decode: num_preds must be %d" % ops.GOAL_STEPS)
+        ids, spans = self._interest(subgraph)                       # host integers
+        n_agt = len(ids)
+        pred_spans = [0]
+        for lo, hi in spans:
+            pred_spans.append(pred_spans[-1] + hi - lo)
+        feats = torch.cat([roi_feat[lo:hi] for lo, hi in spans], 0)
+        pred = self.pred(feats)                                       # [n, 5]
+        anchor_ctrs = torch.cat(subgraph["ctrs"], 0)
+        anchor_dirs = torch.cat(subgraph["dirs"], 0)
+        # the first valid agent of every scene: centre, observed steps and their directions (:835-841)
+        first = lambda key: torch.cat([x.to(dev).index_select(0, v.to(dev).long()[:1]) for v, x in
+                                       zip(data["valid_agent_ids"], data[key])], 0)
+        agt_ctrs = first("ctrs").view(-1, 2).float()
+        agt_dirs = first("feats").view(-1, 20, 3)[:, :, :2]
+        agt_trajs = first("obs_trajs").view(-1, 20, 3)[:, :, :2]
+        vel = subgraph["agent_vel"]
+        agt_vels = torch.tensor([float(vel[i]) for i in ids], dtype=torch.float32).to(dev, non_blocking=True)
+        dir_last = agt_dirs[:, -1, :].float()
+        train = ops.wants_grad(roi_feat, *ops.module_params(self))
+
+        if train:
+            top, goals, logits, coefs, s_samples = self._decode_torch(pred, pred_spans, anchor_ctrs, anchor_dirs, spans,
+                                                                      agt_ctrs, dir_last, agt_vels, k)
+        else:
+            top, goals, logits, coef, s_samples = ops.goal_decode(pred, pred_spans, anchor_ctrs, anchor_dirs,
+                                                                  [lo for lo, _ in spans], agt_ctrs, dir_last, agt_vels, k)
+
+        # the agent's observed motion, pooled into its RoI (:873-887); row order: see the class docstring
+        rows = (torch.arange(n_agt, device=dev).view(-1, 1) + torch.arange(20, device=dev).view(1, -1)).reshape(-1)
+        trajs_q = agt_trajs.reshape(-1, 2).float().index_select(0, rows)
+        dirs_q = agt_dirs.reshape(-1, 2).float().index_select(0, rows)
+        agt_feat = _stem(self.agt_layer1, self.agt_layer2, trajs_q, dirs_q)
+        pose_q = torch.cat([trajs_q, dirs_q], -1)
+        motion = {"ctrs": [agt_trajs[i].float() for i in range(n_agt)], "pose": list(pose_q.split(20, 0))}
+        roi_map = {"ctrs": [anchor_ctrs[lo:hi] for lo, hi in spans],
+                   "pose": [torch.cat([anchor_ctrs[lo:hi], anchor_dirs[lo:hi]], -1) for lo, hi in spans]}
+        pooled = self.lane_pool(agt_feat, motion, feats, roi_map)
+
+        base = torch.tensor(pred_spans[:-1], dtype=torch.int32).to(dev, non_blocking=True)
+        flat = (top + base.view(-1, 1)).reshape(-1)                   # rows of `pooled`, [A * k]
+        if train:
+            traj_feats = pooled.index_select(0, flat.long())
+        else:
+            n_rows = torch.tensor([n_agt * k], dtype=torch.int32).to(dev, non_blocking=True)
+            traj_feats = ops.gather_rows(pooled, flat.contiguous(), n_rows, n_agt * k)
+        traj_delta = self.refinement(traj_feats).view(n_agt, k, ops.GOAL_STEPS, 2)
+
+        if train:
+            s = s_samples + traj_delta[..., 0]
+            s = s / s.max(2, keepdim=True)[0]
+            s = torch.where(s == 0.0, torch.ones_like(s), s)
+            tangent = sample_d1_trajectory(s, *coefs)
+            normal = torch.stack([-tangent[..., 1], tangent[..., 0]], -1)
+            pred_trajs = sample_trajectory(s, *coefs) + normal * traj_delta[..., 1:2]
+        else:
+            pred_trajs = ops.goal_refine(s_samples, coef, traj_delta)
+        return {"pred": pred, "top_idx": top, "goals": goals, "logits": logits, "s_samples": s_samples, "pooled": pooled,
+                "traj_delta": traj_delta, "pred_trajs": pred_trajs}
+
+    def _decode_torch(self, pred, pred_spans, anchor_ctrs, anchor_dirs, spans, agt_ctrs, dir_last, agt_vels, k):
+        """The differentiable restatement of :802-865 on stock ops; the indices come from lgcn_nms_select."""
+        dev = pred.device
+        n_agt = len(spans)
+        for a in range(n_agt):
+            if pred_spans[a + 1] - pred_spans[a] < k:
+                raise L.LgcnError("Decode: interest RoI %d has fewer than %d nodes" % (a, k))
+        anc_rows = torch.cat([torch.arange(lo, hi) for lo, hi in spans]).to(dev, non_blocking=True)
+        anc_c, anc_d = anchor_ctrs.index_select(0, anc_rows), anchor_dirs.index_select(0, anc_rows)
+        xy = anc_c + pred[:, 1:3]
+        theta = torch.atan2(anc_d[:, 1], anc_d[:, 0]) + torch.atan(pred[:, 3] / pred[:, 4])
+        idx, _ = ops.nms_select_segments(xy.detach(), pred[:, 0].detach(), pred_spans, 2.0, k, k)
+        off = torch.tensor(pred_spans[:-1]).to(dev, non_blocking=True)
+        sel = off.view(-1, 1) + torch.arange(k, device=dev).view(1, -1)          # list positions [A, k]
+        top = idx.index_select(0, sel.reshape(-1)).view(n_agt, k)
+        flat = (top.long() + off.view(-1, 1)).reshape(-1)
+        goals = xy.index_select(0, flat).view(n_agt, k, 2)
+        thetas = theta.index_select(0, flat).view(n_agt, k)
+        logits = pred[:, 0].index_select(0, flat).view(n_agt, k)
+        pdirs = torch.stack([torch.cos(thetas), torch.sin(thetas)], -1)
+        nrm = torch.linalg.norm(dir_last, dim=1)
+        adir = torch.where((nrm < 1e-6).view(-1, 1), torch.zeros_like(dir_last), dir_last / nrm.view(-1, 1))
+        coefs = compute_coefficent(agt_ctrs, adir, goals, pdirs)
+        s31 = (1.0 / 30) * torch.arange(0, 31, device=dev).float()
+        pts = sample_trajectory(s31, *coefs)
+        length = torch.sqrt(((pts[:, :, 1:] - pts[:, :, :-1]) ** 2).sum(-1)).sum(-1)
+        acc = 2 * (length - agt_vels.view(-1, 1) * 3.0) / 9.0
+        t31 = 0.1 * torch.arange(0, 31, device=dev).float()
+        v = (agt_vels.view(-1, 1, 1) + acc.unsqueeze(2) * t31).clamp_min(0.0)
+        s_samples = (v[:, :, :1] + v[:, :, 1:]) * t31[1:] / 2
+        return top, goals, logits, coefs, s_samples

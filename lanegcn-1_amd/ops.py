@@ -1645,3 +1645,100 @@ def pair_add(c, U, hi, V, wi, n_dev, cap):
     L.check(lib.lgcn_pair_add(_ptr(c), _ptr(U), _ptr(hi), _ptr(V), _ptr(wi), _ptr(n_dev), cap, _ptr(out), _stream()),
             "lgcn_pair_add")
     return out
+
+
+# ------------------------------------------------------------------ goal decoder of the fork model (lanercnn.py:683-924)
+GOAL_MAX_MODS, GOAL_STEPS = 8, 30
+
+
+def _offsets(spans, name):
+    """Host span table [0, n_0, n_0 + n_1, ...] as (CPU int32 tensor, plain ints)."""
+    off = [int(v) for v in spans]
+    if len(off) < 1 or off[0] != 0 or any(b < a for a, b in zip(off, off[1:])):
+        raise L.LgcnError("%s must start at 0 and ascend, got %s" % (name, off[:8]))
+    return torch.tensor(off, dtype=torch.int32), off
+
+
+def nms_select_segments(xys: torch.Tensor, logits: torch.Tensor, seg_off, threshold: float = 2.0, min_len: int = 6,
+                        max_keep: int = 0):
+    """Segmented greedy NMS (lgcn_nms_select): seg_off = host span table of the segments (RoIs) or an int32 CUDA tensor.
+    Returns (idx [n] int32 segment-local, -1 past the count, count [n_seg] int32), both on the device."""
+    lib = L.load()
+    xys = _dev(xys, torch.float32, "xys")
+    logits = _dev(logits, torch.float32, "logits")
+    n = logits.shape[0]
+    if xys.dim() != 2 or xys.shape[1] != 2 or xys.shape[0] != n or logits.dim() != 1:
+        raise L.LgcnError("nms_select_segments: xys [n, 2] and logits [n] expected, got %s and %s"
+                          % (tuple(xys.shape), tuple(logits.shape)))
+    if torch.is_tensor(seg_off) and seg_off.is_cuda:
+        seg_dev = _dev(seg_off, torch.int32, "seg_off")
+    else:
+        host, off = _offsets(seg_off, "seg_off")
+        if off[-1] > n:
+            raise L.LgcnError("nms_select_segments: seg_off ends at %d, past the %d rows" % (off[-1], n))
+        seg_dev = host.to(xys.device, non_blocking=True)
+    n_seg = seg_dev.shape[0] - 1
+    if n_seg < 0:
+        raise L.LgcnError("nms_select_segments: seg_off needs at least one entry")
+    idx = torch.full((n,), -1, dtype=torch.int32, device=xys.device)
+    count = torch.zeros((n_seg,), dtype=torch.int32, device=xys.device)
+    L.check(lib.lgcn_nms_select(_ptr(xys), _ptr(logits), _ptr(seg_dev), n, n_seg, float(threshold), int(min_len),
+                                int(max_keep), _ptr(idx), _ptr(count), _stream()), "lgcn_nms_select")
+    return idx, count
+
+
+def goal_decode(pred: torch.Tensor, pred_spans, anc_ctrs: torch.Tensor, anc_dirs: torch.Tensor, anc_first,
+                agt_ctrs: torch.Tensor, agt_dir_last: torch.Tensor, agt_vel: torch.Tensor, k: int = 6, threshold: float = 2.0):
+    """lgcn_goal_decode: pred [n, 5] with the host span table pred_spans [n_agt + 1]; anc_first = host list of the first
+    anchor row of each interest RoI.  Returns (top_idx [A, k] int32, goals [A, k, 2], logits [A, k], coef [A, k, 6],
+    s_samples [A, k, 30])."""
+    lib = L.load()
+    pred = _dev(pred, torch.float32, "pred")
+    anc_ctrs = _dev(anc_ctrs, torch.float32, "anc_ctrs")
+    anc_dirs = _dev(anc_dirs, torch.float32, "anc_dirs")
+    agt_ctrs = _dev(agt_ctrs, torch.float32, "agt_ctrs")
+    agt_dir_last = _dev(agt_dir_last, torch.float32, "agt_dir_last")
+    agt_vel = _dev(agt_vel, torch.float32, "agt_vel")
+    off_host, off = _offsets(pred_spans, "pred_spans")
+    A_ = len(off) - 1
+    if pred.dim() != 2 or pred.shape[1] != 5 or off[-1] != pred.shape[0]:
+        raise L.LgcnError("goal_decode: pred [n, 5] covered by pred_spans expected, got %s and a table ending at %d"
+                          % (tuple(pred.shape), off[-1]))
+    if anc_ctrs.dim() != 2 or anc_ctrs.shape[1] != 2 or anc_dirs.shape != anc_ctrs.shape:
+        raise L.LgcnError("goal_decode: anc_ctrs / anc_dirs [N, 2] expected")
+    if tuple(agt_ctrs.shape) != (A_, 2) or tuple(agt_dir_last.shape) != (A_, 2) or tuple(agt_vel.shape) != (A_,):
+        raise L.LgcnError("goal_decode: agt_ctrs [A, 2], agt_dir_last [A, 2], agt_vel [A] expected for A = %d" % A_)
+    first_host = torch.tensor([int(v) for v in anc_first], dtype=torch.int32)
+    if first_host.shape[0] != A_:
+        raise L.LgcnError("goal_decode: %d anchor offsets for %d agents" % (first_host.shape[0], A_))
+    dev = pred.device
+    off_dev, first_dev = off_host.to(dev, non_blocking=True), first_host.to(dev, non_blocking=True)
+    top = torch.empty((A_, k), dtype=torch.int32, device=dev)
+    goals = torch.empty((A_, k, 2), dtype=torch.float32, device=dev)
+    logits = torch.empty((A_, k), dtype=torch.float32, device=dev)
+    coef = torch.empty((A_, k, 6), dtype=torch.float32, device=dev)
+    ss = torch.empty((A_, k, GOAL_STEPS), dtype=torch.float32, device=dev)
+    L.check(lib.lgcn_goal_decode(_ptr(pred), _ptr(off_dev), C.c_void_p(off_host.data_ptr()), pred.shape[0],
+                                 _ptr(anc_ctrs), _ptr(anc_dirs), anc_ctrs.shape[0], _ptr(first_dev),
+                                 C.c_void_p(first_host.data_ptr()), _ptr(agt_ctrs), _ptr(agt_dir_last), _ptr(agt_vel),
+                                 A_, int(k), float(threshold), _ptr(top), _ptr(goals), _ptr(logits), _ptr(coef), _ptr(ss),
+                                 _stream()), "lgcn_goal_decode")
+    return top, goals, logits, coef, ss
+
+
+def goal_refine(s_samples: torch.Tensor, coef: torch.Tensor, traj_delta: torch.Tensor) -> torch.Tensor:
+    """lgcn_goal_refine: s_samples [A, k, 30], coef [A, k, 6], traj_delta [A, k, 30, 2] -> pred_trajs [A, k, 30, 2]."""
+    lib = L.load()
+    s_samples = _dev(s_samples, torch.float32, "s_samples")
+    coef = _dev(coef, torch.float32, "coef")
+    traj_delta = _dev(traj_delta, torch.float32, "traj_delta")
+    if s_samples.dim() != 3 or s_samples.shape[2] != GOAL_STEPS:
+        raise L.LgcnError("goal_refine: s_samples [A, k, 30] expected, got %s" % (tuple(s_samples.shape),))
+    A_, k = s_samples.shape[:2]
+    if tuple(coef.shape) != (A_, k, 6) or tuple(traj_delta.shape) != (A_, k, GOAL_STEPS, 2):
+        raise L.LgcnError("goal_refine: coef [A, k, 6] and traj_delta [A, k, 30, 2] expected, got %s and %s"
+                          % (tuple(coef.shape), tuple(traj_delta.shape)))
+    out = torch.empty_like(traj_delta)
+    L.check(lib.lgcn_goal_refine(_ptr(s_samples), _ptr(coef), _ptr(traj_delta), A_ * k, _ptr(out), _stream()),
+            "lgcn_goal_refine")
+    return out

@@ -991,6 +991,76 @@ int lgcn_goal_decode(const float *pred, const int32_t *pred_off, const int32_t *
 int lgcn_goal_refine(const float *s_samples, const float *coef, const float *traj_delta, int64_t n_rows,
                      float *pred_trajs, void *stream);
 
+/*
+ * Training the goal decoder: the backward of lgcn_goal_refine and lgcn_goal_decode, one launch each.  Exact fp32 like
+ * the forward (no fused multiply-add), asynchronous on `stream`, no workspace, no floating-point atomics, every sum in
+ * a fixed order (bitwise repeatable), every output element written.  Nothing is saved by the forward besides top_idx:
+ * both kernels recompute what they need with the forward's own operations, so the masks below are the forward's.
+ * Not differentiated, as in the reference and in autograd of the stock ops: the selection top_idx; a speed that was
+ * clamped (v_j <= 0, the reference's in-place v[v <= 0] = 0); a normalised sample that was exactly 0 and became 1.
+ *
+ * lgcn_goal_refine_bwd -- one wave per (agent, mode) row, n_rows = n_agt * k.  Inputs as lgcn_goal_refine plus
+ *   d_pred_trajs [n_rows, 30, 2]; outputs d_s_samples [n_rows, 30], d_coef [n_rows, 6], d_traj_delta [n_rows, 30, 2].
+ *   With s_t = s_samples[t] + delta[t, 0], mx = max_t s_t, u_t = s_t / mx, z_t = u_t (1 where u_t == 0), n_t = delta[t, 1],
+ *   T = (2 a0 z + a1, 2 b0 z + b1) and g = d_pred_trajs[t]:
+ *     d n_t  = g.y T.x - g.x T.y
+ *     d z_t  = g.x T.x + g.y T.y + 2 n_t (g.y a0 - g.x b0)            d u_t = d z_t, 0 where u_t == 0
+ *     d a0 = sum_t g.x z^2 + 2 g.y z n    d a1 = sum_t g.x z + g.y n    d a2 = sum_t g.x
+ *     d b0 = sum_t g.y z^2 - 2 g.x z n    d b1 = sum_t g.y z - g.x n    d b2 = sum_t g.y
+ *     d s_t  = d u_t / mx, and the first t with s_t == mx also receives -sum_t (d u_t u_t / mx)   (autograd's max + div)
+ *     d_s_samples[t] = d_traj_delta[t, 0] = d s_t;   d_traj_delta[t, 1] = d n_t.
+ *   LGCN_EINVAL: n_rows < 0 or with n_rows > 0 a NULL tensor; LGCN_ESHAPE: n_rows * 60 > 2^31 - 1.  n_rows == 0: LGCN_OK
+ *   without a launch.
+ *
+ * lgcn_goal_decode_bwd -- one workgroup per interest agent.  Inputs: those of lgcn_goal_decode (threshold is not
+ *   needed), the forward's top_idx [n_agt, k] and the upstream d_goals [n_agt, k, 2], d_logits [n_agt, k],
+ *   d_coef [n_agt, k, 6], d_s_samples [n_agt, k, 30].  Output d_pred [n, 5]: the workgroup zero-fills its span, then one
+ *   thread per mode fills row top_idx[m] (the entries of top_idx are distinct).  Per mode, in the notation of
+ *   lgcn_goal_decode, with t_j = 0.1 j and s_j = j / 30:
+ *     d acc  = sum_j d_s_samples[j - 1] (t_j / 2) t_j  over the j with v_j > 0         d L = 2 d acc / 9
+ *     e_j = P(s_j) - P(s_(j-1)):   d a0 = d_coef[0] + sum_j d L (e_j.x / |e_j|) (s_j^2 - s_(j-1)^2)
+ *                                  d a1 = d_coef[1] + sum_j d L (e_j.x / |e_j|) (s_j - s_(j-1))        (b0, b1: in y;
+ *                                  a segment of length 0 passes nothing; a2 = c.x and b2 = c.y are inputs)
+ *     a0 = g.x - c.x - a1, a1 = N / D, N = 2 g.x d.x + 2 c.x d.x, D = 2 + d.x - p.x:
+ *       d g.x = d_goals.x + d a0 + (d a1 - d a0) 2 d.x / D            d p.x = (d a1 - d a0) a1 / D       (and in y)
+ *     d theta = d p.y cos theta - d p.x sin theta;  theta includes atan(p3 / p4):
+ *       d_pred[i] = (d_logits, d g.x, d g.y, d theta p4 / (p3^2 + p4^2), -d theta p3 / (p3^2 + p4^2)),  i = top_idx[m].
+ *   LGCN_EINVAL: as lgcn_goal_decode, and pred_off_host[n_agt] != n (the spans must cover d_pred).  n_agt == 0: LGCN_OK
+ *   without a launch.  An agent whose top_idx holds an index outside its RoI gets its zero rows only.
+ */
+int lgcn_goal_refine_bwd(const float *s_samples, const float *coef, const float *traj_delta, const float *d_pred_trajs,
+                         int64_t n_rows, float *d_s_samples, float *d_coef, float *d_traj_delta, void *stream);
+int lgcn_goal_decode_bwd(const float *pred, const int32_t *pred_off, const int32_t *pred_off_host, int64_t n,
+                         const float *anc_ctrs, const float *anc_dirs, int64_t n_anc, const int32_t *anc_off,
+                         const int32_t *anc_off_host, const float *agt_ctrs, const float *agt_dir_last,
+                         const float *agt_vel, int n_agt, int k, const int32_t *top_idx, const float *d_goals,
+                         const float *d_logits, const float *d_coef, const float *d_s_samples, float *d_pred, void *stream);
+
+/*
+ * RoiLoss of the fork model (reference lanercnn.py:1214-1301): one forward launch, one backward launch, the rules of
+ * lgcn_pred_loss_fwd / _bwd (exact fp32, fixed-order sums, no atomics).  logits [n_agt, n_mod], goals [n_agt, n_mod, 2],
+ * trajs [n_agt, n_mod, n_t, 2], gt [n_agt, n_t, 2], has [n_agt, n_t] bytes; n_mod in 1..8, n_t in 1..64.  Per agent
+ * (none is dropped: without an observed step last = n_t - 1, the class term counts, the regressions do not):
+ *   last    = argmax_t(has[t] + 0.1 t / n_t), first maximum, the fp32 values formed as in lgcn_pred_loss_fwd
+ *   dist_j  = sqrt(|goals[j] - gt[last]|^2);  min_idx = first minimum
+ *   cls    += sum_j (1 - y) x + max(-x, 0) + log(exp(-max(-x, 0)) + exp(-x - max(-x, 0))),  x = logits[j], y = (j == min_idx)
+ *   goal   += SmoothL1(goals[min_idx] - gt[last]) (beta 1) if has[last]
+ *   traj   += SmoothL1(trajs[min_idx, t] - gt[t]) over the t with has[t]
+ * sums [3] = (cls, reg_coef * goal, reg_coef * traj); counts [3] int32 = (n_agt, #agents with has[last], #has);
+ * sel [n_agt] int32 = min_idx | has[last] << 8; pred_goals [n_agt, 2] = goals[min_idx].
+ * lgcn_roi_loss_bwd: given sel and the upstream gradients of the three sums (device scalars g_cls, g_goal, g_traj), writes
+ * every element of dlogits (g_cls (sigmoid(x) - y)), dgoals and dtrajs (zero off the selected mode / unobserved steps).
+ * LGCN_EINVAL: n_agt < 0, n_mod outside 1..8, n_t outside 1..64, or with n_agt > 0 a NULL tensor; LGCN_ESHAPE:
+ * n_agt * n_mod * n_t * 2 > 2^31 - 1.  n_agt == 0: LGCN_OK without a launch (nothing is written: the sums of an empty
+ * problem are the caller's zeros).
+ */
+int lgcn_roi_loss_fwd(const float *logits, const float *goals, const float *trajs, const float *gt, const unsigned char *has,
+                      int64_t n_agt, int n_mod, int n_t, float reg_coef, float *sums, int32_t *counts, int32_t *sel,
+                      float *pred_goals, void *stream);
+int lgcn_roi_loss_bwd(const float *logits, const float *goals, const float *trajs, const float *gt, const unsigned char *has,
+                      int64_t n_agt, int n_mod, int n_t, float reg_coef, const int32_t *sel, const float *g_cls,
+                      const float *g_goal, const float *g_traj, float *dlogits, float *dgoals, float *dtrajs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

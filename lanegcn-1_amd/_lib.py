@@ -213,6 +213,10 @@ SIGNATURES = {
     "lgcn_nms_select": (C.c_int, [_P, _P, _P, _L, _I, _F, _I, _I, _P, _P, _P]),
     "lgcn_goal_decode": (C.c_int, [_P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P, _P]),
     "lgcn_goal_refine": (C.c_int, [_P, _P, _P, _L, _P, _P]),
+    "lgcn_goal_refine_bwd": (C.c_int, [_P, _P, _P, _P, _L, _P, _P, _P, _P]),
+    "lgcn_goal_decode_bwd": (C.c_int, [_P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "lgcn_roi_loss_fwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "lgcn_roi_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -510,3 +510,65 @@ class PredLossFn(torch.autograd.Function):
         z = lambda g: torch.zeros(1, dtype=torch.float32, device=cls.device) if g is None else g.reshape(1).float().contiguous()
         dcls, dreg = ops.pred_loss_bwd(cls, reg, gt, has, ctx.cfg, sel, z(g_cls), z(g_reg))
         return dcls, dreg, None, None, None
+
+
+class GoalDecodeFn(Function):
+    """lgcn_goal_decode under autograd (Decode.train_hip): the forward is the inference launch, the backward one
+    lgcn_goal_decode_bwd launch.  Returns (top_idx, goals, logits, coef, s_samples); only pred receives a gradient and
+    the selection top_idx is not differentiated."""
+
+    @staticmethod
+    def forward(ctx, pred, pred_spans, anc_ctrs, anc_dirs, anc_first, agt_ctrs, agt_dir_last, agt_vel, k, threshold):
+        pred = pred.contiguous()
+        top, goals, logits, coef, ss = ops.goal_decode(pred, pred_spans, anc_ctrs, anc_dirs, anc_first, agt_ctrs, agt_dir_last,
+                                                       agt_vel, k, threshold)
+        ctx.save_for_backward(pred, anc_ctrs, anc_dirs, agt_ctrs, agt_dir_last, agt_vel, top)
+        ctx.tables = (list(pred_spans), list(anc_first))
+        ctx.mark_non_differentiable(top)
+        return top, goals, logits, coef, ss
+
+    @staticmethod
+    def backward(ctx, _, d_goals, d_logits, d_coef, d_ss):
+        pred, anc_ctrs, anc_dirs, agt_ctrs, agt_dir_last, agt_vel, top = ctx.saved_tensors
+        pred_spans, anc_first = ctx.tables
+        d_pred = ops.goal_decode_bwd(pred, pred_spans, anc_ctrs, anc_dirs, anc_first, agt_ctrs, agt_dir_last, agt_vel, top,
+                                     d_goals, d_logits, d_coef, d_ss)
+        return (d_pred,) + (None,) * 9
+
+
+class GoalRefineFn(Function):
+    """lgcn_goal_refine under autograd: pred_trajs = refine(s_samples, coef, traj_delta); backward = one
+    lgcn_goal_refine_bwd launch."""
+
+    @staticmethod
+    def forward(ctx, s_samples, coef, traj_delta):
+        s_samples, coef, traj_delta = s_samples.contiguous(), coef.contiguous(), traj_delta.contiguous()
+        ctx.save_for_backward(s_samples, coef, traj_delta)
+        return ops.goal_refine(s_samples, coef, traj_delta)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        s_samples, coef, traj_delta = ctx.saved_tensors
+        return ops.goal_refine_bwd(s_samples, coef, traj_delta, d_out.contiguous())
+
+
+class RoiLossFn(Function):
+    """RoiLoss's three sums (reference lanercnn.py:1214-1301) in one launch, gradients in one more (csrc/lgcn_loss.hip).
+    Returns (cls_loss, reg_goal_loss, reg_traj_loss, counts [3] int32 on the device: num_cls, num_reg_goal,
+    num_reg_traj, pred_goals [A, 2] = the goal of the selected mode, not differentiated)."""
+
+    @staticmethod
+    def forward(ctx, logits, goals, trajs, gt, has, reg_coef):
+        logits, goals, trajs = logits.contiguous(), goals.contiguous(), trajs.contiguous()
+        sums, counts, sel, pred_goals = ops.roi_loss_fwd(logits, goals, trajs, gt, has, reg_coef)
+        ctx.save_for_backward(logits, goals, trajs, gt, has, sel)
+        ctx.reg_coef = reg_coef
+        ctx.mark_non_differentiable(counts, pred_goals)
+        return sums[0], sums[1], sums[2], counts, pred_goals
+
+    @staticmethod
+    def backward(ctx, g_cls, g_goal, g_traj, _c, _p):
+        logits, goals, trajs, gt, has, sel = ctx.saved_tensors
+        z = lambda g: torch.zeros(1, dtype=torch.float32, device=logits.device) if g is None else g.reshape(1).float().contiguous()
+        dlogits, dgoals, dtrajs = ops.roi_loss_bwd(logits, goals, trajs, gt, has, ctx.reg_coef, sel, z(g_cls), z(g_goal), z(g_traj))
+        return dlogits, dgoals, dtrajs, None, None, None

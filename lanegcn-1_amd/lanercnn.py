@@ -10,6 +10,9 @@ Same class names, constructor arguments, forward signatures and state_dict names
   Interactor     lanercnn.py:603-642  stem (MapNet's input form) -> LanePooling -> GlobalGraphNet -> LanePooling
   Decode         lanercnn.py:740-924  goal head, NMS + trajectory coefficients (lgcn_goal_decode), pooling of the agent's
                                       motion into its RoI, refinement head, refined trajectories (lgcn_goal_refine)
+  RoiLoss / Loss :1205-1325           BCE of the mode logits against the mode closest to the last observed step +
+                                      SmoothL1 of that mode's goal and trajectory: lgcn_roi_loss_fwd / _bwd, one launch each
+  PostProcess    :1328-1423           and pred_metrics / pred_metrics_ade (:1426-1463), host-side bookkeeping
 and the module-level nms_select / compute_coefficent / sample_trajectory / sample_d1_trajectory (:687-737).
 
 Inference (no_grad) runs on the HIP kernels; under autograd LaneRoI / GlobalGraphNet train through the LaneConv
@@ -29,6 +32,7 @@ from . import autograd as A
 from . import ops
 from .lanegcn import _fuse_modules, _gn, build_pairs, lane_conv, lane_conv_train, lane_plan, lane_plan_t
 from .layers import Linear
+from .utils import gpu, to_long
 
 
 def _need_cuda(*ts):
@@ -177,16 +181,52 @@ class LanePooling(nn.Module):
                            gn1=_gn(m1.norm), res=target_feat, eps=m1.norm.eps)
 
 
-def _stem(a: nn.Sequential, s: nn.Sequential, xa: Tensor, xs: Tensor) -> Tensor:
-    """ReLU(a(xa) + s(xs)) for two Linear(2,128) -> ReLU -> Linear(128,128,GN) branches: MapNet's stem form
-    (lgcn_mapnet_input, one launch); under autograd composed as MapNet.forward composes it."""
-    xa, xs = xa.contiguous(), xs.contiguous()
-    if ops.wants_grad(xa, xs, *ops.module_params(a), *ops.module_params(s)):
-        fa = A.linear_gn(F.relu(a[0](xa)), a[2].linear.weight, gn=a[2].norm)
-        fs = A.linear_gn(F.relu(s[0](xs)), s[2].linear.weight, gn=s[2].norm)
-        return F.relu(fa + fs)
+def _stem_train(a: nn.Sequential, s: nn.Sequential, xa: Tensor, xs: Tensor) -> Tensor:
+    """_stem composed of differentiable ops, as MapNet.forward composes it."""
+    fa = A.linear_gn(F.relu(a[0](xa)), a[2].linear.weight, gn=a[2].norm)
+    fs = A.linear_gn(F.relu(s[0](xs)), s[2].linear.weight, gn=s[2].norm)
+    return F.relu(fa + fs)
+
+
+def _stem_infer(a: nn.Sequential, s: nn.Sequential, xa: Tensor, xs: Tensor) -> Tensor:
     return ops.mapnet_input(xa, xs, a[0].weight, a[0].bias, ops.packed(a[2].linear.weight), _gn(a[2].norm),
                             s[0].weight, s[0].bias, ops.packed(s[2].linear.weight), _gn(s[2].norm), eps=a[2].norm.eps)
+
+
+class _StemInferFn(torch.autograd.Function):
+    """_stem for inputs that need no gradient, with the inference launch as its forward (Decode.train_hip: the K = 2
+    Linears of the composed path run on ATen and round differently from lgcn_mapnet_input, which would make the
+    training forward differ from the no_grad one in the last bit).  The backward re-runs the composed path and
+    differentiates that: the parameters' gradients are those of _stem_train at the same inputs."""
+
+    @staticmethod
+    def forward(ctx, a, s, xa, xs, *params):
+        ctx.mods = (a, s)
+        ctx.save_for_backward(xa, xs)
+        return _stem_infer(a, s, xa, xs)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, s = ctx.mods
+        xa, xs = ctx.saved_tensors
+        params = [*ops.module_params(a), *ops.module_params(s)]
+        need = [p for p in params if p.requires_grad]
+        with torch.enable_grad():
+            grads = iter(torch.autograd.grad(_stem_train(a, s, xa, xs), need, g.contiguous()))
+        return (None, None, None, None, *[next(grads) if p.requires_grad else None for p in params])
+
+
+def _stem(a: nn.Sequential, s: nn.Sequential, xa: Tensor, xs: Tensor, infer_fwd: bool = False) -> Tensor:
+    """ReLU(a(xa) + s(xs)) for two Linear(2,128) -> ReLU -> Linear(128,128,GN) branches: MapNet's stem form
+    (lgcn_mapnet_input, one launch); under autograd composed as MapNet.forward composes it, or with infer_fwd (and
+    inputs that need no gradient) the same launch with a recomputing backward."""
+    xa, xs = xa.contiguous(), xs.contiguous()
+    params = (*ops.module_params(a), *ops.module_params(s))
+    if ops.wants_grad(xa, xs, *params):
+        if infer_fwd and not (xa.requires_grad or xs.requires_grad):
+            return _StemInferFn.apply(a, s, xa, xs, *params)
+        return _stem_train(a, s, xa, xs)
+    return _stem_infer(a, s, xa, xs)
 
 
 def _stem_branch(n: int) -> nn.Sequential:
@@ -262,12 +302,19 @@ class Decode(nn.Module):
     observed motion (stem form) pooled into its RoI, the refinement head on the k gathered rows and one
     lgcn_goal_refine launch -- no device -> host read besides the pair count inside LanePooling.  Under autograd the
     indices still come from lgcn_nms_select (the reference does not propagate through the selection either) and
-    everything else runs on differentiable ops.
+    everything else runs on differentiable ops; with Decode.train_hip set the decode and refine stages stay on the
+    inference launches and their backward is lgcn_goal_refine_bwd + lgcn_goal_decode_bwd.
 
     The reference hands the motion graph's centres to LanePooling as [1, 20, 2] tensors, whose len() is 1, so its
     context row offset grows by 1 per scene, not by 20: scene b pools rows b .. b + 19 of the concatenated [A * 20]
     motion features and poses (distances still come from scene b's own trajectory).  That numbering is reproduced
     here: the stem and pose rows are gathered in that order before LanePooling sees [20, 2] centres."""
+    # Train the decode and refine stages on the inference launches (autograd.GoalDecodeFn / GoalRefineFn): the training
+    # forward is lgcn_goal_decode + lgcn_goal_refine, their backward lgcn_goal_refine_bwd + lgcn_goal_decode_bwd, instead
+    # of the stock ops of _decode_torch and of the tail of decode(); the motion stem keeps the inference launch as its
+    # forward too (_StemInferFn), so the whole training forward is the no_grad forward bit for bit.  Opt-in, like
+    # Att.train_hip; read on each forward.
+    train_hip = False
 
     def __init__(self, config):
         super().__init__()
@@ -318,7 +365,12 @@ class Decode(nn.Module):
         dir_last = agt_dirs[:, -1, :].float()
         train = ops.wants_grad(roi_feat, *ops.module_params(self))
 
-        if train:
+        fused = train and Decode.train_hip
+        if fused:
+            top, goals, logits, coef, s_samples = A.GoalDecodeFn.apply(pred, pred_spans, anchor_ctrs, anchor_dirs,
+                                                                       [lo for lo, _ in spans], agt_ctrs, dir_last, agt_vels,
+                                                                       k, 2.0)
+        elif train:
             top, goals, logits, coefs, s_samples = self._decode_torch(pred, pred_spans, anchor_ctrs, anchor_dirs, spans,
                                                                       agt_ctrs, dir_last, agt_vels, k)
         else:
@@ -329,7 +381,7 @@ class Decode(nn.Module):
         rows = (torch.arange(n_agt, device=dev).view(-1, 1) + torch.arange(20, device=dev).view(1, -1)).reshape(-1)
         trajs_q = agt_trajs.reshape(-1, 2).float().index_select(0, rows)
         dirs_q = agt_dirs.reshape(-1, 2).float().index_select(0, rows)
-        agt_feat = _stem(self.agt_layer1, self.agt_layer2, trajs_q, dirs_q)
+        agt_feat = _stem(self.agt_layer1, self.agt_layer2, trajs_q, dirs_q, infer_fwd=Decode.train_hip)
         pose_q = torch.cat([trajs_q, dirs_q], -1)
         motion = {"ctrs": [agt_trajs[i].float() for i in range(n_agt)], "pose": list(pose_q.split(20, 0))}
         roi_map = {"ctrs": [anchor_ctrs[lo:hi] for lo, hi in spans],
@@ -345,7 +397,9 @@ class Decode(nn.Module):
             traj_feats = ops.gather_rows(pooled, flat.contiguous(), n_rows, n_agt * k)
         traj_delta = self.refinement(traj_feats).view(n_agt, k, ops.GOAL_STEPS, 2)
 
-        if train:
+        if fused:
+            pred_trajs = A.GoalRefineFn.apply(s_samples, coef, traj_delta)
+        elif train:
             s = s_samples + traj_delta[..., 0]
             s = s / s.max(2, keepdim=True)[0]
             s = torch.where(s == 0.0, torch.ones_like(s), s)
@@ -388,3 +442,116 @@ class Decode(nn.Module):
         v = (agt_vels.view(-1, 1, 1) + acc.unsqueeze(2) * t31).clamp_min(0.0)
         s_samples = (v[:, :, :1] + v[:, :, 1:]) * t31[1:] / 2
         return top, goals, logits, coefs, s_samples
+
+
+# ------------------------------------------------------------------ loss and metrics (reference lanercnn.py:1205-1463)
+class RoiLoss(nn.Module):
+    """Goal / trajectory loss of the fork model (reference lanercnn.py:1205-1301): per scene the first valid agent's
+    future is compared with the mode whose goal is closest to its last observed step.  The first valid agents are
+    picked on the device, the three sums and their gradients are one launch each (autograd.RoiLossFn), and the only
+    device -> host read is the one of the two counts the reference reads with .item() (:1284, :1294)."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.num_mods = config["num_mods"]
+        self.bce_loss = nn.BCELoss()
+        self.reg_loss = nn.SmoothL1Loss(reduction="sum")
+
+    def forward(self, data: Dict, out: Dict, gt_preds: List[Tensor], has_preds: List[Tensor]) -> Dict:
+        pred_logics, pred_goals, pred_trajs = out["pred_logics"], out["pred_goals"], out["pred_trajs"]
+        valid_agent_ids = to_long(gpu(data["valid_agent_ids"]))
+        _need_cuda(pred_logics, pred_goals, pred_trajs, *gt_preds, *has_preds)
+        num_preds = pred_trajs.shape[2]
+        first = lambda xs, tail: torch.cat([x.index_select(0, ids.long()[:1]).view(-1, *tail)
+                                            for ids, x in zip(valid_agent_ids, xs)], 0)
+        gt = first(gt_preds, (num_preds, 2)).float().contiguous()             # [bs, 30, 2]
+        has = first(has_preds, (num_preds,)).bool().contiguous()              # [bs, 30]
+        cls_loss, goal_loss, traj_loss, counts, best_goals = A.RoiLossFn.apply(
+            pred_logics.float(), pred_goals.float(), pred_trajs.float(), gt, has, float(self.config["reg_coef"]))
+        _, n_goal, n_traj = counts.tolist()
+        return {"cls_loss": cls_loss, "num_cls": len(pred_logics), "pred_goals": best_goals,
+                "reg_goal_loss": goal_loss, "num_reg_goal": n_goal, "pred_trajs": pred_trajs,
+                "reg_traj_loss": traj_loss, "num_reg_traj": n_traj, "stage_one_loss": 0, "num_stage_one": 1}
+
+
+class Loss(nn.Module):
+    """loss = cls / num_cls + reg_goal / num_reg_goal + reg_traj / num_reg_traj (reference lanercnn.py:1305-1325)."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.pred_loss = RoiLoss(config)
+
+    def forward(self, out: Dict, data: Dict) -> Dict:
+        loss_out = self.pred_loss(data, out, gpu(data["gt_preds"]), gpu(data["has_preds"]))
+        loss_out["loss"] = (loss_out["cls_loss"] / (loss_out["num_cls"] + 1e-10)
+                            + loss_out["reg_goal_loss"] / (loss_out["num_reg_goal"] + 1e-10)
+                            + loss_out["reg_traj_loss"] / (loss_out["num_reg_traj"] + 1e-10)
+                            + loss_out["stage_one_loss"] / (loss_out["num_stage_one"] + 1e-10))
+        return loss_out
+
+
+def pred_metrics_ade(goals, gt_preds, has_preds):
+    """Mean distance of the chosen goals to the last ground-truth step (reference lanercnn.py:1426-1444)."""
+    assert has_preds.all()
+    goals = np.asarray(goals, np.float32).reshape(-1, 2)
+    gt_preds = np.asarray(gt_preds, np.float32)
+    return np.sqrt(((goals - gt_preds[:, -1]) ** 2).sum(-1)).mean()
+
+
+def pred_metrics(preds, gt_preds, has_preds):
+    """ade1, fde1, ade, fde, min_idcs (reference lanercnn.py:1446-1463)."""
+    assert has_preds.all()
+    preds, gt_preds = np.asarray(preds, np.float32), np.asarray(gt_preds, np.float32)
+    err = np.sqrt(((preds - np.expand_dims(gt_preds, 1)) ** 2).sum(3))
+    ade1, fde1 = err[:, 0].mean(), err[:, 0, -1].mean()
+    min_idcs = err[:, :, -1].argmin(1)
+    best = err[np.arange(len(min_idcs)).astype(np.int64), min_idcs]
+    return ade1, fde1, best.mean(), best[:, -1].mean(), min_idcs
+
+
+class PostProcess(nn.Module):
+    """Collects the chosen goals, all trajectories and the first agent's ground truth per scene, and prints the
+    running losses with ADE / FDE (reference lanercnn.py:1328-1423)."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+
+    def forward(self, out, data, loss_out):
+        return {"goals": [loss_out["pred_goals"].detach().cpu().numpy()],
+                "trajs": [loss_out["pred_trajs"].detach().cpu().numpy()],
+                "gt_preds": [x[0:1].numpy() for x in data["gt_preds"]],
+                "has_preds": [x[0:1].numpy() for x in data["has_preds"]]}
+
+    def append(self, metrics: Dict, loss_out: Dict, post_out=None) -> Dict:
+        if len(metrics.keys()) == 0:
+            for key in loss_out:
+                if key != "loss":
+                    metrics[key] = 0.0
+            for key in post_out:
+                metrics[key] = []
+        for key, val in loss_out.items():
+            if key in ("loss", "pred_goals", "pred_trajs"):
+                continue
+            metrics[key] += val.item() if isinstance(val, torch.Tensor) else val
+        for key in post_out:
+            metrics[key] += post_out[key]
+        return metrics
+
+    def display(self, metrics, dt, epoch, lr=None):
+        if lr is not None:
+            print("Epoch %3.3f, lr %.5f, time %3.2f" % (epoch, lr, dt))
+        else:
+            print("************************* Validation, time %3.2f *************************" % dt)
+        cls = metrics["cls_loss"] / (metrics["num_cls"] + 1e-10)
+        reg_goal = metrics["reg_goal_loss"] / (metrics["num_reg_goal"] + 1e-10)
+        reg_traj = metrics["reg_traj_loss"] / (metrics["num_reg_traj"] + 1e-10)
+        stg1_cls = metrics["stage_one_loss"] / (metrics["num_stage_one"] + 1e-10)
+        loss = cls + reg_goal + reg_traj + stg1_cls
+        ade1, fde1, ade, fde, _ = pred_metrics(np.concatenate(metrics["trajs"], 0), np.concatenate(metrics["gt_preds"], 0),
+                                               np.concatenate(metrics["has_preds"], 0))
+        print("loss %2.4f - %2.4f %2.4f %2.4f, %2.4f - ade1=%2.4f fde1=%2.4f ade=%2.4f fde=%2.4f"
+              % (loss, cls, reg_goal, reg_traj, stg1_cls, ade1, fde1, ade, fde))
+        print()

@@ -1742,3 +1742,121 @@ def goal_refine(s_samples: torch.Tensor, coef: torch.Tensor, traj_delta: torch.T
     L.check(lib.lgcn_goal_refine(_ptr(s_samples), _ptr(coef), _ptr(traj_delta), A_ * k, _ptr(out), _stream()),
             "lgcn_goal_refine")
     return out
+
+
+def goal_refine_bwd(s_samples: torch.Tensor, coef: torch.Tensor, traj_delta: torch.Tensor, d_pred_trajs: torch.Tensor):
+    """lgcn_goal_refine_bwd: (d_s_samples [A, k, 30], d_coef [A, k, 6], d_traj_delta [A, k, 30, 2]) of goal_refine."""
+    lib = L.load()
+    s_samples = _dev(s_samples, torch.float32, "s_samples")
+    coef = _dev(coef, torch.float32, "coef")
+    traj_delta = _dev(traj_delta, torch.float32, "traj_delta")
+    d_pred_trajs = _dev(d_pred_trajs, torch.float32, "d_pred_trajs")
+    if s_samples.dim() != 3 or s_samples.shape[2] != GOAL_STEPS:
+        raise L.LgcnError("goal_refine_bwd: s_samples [A, k, 30] expected, got %s" % (tuple(s_samples.shape),))
+    A_, k = s_samples.shape[:2]
+    if (tuple(coef.shape) != (A_, k, 6) or tuple(traj_delta.shape) != (A_, k, GOAL_STEPS, 2)
+            or d_pred_trajs.shape != traj_delta.shape):
+        raise L.LgcnError("goal_refine_bwd: coef [A, k, 6], traj_delta and d_pred_trajs [A, k, 30, 2] expected, got %s, %s, %s"
+                          % (tuple(coef.shape), tuple(traj_delta.shape), tuple(d_pred_trajs.shape)))
+    d_ss, d_coef, d_delta = torch.empty_like(s_samples), torch.empty_like(coef), torch.empty_like(traj_delta)
+    L.check(lib.lgcn_goal_refine_bwd(_ptr(s_samples), _ptr(coef), _ptr(traj_delta), _ptr(d_pred_trajs), A_ * k, _ptr(d_ss),
+                                     _ptr(d_coef), _ptr(d_delta), _stream()), "lgcn_goal_refine_bwd")
+    return d_ss, d_coef, d_delta
+
+
+def goal_decode_bwd(pred: torch.Tensor, pred_spans, anc_ctrs: torch.Tensor, anc_dirs: torch.Tensor, anc_first,
+                    agt_ctrs: torch.Tensor, agt_dir_last: torch.Tensor, agt_vel: torch.Tensor, top_idx: torch.Tensor,
+                    d_goals=None, d_logits=None, d_coef=None, d_s_samples=None) -> torch.Tensor:
+    """lgcn_goal_decode_bwd: d_pred [n, 5] of goal_decode for its inputs, its top_idx [A, k] and the upstream gradients
+    of goals [A, k, 2], logits [A, k], coef [A, k, 6] and s_samples [A, k, 30] (None = zero)."""
+    lib = L.load()
+    pred = _dev(pred, torch.float32, "pred")
+    anc_ctrs = _dev(anc_ctrs, torch.float32, "anc_ctrs")
+    anc_dirs = _dev(anc_dirs, torch.float32, "anc_dirs")
+    agt_ctrs = _dev(agt_ctrs, torch.float32, "agt_ctrs")
+    agt_dir_last = _dev(agt_dir_last, torch.float32, "agt_dir_last")
+    agt_vel = _dev(agt_vel, torch.float32, "agt_vel")
+    top_idx = _dev(top_idx, torch.int32, "top_idx")
+    off_host, off = _offsets(pred_spans, "pred_spans")
+    A_ = len(off) - 1
+    if pred.dim() != 2 or pred.shape[1] != 5 or off[-1] != pred.shape[0]:
+        raise L.LgcnError("goal_decode_bwd: pred [n, 5] covered by pred_spans expected, got %s and a table ending at %d"
+                          % (tuple(pred.shape), off[-1]))
+    if anc_ctrs.dim() != 2 or anc_ctrs.shape[1] != 2 or anc_dirs.shape != anc_ctrs.shape:
+        raise L.LgcnError("goal_decode_bwd: anc_ctrs / anc_dirs [N, 2] expected")
+    if tuple(agt_ctrs.shape) != (A_, 2) or tuple(agt_dir_last.shape) != (A_, 2) or tuple(agt_vel.shape) != (A_,):
+        raise L.LgcnError("goal_decode_bwd: agt_ctrs [A, 2], agt_dir_last [A, 2], agt_vel [A] expected for A = %d" % A_)
+    if top_idx.dim() != 2 or top_idx.shape[0] != A_ or not 1 <= top_idx.shape[1] <= GOAL_MAX_MODS:
+        raise L.LgcnError("goal_decode_bwd: top_idx [A, k] with k in 1..8 expected, got %s" % (tuple(top_idx.shape),))
+    k = top_idx.shape[1]
+    first_host = torch.tensor([int(v) for v in anc_first], dtype=torch.int32)
+    if first_host.shape[0] != A_:
+        raise L.LgcnError("goal_decode_bwd: %d anchor offsets for %d agents" % (first_host.shape[0], A_))
+    dev = pred.device
+    ups = []
+    for g, shape, name in ((d_goals, (A_, k, 2), "d_goals"), (d_logits, (A_, k), "d_logits"), (d_coef, (A_, k, 6), "d_coef"),
+                           (d_s_samples, (A_, k, GOAL_STEPS), "d_s_samples")):
+        if g is None:
+            g = torch.zeros(shape, dtype=torch.float32, device=dev)
+        g = _dev(g, torch.float32, name)
+        if tuple(g.shape) != shape:
+            raise L.LgcnError("goal_decode_bwd: %s %s expected, got %s" % (name, shape, tuple(g.shape)))
+        ups.append(g)
+    off_dev, first_dev = off_host.to(dev, non_blocking=True), first_host.to(dev, non_blocking=True)
+    d_pred = torch.empty_like(pred)
+    L.check(lib.lgcn_goal_decode_bwd(_ptr(pred), _ptr(off_dev), C.c_void_p(off_host.data_ptr()), pred.shape[0],
+                                     _ptr(anc_ctrs), _ptr(anc_dirs), anc_ctrs.shape[0], _ptr(first_dev),
+                                     C.c_void_p(first_host.data_ptr()), _ptr(agt_ctrs), _ptr(agt_dir_last), _ptr(agt_vel),
+                                     A_, k, _ptr(top_idx), _ptr(ups[0]), _ptr(ups[1]), _ptr(ups[2]), _ptr(ups[3]),
+                                     _ptr(d_pred), _stream()), "lgcn_goal_decode_bwd")
+    return d_pred
+
+
+def _roi_loss_args(logits, goals, trajs, gt, has, who):
+    logits = _dev(logits, torch.float32, "logits")
+    goals = _dev(goals, torch.float32, "goals")
+    trajs = _dev(trajs, torch.float32, "trajs")
+    gt = _dev(gt, torch.float32, "gt")
+    has = _dev(has, torch.uint8 if has.dtype == torch.uint8 else torch.bool, "has")
+    if logits.dim() != 2 or trajs.dim() != 4:
+        raise L.LgcnError("%s: logits [A, M] and trajs [A, M, T, 2] expected, got %s and %s"
+                          % (who, tuple(logits.shape), tuple(trajs.shape)))
+    A_, M = logits.shape
+    T = trajs.shape[2]
+    if (tuple(goals.shape) != (A_, M, 2) or tuple(trajs.shape) != (A_, M, T, 2) or tuple(gt.shape) != (A_, T, 2)
+            or tuple(has.shape) != (A_, T)):
+        raise L.LgcnError("%s: goals [A, M, 2], trajs [A, M, T, 2], gt [A, T, 2], has [A, T] expected for A = %d, M = %d, "
+                          "T = %d; got %s, %s, %s, %s" % (who, A_, M, T, tuple(goals.shape), tuple(trajs.shape),
+                                                          tuple(gt.shape), tuple(has.shape)))
+    return logits, goals, trajs, gt, has, A_, M, T
+
+
+def roi_loss_fwd(logits, goals, trajs, gt, has, reg_coef: float = 1.0):
+    """lgcn_roi_loss_fwd: (sums [3] fp32 = cls, reg_goal, reg_traj; counts [3] int32 = num_cls, num_reg_goal,
+    num_reg_traj; sel [A] int32 = min_idx | has_goal << 8; pred_goals [A, 2])."""
+    lib = L.load()
+    logits, goals, trajs, gt, has, A_, M, T = _roi_loss_args(logits, goals, trajs, gt, has, "roi_loss_fwd")
+    dev = logits.device
+    new = torch.zeros if A_ == 0 else torch.empty          # an empty problem launches nothing: its sums are these zeros
+    sums = new(3, dtype=torch.float32, device=dev)
+    counts = new(3, dtype=torch.int32, device=dev)
+    sel = torch.empty(A_, dtype=torch.int32, device=dev)
+    pred_goals = torch.empty((A_, 2), dtype=torch.float32, device=dev)
+    L.check(lib.lgcn_roi_loss_fwd(_ptr(logits), _ptr(goals), _ptr(trajs), _ptr(gt), _ptr(has), A_, M, T, float(reg_coef),
+                                  _ptr(sums), _ptr(counts), _ptr(sel), _ptr(pred_goals), _stream()), "lgcn_roi_loss_fwd")
+    return sums, counts, sel, pred_goals
+
+
+def roi_loss_bwd(logits, goals, trajs, gt, has, reg_coef, sel, g_cls, g_goal, g_traj):
+    """lgcn_roi_loss_bwd: (dlogits, dgoals, dtrajs), every element written; g_*: device scalars [1]."""
+    lib = L.load()
+    logits, goals, trajs, gt, has, A_, M, T = _roi_loss_args(logits, goals, trajs, gt, has, "roi_loss_bwd")
+    sel = _dev(sel, torch.int32, "sel")
+    gs = [_dev(g, torch.float32, "upstream gradient") for g in (g_cls, g_goal, g_traj)]
+    if sel.numel() != A_ or any(g.numel() != 1 for g in gs):
+        raise L.LgcnError("roi_loss_bwd: sel [A] and three one-element gradients expected")
+    dlogits, dgoals, dtrajs = torch.empty_like(logits), torch.empty_like(goals), torch.empty_like(trajs)
+    L.check(lib.lgcn_roi_loss_bwd(_ptr(logits), _ptr(goals), _ptr(trajs), _ptr(gt), _ptr(has), A_, M, T, float(reg_coef),
+                                  _ptr(sel), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(dlogits), _ptr(dgoals), _ptr(dtrajs),
+                                  _stream()), "lgcn_roi_loss_bwd")
+    return dlogits, dgoals, dtrajs

@@ -5,7 +5,10 @@ arithmetic as ~80 elementwise ATen launches.  Both share the module's weights an
 stock side are F.linear + F.group_norm.  Prints the medians and one JSON line.  A number for DESIGN.md; no bar.
 
   --agents N --nodes M   interest agents and nodes per RoI (default 32 x 300)
-  --steps K --warmup W   timed and untimed forwards per variant, alternating call by call"""
+  --steps K --warmup W   timed and untimed forwards per variant, alternating call by call
+  --train                instead: forward + backward of Decode + lanercnn.Loss with Decode.train_hip off and on, alternating
+                         step by step in this process after the warm-up; medians, and the kernel launches per step of each
+                         path (torch.profiler; null where it is unavailable)"""
 import argparse
 import json
 import os
@@ -134,6 +137,72 @@ def stock_decode(m, roi_feat, sub, data, k=6):
     return logits, goals, R.sample_trajectory(s, *coefs) + shift, torch.stack(tops)
 
 
+def count_launches(step):
+    """Device kernel launches of one step() as torch.profiler sees them, or None."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            step()
+            torch.cuda.synchronize()
+        kernels = [e for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower()
+                   and "memset" not in e.name.lower()]
+        return len(kernels) or None
+    except Exception as exc:  # noqa: BLE001  (a number for a document; never a reason to lose the timings)
+        print("launch count unavailable: %r" % (exc,), flush=True)
+        return None
+
+
+def train_mode(args):
+    """Forward + backward of Decode + Loss, Decode.train_hip off / on."""
+    torch.manual_seed(0)
+    cfg = dict(M.config, num_mods=6, num_preds=30)
+    m = R.Decode(cfg).cuda().train()
+    loss = R.Loss(cfg)
+    sub, data, roi_feat = make_inputs(args.agents, args.nodes)
+    rng = np.random.default_rng(1)
+    data["gt_preds"], data["has_preds"] = [], []
+    for c, f in zip(data["ctrs"], data["feats"]):              # the future: the last observed step continued, all observed
+        step = f[0, -1, :2].cpu().numpy().astype(np.float64)
+        gt = c.cpu().numpy() + np.outer(np.arange(1, 31), step) + rng.normal(0, 0.3, (30, 2))
+        data["gt_preds"].append(torch.from_numpy(gt[None].astype(np.float32)).cuda())
+        data["has_preds"].append(torch.ones(1, 30, dtype=torch.bool).cuda())
+    x = roi_feat.clone().requires_grad_(True)
+
+    def step(on):
+        R.Decode.train_hip = on
+        try:
+            m.zero_grad(set_to_none=True)
+            x.grad = None
+            logits, goals, trajs = m(x, sub, data)
+            lo = loss({"pred_logics": logits, "pred_goals": goals, "pred_trajs": trajs}, data)
+            lo["loss"].backward()
+            return lo["loss"].detach()
+        finally:
+            R.Decode.train_hip = False
+
+    names = {"off": False, "on": True}
+    times = {k: [] for k in names}
+    for _ in range(max(args.warmup, 3)):
+        for on in names.values():
+            step(on)
+    torch.cuda.synchronize()
+    for _ in range(max(args.steps, 20)):
+        for name, on in names.items():
+            t0 = time.perf_counter()
+            step(on)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    launches = {name: count_launches(lambda on=on: step(on)) for name, on in names.items()}
+    values = {name: float(step(on)) for name, on in names.items()}
+    res = {"metric": "Decode + Loss forward + backward, %d interest agents x %d nodes" % (args.agents, args.nodes),
+           "mma": ops.get_mma(), "steps": len(times["on"]), "median_ms": {k: float(np.median(v)) for k, v in times.items()},
+           "min_ms": {k: min(v) for k, v in times.items()}, "launches_per_step": launches, "loss": values}
+    for name in names:
+        print("Decode + Loss step, train_hip %s: median %.3f ms (min %.3f), %s launches" % (name, res["median_ms"][name],
+                                                                                          res["min_ms"][name], launches[name]), flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--agents", type=int, default=32)
@@ -141,9 +210,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--mma", default=None)
+    ap.add_argument("--train", action="store_true")
     args = ap.parse_args()
     if args.mma:
         ops.set_mma(args.mma)
+    if args.train:
+        return train_mode(args)
     torch.manual_seed(0)
     m = R.Decode(M.config).cuda().eval()
     sub, data, roi_feat = make_inputs(args.agents, args.nodes)

@@ -88,13 +88,13 @@ def gather_sum(x, edges, n_rows, model=True):
     """A[n] = sum_{e: u[e] = n} x[v[e]], sources in ascending order of v, duplicates kept (LGCN_REL_CSR).  The kernels
     form the sum in fp32 and split the sum; model=False: the float64 sum."""
     if edges is None:
-        return arr(x, np.float32)[:n_rows]
+        return arr(x, np.float32 if model else None)[:n_rows]
     u, v = (arr(t, np.int64) for t in edges)
     order = np.lexsort((v, u))
     u, v = u[order], v[order]
     dt = np.float32 if model else np.float64
     out = np.zeros((n_rows, arr(x).shape[1]), dt)
-    np.add.at(out, u, arr(x, np.float32).astype(dt)[v])       # unbuffered: one addition per edge, in order
+    np.add.at(out, u, arr(x, np.float32 if model else None).astype(dt)[v])       # unbuffered: one addition per edge, in order
     return out
 
 
@@ -141,14 +141,16 @@ def lane_conv(x, units, gn1, w2, gn2, mode, eps=EPS, model=True):
 
 def lin2_relu(xy, w1, b1, model):
     """ReLU(w1 xy + b1) of an [n, 2] input, held in fp32."""
-    h = arr(xy, np.float32).astype(np.float64) @ arr(w1, np.float32).astype(np.float64).T + arr(b1, np.float64)
+    h = arr(xy, np.float64) @ arr(w1, np.float32).astype(np.float64).T + arr(b1, np.float64)
     return _hold(np.maximum(h, 0.0), model)
 
 
-def att_pairs(agt_ctrs, ctx_ctrs, hi, wi, wd0, bd0, w_d2, gn_d, w_c0e, U, V, gn_c, mode, eps=EPS, model=True):
-    """m [P, 128] of lgcn_att_pairs / _ws / _wi (include/lgcn.h); w_c0e = columns 0:128 of ctx.0's weight."""
+def att_pairs(agt_ctrs, ctx_ctrs, hi, wi, wd0, bd0, w_d2, gn_d, w_c0e, U, V, gn_c, mode, eps=EPS, model=True, exact_d=False):
+    """m [P, 128] of lgcn_att_pairs / _ws / _wi (include/lgcn.h); w_c0e = columns 0:128 of ctx.0's weight.  exact_d: the
+    centre offsets in float64 (what a float64 run of the reference forms) instead of the kernels' fp32 difference."""
     hi, wi = arr(hi, np.int64), arr(wi, np.int64)
-    d = arr(agt_ctrs, np.float32)[hi] - arr(ctx_ctrs, np.float32)[wi]                 # fp32, as the kernels form it
+    dt = np.float64 if exact_d else np.float32
+    d = arr(agt_ctrs, np.float32).astype(dt)[hi] - arr(ctx_ctrs, np.float32).astype(dt)[wi]      # default: fp32, as the kernels form it
     h1 = lin2_relu(d, wd0, bd0, model)
     e = np.maximum(gn(_mm(h1, w_d2, mode, model), *gn_d, eps), 0.0)
     c = _mm(_hold(e, model), w_c0e, mode, model) + arr(U, np.float64)[hi] + arr(V, np.float64)[wi]
@@ -160,6 +162,85 @@ def mapnet_input(ctrs, feats, wa1, ba1, wa2, gn_a, ws1, bs1, ws2, gn_s, mode, ep
     a = gn(_mm(lin2_relu(ctrs, wa1, ba1, model), wa2, mode, model), *gn_a, eps)
     s = gn(_mm(lin2_relu(feats, ws1, bs1, model), ws2, mode, model), *gn_s, eps)
     return np.maximum(a + s, 0.0)
+
+
+def seg_sum(m, hi, n_rows, model=True):
+    """S[t] = sum_{p: hi[p] = t} m[p] (LGCN_REL_RANGE / RANGE16): the float64 sum of the rows as held, then held itself.
+    The kernels add in fp32 in an order that depends on the pair kernel (whole segments, or 16-aligned pieces first)."""
+    out = np.zeros((n_rows, arr(m).shape[1]))
+    np.add.at(out, arr(hi, np.int64), arr(_hold(m, model), np.float64))
+    return _hold(out, model)
+
+
+HOT_CFG = {"actor2map_dist": 7.0, "map2actor_dist": 6.0, "actor2actor_dist": 100.0, "num_scales": 6}
+STAGES = ("map_net", "a2m", "m2m", "m2a", "a2a")
+
+
+def hot_path(graph, actors, actor_ctrs, sd, mode, model=True, cfg=None):
+    """MapNet -> A2M -> M2M -> M2A -> A2A (oracle.hot_path's arguments: the gathered graph, ActorNet's output rows, the
+    per-scene actor centres, a state dict) as the launches of lanegcn.py compose them: lgcn_mapnet_input, 4 LaneConv
+    layers, A2M.meta_kw (128 columns through the matrix cores, the four meta columns w4 beside them), per Att layer
+    u_kw / v_kw (U per target row, V per context row), the pair stage and pairs_tail (segment sum, agt + ctx.1, norm,
+    linear, residual), 4 more LaneConv layers, M2A, A2A.  Every GEMM over a 128-column block goes through mm(); a value
+    one kernel hands to the next, or one GEMM of a kernel to the next, is rounded to fp32 (_hold).  The [*, 2] Linears,
+    w4, GroupNorm, U[hi] + V[wi], the segment sum and the residuals are float64 behind their fp32 inputs.  Pairs come
+    from oracle.pair_search (fp32, as lgcn_pairs_build).  model=False: the exact float64 value of the reference's
+    formulas (centre offsets in float64 too).  Returns {stage: float64 [rows, 128]}."""
+    from oracle import lanegcn_oracle as O
+    cfg = cfg or HOT_CFG
+    W = lambda name: arr(sd[name], np.float32)
+    G = lambda name: (W(name + ".weight"), W(name + ".bias"))
+    node_ctrs = graph["ctrs"]                                            # per-scene torch tensors, as the oracle takes them
+    cat = lambda cs: np.concatenate([arr(c, np.float32) for c in cs], 0)
+    nodes_c, actors_c = cat(node_ctrs), cat(actor_ctrs)
+    keys = [(k1, i) for i in range(cfg["num_scales"]) for k1 in ("pre", "suc")]
+    edges = [("%s%d" % k, (graph[k[0]][k[1]]["u"], graph[k[0]][k[1]]["v"])) for k in keys]
+    edges += [(k, (graph[k]["u"], graph[k]["v"])) for k in ("left", "right")]
+    edges = [(k, e) for k, e in edges if len(e[0]) > 0]
+
+    def fuse(x, prefix):
+        for i in range(4):
+            units = [(W("%s.ctr.%d.weight" % (prefix, i)), None)] + [(W("%s.%s.%d.weight" % (prefix, k, i)), e) for k, e in edges]
+            c2 = "%s.ctr2.%d" % (prefix, i)
+            x = _hold(lane_conv(x, units, G("%s.norm.%d" % (prefix, i)), W(c2 + ".linear.weight"), G(c2 + ".norm"), mode,
+                                model=model), model)
+        return x
+
+    def att(agts, agt_c, ctx, ctx_c, hi, wi, name):
+        wc0 = W(name + ".ctx.0.linear.weight")
+        q = np.maximum(gn(_mm(agts, W(name + ".query.linear.weight"), mode, model), *G(name + ".query.norm")), 0.0)
+        U = _hold(_mm(_hold(q, model), wc0[:, C:2 * C], mode, model), model)
+        V = _hold(_mm(ctx, wc0[:, 2 * C:], mode, model), model)
+        m = att_pairs(agt_c, ctx_c, hi, wi, W(name + ".dist.0.weight"), W(name + ".dist.0.bias"), W(name + ".dist.2.linear.weight"),
+                      G(name + ".dist.2.norm"), wc0[:, :C], U, V, G(name + ".ctx.0.norm"), mode, model=model, exact_d=not model)
+        T = agts.shape[0]
+        rels = [(agts, W(name + ".agt.weight"), None), (seg_sum(m, hi, T, model), W(name + ".ctx.1.weight"), None)]
+        return _hold(row_block(T, rels, mode, gn1=G(name + ".norm"), relu1=True, w2=W(name + ".linear.linear.weight"),
+                               gn2=G(name + ".linear.norm"), res=agts, relu2=True, model=model)["out"], model)
+
+    def block(agts, agt_cs, agt_c, ctx, ctx_cs, ctx_c, th, prefix):
+        hi, wi = O.pair_search(agt_cs, ctx_cs, th)
+        for i in range(2):
+            agts = att(agts, agt_c, agts if ctx is None else ctx, ctx_c, hi, wi, "%s.att.%d" % (prefix, i))
+        return agts
+
+    out = {}
+    a, s = "map_net.input", "map_net.seg"
+    x = mapnet_input(nodes_c, arr(graph["feats"], np.float32), W(a + ".0.weight"), W(a + ".0.bias"), W(a + ".2.linear.weight"),
+                     G(a + ".2.norm"), W(s + ".0.weight"), W(s + ".0.bias"), W(s + ".2.linear.weight"), G(s + ".2.norm"), mode,
+                     model=model)
+    out["map_net"] = x = fuse(_hold(x, model), "map_net.fuse")
+    wm = W("a2m.meta.linear.weight")
+    meta4 = np.concatenate([arr(graph["turn"], np.float64), arr(graph["control"], np.float64)[:, None],
+                            arr(graph["intersect"], np.float64)[:, None]], 1)
+    x = _mm(x, wm[:, :C], mode, model) + meta4 @ wm[:, C:].astype(np.float64).T
+    x = _hold(np.maximum(gn(x, *G("a2m.meta.norm")), 0.0), model)
+    acts = arr(actors, np.float32)
+    out["a2m"] = x = block(x, node_ctrs, nodes_c, acts, actor_ctrs, actors_c, cfg["actor2map_dist"], "a2m")
+    out["m2m"] = x = fuse(x, "m2m.fuse")
+    out["m2a"] = y = block(acts, actor_ctrs, actors_c, x, node_ctrs, nodes_c, cfg["map2actor_dist"], "m2a")
+    out["a2a"] = block(y, actor_ctrs, actors_c, None, actor_ctrs, actors_c, cfg["actor2actor_dist"], "a2a")
+    return {k: arr(v, np.float64) for k, v in out.items()}
 
 
 def conv1d_unit(x, w, stride, gamma, beta, mode, eps=EPS, relu=False, model=True):

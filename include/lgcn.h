@@ -676,6 +676,29 @@ int64_t lgcn_att_pairs_bwd_ws_elems(int64_t cap, int n_chunks);
 int lgcn_att_pairs_bwd(const lgcn_att_pairs_bwd_t *p_host, void *stream);
 
 /*
+ * The pair stage of the fork's LanePooling (reference lanercnn.py:492-499) in one launch, exact fp32 whatever the matrix
+ * mode of the rest of the network.  Per pair p < *n_pairs (a negative or larger count is clamped to cap, as in
+ * lgcn_att_pairs), t = ti[p] the target row and c = ci[p] the context row:
+ *   d    = ctx_pose[c] - tgt_pose[t]                 4 floats, one fp32 subtraction each (:494)
+ *   h    = ReLU(W_p d + b_p)                         relpose.0 (:495)
+ *   z    = W_0[:, 128:256] h + U[c]                  ctx.0's Linear over cat(context feature, h) (:497-499)
+ *   m[p] = ReLU(GN(z; g, bt, eps))                   ctx.0's GroupNorm(1,128) and ReLU
+ * where U = context_feat W_0[:, 0:128]^T (one row per context row) was hoisted out of the pair loop.  ctx.1 (linear) is
+ * applied after the per-target segment sum by lgcn_agg_mlp (an LGCN_REL_RANGE relation over m).
+ *   ctx_pose [C,4], tgt_pose [T,4]: rows of 16 bytes, 16-byte aligned; ti, ci: [cap] int32
+ *   wp [128,4], bp [128]: relpose.0; wpc0h: lgcn_pack_weight image (LGCN_MMA_F32) of ctx.0's columns 128:256
+ *   m: [cap,128]; only rows < the count are written.  No atomics, no workspace: results are bitwise repeatable.
+ * NULL pointers and cap < 0: LGCN_EINVAL; misaligned pointers: LGCN_EALIGN; cap > 0x7ffffff0: LGCN_ESHAPE; cap == 0
+ * returns LGCN_OK without a launch.
+ */
+int lgcn_pool_pairs(const float *ctx_pose, const float *tgt_pose,
+                    const int32_t *ti, const int32_t *ci,
+                    const int32_t *n_pairs, int64_t cap,
+                    const float *wp, const float *bp, const float *wpc0h,
+                    const float *U, const float *g, const float *bt,
+                    float eps, float *m, void *stream);
+
+/*
  * PredLoss (reference lanegcn.py:740-807), forward and backward, one launch each.
  *   cls [A, M], reg [A, M, T, 2], gt [A, T, 2] fp32; has [A, T] bytes (torch.bool); M <= 8, T <= 64.
  * Per actor: last = argmax_t(has[t] + 0.1 t / T), kept iff that maximum > 1.0; dist_j = |reg[j, last] - gt[last]|;

@@ -169,6 +169,7 @@ SIGNATURES = {
     "lgcn_mapnet_input": (C.c_int, [_P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs_train": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _P, _P, _P]),
+    "lgcn_pool_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 6 + [_F, _P, _P]),
     "lgcn_att_pairs_bwd_ws_elems": (C.c_int64, [_L, _I]),
     "lgcn_att_pairs_bwd": (C.c_int, [C.POINTER(AttPairsBwd), _P]),
     "lgcn_laneconv_bwd_ws_elems": (C.c_int64, [_L, _I, _I]),

@@ -405,6 +405,67 @@ __global__ __launch_bounds__(256) void k_att_pairs(const PairParams p, uint4 *__
     }
 }
 
+// --------------------------------------------------------- pool pairs -----
+// The pair stage of the fork's LanePooling (reference lanercnn.py:492-499): k_att_pairs with a 4-d relative pose in
+// place of the 2-d offset, one GEMM instead of two and one hoisted row block (U, per context row) instead of two.
+// h[row][c] = ReLU(w[c] . d + b[c]) for the thread's 16 columns; w: [128,4], one float4 per channel
+__device__ __forceinline__ void lin4_relu_to_lds(float *T, int t, float4 d, const float *__restrict__ w,
+                                                 const float *__restrict__ b) {
+    float *p = T + (t >> 3) * kLDA + 4 * (t & 7);
+    const int c0 = 4 * (t & 7);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float4 *wc = reinterpret_cast<const float4 *>(w) + (c0 + 32 * j);
+        const float4 bb = *reinterpret_cast<const float4 *>(b + c0 + 32 * j);
+        const float4 w0 = wc[0], w1 = wc[1], w2 = wc[2], w3 = wc[3];
+        float4 o;
+        o.x = relu_nan(d.x * w0.x + d.y * w0.y + d.z * w0.z + d.w * w0.w + bb.x);
+        o.y = relu_nan(d.x * w1.x + d.y * w1.y + d.z * w1.z + d.w * w1.w + bb.y);
+        o.z = relu_nan(d.x * w2.x + d.y * w2.y + d.z * w2.z + d.w * w2.w + bb.z);
+        o.w = relu_nan(d.x * w3.x + d.y * w3.y + d.z * w3.z + d.w * w3.w + bb.w);
+        *reinterpret_cast<float4 *>(p + 32 * j) = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pool_pairs(const PoolParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * kTileFloats];
+    float *T1 = smem, *T2 = smem + kTileFloats;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int64_t P = *p.n_pairs;
+    if (P < 0 || P > p.cap) P = p.cap;
+    const int64_t n_tiles = (P + kTM32 - 1) / kTM32;
+    f32x16 acc;
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t pr = tile * kTM32 + (tid >> 3);
+        const bool live = pr < P;
+        int c = 0;
+        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) {
+            c = p.ci[pr];
+            const float4 a = reinterpret_cast<const float4 *>(p.ctx_pose)[c];
+            const float4 b = reinterpret_cast<const float4 *>(p.tgt_pose)[p.ti[pr]];
+            d = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
+        }
+        lin4_relu_to_lds(T1, tid, d, p.wp, p.bp);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        tile_gemm(T1, reinterpret_cast<const float4 *>(p.wpc0h) + wave * (16 * 64), acc, lane, 16);
+        acc_to_lds(T2, acc, lane, wave);
+        __syncthreads();
+        {
+            RowVals r = row_load(T2, tid);
+            if (live) row_add_global(r, p.U + (int64_t)c * kC, tid);
+            row_gn(r, tid, p.g, p.bt, p.eps);
+            row_relu(r);
+            if (live) row_store_global(p.m + pr * kC, tid, r);
+        }
+        // T1 is rewritten only after every wave's tile_gemm (the barrier above); T2 only after the next iteration's
+        // first barrier, which every thread reaches after its row_load.
+    }
+}
+
 
 // ------------------------------------------------------------- wgrad ------
 // One 32-row tile of dW += D^T S for the 64 x 64 block (q >> 1, q & 1) of the 128 x 128 result: D (the dT rows) and S (the
@@ -1250,6 +1311,23 @@ int lgcn_att_pairs_train(const float *agt_ctrs, const float *ctx_ctrs, const int
     const int64_t tiles = (cap + kTM32 - 1) / kTM32;
     const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
     hipLaunchKernelGGL(k_att_pairs<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, reinterpret_cast<uint4 *>(masks));
+    return launch_status();
+}
+
+int lgcn_pool_pairs(const float *ctx_pose, const float *tgt_pose, const int32_t *ti, const int32_t *ci,
+                    const int32_t *n_pairs, int64_t cap, const float *wp, const float *bp, const float *wpc0h,
+                    const float *U, const float *g, const float *bt, float eps, float *m, void *stream) {
+    if (cap < 0) return LGCN_EINVAL;
+    if (cap == 0) return LGCN_OK;
+    if (cap > 0x7ffffff0) return LGCN_ESHAPE;
+    const void *ptrs[] = {ctx_pose, tgt_pose, ti, ci, n_pairs, wp, bp, wpc0h, U, g, bt, m};
+    for (const void *q : ptrs) LGCN_CHECK_PTR(q);
+    const void *al[] = {ctx_pose, tgt_pose, wp, bp, wpc0h, U, g, bt, m};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);
+    PoolParams p{ctx_pose, tgt_pose, ti, ci, n_pairs, cap, wp, bp, wpc0h, U, g, bt, eps, m};
+    const int64_t tiles = (cap + kTM32 - 1) / kTM32;
+    const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
+    hipLaunchKernelGGL(k_pool_pairs, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     return launch_status();
 }
 

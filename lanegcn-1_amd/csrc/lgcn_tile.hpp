@@ -200,6 +200,16 @@ struct PairParams {
     float *m;
 };
 
+// lgcn_pool_pairs: the pair stage of the fork's LanePooling (see include/lgcn.h)
+struct PoolParams {
+    const float *ctx_pose, *tgt_pose;
+    const int32_t *ti, *ci, *n_pairs;
+    int64_t cap;
+    const float *wp, *bp, *wpc0h, *U, *g, *bt;
+    float eps;
+    float *m;
+};
+
 // lgcn_att_pairs_bwd: the forward's inputs, what it saved and the gradient outputs (see include/lgcn.h)
 struct PairBwdParams {
     PairParams f;

@@ -191,6 +191,85 @@ def synth_batch(kind="S2", seed=0, n_scenes=None, idx_dtype=np.int64):
     raise ValueError(kind)
 
 
+def agent_speeds(feats, cycle_time=0.1):
+    """Mean speed of every agent over its observed window: path length of the steps feats [A,20,>=2] over the time from
+    the first to the last moving step (the reference's get_velocity_per_agent, data_lrcnn.py:666-684); 0 for an agent
+    that never moves."""
+    direct = np.sqrt((np.asarray(feats)[:, :, :2].astype(np.float64) ** 2).sum(-1))
+    moving = direct > 0
+    any_move = moving.any(1)
+    first = moving.argmax(1)
+    last = moving.shape[1] - 1 - moving[:, ::-1].argmax(1)
+    vel = np.zeros(len(direct), np.float32)
+    vel[any_move] = (direct.sum(1) / ((last - first + 1) * cycle_time))[any_move]
+    return vel
+
+
+def synth_subgraphs(scene, horizon_time=3.0, horizon_buffer=20.0, max_rois=None, min_nodes=6, near=5.0):
+    """Lane RoIs on a synth_scene, laid out as the reference's generate_lane_roi lays them out (data_lrcnn.py:789-837):
+    adds scene["subgraphs"] (one RoI per moving agent) and scene["valid_agent_ids"] (int16), and fills
+    scene["obs_trajs"] [A,20,3] (positions that end at ctrs) where the scene lacks it.  Returns the scene.
+
+    A RoI holds the nodes of every lane with a node within speed * horizon_time + horizon_buffer metres of the agent,
+    in ascending node order, and the induced subgraph of all 14 relations over them (edges sorted by (u, v), local
+    numbering): feats [n,8] = (ctr, direction, turn, control, intersect), agent_feat [80] = the observed positions and
+    steps, agent_vel, a2m (u = 0, v = the RoI's nodes within `near` metres of the agent), num_nodes, node_mask.  Agents
+    that do not move, whose RoI has fewer than min_nodes nodes or neither a pre0 nor a suc0 edge get none, as in the
+    reference.  A generator for tests and benchmarks: the reference's directional lane search (DFS over dense [N,N]
+    masks) is not ported."""
+    graph = scene["graph"]
+    a_feats, a_ctrs = np.asarray(scene["feats"]), np.asarray(scene["ctrs"])
+    if "obs_trajs" not in scene:
+        steps = a_feats[:, :, :2].astype(np.float64)
+        after = np.cumsum(steps[:, ::-1], 1)[:, ::-1] - steps                 # sum of the steps after t
+        pos = a_ctrs[:, None, :].astype(np.float64) - after
+        scene["obs_trajs"] = np.concatenate([pos, a_feats[:, :, 2:3]], 2).astype(np.float32)
+    ctrs, lane_idcs, N = np.asarray(graph["ctrs"]), np.asarray(graph["lane_idcs"]), int(graph["num_nodes"])
+    rels = [(k1, i) for k1 in ("pre", "suc") for i in range(len(graph["pre"]))] + [("left", None), ("right", None)]
+    edges = lambda k1, i: graph[k1] if i is None else graph[k1][i]
+    node_feats = np.zeros((N, 8), np.float32)
+    node_feats[:, :2], node_feats[:, 2:4], node_feats[:, 4:6] = ctrs, graph["feats"], graph["turn"]
+    node_feats[:, 6], node_feats[:, 7] = graph["control"], graph["intersect"]
+    vel = agent_speeds(a_feats)
+    subgraphs, valid = [], []
+    for a in range(len(a_ctrs)):
+        if max_rois is not None and len(subgraphs) >= max_rois:
+            break
+        if vel[a] == 0:
+            continue
+        dist = np.sqrt(((ctrs - a_ctrs[a][None, :]) ** 2).sum(-1))
+        lanes = np.unique(lane_idcs[dist <= vel[a] * horizon_time + horizon_buffer])
+        node_mask = np.nonzero(np.isin(lane_idcs, lanes))[0]
+        if len(node_mask) < min_nodes:
+            continue
+        local = np.full(N, -1, np.int64)
+        local[node_mask] = np.arange(len(node_mask))
+        sg = {"pre": [], "suc": []}
+        for k1, i in rels:
+            e = edges(k1, i)
+            u, v = local[np.asarray(e["u"], np.int64)], local[np.asarray(e["v"], np.int64)]
+            keep = (u >= 0) & (v >= 0)
+            key = np.unique(u[keep] * len(node_mask) + v[keep])
+            rel = {"u": key // len(node_mask), "v": key % len(node_mask)}
+            if i is None:
+                sg[k1] = rel
+            else:
+                sg[k1].append(rel)
+        if len(sg["pre"][0]["u"]) == 0 and len(sg["suc"][0]["u"]) == 0:
+            continue
+        vs = np.nonzero(dist[node_mask] < near)[0].astype(np.int32)
+        sg["a2m"] = {"u": np.zeros(len(vs), np.int32), "v": vs}
+        sg["node_mask"], sg["num_nodes"] = node_mask, len(node_mask)
+        sg["feats"] = node_feats[node_mask]
+        sg["agent_feat"] = np.concatenate([scene["obs_trajs"][a, :, :2], a_feats[a, :, :2]], -1).reshape(-1).astype(np.float32)
+        sg["agent_vel"] = vel[a]
+        subgraphs.append(sg)
+        valid.append(a)
+    scene["subgraphs"] = subgraphs
+    scene["valid_agent_ids"] = np.asarray(valid, np.int16)
+    return scene
+
+
 class SyntheticArgoDataset(torch.utils.data.Dataset):
     """Stands in for ArgoDataset(split, config, train) (reference data.py:16-361, needs argoverse-api and
     the dataset, both absent): same constructor signature and item schema, scenes from synth_scene."""
@@ -210,4 +289,17 @@ class SyntheticArgoDataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         scene = synth_scene(np.random.default_rng(self.seed * 1000003 + idx), self.roads, self.n_actors)
         scene["idx"] = idx
+        return scene
+
+
+class SyntheticLaneRoIDataset(SyntheticArgoDataset):
+    """SyntheticArgoDataset whose items carry lane RoIs (synth_subgraphs): the item schema of the fork's dataset
+    (reference data_lrcnn.py), for lanercnn.get_model."""
+
+    def __init__(self, split=None, config=None, train=True, length=64, roads=(6, 6, 6), n_actors=12, seed=0):
+        super().__init__(split, config, train, length, roads, n_actors, seed)
+
+    def __getitem__(self, idx):
+        scene = synth_subgraphs(super().__getitem__(idx))
+        assert len(scene["subgraphs"]) > 0, "synthetic scene %d has no lane RoI" % idx
         return scene

@@ -145,6 +145,11 @@ def graph_gather(graphs: List[Dict]) -> Dict:
     return graph
 
 
+def _n_nodes(graph: Dict) -> int:
+    """Rows of the merged graph: of its feature tensor, or (the fork's RoI graph keeps per-scene lists) its node count."""
+    return int(graph["feats"].shape[0]) if torch.is_tensor(graph["feats"]) else int(graph["num_nodes"])
+
+
 def lane_plan(graph: Dict) -> ops.LanePlan:
     """CSR-by-destination plan of the 14 relations, built once per batch and cached on the graph
     dict (the graph is identical for the 8 LaneConv layers of MapNet and M2M)."""
@@ -159,7 +164,7 @@ def lane_plan(graph: Dict) -> ops.LanePlan:
         for k1 in ("left", "right"):
             us.append(graph[k1]["u"])
             vs.append(graph[k1]["v"])
-        plan = ops.csr_build(us, vs, int(graph["feats"].shape[0]))
+        plan = ops.csr_build(us, vs, _n_nodes(graph))
         graph["_plan"] = plan
     return plan
 
@@ -182,7 +187,7 @@ def lane_plan_t(graph: Dict) -> ops.LanePlan:
     plan = graph.get("_plan_t")
     if plan is None:
         us, vs = _coo_lists(graph)
-        plan = ops.csr_build(vs, us, int(graph["feats"].shape[0]))
+        plan = ops.csr_build(vs, us, _n_nodes(graph))
         graph["_plan_t"] = plan
     return plan
 

@@ -13,12 +13,19 @@ Same class names, constructor arguments, forward signatures and state_dict names
   RoiLoss / Loss :1205-1325           BCE of the mode logits against the mode closest to the last observed step +
                                       SmoothL1 of that mode's goal and trajectory: lgcn_roi_loss_fwd / _bwd, one launch each
   PostProcess    :1328-1423           and pred_metrics / pred_metrics_ade (:1426-1463), host-side bookkeeping
-and the module-level nms_select / compute_coefficent / sample_trajectory / sample_d1_trajectory (:687-737).
+and the module-level nms_select / compute_coefficent / sample_trajectory / sample_d1_trajectory (:687-737); on top of
+them the whole model:
+  config         :30-82               the reference's keys and values
+  Net            :85-119              input -> roi_net1 -> interactor -> roi_net2 -> decode on a collated batch
+  subgraph_gather / graph_gather :122-277   lane RoIs / scenes merged into one block-diagonal graph each; every index
+                                      array offset by one lgcn_graph_gather launch
+  get_model / get_model_for_torch_dist :1466-1490   the plugin entry points (lanercnn_mi355x.py loads them by name)
 
 Inference (no_grad) runs on the HIP kernels; under autograd LaneRoI / GlobalGraphNet train through the LaneConv
 autograd path of lanegcn.py, LanePooling and LaneInput through the row-block / pair / gather Functions of autograd.py
 (the same composition as Att.run_train): every 128-d contraction of the backward is a HIP launch as well.
 """
+import os
 from math import gcd
 from typing import Dict, List, Tuple
 
@@ -30,15 +37,134 @@ from torch.nn import functional as F
 from . import _lib as L
 from . import autograd as A
 from . import ops
-from .lanegcn import _fuse_modules, _gn, build_pairs, lane_conv, lane_conv_train, lane_plan, lane_plan_t
+from . import lanegcn as _base
+from .data import collate_fn
+from .lanegcn import _fuse_modules, _gn, build_pairs, lane_conv, lane_conv_train, lane_plan, lane_plan_t, rel_keys
 from .layers import Linear
-from .utils import gpu, to_long
+from .utils import Optimizer, StepLR, gpu, to_long
+
+file_path = os.path.abspath(__file__)
+root_path = os.path.dirname(file_path)
+model_name = os.path.basename(file_path).split(".")[0]
+
+# Same keys and values as the reference's module-level config (lanercnn.py:30-82).
+config = dict(
+    display_iters=205942, val_iters=205942 * 2, save_freq=1.0, epoch=0, horovod=True, opt="adamw",
+    num_epochs=36, lr=[1e-3, 1e-4], lr_epochs=[32], weight_decay=0.01,
+    batch_size=10, val_batch_size=10, workers=0, val_workers=0,
+    preprocess=True, rot_aug=False, pred_range=[-100.0, 100.0, -100.0, 100.0],
+    num_scales=6, n_actor=128, n_map=128,
+    actor2map_dist=7.0, map2actor_dist=6.0, actor2actor_dist=100.0,
+    pred_size=30, pred_step=1, num_mods=6, cls_coef=1.0, reg_coef=1.0, mgn=0.2, cls_th=2.0, cls_ignore=0.2,
+)
+config["lr_func"] = StepLR(config["lr"], config["lr_epochs"])
+config["num_preds"] = config["pred_size"] // config["pred_step"]
+config["save_dir"] = os.path.join(root_path, "results", model_name)
+for _k, _p in (("train_split", "dataset/train/data"), ("val_split", "dataset/val/data"),
+               ("test_split", "dataset/test_obs/data"),
+               ("preprocess_train", "dataset/preprocess/train_crs_dist6_angle90.p"),
+               ("preprocess_val", "dataset/preprocess/val_crs_dist6_angle90.p"),
+               ("preprocess_test", "dataset/preprocess/test_test.p")):
+    config[_k] = os.path.join(root_path, _p)
 
 
 def _need_cuda(*ts):
     for t in ts:
         if torch.is_tensor(t) and not t.is_cuda:
             raise L.LgcnError("lanercnn modules need CUDA tensors (the HIP hot path has no CPU fallback)")
+
+
+# ------------------------------------------------------------------ gathers (reference lanercnn.py:122-277)
+def subgraph_bookkeeping(subgraphs_in_batch) -> Dict:
+    """The host side of subgraph_gather (lanercnn.py:125-163): everything that is a Python int or list in the reference's
+    dict -- num_nodes, counts (node offset per RoI), batch_spans, num_atgs_per_batch, roi_spans -- plus interest_roi (the
+    first RoI of every scene, a CPU LongTensor).  Reads only the RoI sizes; touches no GPU."""
+    counts, num_atgs, batch_spans, interest, count = [], [], [], [], 0
+    for b, subgraphs in enumerate(subgraphs_in_batch):
+        assert len(subgraphs) > 0, "batch {} have empty subgraphs".format(b)               # lanercnn.py:180
+        interest.append(len(counts))
+        num_atgs.append(len(subgraphs))
+        start = count
+        for sg in subgraphs:
+            counts.append(count)
+            count += int(len(sg["feats"]))
+        batch_spans.append([start, count])
+    ends = counts[1:] + [count]
+    return {"num_nodes": count, "counts": counts, "batch_spans": batch_spans, "num_atgs_per_batch": num_atgs,
+            "roi_spans": [[lo, hi] for lo, hi in zip(counts, ends)],
+            "interest_roi": torch.tensor(interest, dtype=torch.long)}
+
+
+def _as_tensor(x) -> Tensor:
+    return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _offset_indices(pieces: List, bases: List[int], dev) -> Tuple[Tensor, np.ndarray]:
+    """out[e] = piece(e)[.] + base(piece) for the concatenation of `pieces` (numpy arrays, CPU or GPU tensors of any
+    integer type) with ONE lgcn_graph_gather launch: (int64 device tensor, element offsets of the pieces)."""
+    pieces = [_as_tensor(x).reshape(-1) for x in pieces]
+    off = np.zeros(len(pieces) + 1, np.int64)
+    np.cumsum([int(x.numel()) for x in pieces], out=off[1:])
+    if any(x.is_cuda for x in pieces):
+        flat = torch.cat([x.to(dev).long() for x in pieces], 0)
+    else:      # one host concatenation, one copy
+        flat = torch.from_numpy(np.concatenate([x.numpy().astype(np.int64, copy=False) for x in pieces]
+                                              + [np.zeros(0, np.int64)])).to(dev, non_blocking=True)
+    if flat.numel() == 0:
+        return flat, off
+    tables = torch.from_numpy(np.stack([off, np.asarray(list(bases) + [0], np.int64)])).to(dev)
+    out64, _ = ops.graph_gather_indices(flat, tables[0].contiguous(), tables[1, :-1].contiguous())
+    return out64, off
+
+
+def subgraph_gather(subgraphs_in_batch) -> Dict:
+    """Merge the lane RoIs of a batch into one block-diagonal graph (reference lanercnn.py:122-231): the reference's
+    dict, key for key.  The 28 local index arrays of every RoI and its two a2m arrays are offset by ONE
+    lgcn_graph_gather launch over one concatenation (segment base: the RoI's node offset, or the RoI's number for
+    a2m.u) instead of hundreds of adds and cats.  Leaves may be numpy arrays, CPU or GPU tensors, int16 / int32 / int64.
+    A relation without edges comes out as an empty int64 tensor (the reference's float zeros((0,)) is not mirrored)."""
+    graph = subgraph_bookkeeping(subgraphs_in_batch)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    counts = graph["counts"]
+    rois = [sg for subgraphs in subgraphs_in_batch for sg in subgraphs]
+    graph["node_idcs"] = torch.arange(graph["num_nodes"], device=dev)
+    fdev = lambda x: _as_tensor(x).to(dev, non_blocking=True)
+    feats, agt_feat = [], []
+    for subgraphs in subgraphs_in_batch:
+        feats.append(torch.cat([fdev(sg["feats"]) for sg in subgraphs], 0))
+        agt_feat.append(torch.cat([fdev(sg["agent_feat"]).view(1, -1) for sg in subgraphs], 0))
+    graph["feats"], graph["agent_feat"] = feats, agt_feat
+    graph["ctrs"] = [f[:, :2] for f in feats]
+    graph["dirs"] = [f[:, 2:4] for f in feats]
+    graph["pose"] = [f[:, :4] for f in feats]
+    graph["agent_vel"] = [sg["agent_vel"] for sg in rois]
+
+    num_scales = len(rois[0]["pre"])
+    getters = [lambda sg, k1=k1, i=i, k2=k2: sg[k1][i][k2] for k1 in ("pre", "suc") for i in range(num_scales) for k2 in "uv"]
+    getters += [lambda sg, k1=k1, k2=k2: sg[k1][k2] for k1 in ("left", "right") for k2 in "uv"]
+    getters += [lambda sg: sg["a2m"]["u"], lambda sg: sg["a2m"]["v"]]
+    pieces = [get(sg) for get in getters for sg in rois]
+    bases = [list(range(len(rois))) if j == len(getters) - 2 else counts for j in range(len(getters))]
+    out64, off = _offset_indices(pieces, [b for bs in bases for b in bs], dev)
+    R = len(rois)
+    it = iter(out64[off[j * R]:off[(j + 1) * R]] for j in range(len(getters)))
+    for k1 in ("pre", "suc"):
+        graph[k1] = [{"u": next(it), "v": next(it)} for _ in range(num_scales)]
+    for k1 in ("left", "right"):
+        graph[k1] = {"u": next(it), "v": next(it)}
+    graph["a2m"] = {"u": next(it), "v": next(it)}
+    return graph
+
+
+def graph_gather(graphs: List[Dict]) -> Dict:
+    """lanegcn.graph_gather plus the fork's num_nodes, counts and pose = cat(ctrs, feats) per scene (reference
+    lanercnn.py:234-277)."""
+    graph = _base.graph_gather(graphs)
+    dev = graph["feats"].device
+    graph["num_nodes"] = [int(g["num_nodes"]) for g in graphs]
+    graph["counts"] = [int(v) for v in np.cumsum([0] + graph["num_nodes"][:-1])]
+    graph["pose"] = [torch.cat([c, g["feats"].to(dev, non_blocking=True)], -1) for c, g in zip(graph["ctrs"], graphs)]
+    return graph
 
 
 class LaneInput(nn.Module):
@@ -76,6 +202,29 @@ class LaneInput(nn.Module):
         return ops.gn_fwd(base.contiguous(), _gn(self.bn), relu=True, eps=self.bn.eps)
 
 
+class _UnusedParamsFn(torch.autograd.Function):
+    """Identity on x that hands zero gradients to parameters the forward did not read.  lane_conv_train leaves out a
+    relation without a single edge in the batch (its term is an empty sum); the reference's empty index_add_ leaves a
+    zero gradient on that relation's weights, not None, so every parameter of the fork's Net receives a gradient and the
+    optimizer's weight decay reaches it."""
+
+    @staticmethod
+    def forward(ctx, x, *params):
+        ctx.save_for_backward(*params)
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g, *[torch.zeros_like(p) for p in ctx.saved_tensors])
+
+
+def _lane_conv_train(fuse: nn.ModuleDict, feat: Tensor, graph: Dict) -> Tensor:
+    plan, num_scales = lane_plan(graph), len(graph["pre"])
+    out = lane_conv_train(fuse, feat, plan, lane_plan_t(graph), num_scales)
+    unused = [m.weight for r, key in enumerate(rel_keys(num_scales)) if plan.n_edges[r] == 0 for m in fuse[key]]
+    return _UnusedParamsFn.apply(out, *unused) if unused else out
+
+
 class LaneRoI(nn.Module):
     """Lane-RoI encoder: input Linear + 4 LaneConv layers (reference lanercnn.py:354-430)."""
 
@@ -91,7 +240,7 @@ class LaneRoI(nn.Module):
         _need_cuda(feat)
         feat = self.input(feat)
         if ops.wants_grad(feat, *ops.module_params(self)):
-            return lane_conv_train(self.fuse, feat, lane_plan(graph), lane_plan_t(graph), len(graph["pre"]))
+            return _lane_conv_train(self.fuse, feat, graph)
         return ops.guarded(lambda: lane_conv(self.fuse, feat, lane_plan(graph), len(graph["pre"])))
 
 
@@ -110,13 +259,18 @@ class GlobalGraphNet(nn.Module):
             return (temp.new().resize_(0),)
         _need_cuda(feat)
         if ops.wants_grad(feat, *ops.module_params(self)):
-            return lane_conv_train(self.fuse, feat, lane_plan(graph), lane_plan_t(graph), len(graph["pre"]))
+            return _lane_conv_train(self.fuse, feat, graph)
         return ops.guarded(lambda: lane_conv(self.fuse, feat, lane_plan(graph), len(graph["pre"])))
 
 
 class LanePooling(nn.Module):
     """Distance-gated pooling of a context lane graph into a target lane graph (reference lanercnn.py:433-514)."""
     legacy_offsets = True     # scenes without a pair do not advance the index offsets (lanercnn.py:476-483)
+    # Run the pair stage (:492-499: relative pose, relpose.0, ctx.0's pose half + the context row block, GroupNorm, ReLU)
+    # of a forward that needs no gradient as ONE exact-fp32 launch (lgcn_pool_pairs) instead of the chain of generic
+    # ones; only m [P,128] reaches memory.  Under autograd the composed path runs whatever the switch says, so with it
+    # on a training forward can differ from the no_grad forward in the last bits.  Opt-in; read on each forward.
+    fused = False
 
     def __init__(self, in_dim: int, out_dim: int) -> None:
         super().__init__()
@@ -148,11 +302,16 @@ class LanePooling(nn.Module):
         if P == 0:
             raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")          # lanercnn.py:484
         T = target_feat.shape[0]
-        t_idx, c_idx = ps.hi[:P].long(), ps.wi[:P].long()
         c_pose = torch.cat(context_graph["pose"], 0)
         t_pose = torch.cat(target_graph["pose"], 0)
-        h = F.relu(self.relpose[0](c_pose[c_idx] - t_pose[t_idx]))                        # [P,128]; K = 4: stock op
         w0 = self.ctx[0].linear.weight                                                     # [128, 256] = [feat | pose]
+        if not train and LanePooling.fused:
+            per_ctx = ops.agg_mlp(context_feat.shape[0], [ops.RelSpec(context_feat, ops.packed(w0, 0, 128))], 0)
+            m = ops.pool_pairs(ps, c_pose, t_pose, self.relpose[0].weight, self.relpose[0].bias, w0, per_ctx,
+                               _gn(self.ctx[0].norm), cap=P, eps=self.ctx[0].norm.eps)
+            return self._tail(m, ps, target_feat)
+        t_idx, c_idx = ps.hi[:P].long(), ps.wi[:P].long()
+        h = F.relu(self.relpose[0](c_pose[c_idx] - t_pose[t_idx]))                        # [P,128]; K = 4: stock op
         if train:      # the differentiable composition of the same arithmetic (cf. Att.run_train)
             m0, m1 = self.mlp[0], self.mlp[1]
             per_ctx = A.linear_gn(context_feat, w0, col0=0)
@@ -171,6 +330,10 @@ class LanePooling(nn.Module):
         zero_idx = torch.zeros(P, dtype=torch.int32, device=per_pair.device)
         pre = ops.pair_add(per_pair, per_ctx, ps.wi, zero_row, zero_idx, ps.n_pairs, P)
         m = ops.gn_fwd(pre, _gn(self.ctx[0].norm), relu=True, eps=self.ctx[0].norm.eps)
+        return self._tail(m, ps, target_feat)
+
+    def _tail(self, m, ps, target_feat):
+        T = target_feat.shape[0]
         m0, m1 = self.mlp[0], self.mlp[1]
         # ctx.1 is linear: applied to the per-target segment sum (pairs sorted by target: a RANGE relation)
         y = ops.agg_mlp(T, [ops.RelSpec(target_feat, ops.packed(self.input.weight)),
@@ -256,6 +419,32 @@ class Interactor(nn.Module):
         graph_feat = self.roi2graph(roi_feat, subgraph, self.graph_input(graph), graph)
         graph_feat = self.global_graph_net(graph_feat, graph)
         return self.graph2roi(graph_feat, graph, roi_feat, subgraph)
+
+
+class Net(nn.Module):
+    """The fork model (reference lanercnn.py:85-119): LaneInput -> LaneRoI -> Interactor -> LaneRoI -> Decode on a batch
+    as collate_fn delivers it (per-scene lists, on the CPU or the GPU).  Under no_grad every stage runs its inference
+    launches (with the modules' own range guard); under autograd their Functions, honouring Decode.train_hip and the
+    other *.train_hip switches."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+        self.input = LaneInput(config)
+        self.roi_net1 = LaneRoI(config, input_dim=config["n_map"])
+        self.interactor = Interactor(config)
+        self.roi_net2 = LaneRoI(config, input_dim=config["n_map"])
+        self.decode = Decode(config)
+
+    def forward(self, data: Dict) -> Dict[str, Tensor]:
+        graph = graph_gather(data["graph"])
+        graph_roi = subgraph_gather(data["subgraphs"])
+        roi_feat = self.input(graph_roi)
+        roi_feat = self.roi_net1(roi_feat, graph_roi)
+        roi_feat = self.interactor(graph, graph_roi, roi_feat)
+        roi_feat = self.roi_net2(roi_feat, graph_roi)
+        pred_logics, pred_goals, pred_trajs = self.decode(roi_feat, graph_roi, data)
+        return {"pred_logics": pred_logics, "pred_goals": pred_goals, "pred_trajs": pred_trajs}
 
 
 # ------------------------------------------------------------------ goal decoding (reference lanercnn.py:683-924)
@@ -555,3 +744,24 @@ class PostProcess(nn.Module):
         print("loss %2.4f - %2.4f %2.4f %2.4f, %2.4f - ade1=%2.4f fde1=%2.4f ade=%2.4f fde=%2.4f"
               % (loss, cls, reg_goal, reg_traj, stg1_cls, ade1, fde1, ade, fde))
         print()
+
+
+def _plugin_parts():
+    from .data import SyntheticLaneRoIDataset
+    # Dataset: the reference returns its ArgoDataset (needs argoverse-api and the dataset, both absent here); a caller that
+    # has them injects the class as config["dataset_cls"], as for lanegcn.get_model
+    dataset = config.get("dataset_cls") or SyntheticLaneRoIDataset
+    return dataset, Net(config).cuda(), Loss(config).cuda(), PostProcess(config).cuda()
+
+
+def get_model():
+    """The reference's plugin entry point (lanercnn.py:1466-1477): (config, Dataset, collate_fn, net, loss, post_process,
+    opt)."""
+    dataset, net, loss, post_process = _plugin_parts()
+    return config, dataset, collate_fn, net, loss, post_process, Optimizer(net.parameters(), config)
+
+
+def get_model_for_torch_dist():
+    """get_model without the optimizer (lanercnn.py:1479-1490): the caller builds it after wrapping the net."""
+    dataset, net, loss, post_process = _plugin_parts()
+    return config, dataset, collate_fn, net, loss, post_process

@@ -1266,6 +1266,38 @@ def att_pairs_train(ps: PairSet, wd0, bd0, w_d2, gn_d, w_c0, U, V, gn_c, m=None,
     return m, masks
 
 
+def pool_pairs(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=None, cap=None, eps=EPS, tag="pool_pairs"):
+    """m [cap,128] of lgcn_pool_pairs: the pair stage of the fork's LanePooling (reference lanercnn.py:492-499) in one
+    launch, exact fp32 in every matrix mode.  ps: pairs with hi = target row, wi = context row; ctx_pose [C,4], tgt_pose
+    [T,4]; wp [128,4] / bp [128]: relpose.0; w_c0 [128,256]: ctx.0's Linear weight (the F32 image of its columns 128:256
+    is made here); U [C,128] = context_feat w_c0[:, 0:128]^T; gn = (weight, bias) of ctx.0's norm.  cap: rows of m the
+    launch may write (default: the pair search's capacity; a caller that knows P passes it and gets a [P,128] m).  Rows
+    >= *n_pairs of m are not written."""
+    lib = L.load()
+    ctx_pose, tgt_pose = _dev(ctx_pose, torch.float32, "ctx_pose"), _dev(tgt_pose, torch.float32, "tgt_pose")
+    U = _dev(U, torch.float32, "U")
+    if ctx_pose.dim() != 2 or ctx_pose.shape[1] != 4 or tgt_pose.dim() != 2 or tgt_pose.shape[1] != 4:
+        raise L.LgcnError("pool_pairs: poses must be [rows, 4]")
+    if U.shape != (ctx_pose.shape[0], C_FEAT):
+        raise L.LgcnError("pool_pairs: U must be [context rows, 128]")
+    if tuple(w_c0.shape) != (C_FEAT, 2 * C_FEAT) or tuple(wp.shape) != (C_FEAT, 4):
+        raise L.LgcnError("pool_pairs: need relpose.0 [128,4] and ctx.0 [128,256] weights")
+    wp, bp = _dev(wp.detach(), torch.float32, "wp"), _dev(bp.detach(), torch.float32, "bp")
+    with exact_mma():
+        wpc0h = packed(w_c0, C_FEAT, C_FEAT)
+    cap = ps.cap if cap is None else min(int(cap), ps.cap)
+    if m is None:
+        m = torch.empty((max(cap, 1), C_FEAT), dtype=torch.float32, device=U.device)
+    elif m.shape[0] < cap or not m.is_contiguous():
+        raise L.LgcnError("pool_pairs: m must be a contiguous [>= cap, 128] tensor")
+    with _Timed(tag):
+        rc = lib.lgcn_pool_pairs(_ptr(ctx_pose), _ptr(tgt_pose), _ptr(ps.hi), _ptr(ps.wi), _ptr(ps.n_pairs), cap,
+                                 _ptr(wp), _ptr(bp), _ptr(wpc0h), _ptr(U), _ptr(gn[0]), _ptr(gn[1]), eps, _ptr(m),
+                                 _stream())
+    L.check(rc, "lgcn_pool_pairs")
+    return m
+
+
 def att_pair_masks(masks: torch.Tensor, P: int) -> torch.Tensor:
     """bool [P,3,128] of the first P rows of att_pairs_train's masks: [p, k, c] = mask k of channel c of pair p, k = 0:
     W_d0 d + b_d0 > 0, 1: e > 0, 2: m > 0.  Layout: word 4 k + j of a row holds channels 32 j .. 32 j + 31, bit b =

@@ -1,0 +1,121 @@
+"""Net.forward of the fork model (lanegcn_amd.lanercnn.Net, reference lanercnn.py:85-119) on a synthetic batch with lane
+RoIs (data.synth_scene + data.synth_subgraphs), with LanePooling.fused off -- the chain of generic launches -- and on --
+the pair stage of every pooling as one lgcn_pool_pairs launch -- alternating call by call in one process after the warm-up.
+Prints the medians, the kernel launches per forward of each path (torch.profiler; null where it is unavailable), the pair
+count P of each of the three poolings, the same two timings for the largest pooling alone (Interactor.roi2graph on the
+inputs it receives inside the forward, pair search included) and one JSON line.  Numbers for DESIGN.md; no bar.
+
+  --scenes B --agents A --roads L,L,..   scenes per batch, agents (= RoIs at most) per scene, lanes per road (default
+                                         10 x 12 on roads 6,6,6: 324 nodes per scene)
+  --steps K --warmup W                   timed and untimed forwards per variant (default 30 / 5)
+  --mma MODE                             matrix mode of everything but the fused pair stage (which is exact fp32)"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import lanegcn_amd  # noqa: E402,F401
+from bench_decode import count_launches  # noqa: E402
+from lanegcn_amd import data as gen  # noqa: E402
+from lanegcn_amd import lanercnn as R  # noqa: E402
+from lanegcn_amd import ops  # noqa: E402
+
+
+def make_batch(n_scenes, n_agents, roads, seed=0):
+    rng = np.random.default_rng(seed)
+    scenes = []
+    while len(scenes) < n_scenes:
+        s = gen.synth_subgraphs(gen.synth_scene(rng, roads, n_agents))
+        if len(s["subgraphs"]) > 0:
+            scenes.append(s)
+    return gen.collate_fn(scenes)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", type=int, default=10)
+    ap.add_argument("--agents", type=int, default=12)
+    ap.add_argument("--roads", default="6,6,6")
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--mma", default=None)
+    args = ap.parse_args()
+    if args.mma:
+        ops.set_mma(args.mma)
+    torch.manual_seed(0)
+    net = R.Net(R.config).cuda().eval()
+    data = make_batch(args.scenes, args.agents, [int(v) for v in args.roads.split(",")])
+    n_rois = sum(len(s) for s in data["subgraphs"])
+    roi_nodes = sum(int(len(sg["feats"])) for s in data["subgraphs"] for sg in s)
+    graph_nodes = sum(int(g["num_nodes"]) for g in data["graph"])
+
+    def forward(on):
+        R.LanePooling.fused = on
+        try:
+            with torch.no_grad():
+                return net(data)
+        finally:
+            R.LanePooling.fused = False
+
+    pairs, real_pairs, pool_args = [], R.build_pairs, []
+    R.build_pairs = lambda *a, **k: pairs.append(real_pairs(*a, **k)) or pairs[-1]
+    hook = net.interactor.roi2graph.register_forward_pre_hook(lambda m, a: pool_args.append(a))
+    try:
+        forward(False)
+    finally:
+        R.build_pairs = real_pairs
+        hook.remove()
+    P = {name: ps.count() for name, ps in zip(("roi2graph", "graph2roi", "lane_pool"), pairs)}
+
+    def pooling(on):
+        R.LanePooling.fused = on
+        try:
+            with torch.no_grad():
+                return net.interactor.roi2graph(*pool_args[0])
+        finally:
+            R.LanePooling.fused = False
+
+    names = {"off": False, "on": True}
+
+    def timed(fn):
+        times = {k: [] for k in names}
+        for _ in range(args.warmup):
+            for on in names.values():
+                fn(on)
+        torch.cuda.synchronize()
+        for _ in range(args.steps):
+            for name, on in names.items():
+                t0 = time.perf_counter()
+                fn(on)
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) * 1e3)
+        return times
+
+    times, pool_times = timed(forward), timed(pooling)
+    launches = {name: count_launches(lambda on=on: forward(on)) for name, on in names.items()}
+    off, on = forward(False), forward(True)
+    diff = {k: float((off[k] - on[k]).abs().max() / off[k].abs().max()) for k in off}
+    pool_launches = {name: count_launches(lambda on=on: pooling(on)) for name, on in names.items()}
+    res = {"metric": "lanercnn.Net.forward, %d scenes, %d RoIs, %d RoI nodes, %d graph nodes" % (args.scenes, n_rois, roi_nodes, graph_nodes),
+           "mma": ops.get_mma(), "steps": args.steps, "pairs": P,
+           "median_ms": {k: float(np.median(v)) for k, v in times.items()}, "min_ms": {k: min(v) for k, v in times.items()},
+           "launches_per_forward": launches, "max_rel_diff_on_off": diff,
+           "roi2graph_median_ms": {k: float(np.median(v)) for k, v in pool_times.items()},
+           "roi2graph_min_ms": {k: min(v) for k, v in pool_times.items()}, "roi2graph_launches": pool_launches}
+    print("P per pooling: %s" % P, flush=True)
+    for name in names:
+        print("Net.forward, LanePooling.fused %s: median %.3f ms (min %.3f), %s launches"
+              % (name, res["median_ms"][name], res["min_ms"][name], launches[name]), flush=True)
+        print("roi2graph alone (P = %d), fused %s: median %.3f ms (min %.3f), %s launches"
+              % (P["roi2graph"], name, res["roi2graph_median_ms"][name], res["roi2graph_min_ms"][name], pool_launches[name]), flush=True)
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

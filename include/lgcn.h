@@ -732,6 +732,12 @@ int lgcn_pred_loss_bwd(const float *cls, const float *reg, const float *gt, cons
  * gamma == NULL: no normalisation (dx = g), used for plain ReLU masks.
  * dgamma / dbeta: [128] outputs; part: workspace of 2 * ceil(n_rows/32) * 128 floats.
  * Deterministic (two-level tree, no atomics).
+ * Statistics: mean in two steps (the fp32 mean, then the mean of the centred values: a row at 2^10 with a spread of 1 keeps
+ * xhat at fp32 rounding), and rows whose fp32 sum of squares overflows (beyond ~2^60) take the forward's wide path: rstd
+ * from the centred values scaled by 2^-68, so forward and backward agree on such rows (dx ~ rstd dy stays inside fp32).
+ * The same holds for the recomputations inside lgcn_laneconv_bwd, lgcn_rowblock_bwd and lgcn_att_pairs_bwd; a row in which
+ * two such norms meet (laneconv: T and Z both beyond 2^60) has gradients ~ 2^-140 that leave fp32 by themselves.
+ * lgcn_gn_cl_bwd and lgcn_conv1d_gn_bwd take the two-step mean only (their forward has no wide path).
  */
 int lgcn_gn_bwd(const float *dy, const float *x, const float *post, const float *gamma,
                 int64_t n_rows, float eps, float *dx, float *dg_out,

@@ -43,18 +43,36 @@ __global__ __launch_bounds__(256) void k_gn_bwd(const float *__restrict__ dy, co
 #pragma unroll
         for (int j = 0; j < 4; ++j) xh.v[j] = *reinterpret_cast<const float4 *>(x + n * kC + c0 + 32 * j);
     }
-    {   // xhat = (x - mean) * rstd, two-pass like the forward
+    {   // xhat = (x - mean) * rstd, two-pass like the forward, the mean taken in two steps
         float s = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) s += (xh.v[j].x + xh.v[j].y) + (xh.v[j].z + xh.v[j].w);
         const float mean = sum8(s) * (1.0f / kC);
-        float q = 0.f;
+        float e = 0.f;                                         // corrected two-pass, as row_gn_hat
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             xh.v[j].x -= mean; xh.v[j].y -= mean; xh.v[j].z -= mean; xh.v[j].w -= mean;
+            e += (xh.v[j].x + xh.v[j].y) + (xh.v[j].z + xh.v[j].w);
+        }
+        const float rest = sum8(e) * (1.0f / kC);
+        float q = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            xh.v[j].x -= rest; xh.v[j].y -= rest; xh.v[j].z -= rest; xh.v[j].w -= rest;
             q += (xh.v[j].x * xh.v[j].x + xh.v[j].y * xh.v[j].y) + (xh.v[j].z * xh.v[j].z + xh.v[j].w * xh.v[j].w);
         }
-        rstd = 1.0f / sqrtf(sum8(q) * (1.0f / kC) + eps);
+        const float var = sum8(q) * (1.0f / kC);
+        rstd = 1.0f / sqrtf(var + eps);
+        if (__builtin_expect(!(var <= 3.4028234e38f), 0)) {   // the squares left fp32: row_rstd_wide on the centred values
+            constexpr float k = 0x1p-68f;
+            float qs = 0.f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float a = xh.v[j].x * k, bb = xh.v[j].y * k, c = xh.v[j].z * k, d = xh.v[j].w * k;
+                qs += (a * a + bb * bb) + (c * c + d * d);
+            }
+            rstd = k / sqrtf(sum8(qs) * (1.0f / kC) + eps * (k * k));
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) { xh.v[j].x *= rstd; xh.v[j].y *= rstd; xh.v[j].z *= rstd; xh.v[j].w *= rstd; }
     }
@@ -267,22 +285,25 @@ __global__ __launch_bounds__(256) void k_gn_cl_bwd(const float *__restrict__ dy,
     float s = 0.f;
     for (int i = lane; i < n; i += 64) s += xi[i];
     const float mean = wave_sum(s) / (float)n;
+    float e = 0.f;                                             // corrected two-pass, as row_gn_hat (lgcn_tile.hpp)
+    for (int i = lane; i < n; i += 64) e += xi[i] - mean;
+    const float rest = wave_sum(e) / (float)n;
     float q = 0.f;
-    for (int i = lane; i < n; i += 64) { const float d = xi[i] - mean; q += d * d; }
+    for (int i = lane; i < n; i += 64) { const float d = (xi[i] - mean) - rest; q += d * d; }
     const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)n + eps);
     float s1 = 0.f, s2 = 0.f;
     for (int i = lane; i < n; i += 64) {
         const float gv = (pi == nullptr || pi[i] > 0.f) ? di[i] : 0.f;
         const float gg = gv * gamma[i / L];
         s1 += gg;
-        s2 += gg * ((xi[i] - mean) * rstd);
+        s2 += gg * (((xi[i] - mean) - rest) * rstd);
     }
     const float m1 = wave_sum(s1) / (float)n, m2 = wave_sum(s2) / (float)n;
     float *dxi = dx + item * n;
     float *gi = g_out ? g_out + item * n : nullptr;
     for (int i = lane; i < n; i += 64) {
         const float gv = (pi == nullptr || pi[i] > 0.f) ? di[i] : 0.f;
-        const float xh = (xi[i] - mean) * rstd;
+        const float xh = ((xi[i] - mean) - rest) * rstd;
         dxi[i] = rstd * (gv * gamma[i / L] - m1 - xh * m2);
         if (gi) gi[i] = gv;
     }
@@ -292,7 +313,7 @@ __global__ __launch_bounds__(256) void k_gn_cl_bwd(const float *__restrict__ dy,
         for (int l = 0; l < L; ++l) {
             const int i = c * L + l;
             const float gv = (pi == nullptr || pi[i] > 0.f) ? di[i] : 0.f;
-            a += gv * ((xi[i] - mean) * rstd);
+            a += gv * (((xi[i] - mean) - rest) * rstd);
             b += gv;
         }
         pt[c] = a;

@@ -75,12 +75,27 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
     }
     float mean, rstd;
     conv_gn_stats(yv, m, s_red, p.eps, mean, rstd);
+    // corrected two-pass, as row_gn_hat (lgcn_tile.hpp): the mean of the centred values is what the fp32 mean left behind.
+    // s_red[0] is free again: its readers passed the second barrier of conv_gn_stats.
+    float rest = 0.f;
+    {
+        float e = 0.f;
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+            if (m.has(k)) e += ((yv[k].x - mean) + (yv[k].y - mean)) + ((yv[k].z - mean) + (yv[k].w - mean));
+        e = conv_half_sum(e);
+        if ((tid & 31) == 0) s_red[0][tid >> 5] = e;
+        lds_barrier();
+        for (int k = 0; k < m.ng; ++k) rest += s_red[0][m.g0 + k];
+        rest = rest / m.per;
+    }
     // GroupNorm backward: dy = rstd (g gamma - mean(g gamma) - xhat mean(g gamma xhat))
     const float4 gm = *reinterpret_cast<const float4 *>(p.gamma + m.c);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        yv[k] = make_float4((yv[k].x - mean) * rstd, (yv[k].y - mean) * rstd, (yv[k].z - mean) * rstd, (yv[k].w - mean) * rstd);
+        yv[k] = make_float4(((yv[k].x - mean) - rest) * rstd, ((yv[k].y - mean) - rest) * rstd, ((yv[k].z - mean) - rest) * rstd,
+                            ((yv[k].w - mean) - rest) * rstd);
         const float4 gg = make_float4(gv[k].x * gm.x, gv[k].y * gm.y, gv[k].z * gm.z, gv[k].w * gm.w);
         s1 += (gg.x + gg.y) + (gg.z + gg.w);
         s2 += (gg.x * yv[k].x + gg.y * yv[k].y) + (gg.z * yv[k].z + gg.w * yv[k].w);

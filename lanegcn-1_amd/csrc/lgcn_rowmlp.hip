@@ -918,7 +918,11 @@ __global__ __launch_bounds__(512) void k_lc_bwd_rows(const LcBwdParams p) {
         __syncthreads();      // every tile is next written behind this barrier, G two barriers from here
         if (want_dx && live) {
             RowVals dx = row_load(G, tid);
-            row_add(dx, g2);
+            // g2 again from memory (the same bits) instead of 16 registers held across the tile's four barriers: with them the
+            // row waves' GroupNorm recomputation does not fit next to the eight accumulator tiles
+            RowVals gr = row_load_global(p.d_out + n * kC, tid);
+            row_mask_pos(gr, row_load_global(p.out + n * kC, tid));
+            row_add(dx, gr);
             row_store_global(p.dX + n * kC, tid, dx);
         }
     }

@@ -47,8 +47,10 @@ __device__ __forceinline__ float sum8(float x) {
 // row_gn compiles it in with WIDE (the default): the f32 kernels and the split kernels of the range-safe three-plane
 // mode (Fmt<0>) do.  The fp16-plane kernels pass WIDE = false: their GEMM outputs cannot pass 128 * 15 * 65520^2 < 2^50,
 // whose squares fit (what else reaches a GroupNorm there -- U + V of the pair stage, the rank-4 meta update -- are such
-// outputs or O(1) inputs in this network), and they keep the register budget that lets two workgroups share a CU.  (row_gn_hat, the backward's
-// recomputation, is left as it was: gradients of rows that large leave fp32's range on their own.)
+// outputs or O(1) inputs in this network), and they keep the register budget that lets two workgroups share a CU.
+// row_gn_hat, the backward's recomputation, and k_gn_bwd take the same path: with rstd ~ 2^-70 the gradients of such a row
+// (dx ~ rstd dy, dW = dT^T x ~ dy) stay inside fp32, and a backward that returned rstd = 0 where the forward did not
+// would hand back silent zeros.
 __device__ __forceinline__ float row_rstd_wide(const RowVals &r, float mean, float eps) {
     constexpr float k = 0x1p-68f;
     float q = 0.f;
@@ -92,26 +94,34 @@ __device__ __forceinline__ void row_gn(RowVals &r, int t, const float *__restric
 }
 
 // The two halves of row_gn for a backward that recomputes the forward: r becomes xhat = (x - mean) * rstd (returns rstd),
-// and row_affine(xhat) = xhat * g + b restates row_gn's output with the same source operations in the same order (the
-// library is built with -ffp-contract=off).  Nothing downstream needs the two to agree to the bit: the backward takes its
-// ReLU decisions from the stored masks.
+// and row_affine(xhat) = xhat * g + b restates row_gn's output.  Nothing downstream needs the two to agree to the bit (they
+// do not: row_gn_hat centres twice): the backward takes its ReLU decisions from the stored masks.
 __device__ __forceinline__ float row_gn_hat(RowVals &r, float eps) {
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) s += (r.v[j].x + r.v[j].y) + (r.v[j].z + r.v[j].w);
     const float mean = sum8(s) * (1.0f / kC);
+    // The fp32 mean of a row that sits far from zero is off by up to half an ulp of the mean (6e-5 at 2^10) however it is
+    // summed, and that goes straight into xhat and from there into dgamma = sum g xhat.  x - mean is exact there (Sterbenz),
+    // so the mean of the centred values is what the first mean left behind: take it out too (a corrected two-pass).
+    float e = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        r.v[j].x -= mean; r.v[j].y -= mean; r.v[j].z -= mean; r.v[j].w -= mean;
+        e += (r.v[j].x + r.v[j].y) + (r.v[j].z + r.v[j].w);
+    }
+    const float rest = sum8(e) * (1.0f / kC);
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float a = r.v[j].x - mean, bb = r.v[j].y - mean, c = r.v[j].z - mean, d = r.v[j].w - mean;
-        q += (a * a + bb * bb) + (c * c + d * d);
+        r.v[j].x -= rest; r.v[j].y -= rest; r.v[j].z -= rest; r.v[j].w -= rest;
+        q += (r.v[j].x * r.v[j].x + r.v[j].y * r.v[j].y) + (r.v[j].z * r.v[j].z + r.v[j].w * r.v[j].w);
     }
-    const float rstd = 1.0f / sqrtf(sum8(q) * (1.0f / kC) + eps);
+    const float var = sum8(q) * (1.0f / kC);
+    float rstd = 1.0f / sqrtf(var + eps);
+    if (__builtin_expect(!(var <= 3.4028234e38f), 0)) rstd = row_rstd_wide(r, 0.f, eps);      // r is centred already
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        r.v[j].x = (r.v[j].x - mean) * rstd; r.v[j].y = (r.v[j].y - mean) * rstd;
-        r.v[j].z = (r.v[j].z - mean) * rstd; r.v[j].w = (r.v[j].w - mean) * rstd;
-    }
+    for (int j = 0; j < 4; ++j) { r.v[j].x *= rstd; r.v[j].y *= rstd; r.v[j].z *= rstd; r.v[j].w *= rstd; }
     return rstd;
 }
 

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import test_gpu_training as TG
+from backward_cases import bar, gn_bwd64, hat64
 from conftest import to_torch_scene
 from golden_io import load_scenes
 from test_gpu_training import rel_err
@@ -83,12 +84,6 @@ def err(got, want):
     return rel_err(got.detach().double().cpu().numpy(), want.detach().double().cpu().numpy())
 
 
-def bar(e_cmp):
-    """Twice the composed path's error against the same reference (both are fp32 chains of the same length that differ in
-    summation order), floored at 1e-6, never above 1e-4, the project's parity bar."""
-    return min(max(2 * e_cmp, 1e-6), 1e-4)
-
-
 def check_rows(rows, label):
     for name, e_new, e_cmp in rows:
         print("%s %-28s fused %.3e composed %.3e" % (label, name, e_new, e_cmp))
@@ -144,17 +139,6 @@ def forward_saved(mods, inp, csr=False):
         plan = ops.csr_build([u.cuda() for u in inp["us"]], [v.cuda() for v in inp["vs"]], d["x"].shape[0])
         rel_ws = [(inp["w_rel"][r].cuda(), r) for r in range(4) if plan.n_edges[r] > 0]
     return hip_forward(mods, d["x"], d["w1"], rel_ws, plan, d["g1"], d["b1"], d["w2"], d["g2"], d["b2"])
-
-
-def hat64(v):
-    mu = v.mean(1, keepdim=True)
-    rstd = 1.0 / torch.sqrt(((v - mu) ** 2).mean(1, keepdim=True) + EPS)
-    return (v - mu) * rstd, rstd
-
-
-def gn_bwd64(g, xh, rstd, gamma):
-    d = g * gamma
-    return rstd * (d - d.mean(1, keepdim=True) - xh * (d * xh).mean(1, keepdim=True))
 
 
 def reference64(inp, saved, ident1):

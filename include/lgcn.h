@@ -699,6 +699,61 @@ int lgcn_pool_pairs(const float *ctx_pose, const float *tgt_pose,
                     float eps, float *m, void *stream);
 
 /*
+ * Training of the pair stage of LanePooling, exact fp32 whatever the matrix mode of the rest of the network.  Notation of
+ * lgcn_pool_pairs: per pair p < *n_pairs (clamped to cap), t = ti[p], c = ci[p], d = ctx_pose[c] - tgt_pose[t]:
+ *   y0 = W_p d + b_p;             h = ReLU(y0)          mask0 = y0 > 0
+ *   z  = W_0[:, 128:256] h + U[c]
+ *   m  = ReLU(GN(z; g, bt))                             mask1 = m  > 0
+ * and S[t] = sum of m_p over the pairs of target t (lgcn_gather_sum over the pair search's rowptr).
+ *
+ * lgcn_pool_pairs_train: lgcn_pool_pairs with one more output, the two masks as bits; m is bit for bit what
+ * lgcn_pool_pairs writes.
+ *   masks: [cap, 2, 4] uint32, rows < *n_pairs written: masks[p][k][j] bit b = mask k of channel 32 j + b (the layout of
+ *           lgcn_att_pairs_train), 32 bytes per pair.
+ *
+ * lgcn_pool_pairs_bwd, for dS [T,128] (one main launch + one fixed-order reduction launch; no atomics, no host read):
+ *   g  = dS[t] * mask1;  dgamma += g * zhat;  dbeta += g;  dz = GN backward of g (formula of lgcn_gn_bwd)
+ *   dW_0[:, 128:256] += dz (x) h;  dh = dz W_0[:, 128:256]
+ *   dy0 = dh * mask0;  dW_p += dy0 (x) d  ([128,4]);  db_p += dy0
+ * h, z and the GroupNorm statistics are recomputed per 32-pair tile with the forward's device functions; the masks are
+ * read, not re-derived.  dU[c] += dz is an lgcn_gather_sum launch over dz by a CSR of the pairs by context row.  The
+ * poses get no gradient.
+ *   wptc0h: lgcn_pack_weight_t image (LGCN_MMA_F32) of W_0[:, 128:256]; needed when d_wp or d_bp is given
+ *   dz:     [cap,128], rows < *n_pairs written -- the only per-pair tensor that reaches memory; may be NULL
+ *   d_*:    gradient outputs, each may be NULL and its work is then skipped: d_w0h [128,128] (the dense block of columns
+ *           128:256), d_wp [128,4], d_bp, d_g, d_bt [128].  With none of them the launch stops after the GroupNorm
+ *           backward; without d_wp and d_bp it skips the dh GEMM.
+ *   n_chunks: 1..1024 workgroups (never more than ceil(cap / 32) are launched): workgroup k owns the tiles k,
+ *           k + n_chunks, ... and writes one record of 128 * 128 + 7 * 128 floats -- dW_0h, dgamma, dbeta, db_p,
+ *           dW_p[:,0..3]; the second launch sums the records in chunk order.
+ *   ws:     lgcn_pool_pairs_bwd_ws_elems(cap, n_chunks) floats (negative: LGCN_EINVAL for cap < 0, cap too large or
+ *           n_chunks outside 1..1024); needed when any d_* is given.
+ * NULL required pointers, cap < 0, n_chunks outside 1..1024, a missing ws: LGCN_EINVAL; misaligned pointers: LGCN_EALIGN;
+ * cap > 0x7ffffff0: LGCN_ESHAPE; cap == 0 returns LGCN_OK without a launch.  All decided before anything is launched.
+ */
+typedef struct {
+    const float *ctx_pose, *tgt_pose;
+    const int32_t *ti, *ci, *n_pairs;
+    int64_t cap;
+    const float *wp, *bp, *wpc0h, *U, *g, *bt;
+    const float *wptc0h;
+    const uint32_t *masks;
+    const float *dS;
+    float *dz, *d_w0h, *d_wp, *d_bp, *d_g, *d_bt, *ws;
+    float eps;
+    int32_t n_chunks;
+} lgcn_pool_pairs_bwd_t;
+
+int lgcn_pool_pairs_train(const float *ctx_pose, const float *tgt_pose,
+                          const int32_t *ti, const int32_t *ci,
+                          const int32_t *n_pairs, int64_t cap,
+                          const float *wp, const float *bp, const float *wpc0h,
+                          const float *U, const float *g, const float *bt,
+                          float eps, float *m, uint32_t *masks, void *stream);
+int64_t lgcn_pool_pairs_bwd_ws_elems(int64_t cap, int n_chunks);
+int lgcn_pool_pairs_bwd(const lgcn_pool_pairs_bwd_t *p_host, void *stream);
+
+/*
  * PredLoss (reference lanegcn.py:740-807), forward and backward, one launch each.
  *   cls [A, M], reg [A, M, T, 2], gt [A, T, 2] fp32; has [A, T] bytes (torch.bool); M <= 8, T <= 64.
  * Per actor: last = argmax_t(has[t] + 0.1 t / T), kept iff that maximum > 1.0; dist_j = |reg[j, last] - gt[last]|;

@@ -73,6 +73,18 @@ class AttPairsBwd(C.Structure):   # lgcn_att_pairs_bwd_t
     ]
 
 
+class PoolPairsBwd(C.Structure):  # lgcn_pool_pairs_bwd_t
+    _fields_ = [
+        ("ctx_pose", C.c_void_p), ("tgt_pose", C.c_void_p), ("ti", C.c_void_p), ("ci", C.c_void_p), ("n_pairs", C.c_void_p),
+        ("cap", C.c_int64),
+        ("wp", C.c_void_p), ("bp", C.c_void_p), ("wpc0h", C.c_void_p), ("U", C.c_void_p), ("g", C.c_void_p), ("bt", C.c_void_p),
+        ("wptc0h", C.c_void_p), ("masks", C.c_void_p), ("dS", C.c_void_p),
+        ("dz", C.c_void_p), ("d_w0h", C.c_void_p), ("d_wp", C.c_void_p), ("d_bp", C.c_void_p), ("d_g", C.c_void_p),
+        ("d_bt", C.c_void_p), ("ws", C.c_void_p),
+        ("eps", C.c_float), ("n_chunks", C.c_int32),
+    ]
+
+
 class LaneConvBwd(C.Structure):   # lgcn_laneconv_bwd_t
     _fields_ = [
         ("d_out", C.c_void_p), ("out", C.c_void_p), ("Z", C.c_void_p), ("Y", C.c_void_p), ("T", C.c_void_p), ("X", C.c_void_p),
@@ -170,6 +182,9 @@ SIGNATURES = {
     "lgcn_att_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs_train": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _P, _P, _P]),
     "lgcn_pool_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 6 + [_F, _P, _P]),
+    "lgcn_pool_pairs_train": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 6 + [_F, _P, _P, _P]),
+    "lgcn_pool_pairs_bwd_ws_elems": (C.c_int64, [_L, _I]),
+    "lgcn_pool_pairs_bwd": (C.c_int, [C.POINTER(PoolPairsBwd), _P]),
     "lgcn_att_pairs_bwd_ws_elems": (C.c_int64, [_L, _I]),
     "lgcn_att_pairs_bwd": (C.c_int, [C.POINTER(AttPairsBwd), _P]),
     "lgcn_laneconv_bwd_ws_elems": (C.c_int64, [_L, _I, _I]),

@@ -9,7 +9,9 @@ kernels on transposed plans / transposed weights plus three backward kernels:
 Every Function also has a fused exact-fp32 backward, opt-in: RowBlockFn with RowBlockFn.train_hip (one or two IDENT
 relations: lgcn_rowblock_bwd does the whole backward in one launch pair; blocks with a RANGE or CSR relation keep the
 composition above) and LaneConvFn with BlockSpec.fused_bwd (lgcn_laneconv_bwd).
-Att's pair stage has a fused pair of its own (Att.train_hip): AttPairsFn on lgcn_att_pairs_train / lgcn_att_pairs_bwd.
+Att's pair stage has a fused pair of its own (Att.train_hip): AttPairsFn on lgcn_att_pairs_train / lgcn_att_pairs_bwd,
+and so has the pair stage of the fork's LanePooling (LanePooling.train_hip): PoolPairsFn on lgcn_pool_pairs_train /
+lgcn_pool_pairs_bwd.
 PredNet's tail (the heads' nn.Linear(128, 2 T), AttDest's first layer, the score Linear, the sort and the gather) has
 its own pair: PredRegFn / PredFinalFn on lgcn_pred_reg / lgcn_pred_final_train and their backward entries.
 Only the K = 2 / K = 4 input Linears (nn.Linear(2,128) of the stems, the 4 meta columns) stay on stock
@@ -453,6 +455,47 @@ class AttPairsFn(Function):
         if ni[8]:
             rp, col = ps.csr_by_wi(V.shape[0])
             out[8] = ops.gather_sum(g["dc"], rp, col, V.shape[0])
+        return tuple(out)
+
+
+class PoolPairsFn(Function):
+    """S [T,128] = per-target sum of the pair stage of the fork's LanePooling (reference lanercnn.py:492-499; formulas:
+    include/lgcn.h, lgcn_pool_pairs_train) of (pairs with hi = target row and wi = context row, context poses [C,4],
+    target poses [T,4], relpose.0 weight / bias, ctx.0 weight [128,256], U [C,128], ctx.0 norm weight / bias).  Exact fp32
+    in every matrix mode.  Forward = lgcn_pool_pairs_train + the segment sum; only the inputs and the ReLU masks (32 B per
+    pair) are saved -- m is not.  Backward = lgcn_pool_pairs_bwd, then dU as the segment sum of dz over the pairs by
+    context row.  The gradient of ctx.0's weight fills columns 128:256 of a zero [128,256]; the U row block adds columns
+    0:128.  The poses get no gradient."""
+
+    @staticmethod
+    def forward(ctx, pairs, ctx_pose, tgt_pose, wp, bp, w_c0, U, g_w, g_b, eps: float = ops.EPS):
+        ctx_pose, tgt_pose, U = ctx_pose.contiguous(), tgt_pose.contiguous(), U.contiguous()
+        P = pairs.count()
+        m, masks = ops.pool_pairs_train(pairs, ctx_pose, tgt_pose, wp, bp, w_c0, U, (g_w, g_b), cap=P, eps=eps)
+        ctx.pairs, ctx.eps, ctx.P = pairs, eps, P
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(ctx_pose, tgt_pose, wp, bp, w_c0, U, g_w, g_b, masks)
+        return ops.gather_sum(m, pairs.rowptr, None, tgt_pose.shape[0])
+
+    @staticmethod
+    def backward(ctx, dS):
+        if dS is None:
+            return (None,) * 10
+        ctx_pose, tgt_pose, wp, bp, w_c0, U, g_w, g_b, masks = ctx.saved_tensors
+        ps, ni = ctx.pairs, ctx.needs_input_grad
+        names = {3: "d_wp", 4: "d_bp", 5: "d_w0h", 7: "d_g", 8: "d_bt"}
+        want = [n for i, n in names.items() if ni[i]]
+        g = ops.pool_pairs_bwd(ps, dS.contiguous(), masks, ctx_pose, tgt_pose, wp, bp, w_c0, U, (g_w, g_b), want=want,
+                               want_dz=ni[6], cap=ctx.P, eps=ctx.eps)
+        out = [None] * 10
+        for i, n in names.items():
+            out[i] = g.get(n)
+        if ni[5]:
+            out[5] = torch.zeros_like(w_c0)
+            out[5][:, C_FEAT:] = g["d_w0h"]
+        if ni[6]:
+            rp, col = ps.csr_by_wi(U.shape[0])
+            out[6] = ops.gather_sum(g["dz"], rp, col, U.shape[0])
         return tuple(out)
 
 

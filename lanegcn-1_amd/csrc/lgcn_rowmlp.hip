@@ -427,7 +427,10 @@ __device__ __forceinline__ void lin4_relu_to_lds(float *T, int t, float4 d, cons
     }
 }
 
-__global__ __launch_bounds__(256) void k_pool_pairs(const PoolParams p) {
+// MASKS: the training forward (lgcn_pool_pairs_train).  masks[p][k] = the four words of mask k of pair p, k = 0: W_p d + b_p
+// > 0, 1: m > 0 (the layout of k_att_pairs); the arithmetic of m is the inference kernel's.
+template <bool MASKS>
+__global__ __launch_bounds__(256) void k_pool_pairs(const PoolParams p, uint4 *__restrict__ masks) {
     __shared__ __attribute__((aligned(16))) float smem[2 * kTileFloats];
     float *T1 = smem, *T2 = smem + kTileFloats;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -448,6 +451,10 @@ __global__ __launch_bounds__(256) void k_pool_pairs(const PoolParams p) {
             d = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
         }
         lin4_relu_to_lds(T1, tid, d, p.wp, p.bp);
+        if constexpr (MASKS) {      // ReLU(y0) > 0 <=> y0 > 0; the thread reads back its own elements
+            const uint4 mw = row_mask_words(row_load(T1, tid), tid);
+            if (live && (tid & 7) == 0) masks[pr * 2] = mw;
+        }
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -460,6 +467,10 @@ __global__ __launch_bounds__(256) void k_pool_pairs(const PoolParams p) {
             row_gn(r, tid, p.g, p.bt, p.eps);
             row_relu(r);
             if (live) row_store_global(p.m + pr * kC, tid, r);
+            if constexpr (MASKS) {
+                const uint4 mw = row_mask_words(r, tid);
+                if (live && (tid & 7) == 0) masks[pr * 2 + 1] = mw;
+            }
         }
         // T1 is rewritten only after every wave's tile_gemm (the barrier above); T2 only after the next iteration's
         // first barrier, which every thread reaches after its row_load.
@@ -956,6 +967,159 @@ __global__ __launch_bounds__(256) void k_lc_bwd_reduce(const float *__restrict__
     *dst = s;
 }
 
+// ----------------------------------------------------- pool pairs bwd -----
+// Backward of the pair stage of LanePooling for dS [T,128] (include/lgcn.h, lgcn_pool_pairs_bwd), shaped like k_att_pairs_bwd
+// with one GEMM and one GroupNorm less: workgroup `chunk` walks the 32-pair tiles chunk, chunk + n_chunks, ...  Per tile,
+// waves 0-3 recompute h and z and the GroupNorm statistics with the forward's device functions, apply the stored masks, run
+// the GroupNorm backward in registers (dz -> G and memory) and the dh GEMM on the transposed image.  Waves 4-7 own what is
+// summed over pairs, in registers across the workgroup's tiles: dW_0h on wgrad_tile (wave 4 + q: block q, A[0..3]) and the
+// seven [128] vectors as column sums over the tile's rows, in row order: dgamma / dbeta from the tiles P1 = g * zhat and
+// P2 = g, and db_p and the four columns of dW_p from ONE tile, dy0, whose column c thread (which, c) sums plainly (db_p) and
+// weighted with the rows' d (D4, 32 x 4 floats, broadcast reads).  Five product tiles dy0, dy0 * d.x, ... would have to sit
+// in H and X as well, which the next tile's first two phases rewrite while waves 4-7 still sum them: that costs two more
+// barriers per tile or two more tiles of LDS, and four more tile stores per row thread either way.
+// LDS: H (h), X (GEMM output), G (dz), P1 / P2 (g * zhat / g, then dy0 in P1), D4: 5 x 16.5 KiB + 512 B.  Four barriers per
+// tile.
+constexpr int kPoolRecTail = 7 * kC;
+constexpr int kPoolRec = kC * kC + kPoolRecTail;          // floats per chunk record
+
+// sum over the 32 rows of T[r][c] * w[4 r], in row order (w: one of the four columns of a 32 x 4 LDS array)
+__device__ __forceinline__ float tile_colsum_w(const float *T, int c, const float *w) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int r = 0; r < 32; ++r) s += T[r * kLDA + c] * w[4 * r];
+    return s;
+}
+
+__global__ __launch_bounds__(512) void k_pool_pairs_bwd(const PoolBwdParams p) {
+    __shared__ __attribute__((aligned(16))) float smem[5 * kTileFloats + 4 * kTM32];
+    float *H = smem, *X = smem + kTileFloats, *G = smem + 2 * kTileFloats, *P1 = smem + 3 * kTileFloats;
+    float *P2 = smem + 4 * kTileFloats, *D4 = smem + 5 * kTileFloats;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool rowt = tid < 256;
+    const int which = (tid >> 7) & 1, col = tid & 127;       // waves 4-7: column sums
+    const PoolParams &f = p.f;
+    int64_t P = *f.n_pairs;
+    if (P < 0 || P > f.cap) P = f.cap;
+    const int64_t n_tiles = (P + kTM32 - 1) / kTM32;
+    const bool want_rec = p.rec != nullptr, want_p = p.want_p != 0, want_w = p.want_w != 0;
+
+    f32x16 A[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) A[k][i] = 0.f;
+    float s_g = 0.f, s_b = 0.f, s_w0 = 0.f, s_w1 = 0.f;      // which = 0: dgamma, db_p, dW_p[:,0], dW_p[:,1]; 1: dbeta, -, dW_p[:,2], dW_p[:,3]
+    bool pend = false;           // dy0 (P1) and d (D4) of the tile before are waiting
+    f32x16 acc;
+
+    auto pending_sums = [&]() {      // waves 4-7
+        if (which == 0) s_b += tile_colsum(P1, col);
+        s_w0 += tile_colsum_w(P1, col, D4 + 2 * which);
+        s_w1 += tile_colsum_w(P1, col, D4 + 2 * which + 1);
+    };
+
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t pr = tile * kTM32 + (tid >> 3);
+        const bool live = rowt && pr < P;
+        const uint4 *mk = live ? p.masks + pr * 2 : nullptr;              // rows past the count: no gradient
+        int t = 0, c = 0;
+        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) {
+            t = f.ti[pr]; c = f.ci[pr];
+            const float4 a = reinterpret_cast<const float4 *>(f.ctx_pose)[c];
+            const float4 b = reinterpret_cast<const float4 *>(f.tgt_pose)[t];
+            d = make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
+        }
+        // ---- forward again: h -> H, W_0h h -> X
+        if (rowt) lin4_relu_to_lds(H, tid, d, f.wp, f.bp);
+        __syncthreads();
+        if (wave < 4) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+            tile_gemm(H, reinterpret_cast<const float4 *>(f.wpc0h) + wave * (16 * 64), acc, lane, 16);
+            acc_to_lds(X, acc, lane, wave);
+        } else if (pend) {      // what the last row phase of the tile before left (P1 is next written behind the next barrier,
+            pending_sums();     // D4 three barriers from here)
+        }
+        pend = false;
+        __syncthreads();
+        // ---- m = ReLU(GN(z)): g = dS[t] * mask1 (P1 = g * zhat, P2 = g), dz -> G and global
+        if (rowt) {
+            RowVals z = row_load(X, tid);
+            RowVals g = row_zero();
+            if (live) {
+                row_add_global(z, f.U + (int64_t)c * kC, tid);
+                row_add_global(g, p.dS + (int64_t)t * kC, tid);
+            }
+            const float rstd = row_gn_hat(z, f.eps);
+            row_apply_mask(g, mk ? mk + 1 : mk, tid);
+            if (want_rec) { row_store_lds(P1, tid, row_mul(g, z)); row_store_lds(P2, tid, g); }
+            row_gn_bwd(g, z, rstd, tid, f.g);
+            row_store_lds(G, tid, g);
+            if (live && p.dz) row_store_global(p.dz + pr * kC, tid, g);
+        }
+        if (!want_rec) continue;                // uniform; H's readers are past the barrier above, X is next written a barrier on
+        __syncthreads();
+        // ---- z = W_0h h + U[c]: dh = dz W_0h -> X (waves 0-3); dW_0h += dz^T h, dgamma, dbeta (waves 4-7)
+        if (wave < 4) {
+            if (want_p) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+                tile_gemm(G, reinterpret_cast<const float4 *>(p.wptc0h) + wave * (16 * 64), acc, lane, 16);
+                acc_to_lds(X, acc, lane, wave);
+            }
+        } else {
+            if (want_w) wgrad_tile(G, H, A[0], A[1], A[2], A[3], wave - 4, lane);
+            s_g += tile_colsum(which ? P2 : P1, col);
+        }
+        __syncthreads();                        // H, G, P1 and P2 are free behind this barrier
+        if (!want_p) continue;                  // uniform
+        // ---- h = ReLU(W_p d + b_p): dy0 = dh * mask0 -> P1, d -> D4; waves 4-7 sum them behind the next barrier (the next
+        // tile's first, or the one after the loop)
+        if (rowt) {
+            RowVals g = row_load(X, tid);
+            row_apply_mask(g, mk, tid);
+            row_store_lds(P1, tid, g);
+            if ((tid & 7) == 0) *reinterpret_cast<float4 *>(D4 + 4 * (tid >> 3)) = d;
+        }
+        pend = true;
+    }
+
+    if (!want_rec) return;
+    if (pend) {
+        __syncthreads();
+        if (wave >= 4) pending_sums();
+    }
+    if (wave >= 4) {
+        float *rec = p.rec + (int64_t)blockIdx.x * kPoolRec;
+        wgrad_store(rec, A[0], A[1], A[2], A[3], wave - 4, lane);
+        float *tail = rec + kC * kC;
+        tail[which * kC + col] = s_g;
+        if (which == 0) tail[2 * kC + col] = s_b;
+        tail[(3 + 2 * which) * kC + col] = s_w0;
+        tail[(4 + 2 * which) * kC + col] = s_w1;
+    }
+}
+
+// out = sum over the chunk records, in chunk order.  Record: dW_0h [128,128], then seven [128] vectors: dgamma, dbeta, db_p,
+// dW_p[:,0], dW_p[:,1], dW_p[:,2], dW_p[:,3].
+__global__ __launch_bounds__(256) void k_pool_pairs_bwd_reduce(const float *__restrict__ rec, int n_rec, const PoolBwdOut o) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kPoolRec) return;
+    float *dst = nullptr;
+    if (e < kC * kC) dst = o.dw0h ? o.dw0h + e : nullptr;
+    else {
+        const int v = (e - kC * kC) >> 7, c = e & 127;
+        float *const vec = v == 0 ? o.dg : v == 1 ? o.dbt : v == 2 ? o.dbp : o.dwp;
+        if (vec != nullptr) dst = v < 3 ? vec + c : vec + 4 * c + (v - 3);
+    }
+    if (dst == nullptr) return;
+    float s = 0.f;
+    for (int k = 0; k < n_rec; ++k) s += rec[(int64_t)k * kPoolRec + e];
+    *dst = s;
+}
+
 // ------------------------------------------------------ row block bwd -----
 // Backward of one row block out = [ReLU]([GN](sum_r src_r W_r^T) [+ res]) with NREL = 1 or 2 IDENT relations
 // (include/lgcn.h, lgcn_rowblock_bwd): the lower half of k_lc_bwd_rows<true> as a kernel of its own.  Workgroup `chunk`
@@ -1331,7 +1495,24 @@ int lgcn_pool_pairs(const float *ctx_pose, const float *tgt_pose, const int32_t 
     PoolParams p{ctx_pose, tgt_pose, ti, ci, n_pairs, cap, wp, bp, wpc0h, U, g, bt, eps, m};
     const int64_t tiles = (cap + kTM32 - 1) / kTM32;
     const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
-    hipLaunchKernelGGL(k_pool_pairs, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_pool_pairs<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, (uint4 *)nullptr);
+    return launch_status();
+}
+
+int lgcn_pool_pairs_train(const float *ctx_pose, const float *tgt_pose, const int32_t *ti, const int32_t *ci,
+                          const int32_t *n_pairs, int64_t cap, const float *wp, const float *bp, const float *wpc0h,
+                          const float *U, const float *g, const float *bt, float eps, float *m, uint32_t *masks, void *stream) {
+    if (cap < 0) return LGCN_EINVAL;
+    if (cap == 0) return LGCN_OK;
+    if (cap > 0x7ffffff0) return LGCN_ESHAPE;
+    const void *ptrs[] = {ctx_pose, tgt_pose, ti, ci, n_pairs, wp, bp, wpc0h, U, g, bt, m, masks};
+    for (const void *q : ptrs) LGCN_CHECK_PTR(q);
+    const void *al[] = {ctx_pose, tgt_pose, wp, bp, wpc0h, U, g, bt, m, masks};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);
+    PoolParams p{ctx_pose, tgt_pose, ti, ci, n_pairs, cap, wp, bp, wpc0h, U, g, bt, eps, m};
+    const int64_t tiles = (cap + kTM32 - 1) / kTM32;
+    const unsigned grid = (unsigned)(tiles < 2048 ? tiles : 2048);
+    hipLaunchKernelGGL(k_pool_pairs<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, reinterpret_cast<uint4 *>(masks));
     return launch_status();
 }
 
@@ -1379,6 +1560,46 @@ int lgcn_att_pairs_bwd(const lgcn_att_pairs_bwd_t *ph, void *stream) {
     if (want_rec) {
         const PairBwdOut o{a.d_wd2, a.d_wc0e, a.d_gc, a.d_btc, a.d_gd, a.d_btd, a.d_bd0, a.d_wd0};
         hipLaunchKernelGGL(k_att_pairs_bwd_reduce, dim3((kPairRec + 255) / 256), dim3(256), 0, st, a.ws, n_rec, o);
+    }
+    return launch_status();
+}
+
+static_assert(sizeof(lgcn_pool_pairs_bwd_t) == 23 * 8,
+              "lgcn_pool_pairs_bwd_t layout: keep lanegcn-1_amd/_lib.py (PoolPairsBwd) and tests/test_host_pool_train_cabi.py in step");
+
+int64_t lgcn_pool_pairs_bwd_ws_elems(int64_t cap, int n_chunks) {
+    if (cap < 0 || cap > 0x7ffffff0 || n_chunks < 1 || n_chunks > 1024) return LGCN_EINVAL;
+    return pair_bwd_chunks(cap, n_chunks) * kPoolRec;
+}
+
+int lgcn_pool_pairs_bwd(const lgcn_pool_pairs_bwd_t *ph, void *stream) {
+    LGCN_CHECK_PTR(ph);
+    const lgcn_pool_pairs_bwd_t &a = *ph;
+    if (a.cap < 0 || a.n_chunks < 1 || a.n_chunks > 1024) return LGCN_EINVAL;
+    if (a.cap == 0) return LGCN_OK;
+    if (a.cap > 0x7ffffff0) return LGCN_ESHAPE;
+    const bool want_p = a.d_wp || a.d_bp;
+    const bool want_rec = want_p || a.d_w0h || a.d_g || a.d_bt;
+    const void *ptrs[] = {a.ctx_pose, a.tgt_pose, a.ti, a.ci, a.n_pairs, a.wp, a.bp, a.wpc0h, a.U, a.g, a.bt, a.masks, a.dS};
+    for (const void *q : ptrs) LGCN_CHECK_PTR(q);
+    if (want_p) LGCN_CHECK_PTR(a.wptc0h);
+    if (want_rec) LGCN_CHECK_PTR(a.ws);
+    const void *al[] = {a.ctx_pose, a.tgt_pose, a.wp, a.bp, a.wpc0h, a.U, a.g, a.bt, a.masks, a.dS, a.wptc0h, a.dz, a.ws,
+                        a.d_w0h, a.d_wp, a.d_bp, a.d_g, a.d_bt};
+    for (const void *q : al) LGCN_CHECK_ALIGN16(q);      // absent (null) ones pass
+    if (!want_rec && a.dz == nullptr) return LGCN_OK;
+    PoolBwdParams p{};
+    p.f = PoolParams{a.ctx_pose, a.tgt_pose, a.ti, a.ci, a.n_pairs, a.cap, a.wp, a.bp, a.wpc0h, a.U, a.g, a.bt, a.eps, nullptr};
+    p.wptc0h = a.wptc0h;
+    p.masks = reinterpret_cast<const uint4 *>(a.masks);
+    p.dS = a.dS; p.dz = a.dz; p.rec = want_rec ? a.ws : nullptr;
+    p.want_p = want_p; p.want_w = a.d_w0h != nullptr;
+    const int n_rec = (int)pair_bwd_chunks(a.cap, a.n_chunks);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_pool_pairs_bwd, dim3(n_rec), dim3(512), 0, st, p);
+    if (want_rec) {
+        const PoolBwdOut o{a.d_w0h, a.d_wp, a.d_bp, a.d_g, a.d_bt};
+        hipLaunchKernelGGL(k_pool_pairs_bwd_reduce, dim3((kPoolRec + 255) / 256), dim3(256), 0, st, a.ws, n_rec, o);
     }
     return launch_status();
 }

@@ -232,6 +232,18 @@ struct PairBwdParams {
 
 struct PairBwdOut { float *dwd2, *dwc0e, *dgc, *dbc, *dgd, *dbd, *dbd0, *dwd0; };
 
+// lgcn_pool_pairs_bwd: the forward's inputs, what it saved and the gradient outputs (see include/lgcn.h)
+struct PoolBwdParams {
+    PoolParams f;
+    const float *wptc0h;              // transposed image of W_0[:, 128:256]
+    const uint4 *masks;
+    const float *dS;
+    float *dz, *rec;
+    int want_p, want_w;               // anything upstream of h (relpose.0's parameters) / dW_0h
+};
+
+struct PoolBwdOut { float *dw0h, *dwp, *dbp, *dg, *dbt; };
+
 // split-bf16 implementations (lgcn_rowmlp_bf.hip)
 int agg_mlp_bf(const lgcn_agg_mlp_t &p, bool lane_conv, hipStream_t st);
 int agg_mlp_pair_bf(const lgcn_agg_mlp_t &a, const lgcn_agg_mlp_t &b, hipStream_t st);

@@ -268,9 +268,17 @@ class LanePooling(nn.Module):
     legacy_offsets = True     # scenes without a pair do not advance the index offsets (lanercnn.py:476-483)
     # Run the pair stage (:492-499: relative pose, relpose.0, ctx.0's pose half + the context row block, GroupNorm, ReLU)
     # of a forward that needs no gradient as ONE exact-fp32 launch (lgcn_pool_pairs) instead of the chain of generic
-    # ones; only m [P,128] reaches memory.  Under autograd the composed path runs whatever the switch says, so with it
-    # on a training forward can differ from the no_grad forward in the last bits.  Opt-in; read on each forward.
+    # ones; only m [P,128] reaches memory.  Under autograd this switch is ignored (train_hip below decides).  Opt-in; read
+    # on each forward.
     fused = False
+    # Train the pair stage on the fused exact-fp32 pair of autograd.PoolPairsFn (lgcn_pool_pairs_train /
+    # lgcn_pool_pairs_bwd) instead of the composition of row blocks in _run: no [P,128] tensor is saved, one (dz) is written
+    # in the backward, and the pair stage's training forward is bit for bit the launch of `fused`.  The tail then takes the
+    # segment sum S as a plain source, so its backward is eligible for RowBlockFn.train_hip; it sums m before ctx.1 in
+    # another order than the inference tail's RANGE relation, so the MODULE's training forward may still differ from its
+    # no_grad forward in the last bits.  Opt-in, like Att.train_hip: the default training path stays the composed one.
+    # Read on each forward.
+    train_hip = False
 
     def __init__(self, in_dim: int, out_dim: int) -> None:
         super().__init__()
@@ -310,6 +318,8 @@ class LanePooling(nn.Module):
             m = ops.pool_pairs(ps, c_pose, t_pose, self.relpose[0].weight, self.relpose[0].bias, w0, per_ctx,
                                _gn(self.ctx[0].norm), cap=P, eps=self.ctx[0].norm.eps)
             return self._tail(m, ps, target_feat)
+        if train and self._train_hip_ok(context_feat, target_feat, c_pose, t_pose, ps):
+            return self.run_train_hip(context_feat, target_feat, c_pose, t_pose, ps)
         t_idx, c_idx = ps.hi[:P].long(), ps.wi[:P].long()
         h = F.relu(self.relpose[0](c_pose[c_idx] - t_pose[t_idx]))                        # [P,128]; K = 4: stock op
         if train:      # the differentiable composition of the same arithmetic (cf. Att.run_train)
@@ -331,6 +341,27 @@ class LanePooling(nn.Module):
         pre = ops.pair_add(per_pair, per_ctx, ps.wi, zero_row, zero_idx, ps.n_pairs, P)
         m = ops.gn_fwd(pre, _gn(self.ctx[0].norm), relu=True, eps=self.ctx[0].norm.eps)
         return self._tail(m, ps, target_feat)
+
+    def _train_hip_ok(self, context_feat, target_feat, c_pose, t_pose, ps) -> bool:
+        rows_ok = max(context_feat.shape[0], target_feat.shape[0]) < (1 << 23)
+        return (LanePooling.train_hip and context_feat.is_cuda and context_feat.dtype == torch.float32
+                and target_feat.dtype == torch.float32 and context_feat.shape[1] == ops.C_FEAT
+                and target_feat.shape[1] == ops.C_FEAT and c_pose.dtype == torch.float32 and t_pose.dtype == torch.float32
+                and c_pose.dim() == 2 and t_pose.dim() == 2 and c_pose.shape[1] == 4 and t_pose.shape[1] == 4
+                and rows_ok and ps.count() > 0 and not (c_pose.requires_grad or t_pose.requires_grad))
+
+    def run_train_hip(self, context_feat, target_feat, c_pose, t_pose, ps):
+        """The training path of _run with the pair stage on PoolPairsFn: U and the two mlp blocks are the same row blocks;
+        the segment sum S comes out of the pair stage, and ctx.1 (linear) is applied to it as an IDENT relation."""
+        T = target_feat.shape[0]
+        w0, c0, rp = self.ctx[0].linear.weight, self.ctx[0].norm, self.relpose[0]
+        m0, m1 = self.mlp[0], self.mlp[1]
+        U = A.linear_gn(context_feat, w0, col0=0)
+        S = A.PoolPairsFn.apply(ps, c_pose, t_pose, rp.weight, rp.bias, w0, U, c0.weight, c0.bias, c0.eps)
+        y = A.row_block([target_feat, S], [self.input.weight, self.ctx[1].weight],
+                        [A.Rel(0, 0, L.REL_IDENT), A.Rel(1, 1, L.REL_IDENT)], T, gn=self.norm, relu=True)
+        y = A.linear_gn(y, m0.linear.weight, gn=m0.norm, relu=True)
+        return A.linear_gn(y, m1.linear.weight, gn=m1.norm, relu=True, res=target_feat)
 
     def _tail(self, m, ps, target_feat):
         T = target_feat.shape[0]

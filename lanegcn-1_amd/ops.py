@@ -1266,6 +1266,26 @@ def att_pairs_train(ps: PairSet, wd0, bd0, w_d2, gn_d, w_c0, U, V, gn_c, m=None,
     return m, masks
 
 
+def _pool_args(what, ps, ctx_pose, tgt_pose, wp, bp, w_c0, U):
+    ctx_pose, tgt_pose = _dev(ctx_pose, torch.float32, "ctx_pose"), _dev(tgt_pose, torch.float32, "tgt_pose")
+    U = _dev(U, torch.float32, "U")
+    if ctx_pose.dim() != 2 or ctx_pose.shape[1] != 4 or tgt_pose.dim() != 2 or tgt_pose.shape[1] != 4:
+        raise L.LgcnError(what + ": poses must be [rows, 4]")
+    if U.shape != (ctx_pose.shape[0], C_FEAT):
+        raise L.LgcnError(what + ": U must be [context rows, 128]")
+    if tuple(w_c0.shape) != (C_FEAT, 2 * C_FEAT) or tuple(wp.shape) != (C_FEAT, 4):
+        raise L.LgcnError(what + ": need relpose.0 [128,4] and ctx.0 [128,256] weights")
+    return ctx_pose, tgt_pose, _dev(wp.detach(), torch.float32, "wp"), _dev(bp.detach(), torch.float32, "bp"), U
+
+
+def _pool_buf(what, name, t, rows, cols, dtype, device):
+    if t is None:
+        return torch.empty((max(rows, 1), cols), dtype=dtype, device=device)
+    if t.shape[0] < rows or not t.is_contiguous() or t.dtype != dtype:
+        raise L.LgcnError("%s: %s must be a contiguous [>= cap, %d] tensor" % (what, name, cols))
+    return t
+
+
 def pool_pairs(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=None, cap=None, eps=EPS, tag="pool_pairs"):
     """m [cap,128] of lgcn_pool_pairs: the pair stage of the fork's LanePooling (reference lanercnn.py:492-499) in one
     launch, exact fp32 in every matrix mode.  ps: pairs with hi = target row, wi = context row; ctx_pose [C,4], tgt_pose
@@ -1274,15 +1294,7 @@ def pool_pairs(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=None, cap
     launch may write (default: the pair search's capacity; a caller that knows P passes it and gets a [P,128] m).  Rows
     >= *n_pairs of m are not written."""
     lib = L.load()
-    ctx_pose, tgt_pose = _dev(ctx_pose, torch.float32, "ctx_pose"), _dev(tgt_pose, torch.float32, "tgt_pose")
-    U = _dev(U, torch.float32, "U")
-    if ctx_pose.dim() != 2 or ctx_pose.shape[1] != 4 or tgt_pose.dim() != 2 or tgt_pose.shape[1] != 4:
-        raise L.LgcnError("pool_pairs: poses must be [rows, 4]")
-    if U.shape != (ctx_pose.shape[0], C_FEAT):
-        raise L.LgcnError("pool_pairs: U must be [context rows, 128]")
-    if tuple(w_c0.shape) != (C_FEAT, 2 * C_FEAT) or tuple(wp.shape) != (C_FEAT, 4):
-        raise L.LgcnError("pool_pairs: need relpose.0 [128,4] and ctx.0 [128,256] weights")
-    wp, bp = _dev(wp.detach(), torch.float32, "wp"), _dev(bp.detach(), torch.float32, "bp")
+    ctx_pose, tgt_pose, wp, bp, U = _pool_args("pool_pairs", ps, ctx_pose, tgt_pose, wp, bp, w_c0, U)
     with exact_mma():
         wpc0h = packed(w_c0, C_FEAT, C_FEAT)
     cap = ps.cap if cap is None else min(int(cap), ps.cap)
@@ -1296,6 +1308,91 @@ def pool_pairs(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=None, cap
                                  _stream())
     L.check(rc, "lgcn_pool_pairs")
     return m
+
+
+# ------------------------------------------------------------------ LanePooling's pair stage, training (exact fp32)
+POOL_MASK_WORDS = 8        # per pair: 2 masks x 4 words of 32 channels
+
+
+def pool_pairs_train(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=None, masks=None, cap=None, eps=EPS,
+                     tag="pool_pairs_train"):
+    """(m [cap,128], masks [cap,8] int32) of lgcn_pool_pairs_train: pool_pairs (same arguments, same bits of m) plus the
+    two ReLU masks as bits (pool_pair_masks decodes them).  Rows >= *n_pairs of m / masks are not written."""
+    lib = L.load()
+    ctx_pose, tgt_pose, wp, bp, U = _pool_args("pool_pairs_train", ps, ctx_pose, tgt_pose, wp, bp, w_c0, U)
+    with exact_mma():
+        wpc0h = packed(w_c0, C_FEAT, C_FEAT)
+    cap = ps.cap if cap is None else min(int(cap), ps.cap)
+    m = _pool_buf("pool_pairs_train", "m", m, cap, C_FEAT, torch.float32, U.device)
+    masks = _pool_buf("pool_pairs_train", "masks", masks, cap, POOL_MASK_WORDS, torch.int32, U.device)
+    with _Timed(tag):
+        rc = lib.lgcn_pool_pairs_train(_ptr(ctx_pose), _ptr(tgt_pose), _ptr(ps.hi), _ptr(ps.wi), _ptr(ps.n_pairs), cap,
+                                       _ptr(wp), _ptr(bp), _ptr(wpc0h), _ptr(U), _ptr(gn[0]), _ptr(gn[1]), eps, _ptr(m),
+                                       _ptr(masks), _stream())
+    L.check(rc, "lgcn_pool_pairs_train")
+    return m, masks
+
+
+def pool_pair_masks(masks: torch.Tensor, P: int) -> torch.Tensor:
+    """bool [P,2,128] of the first P rows of pool_pairs_train's masks: [p, k, c] = mask k of channel c of pair p, k = 0:
+    W_p d + b_p > 0, 1: m > 0.  Layout: word 4 k + j of a row holds channels 32 j .. 32 j + 31, bit b = channel 32 j + b."""
+    w = masks[:P].reshape(P, 2, 4, 1).to(torch.int64) & 0xFFFFFFFF
+    bits = (w >> torch.arange(32, device=masks.device)) & 1
+    return bits.reshape(P, 2, C_FEAT).bool()
+
+
+POOL_BWD_OUTS = ("d_w0h", "d_wp", "d_bp", "d_g", "d_bt")
+
+
+def pool_pairs_bwd(ps: PairSet, dS, masks, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, want=POOL_BWD_OUTS, want_dz=True, dz=None,
+                   cap=None, eps=EPS, n_chunks: Optional[int] = None, tag="pool_pairs_bwd"):
+    """lgcn_pool_pairs_bwd for dS [T,128]: dict with "dz" ([cap,128], rows < P written; None unless want_dz) and the
+    gradients named in `want` -- d_w0h [128,128] (the columns 128:256 of ctx.0's weight), d_wp [128,4], d_bp (relpose.0),
+    d_g, d_bt (ctx.0's norm) [128].  cap: as in pool_pairs.  n_chunks: workgroups, each with one partial record of 69,120 B
+    that the reduction launch reads back (default: the rule of att_pairs_bwd -- one per CU, never more than a quarter of
+    the 32-pair tiles of the pair count when the host already knows it, else of the capacity)."""
+    lib = L.load()
+    dS = _dev(dS, torch.float32, "dS")
+    ctx_pose, tgt_pose, wp, bp, U = _pool_args("pool_pairs_bwd", ps, ctx_pose, tgt_pose, wp, bp, w_c0, U)
+    if dS.dim() != 2 or dS.shape != (tgt_pose.shape[0], C_FEAT):
+        raise L.LgcnError("pool_pairs_bwd: dS must be [target rows, 128]")
+    dev, want = dS.device, tuple(want)
+    with exact_mma():
+        wpc0h, wptc0h = packed(w_c0, C_FEAT, C_FEAT), packed_t(w_c0, C_FEAT)
+    cap = ps.cap if cap is None else min(int(cap), ps.cap)
+    if masks.shape[0] < cap or not masks.is_contiguous() or masks.dtype != torch.int32:
+        raise L.LgcnError("pool_pairs_bwd: masks must be a contiguous int32 [>= cap, 8] tensor")
+    if n_chunks is None:
+        rows = cap if ps._p_host is None else min(ps._p_host, cap)
+        n_chunks = min(cu_count(dev), (rows + 127) // 128)
+    n_chunks = max(1, min(int(n_chunks), (cap + 31) // 32, 1024))
+    out = {"dz": None}
+    q = L.PoolPairsBwd()
+    q.ctx_pose, q.tgt_pose, q.ti, q.ci, q.n_pairs = (t.data_ptr() for t in (ctx_pose, tgt_pose, ps.hi, ps.wi, ps.n_pairs))
+    q.cap = cap
+    q.wp, q.bp, q.wpc0h, q.U, q.g, q.bt = (t.data_ptr() for t in (wp, bp, wpc0h, U, gn[0], gn[1]))
+    q.wptc0h, q.masks, q.dS = wptc0h.data_ptr(), masks.data_ptr(), dS.data_ptr()
+    if want_dz:
+        out["dz"] = _pool_buf("pool_pairs_bwd", "dz", dz, cap, C_FEAT, torch.float32, dev)
+        q.dz = out["dz"].data_ptr()
+    shapes = {"d_w0h": (C_FEAT, C_FEAT), "d_wp": (C_FEAT, 4)}
+    for name in want:
+        if name not in POOL_BWD_OUTS:
+            raise L.LgcnError("pool_pairs_bwd: unknown output %r" % (name,))
+        out[name] = torch.empty(shapes.get(name, (C_FEAT,)), dtype=torch.float32, device=dev)
+        setattr(q, name, out[name].data_ptr())
+    ws = None
+    if want:
+        n_ws = lib.lgcn_pool_pairs_bwd_ws_elems(cap, n_chunks)
+        if n_ws < 0:
+            raise L.LgcnError("pool_pairs_bwd: cap = %d / n_chunks = %d not supported" % (cap, n_chunks))
+        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        q.ws = ws.data_ptr()
+    q.eps, q.n_chunks = eps, n_chunks
+    with _Timed(tag):
+        rc = lib.lgcn_pool_pairs_bwd(C.byref(q), _stream())
+    L.check(rc, "lgcn_pool_pairs_bwd")
+    return out
 
 
 def att_pair_masks(masks: torch.Tensor, P: int) -> torch.Tensor:

@@ -8,7 +8,15 @@ inputs it receives inside the forward, pair search included) and one JSON line. 
   --scenes B --agents A --roads L,L,..   scenes per batch, agents (= RoIs at most) per scene, lanes per road (default
                                          10 x 12 on roads 6,6,6: 324 nodes per scene)
   --steps K --warmup W                   timed and untimed forwards per variant (default 30 / 5)
-  --mma MODE                             matrix mode of everything but the fused pair stage (which is exact fp32)"""
+  --mma MODE                             matrix mode of everything but the fused pair stage (which is exact fp32)
+  --train                                instead: forward + Loss + backward of Net on the same batch with
+                                         LanePooling.train_hip off (the composed pair stage) and on (autograd.PoolPairsFn),
+                                         alternating call by call in one process after the warm-up: median and minimum of
+                                         --steps steps each (host clock around a step that ends in a synchronise), kernel
+                                         launches of one step each (torch.profiler, after the timed steps), the peak of
+                                         torch.cuda.max_memory_allocated over one step each, and the largest relative
+                                         difference of the loss and of any parameter gradient between the two
+  --others                               with --train: RowBlockFn.train_hip and Decode.train_hip on for both variants"""
 import argparse
 import json
 import os
@@ -37,6 +45,75 @@ def make_batch(n_scenes, n_agents, roads, seed=0):
     return gen.collate_fn(scenes)
 
 
+def train_mode(args):
+    from lanegcn_amd import autograd as A
+    torch.manual_seed(0)
+    net, loss_fn = R.Net(R.config).cuda().train(), R.Loss(R.config).cuda()
+    data = make_batch(args.scenes, args.agents, [int(v) for v in args.roads.split(",")])
+    n_rois = sum(len(s) for s in data["subgraphs"])
+    A.RowBlockFn.train_hip = R.Decode.train_hip = bool(args.others)
+
+    def step(on):
+        R.LanePooling.train_hip = on
+        try:
+            net.zero_grad(set_to_none=True)
+            loss = loss_fn(net(data), data)["loss"]
+            loss.backward()
+            return loss.detach()
+        finally:
+            R.LanePooling.train_hip = False
+
+    pairs, real_pairs = [], R.build_pairs
+    R.build_pairs = lambda *a, **k: pairs.append(real_pairs(*a, **k)) or pairs[-1]
+    try:
+        step(False)
+    finally:
+        R.build_pairs = real_pairs
+    P = {name: ps.count() for name, ps in zip(("roi2graph", "graph2roi", "lane_pool"), pairs)}
+    del pairs
+
+    names = {"off": False, "on": True}
+    times = {k: [] for k in names}
+    for _ in range(args.warmup):
+        for on in names.values():
+            step(on)
+    torch.cuda.synchronize()
+    for _ in range(args.steps):
+        for name, on in names.items():
+            t0 = time.perf_counter()
+            step(on)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    peak, grads, loss = {}, {}, {}
+    for name, on in names.items():
+        net.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        loss[name] = float(step(on))
+        torch.cuda.synchronize()
+        peak[name] = {"max_allocated_mib": torch.cuda.max_memory_allocated() / 2 ** 20,
+                      "above_resident_mib": (torch.cuda.max_memory_allocated() - base) / 2 ** 20}
+        grads[name] = {k: p.grad.clone() for k, p in net.named_parameters()}
+    diffs = {k: float((grads["on"][k] - g).abs().max() / g.abs().max().clamp_min(1e-30)) for k, g in grads["off"].items()}
+    diff, worst = max(diffs.values()), sorted(diffs.items(), key=lambda kv: -kv[1])[:5]
+    del grads
+    launches = {name: count_launches(lambda on=on: step(on)) for name, on in names.items()}
+    res = {"metric": "lanercnn.Net forward + Loss + backward, %d scenes, %d RoIs" % (args.scenes, n_rois),
+           "mma": ops.get_mma(), "steps": args.steps, "other_train_hip_switches": bool(args.others), "pairs": P,
+           "median_ms": {k: float(np.median(v)) for k, v in times.items()}, "min_ms": {k: min(v) for k, v in times.items()},
+           "p10_p90_ms": {k: [float(np.percentile(v, 10)), float(np.percentile(v, 90))] for k, v in times.items()},
+           "launches_per_step": launches, "peak_memory": peak, "loss": loss, "max_rel_grad_diff_on_off": diff,
+           "largest_rel_grad_diffs": worst}
+    print("P per pooling: %s" % P, flush=True)
+    for name in names:
+        print("Net step, LanePooling.train_hip %s: median %.3f ms (min %.3f), %s launches, peak %.1f MiB (%.1f above resident)"
+              % (name, res["median_ms"][name], res["min_ms"][name], launches[name], peak[name]["max_allocated_mib"],
+                 peak[name]["above_resident_mib"]), flush=True)
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scenes", type=int, default=10)
@@ -45,9 +122,13 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mma", default=None)
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--others", action="store_true")
     args = ap.parse_args()
     if args.mma:
         ops.set_mma(args.mma)
+    if args.train:
+        return train_mode(args)
     torch.manual_seed(0)
     net = R.Net(R.config).cuda().eval()
     data = make_batch(args.scenes, args.agents, [int(v) for v in args.roads.split(",")])

@@ -1145,6 +1145,68 @@ int lgcn_roi_loss_bwd(const float *logits, const float *goals, const float *traj
                       int64_t n_agt, int n_mod, int n_t, float reg_coef, const int32_t *sel, const float *g_cls,
                       const float *g_goal, const float *g_traj, float *dlogits, float *dgoals, float *dtrajs, void *stream);
 
+/*
+ * Lane-RoI extraction of the fork (reference data_lrcnn.py:620-844, generate_lane_roi) for a BATCH of scenes: the
+ * per-agent lane search, the nodes of every RoI and the 14 induced relations, in four calls that share one struct.
+ * Integer and exact-fp32 kernels (no FMA, correctly rounded sqrt): index arrays, feats, agent_feat and the distances
+ * equal the reference's; lane lengths and step sums are added in numpy's order (pairwise_sum: 8 accumulators; one piece
+ * for lanes of more than 128 nodes, where numpy splits), atan2f is the device's.
+ *
+ * Inputs (device unless said): the scenes' arrays concatenated, indices LOCAL to their scene, int32.
+ *   off_host / off_dev: one table of int32 offsets, the same on the host (validated) and on the device (read by kernels):
+ *       node_off, lane_off, agent_off, slot_off, suc_off, pre_off: n_scenes + 1 entries each, from 0 to n_nodes, n_lanes,
+ *       n_agents, n_slots, n_suc, n_pre; slot_off[s + 1] - slot_off[s] = agents(s) * lanes(s);
+ *       then edge_off [14 * n_scenes + 1]: segment r * n_scenes + s holds relation r (pre 0..5, suc 0..5, left, right)
+ *       of scene s in edge_u / edge_v, from 0 to n_edges.
+ *   ctrs, feats, turn [n_nodes,2], control, intersect [n_nodes], lane_idcs [n_nodes];  a_ctrs [n_agents,2], a_feats,
+ *   a_obs [n_agents,20,2] (steps and positions, 20 observed steps);  suc_pairs [n_suc,2], pre_pairs [n_pre,2] lane pairs.
+ *   ws: lgcn_roi_ws_elems(n_nodes, n_lanes, n_edges, n_slots, n_agents) int32 (negative: LGCN_EINVAL for a negative size,
+ *       LGCN_ESHAPE beyond 2^31 - 1 elements), kept from lgcn_roi_search to lgcn_roi_edge_fill.
+ *
+ * lgcn_roi_search (1 memset + 8 launches): lanes -> nodes tables, the relations as CSR rows, then one workgroup per agent:
+ *   speed (0: dropped), anchor node (closest node within pi/4 of the agent's heading, else pi/2, ties: smaller index; none:
+ *   dropped), level-by-level lane search over suc_pairs (horizon v * 3 + horizon_buffer) and pre_pairs (v * 2 + ...), left /
+ *   right closure, lane order (search order with every lane at its first occurrence when the closure adds none, else
+ *   ascending).  agent_nodes [n_agents + 1]: the RoI's node count, 0 for a dropped agent (speed 0, no anchor, < 6 nodes,
+ *   neither a pre[0] nor a suc[0] edge); the last word is a status: bit 0 = an index out of range was skipped, bit 1 = a
+ *   lane search hit lgcn_roi_max_levels() (a cycle of zero-length lanes).  agent_vel [n_agents].
+ * lgcn_roi_nodes (1 launch): roi_agent [n_rois], roi_base [n_rois + 1] (node offset of every kept RoI, from the counts
+ *   above) -> node_mask [n_out_nodes] int64, out_feats [n_out_nodes,8], agent_feat [n_rois,80], near [n_out_nodes]
+ *   (distance to the agent < 5).
+ * lgcn_roi_edge_count (1 launch): edge_cnt [n_rois * 15]: per RoI the edges of the 14 induced relations, then |a2m|.
+ * lgcn_roi_edge_fill (1 launch): edge_base [n_rois * 15] (exclusive sums of edge_cnt: relations into out_u / out_v
+ *   [n_out_edges] int64, a2m into a2m_v [n_out_a2m] int32) -> local (u, v), sorted by (u, v), each pair once.
+ * No result depends on the arrival order of an atomic: the same inputs give the same bytes.
+ *
+ * Every call first checks, launching nothing on failure: NULL struct or required pointer, negative size, a table that does
+ * not start at 0, decreases or ends elsewhere than its total (LGCN_EINVAL); misaligned pointers (LGCN_EALIGN, 16 bytes for
+ * ws and the float2 arrays); a scene of more than lgcn_roi_max_lanes() = 4096 lanes, or a workspace beyond
+ * 2^31 - 1 elements (LGCN_ESHAPE).  An empty batch (no agent / no RoI) returns LGCN_OK without a launch.
+ */
+typedef struct {
+    int32_t n_scenes, n_agents, n_nodes, n_lanes, n_edges, n_slots, n_suc, n_pre;
+    float horizon_buffer; int32_t n_rois;
+    int32_t n_out_nodes, n_out_edges, n_out_a2m, pad_;
+    const int32_t *off_host, *off_dev;
+    const float *ctrs, *feats, *turn, *control, *intersect;
+    const int32_t *lane_idcs;
+    const float *a_ctrs, *a_feats, *a_obs;
+    const int32_t *suc_pairs, *pre_pairs, *edge_u, *edge_v;
+    int32_t *ws;
+    int32_t *agent_nodes; float *agent_vel;                       /* lgcn_roi_search */
+    const int32_t *roi_agent, *roi_base;                          /* lgcn_roi_nodes .. */
+    int64_t *node_mask; float *out_feats, *agent_feat; int32_t *near;
+    int32_t *edge_cnt;                                            /* lgcn_roi_edge_count */
+    const int32_t *edge_base; int64_t *out_u, *out_v; int32_t *a2m_v;   /* lgcn_roi_edge_fill */
+} lgcn_roi_t;
+int lgcn_roi_max_lanes(void);
+int lgcn_roi_max_levels(void);
+int64_t lgcn_roi_ws_elems(int64_t n_nodes, int64_t n_lanes, int64_t n_edges, int64_t n_slots, int64_t n_agents);
+int lgcn_roi_search(const lgcn_roi_t *p, void *stream);
+int lgcn_roi_nodes(const lgcn_roi_t *p, void *stream);
+int lgcn_roi_edge_count(const lgcn_roi_t *p, void *stream);
+int lgcn_roi_edge_fill(const lgcn_roi_t *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,26 @@ class OptTensor(C.Structure):     # lgcn_opt_tensor_t
     _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64)]
 
 
+class Roi(C.Structure):           # lgcn_roi_t
+    _fields_ = [
+        ("n_scenes", C.c_int32), ("n_agents", C.c_int32), ("n_nodes", C.c_int32), ("n_lanes", C.c_int32),
+        ("n_edges", C.c_int32), ("n_slots", C.c_int32), ("n_suc", C.c_int32), ("n_pre", C.c_int32),
+        ("horizon_buffer", C.c_float), ("n_rois", C.c_int32),
+        ("n_out_nodes", C.c_int32), ("n_out_edges", C.c_int32), ("n_out_a2m", C.c_int32), ("pad_", C.c_int32),
+        ("off_host", C.c_void_p), ("off_dev", C.c_void_p),
+        ("ctrs", C.c_void_p), ("feats", C.c_void_p), ("turn", C.c_void_p), ("control", C.c_void_p), ("intersect", C.c_void_p),
+        ("lane_idcs", C.c_void_p),
+        ("a_ctrs", C.c_void_p), ("a_feats", C.c_void_p), ("a_obs", C.c_void_p),
+        ("suc_pairs", C.c_void_p), ("pre_pairs", C.c_void_p), ("edge_u", C.c_void_p), ("edge_v", C.c_void_p),
+        ("ws", C.c_void_p),
+        ("agent_nodes", C.c_void_p), ("agent_vel", C.c_void_p),
+        ("roi_agent", C.c_void_p), ("roi_base", C.c_void_p),
+        ("node_mask", C.c_void_p), ("out_feats", C.c_void_p), ("agent_feat", C.c_void_p), ("near", C.c_void_p),
+        ("edge_cnt", C.c_void_p),
+        ("edge_base", C.c_void_p), ("out_u", C.c_void_p), ("out_v", C.c_void_p), ("a2m_v", C.c_void_p),
+    ]
+
+
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 OPT_KINDS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}
 
@@ -233,6 +253,13 @@ SIGNATURES = {
     "lgcn_goal_decode_bwd": (C.c_int, [_P, _P, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "lgcn_roi_loss_fwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P]),
     "lgcn_roi_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "lgcn_roi_max_lanes": (C.c_int, []),
+    "lgcn_roi_max_levels": (C.c_int, []),
+    "lgcn_roi_ws_elems": (C.c_int64, [_L, _L, _L, _L, _L]),
+    "lgcn_roi_search": (C.c_int, [C.POINTER(Roi), _P]),
+    "lgcn_roi_nodes": (C.c_int, [C.POINTER(Roi), _P]),
+    "lgcn_roi_edge_count": (C.c_int, [C.POINTER(Roi), _P]),
+    "lgcn_roi_edge_fill": (C.c_int, [C.POINTER(Roi), _P]),
 }
 
 _lib = None

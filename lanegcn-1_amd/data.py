@@ -178,6 +178,46 @@ def synth_scene(rng, roads, n_actors=50, meta_p=0.3, idx_dtype=np.int64, num_sca
     )
 
 
+def lane_pairs(edges, lane_idcs):
+    """[P,2] (lane of u, lane of v) of the node edges that cross lanes, each pair once, sorted: the reference's
+    pre_pairs / suc_pairs read off pre[0] / suc[0]."""
+    lane_idcs = np.asarray(lane_idcs, np.int64)
+    lu, lv = lane_idcs[np.asarray(edges["u"], np.int64)], lane_idcs[np.asarray(edges["v"], np.int64)]
+    cross = lu != lv
+    return np.unique(np.stack([lu[cross], lv[cross]], 1), axis=0).reshape(-1, 2).astype(np.int64)
+
+
+def synth_lane_scene(rng, roads, n_actors=20, p_stand=0.15, p_turned=0.1, meta_p=0.3, idx_dtype=np.int64,
+                     num_scales=NUM_SCALES):
+    """A synth_scene that data_lrcnn.generate_lane_roi can read: graph["pre_pairs"] / ["suc_pairs"] (lane_pairs of
+    pre[0] / suc[0]), agents that drive along the heading of a lane node at a drawn speed of 1..15 m/s (a share p_stand
+    stands still, a share p_turned heads anywhere), and obs_trajs [A,20,3], the observed positions that end at ctrs."""
+    scene = synth_scene(rng, roads, n_actors, meta_p, idx_dtype, num_scales)
+    graph = scene["graph"]
+    graph["pre_pairs"] = lane_pairs(graph["pre"][0], graph["lane_idcs"])
+    graph["suc_pairs"] = lane_pairs(graph["suc"][0], graph["lane_idcs"])
+    a, N = int(n_actors), int(graph["num_nodes"])
+    pick = rng.integers(0, N, a)
+    d = graph["feats"][pick].astype(np.float64)
+    th = np.arctan2(d[:, 1], d[:, 0]) + rng.normal(0.0, 0.2, a)
+    turned = rng.random(a) < p_turned
+    th[turned] = rng.uniform(0.0, 2.0 * np.pi, int(turned.sum()))
+    speed = rng.uniform(1.0, 15.0, a)
+    speed[rng.random(a) < p_stand] = 0.0
+    steps = 0.1 * speed[:, None, None] * np.stack([np.cos(th), np.sin(th)], 1)[:, None, :] * np.ones((1, 20, 1))
+    steps = steps + rng.normal(0.0, 0.02, (a, 20, 2)) * (speed > 0)[:, None, None]
+    steps[:, 0] = 0.0                                                         # the first step has no predecessor
+    ctrs = (graph["ctrs"][pick] + rng.normal(0.0, 1.0, (a, 2))).astype(np.float32)
+    after = np.cumsum(steps[:, ::-1], 1)[:, ::-1] - steps                     # sum of the steps after t
+    pos = ctrs[:, None, :].astype(np.float64) - after
+    ones = np.ones((a, 20, 1))
+    scene["feats"] = np.concatenate([steps, ones], 2).astype(np.float32)
+    scene["ctrs"] = ctrs
+    scene["obs_trajs"] = np.concatenate([pos, ones], 2).astype(np.float32)
+    scene["gt_preds"] = (ctrs[:, None, :] + np.cumsum(np.repeat(steps[:, -1:], 30, 1), 1)).astype(np.float32)
+    return scene
+
+
 def synth_batch(kind="S2", seed=0, n_scenes=None, idx_dtype=np.int64):
     """Canonical workloads of SURVEY.md 8(d): S0 (1 scene, 648 nodes), S1 (one merged graph,
     10,008 nodes), S2 (32 scenes x 324 nodes, 50 actors each).  Returns a list of scene dicts."""
@@ -215,8 +255,8 @@ def synth_subgraphs(scene, horizon_time=3.0, horizon_buffer=20.0, max_rois=None,
     numbering): feats [n,8] = (ctr, direction, turn, control, intersect), agent_feat [80] = the observed positions and
     steps, agent_vel, a2m (u = 0, v = the RoI's nodes within `near` metres of the agent), num_nodes, node_mask.  Agents
     that do not move, whose RoI has fewer than min_nodes nodes or neither a pre0 nor a suc0 edge get none, as in the
-    reference.  A generator for tests and benchmarks: the reference's directional lane search (DFS over dense [N,N]
-    masks) is not ported."""
+    reference.  A generator for tests and benchmarks: the reference's directional lane search is
+    data_lrcnn.generate_lane_roi (on the device, for scenes that carry lane pairs: synth_lane_scene)."""
     graph = scene["graph"]
     a_feats, a_ctrs = np.asarray(scene["feats"]), np.asarray(scene["ctrs"])
     if "obs_trajs" not in scene:

@@ -1989,3 +1989,108 @@ def roi_loss_bwd(logits, goals, trajs, gt, has, reg_coef, sel, g_cls, g_goal, g_
                                   _ptr(sel), _ptr(gs[0]), _ptr(gs[1]), _ptr(gs[2]), _ptr(dlogits), _ptr(dgoals), _ptr(dtrajs),
                                   _stream()), "lgcn_roi_loss_bwd")
     return dlogits, dgoals, dtrajs
+
+
+# ------------------------------------------------------------------ lane-RoI extraction (data_lrcnn.generate_lane_roi)
+ROI_REL = 14
+ROI_STATUS_RANGE, ROI_STATUS_LEVELS = 1, 2
+
+
+def roi_max_lanes() -> int:
+    """Largest lane count of one scene the lane-RoI kernels take (LGCN_ESHAPE above it)."""
+    return int(L.load().lgcn_roi_max_lanes())
+
+
+class RoiJob:
+    """One batch's lgcn_roi_t with the tensors it points to.  ``t``: the concatenated inputs on the device -- ctrs, feats,
+    turn [N,2] fp32, control, intersect [N] fp32, lane_idcs [N] int32, a_ctrs [A,2], a_feats, a_obs [A,20,2] fp32,
+    suc_pairs, pre_pairs [P,2] int32, edge_u, edge_v [E] int32 (scene-local) -- and ``off``: the host int32 offset table
+    of include/lgcn.h.  roi_search / roi_nodes / roi_edge_count / roi_edge_fill fill it stage by stage."""
+
+    def __init__(self, t: dict, off, horizon_buffer: float):
+        import numpy as np
+        self.off = np.ascontiguousarray(off, np.int32)
+        S = (len(self.off) - 7) // (ROI_REL + 6)
+        if S < 0 or len(self.off) != 6 * (S + 1) + ROI_REL * S + 1:
+            raise L.LgcnError("roi: the offset table must hold 6 (S + 1) + 14 S + 1 entries, got %d" % len(self.off))
+        kinds = dict(ctrs=torch.float32, feats=torch.float32, turn=torch.float32, control=torch.float32,
+                     intersect=torch.float32, lane_idcs=torch.int32, a_ctrs=torch.float32, a_feats=torch.float32,
+                     a_obs=torch.float32, suc_pairs=torch.int32, pre_pairs=torch.int32, edge_u=torch.int32, edge_v=torch.int32)
+        self.t = {k: _dev(t[k], dt, "roi " + k) for k, dt in kinds.items()}
+        N, A_ = self.t["lane_idcs"].numel(), self.t["a_ctrs"].shape[0]
+        shapes = dict(ctrs=(N, 2), feats=(N, 2), turn=(N, 2), control=(N,), intersect=(N,), a_feats=(A_, 20, 2), a_obs=(A_, 20, 2),
+                      edge_v=tuple(self.t["edge_u"].shape))
+        for k, shp in shapes.items():
+            if tuple(self.t[k].shape) != shp:
+                raise L.LgcnError("roi: %s must be %s, got %s" % (k, shp, tuple(self.t[k].shape)))
+        self.S, self.N, self.A = S, N, A_
+        dev = self.t["ctrs"].device
+        p = self.p = L.Roi()
+        p.n_scenes, p.n_agents, p.n_nodes = S, A_, N
+        p.n_lanes, p.n_slots = (int(self.off[2 * S + 1]), int(self.off[4 * S + 3])) if S else (0, 0)
+        p.n_edges, p.n_suc, p.n_pre = self.t["edge_u"].numel(), self.t["suc_pairs"].shape[0], self.t["pre_pairs"].shape[0]
+        p.horizon_buffer = float(horizon_buffer)
+        p.off_host = self.off.ctypes.data
+        self.off_dev = torch.from_numpy(self.off).to(dev)
+        p.off_dev = self.off_dev.data_ptr()
+        for k, v in self.t.items():
+            setattr(p, k, v.data_ptr() if v.numel() else None)
+        n_ws = L.load().lgcn_roi_ws_elems(N, p.n_lanes, p.n_edges, p.n_slots, A_)
+        if n_ws < 0:
+            L.check(int(n_ws), "lgcn_roi_ws_elems")
+        self.ws = torch.empty(int(n_ws), dtype=torch.int32, device=dev)
+        # one buffer, one read-back: node counts [A], the status word, then the speeds [A] (fp32 bits)
+        self.agent_out = torch.zeros(2 * A_ + 1, dtype=torch.int32, device=dev)
+        self.agent_nodes, self.agent_vel = self.agent_out[:A_ + 1], self.agent_out[A_ + 1:].view(torch.float32)
+        p.ws, p.agent_nodes, p.agent_vel = self.ws.data_ptr(), self.agent_nodes.data_ptr(), self.agent_vel.data_ptr()
+
+
+def roi_search(job: RoiJob):
+    """lgcn_roi_search: fills job.agent_nodes [A + 1] (node count of every agent's RoI, 0 = dropped; last word = status)
+    and job.agent_vel [A]."""
+    L.check(L.load().lgcn_roi_search(C.byref(job.p), _stream()), "lgcn_roi_search")
+    return job.agent_nodes, job.agent_vel
+
+
+def roi_nodes(job: RoiJob, roi_agent: torch.Tensor, roi_base: torch.Tensor, n_out_nodes: int):
+    """lgcn_roi_nodes: (node_mask [T] int64, feats [T,8], agent_feat [R,80]) of the kept RoIs roi_agent [R] int32 whose
+    nodes start at roi_base [R + 1] int32."""
+    p, dev = job.p, job.ws.device
+    job.roi_agent, job.roi_base = _dev(roi_agent, torch.int32, "roi_agent"), _dev(roi_base, torch.int32, "roi_base")
+    R, T = job.roi_agent.numel(), int(n_out_nodes)
+    if job.roi_base.numel() != R + 1:
+        raise L.LgcnError("roi_nodes: roi_base must hold R + 1 entries")
+    job.node_mask = torch.empty(T, dtype=torch.int64, device=dev)
+    job.out_feats = torch.empty((T, 8), dtype=torch.float32, device=dev)
+    job.agent_feat = torch.empty((R, 80), dtype=torch.float32, device=dev)
+    job.near = torch.empty(T, dtype=torch.int32, device=dev)
+    p.n_rois, p.n_out_nodes = R, T
+    p.roi_agent, p.roi_base = job.roi_agent.data_ptr(), job.roi_base.data_ptr()
+    p.node_mask, p.out_feats, p.agent_feat, p.near = (job.node_mask.data_ptr(), job.out_feats.data_ptr(),
+                                                      job.agent_feat.data_ptr(), job.near.data_ptr())
+    L.check(L.load().lgcn_roi_nodes(C.byref(p), _stream()), "lgcn_roi_nodes")
+    return job.node_mask, job.out_feats, job.agent_feat
+
+
+def roi_edge_count(job: RoiJob) -> torch.Tensor:
+    """lgcn_roi_edge_count: [R, 15] int32 -- per RoI the edge counts of the 14 induced relations, then |a2m|."""
+    job.edge_cnt = torch.empty((job.p.n_rois, ROI_REL + 1), dtype=torch.int32, device=job.ws.device)
+    job.p.edge_cnt = job.edge_cnt.data_ptr()
+    L.check(L.load().lgcn_roi_edge_count(C.byref(job.p), _stream()), "lgcn_roi_edge_count")
+    return job.edge_cnt
+
+
+def roi_edge_fill(job: RoiJob, edge_base: torch.Tensor, n_out_edges: int, n_out_a2m: int):
+    """lgcn_roi_edge_fill: (u, v [n_out_edges] int64, a2m_v [n_out_a2m] int32) at the offsets edge_base [R, 15] int32."""
+    p, dev = job.p, job.ws.device
+    job.edge_base = _dev(edge_base, torch.int32, "edge_base")
+    if job.edge_base.numel() != p.n_rois * (ROI_REL + 1):
+        raise L.LgcnError("roi_edge_fill: edge_base must be [R, 15]")
+    job.out_u = torch.empty(int(n_out_edges), dtype=torch.int64, device=dev)
+    job.out_v = torch.empty(int(n_out_edges), dtype=torch.int64, device=dev)
+    job.a2m_v = torch.empty(int(n_out_a2m), dtype=torch.int32, device=dev)
+    p.n_out_edges, p.n_out_a2m = int(n_out_edges), int(n_out_a2m)
+    p.edge_base, p.out_u, p.out_v, p.a2m_v = (job.edge_base.data_ptr(), job.out_u.data_ptr(), job.out_v.data_ptr(),
+                                              job.a2m_v.data_ptr())
+    L.check(L.load().lgcn_roi_edge_fill(C.byref(p), _stream()), "lgcn_roi_edge_fill")
+    return job.out_u, job.out_v, job.a2m_v

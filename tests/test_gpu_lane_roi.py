@@ -1,0 +1,139 @@
+"""GPU: data_lrcnn.generate_lane_roi / generate_lane_roi_batch (csrc/lgcn_roi.hip) against the reference's recorded
+output (tests/golden/lane_roi_b4.npz) and, on random topologies, against tests/lane_roi_model.py.  Index arrays, feats,
+agent_feat and dtypes are compared exactly, agent_vel to 1e-6; agents whose decisions hang on rounding
+(lane_roi_model.on_edge) are left out of the random comparison (at most 10 % per trial: test_lane_roi_model_host.py)."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import lanegcn_amd  # noqa: F401
+import lane_roi_cases as C
+import lane_roi_model as M
+from lanegcn_amd import data as gen
+from lanegcn_amd import data_lrcnn as D
+from lanegcn_amd._lib import LgcnError
+
+pytestmark = pytest.mark.gpu
+VEL_RTOL = 1e-6
+
+
+def _out(scene):
+    return {"subgraphs": scene["subgraphs"], "valid_agent_ids": scene["valid_agent_ids"]}
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    return C.load_fixture()
+
+
+def test_fixture_parity_per_scene_and_batched(fixture):
+    scenes, want = fixture
+    for b, s in enumerate(scenes):
+        got = D.generate_lane_roi(copy.deepcopy(s))
+        assert got["valid_agent_ids"].dtype == np.int16
+        C.assert_same(_out(got), want[b], "single%d" % b, VEL_RTOL)
+    for b, got in enumerate(D.generate_lane_roi_batch(copy.deepcopy(scenes))):
+        C.assert_same(_out(got), want[b], "batch%d" % b, VEL_RTOL)
+    # tensor leaves, on the host and on the device, give the same RoIs
+    for move in (lambda t: t, lambda t: t.cuda()):
+        tens = [to_tensors(s, move) for s in copy.deepcopy(scenes)]
+        for b, got in enumerate(D.generate_lane_roi_batch(tens)):
+            C.assert_same(_out(got), want[b], "tensor%d" % b, VEL_RTOL)
+
+
+def to_tensors(x, move):
+    """numpy leaves -> tensors through `move`, recursively."""
+    if isinstance(x, dict):
+        return {k: to_tensors(v, move) for k, v in x.items()}
+    if isinstance(x, list):
+        return [to_tensors(v, move) for v in x]
+    return move(torch.from_numpy(x)) if isinstance(x, np.ndarray) and x.ndim else x
+
+
+@pytest.mark.parametrize("seed", C.TRIAL_SEEDS)
+def test_random_topologies_against_the_model(seed):
+    scenes = C.trial(seed)
+    got = D.generate_lane_roi_batch(copy.deepcopy(scenes))
+    for b, s in enumerate(scenes):
+        want = M.generate_lane_roi(copy.deepcopy(s))
+        skip = M.edge_agents(s)
+        C.assert_same(C.drop_agents(_out(got[b]), skip), C.drop_agents(_out(want), skip), "seed%d/scene%d" % (seed, b), VEL_RTOL)
+
+
+def test_repeatable_and_device_leaves():
+    from lanegcn_amd import lanercnn as R
+    scenes = C.trial(C.TRIAL_SEEDS[4]) + C.trial(C.TRIAL_SEEDS[2])[2:]
+    first = D.generate_lane_roi_batch(copy.deepcopy(scenes))
+    again = D.generate_lane_roi_batch(copy.deepcopy(scenes))
+    dev = D.generate_lane_roi_batch(copy.deepcopy(scenes), device=True)
+    for a, b, d in zip(first, again, dev):
+        C.assert_same(_out(b), _out(a), "again")
+        assert len(d["subgraphs"]) == len(a["subgraphs"])
+        for sd, sa in zip(d["subgraphs"], a["subgraphs"]):
+            assert isinstance(sd["num_nodes"], int) and isinstance(sd["agent_vel"], np.float32)
+            leaves = [sd["node_mask"], sd["feats"], sd["agent_feat"], sd["a2m"]["u"], sd["a2m"]["v"], sd["left"]["u"], sd["right"]["v"]]
+            leaves += [e[k] for k1 in ("pre", "suc") for e in sd[k1] for k in "uv"]
+            assert all(torch.is_tensor(x) and x.is_cuda for x in leaves)
+            host = to_tensors(sd, lambda t: t)      # no numpy leaf in it: unchanged
+            as_np = lambda x: x.cpu().numpy() if torch.is_tensor(x) else x
+            conv = lambda x: ({k: conv(v) for k, v in x.items()} if isinstance(x, dict) else
+                              [conv(v) for v in x] if isinstance(x, list) else as_np(x))
+            C.assert_same(conv(host), sa, "device")
+    keep = [i for i, s in enumerate(first) if len(s["subgraphs"])]
+    ga = R.subgraph_gather([dev[i]["subgraphs"] for i in keep])
+    gb = R.subgraph_gather([first[i]["subgraphs"] for i in keep])
+    assert set(ga) == set(gb)
+
+    def same(x, y, path):
+        if isinstance(x, dict):
+            assert set(x) == set(y), path
+            for k in x:
+                same(x[k], y[k], path + "/" + str(k))
+        elif isinstance(x, (list, tuple)):
+            assert len(x) == len(y), path
+            for i, (p, q) in enumerate(zip(x, y)):
+                same(p, q, "%s/%d" % (path, i))
+        elif torch.is_tensor(x):
+            assert x.dtype == y.dtype and x.device == y.device and torch.equal(x, y), path
+        else:
+            assert type(x) is type(y) and x == y, (path, x, y)
+    same(ga, gb, "gather")
+
+
+def test_net_forward_on_device_rois_equals_forward_on_model_rois():
+    """Net.forward (no_grad, seeded weights) on RoIs from generate_lane_roi_batch(device=True) equals, bit for bit, the
+    forward on RoIs the model builds on the host: the inputs are identical."""
+    from lanegcn_amd import lanercnn as R
+    from oracle.lanercnn_oracle import seeded_state
+    rng = np.random.default_rng(3)
+    scenes = [gen.synth_lane_scene(rng, [3, 2], 5, p_stand=0.0, p_turned=0.0), gen.synth_lane_scene(rng, [4], 4, p_stand=0.0, p_turned=0.0)]
+    assert not any(M.edge_agents(s) for s in scenes)
+    on_dev = D.generate_lane_roi_batch(copy.deepcopy(scenes), device=True)
+    on_host = [M.generate_lane_roi(copy.deepcopy(s)) for s in scenes]
+    assert all(len(s["subgraphs"]) for s in on_host)
+    net = R.Net(R.config).eval()
+    net.load_state_dict(seeded_state([(k, tuple(v.shape)) for k, v in net.state_dict().items()], 7))
+    net = net.cuda()
+    outs = []
+    with torch.no_grad():
+        for batch in (on_dev, on_host):
+            out = net(gen.collate_fn(batch))
+            outs.append({k: [x.clone() for x in v] if isinstance(v, (list, tuple)) else v.clone() for k, v in out.items()})
+    assert set(outs[0]) == set(outs[1]) and len(outs[0]) >= 3
+    for k in outs[0]:
+        a, b = outs[0][k], outs[1][k]
+        pairs = zip(a, b) if isinstance(a, list) else [(a, b)]
+        assert all(torch.equal(x, y) for x, y in pairs), k
+
+
+def test_a_scene_above_the_lane_cap_is_refused_before_anything_runs():
+    """An argument check: 4097 lanes of one node.  Nothing is uploaded or launched (the scene's other leaves are not even
+    read: they are placeholders that any use would trip over)."""
+    n = 4097
+    scene = {"graph": {"lane_idcs": np.arange(n, dtype=np.int64)}, "ctrs": None, "feats": None, "obs_trajs": None}
+    with pytest.raises(LgcnError, match="4096"):
+        D.generate_lane_roi_batch([scene])
+    with pytest.raises(LgcnError, match="4096"):
+        D.generate_lane_roi(scene)

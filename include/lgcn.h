@@ -1207,6 +1207,60 @@ int lgcn_roi_nodes(const lgcn_roi_t *p, void *stream);
 int lgcn_roi_edge_count(const lgcn_roi_t *p, void *stream);
 int lgcn_roi_edge_fill(const lgcn_roi_t *p, void *stream);
 
+/*
+ * Device-resident scene store: the arrays of a flat store (lanegcn_amd/flatfile.py: S scenes, concatenated) stay in
+ * device memory, and lgcn_store_gather cuts the FlatBatch and the actor-side extras of any B picked scenes out of them
+ * in ONE launch.  Pure data movement: every output equals what FlatSceneFile.batch builds on the host, byte for byte.
+ *
+ * lgcn_store_t (device pointers, all read-only): node_ctrs, node_feats, turn [n_nodes,2], control, intersect [n_nodes],
+ *   actor_ctrs [n_actors,2], actor_feats [n_actors,20,3], rot [n_scenes,2,2], orig [n_scenes,2], gt_preds
+ *   [n_actors,30,2] fp32; has_preds [n_actors,30] bytes; edge_u, edge_v [n_edges] int32, scene-local.  gt_preds and
+ *   has_preds: both or neither (NULL = the store has none; the batch's pointers for them are then not used).
+ *
+ * lgcn_store_batch_t: B = n_scenes picked scenes (repeats allowed), R = n_rel relations, G = 2 R B index segments;
+ *   segment (r * 2 + w) * B + j holds relation r's u (w = 0) or v (w = 1) of the j-th picked scene.
+ *   tab_host / tab_dev: the per-batch table, lgcn_store_table_elems(B, R) = 5 B + 2 G + 3 int64, the same on the host
+ *   (validated) and on the device (read by the kernel):
+ *       node_off [B + 1], actor_off [B + 1]   prefix sums of the OUTPUT rows, from 0 to n_nodes / n_actors
+ *       node_src [B], actor_src [B]           first node / actor row of the picked scene in the store
+ *       scene [B]                             the picked scene (rot, orig)
+ *       seg_off [G + 1]                       prefix sums of idx_local, from 0 to n_elem
+ *       seg_src [G]                           first element of the segment in edge_u / edge_v
+ *   Outputs (device): node_ctrs, node_feats, turn [n_nodes,2], control, intersect [n_nodes], actor_ctrs [n_actors,2];
+ *   node_off, actor_off [B + 1] int32; idx_local [n_elem], seg_off [G + 1], seg_base [G] int64 (seg_base = node_off of
+ *   the segment's scene); actor_feats [n_actors,3,20] (transposed), rot [n_actors,2,2], orig [n_actors,2] (the scene's,
+ *   per actor), gt_preds [n_actors,30,2], has_preds [n_actors,30].
+ *
+ * One launch over output elements; a thread finds its scene / segment by binary search in the table, so B and G are not
+ * bounded by a wave or by LDS.  No atomics, no allocation, no host synchronisation.
+ *
+ * Checked before anything is launched: NULL struct, a negative size, a NULL pointer next to a non-zero size, only one
+ * of gt_preds / has_preds, a prefix sum that does not start at 0, decreases or ends elsewhere than its total, a source
+ * run or a scene outside the store (LGCN_EINVAL); n_nodes, n_elem, 60 n_actors, G or the table beyond 2^31 - 1
+ * (LGCN_ESHAPE); pointers not aligned to 16 bytes ([.,2] arrays, rot, orig, the int64 arrays, tab_dev), 8 bytes (tab_host)
+ * or 4 bytes (the rest but has_preds) (LGCN_EALIGN).  n_scenes == 0 with all totals 0 returns LGCN_OK without a launch.
+ * lgcn_store_table_elems: LGCN_EINVAL for a negative argument, LGCN_ESHAPE beyond 2^31 - 1 elements.
+ */
+typedef struct {
+    int64_t n_scenes, n_nodes, n_actors, n_edges;
+    const float *node_ctrs, *node_feats, *turn, *control, *intersect;
+    const float *actor_ctrs, *actor_feats, *rot, *orig, *gt_preds;
+    const unsigned char *has_preds;
+    const int32_t *edge_u, *edge_v;
+} lgcn_store_t;
+typedef struct {
+    int32_t n_scenes, n_rel;
+    int64_t n_nodes, n_actors, n_elem;
+    const int64_t *tab_host, *tab_dev;
+    float *node_ctrs, *node_feats, *turn, *control, *intersect, *actor_ctrs;
+    int32_t *node_off, *actor_off;
+    int64_t *idx_local, *seg_off, *seg_base;
+    float *actor_feats, *rot, *orig, *gt_preds;
+    unsigned char *has_preds;
+} lgcn_store_batch_t;
+int64_t lgcn_store_table_elems(int64_t n_scenes, int64_t n_rel);
+int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

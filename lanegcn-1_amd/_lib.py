@@ -160,6 +160,29 @@ class Roi(C.Structure):           # lgcn_roi_t
     ]
 
 
+class Store(C.Structure):         # lgcn_store_t
+    _fields_ = [
+        ("n_scenes", C.c_int64), ("n_nodes", C.c_int64), ("n_actors", C.c_int64), ("n_edges", C.c_int64),
+        ("node_ctrs", C.c_void_p), ("node_feats", C.c_void_p), ("turn", C.c_void_p), ("control", C.c_void_p),
+        ("intersect", C.c_void_p),
+        ("actor_ctrs", C.c_void_p), ("actor_feats", C.c_void_p), ("rot", C.c_void_p), ("orig", C.c_void_p),
+        ("gt_preds", C.c_void_p), ("has_preds", C.c_void_p), ("edge_u", C.c_void_p), ("edge_v", C.c_void_p),
+    ]
+
+
+class StoreBatch(C.Structure):    # lgcn_store_batch_t
+    _fields_ = [
+        ("n_scenes", C.c_int32), ("n_rel", C.c_int32), ("n_nodes", C.c_int64), ("n_actors", C.c_int64), ("n_elem", C.c_int64),
+        ("tab_host", C.c_void_p), ("tab_dev", C.c_void_p),
+        ("node_ctrs", C.c_void_p), ("node_feats", C.c_void_p), ("turn", C.c_void_p), ("control", C.c_void_p),
+        ("intersect", C.c_void_p), ("actor_ctrs", C.c_void_p),
+        ("node_off", C.c_void_p), ("actor_off", C.c_void_p),
+        ("idx_local", C.c_void_p), ("seg_off", C.c_void_p), ("seg_base", C.c_void_p),
+        ("actor_feats", C.c_void_p), ("rot", C.c_void_p), ("orig", C.c_void_p), ("gt_preds", C.c_void_p),
+        ("has_preds", C.c_void_p),
+    ]
+
+
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 OPT_KINDS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}
 
@@ -260,6 +283,8 @@ SIGNATURES = {
     "lgcn_roi_nodes": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_roi_edge_count": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_roi_edge_fill": (C.c_int, [C.POINTER(Roi), _P]),
+    "lgcn_store_table_elems": (C.c_int64, [_L, _L]),
+    "lgcn_store_gather": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
 }
 
 _lib = None

@@ -1,0 +1,206 @@
+// Device-resident scene store (include/lgcn.h, lgcn_store_gather): one launch cuts a FlatBatch and the actor-side
+// extras of any list of scenes out of the arrays of a flat store (lanegcn_amd/flatfile.py) that live in HBM.
+//
+// Pure data movement.  The grid is laid over OUTPUT elements, in five block ranges (one per kind of item); a thread
+// finds the picked scene / index segment of its item by binary search in the per-batch table, so neither the number
+// of scenes nor the number of segments is bounded by a wave or an LDS array.  Every source run is contiguous per scene
+// and threads of a wave hold consecutive items: reads and writes are coalesced but for the run boundaries.
+#include "lgcn_common.hpp"
+
+namespace lgcn {
+
+constexpr int kStoreThreads = 256;
+constexpr int kActorRow = 60;       // floats of one actor in actor_feats [20,3] and in gt_preds [30,2]
+constexpr int kHasRow = 30;         // bytes of one actor in has_preds
+
+// the per-batch table, int64 (B picked scenes, G = 2 * n_rel * B index segments)
+struct StoreTab {
+    const int64_t *node_off, *actor_off;    // [B + 1] prefix sums of the OUTPUT rows
+    const int64_t *node_src, *actor_src;    // [B] first row of the picked scene in the store
+    const int64_t *scene;                   // [B] the picked scene (rot / orig)
+    const int64_t *seg_off;                 // [G + 1] prefix sums of idx_local
+    const int64_t *seg_src;                 // [G] first element of the segment in edge_u / edge_v
+    int64_t total;
+};
+
+__host__ __device__ inline StoreTab store_tab(const int64_t *t, int64_t B, int64_t G) {
+    StoreTab s;
+    s.node_off = t;
+    s.actor_off = s.node_off + B + 1;
+    s.node_src = s.actor_off + B + 1;
+    s.actor_src = s.node_src + B;
+    s.scene = s.actor_src + B;
+    s.seg_off = s.scene + B;
+    s.seg_src = s.seg_off + G + 1;
+    s.total = 5 * B + 2 * G + 3;
+    return s;
+}
+
+// block ranges of the five kinds of item: kind k owns blocks [first[k], first[k + 1])
+struct StoreGrid {
+    uint32_t first[6];
+};
+
+// last k in [0, n) with off[k] <= x, for off[0] = 0 <= x < off[n]: empty runs (off[k] == off[k + 1]) are skipped
+__device__ __forceinline__ int store_find(const int64_t *__restrict__ off, int n, int64_t x) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (off[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store_t s, const lgcn_store_batch_t b,
+                                                                const StoreGrid g) {
+    const int B = b.n_scenes;
+    const int64_t G = 2 * (int64_t)b.n_rel * B;
+    const StoreTab t = store_tab(b.tab_dev, B, G);
+    const uint32_t blk = blockIdx.x;
+    int kind = 0;
+    while (kind < 4 && blk >= g.first[kind + 1]) ++kind;
+    const int64_t i = (int64_t)(blk - g.first[kind]) * kStoreThreads + threadIdx.x;
+
+    if (kind == 0) {                      // one node row: ctrs, feats, turn [.,2], control, intersect
+        if (i >= b.n_nodes) return;
+        const int j = store_find(t.node_off, B, i);
+        const int64_t r = t.node_src[j] + (i - t.node_off[j]);
+        reinterpret_cast<float2 *>(b.node_ctrs)[i] = reinterpret_cast<const float2 *>(s.node_ctrs)[r];
+        reinterpret_cast<float2 *>(b.node_feats)[i] = reinterpret_cast<const float2 *>(s.node_feats)[r];
+        reinterpret_cast<float2 *>(b.turn)[i] = reinterpret_cast<const float2 *>(s.turn)[r];
+        b.control[i] = s.control[r];
+        b.intersect[i] = s.intersect[r];
+    } else if (kind == 1) {               // one actor: ctrs, and the scene's rot / orig
+        if (i >= b.n_actors) return;
+        const int j = store_find(t.actor_off, B, i);
+        const int64_t r = t.actor_src[j] + (i - t.actor_off[j]);
+        const int64_t sc = t.scene[j];
+        reinterpret_cast<float2 *>(b.actor_ctrs)[i] = reinterpret_cast<const float2 *>(s.actor_ctrs)[r];
+        reinterpret_cast<float4 *>(b.rot)[i] = reinterpret_cast<const float4 *>(s.rot)[sc];
+        reinterpret_cast<float2 *>(b.orig)[i] = reinterpret_cast<const float2 *>(s.orig)[sc];
+    } else if (kind == 2) {               // one of an actor's 60 floats: actor_feats [20,3] -> [3,20], gt_preds, has_preds
+        if (i >= b.n_actors * kActorRow) return;
+        const int64_t a = i / kActorRow;
+        const int e = (int)(i - a * kActorRow);
+        const int j = store_find(t.actor_off, B, a);
+        const int64_t r = t.actor_src[j] + (a - t.actor_off[j]);
+        const int c = e / 20, step = e - c * 20;
+        b.actor_feats[i] = s.actor_feats[r * kActorRow + step * 3 + c];
+        if (s.gt_preds != nullptr) {
+            b.gt_preds[i] = s.gt_preds[r * kActorRow + e];
+            if (e < kHasRow) b.has_preds[a * kHasRow + e] = s.has_preds[r * kHasRow + e];
+        }
+    } else if (kind == 3) {               // one element of idx_local, widened
+        if (i >= b.n_elem) return;
+        const int64_t k = store_find(t.seg_off, (int)G, i);
+        const int64_t r = t.seg_src[k] + (i - t.seg_off[k]);
+        const int32_t *src = ((k / B) & 1) ? s.edge_v : s.edge_u;     // segment k = (relation * 2 + u|v) * B + scene
+        b.idx_local[i] = (int64_t)src[r];
+    } else {                              // the offset arrays: node_off, actor_off, seg_off, seg_base
+        int64_t q = i;
+        if (q <= B) { b.node_off[q] = (int32_t)t.node_off[q]; return; }
+        q -= B + 1;
+        if (q <= B) { b.actor_off[q] = (int32_t)t.actor_off[q]; return; }
+        q -= B + 1;
+        if (q <= G) { b.seg_off[q] = t.seg_off[q]; return; }
+        q -= G + 1;
+        if (q < G) b.seg_base[q] = t.node_off[q % B];
+    }
+}
+
+// ------------------------------------------------------------------ host side
+// prefix sums off[0..n] from 0 to total; src[i] + (off[i + 1] - off[i]) inside [0, limit]
+static int store_check_runs(const int64_t *off, const int64_t *src, int64_t n, int64_t total, int64_t limit) {
+    if (off[0] != 0) return LGCN_EINVAL;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = off[i + 1] - off[i];
+        if (len < 0) return LGCN_EINVAL;
+        if (src[i] < 0 || src[i] > limit || len > limit - src[i]) return LGCN_EINVAL;
+    }
+    return off[n] == total ? LGCN_OK : LGCN_EINVAL;
+}
+
+static inline int64_t store_blocks(int64_t n) { return (n + kStoreThreads - 1) / kStoreThreads; }
+
+static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, StoreGrid *grid) {
+    if (s == nullptr || b == nullptr) return LGCN_EINVAL;
+    if (s->n_scenes < 0 || s->n_nodes < 0 || s->n_actors < 0 || s->n_edges < 0) return LGCN_EINVAL;
+    if (b->n_scenes < 0 || b->n_rel < 0 || b->n_nodes < 0 || b->n_actors < 0 || b->n_elem < 0) return LGCN_EINVAL;
+    if (b->n_scenes == 0) return (b->n_nodes | b->n_actors | b->n_elem) ? LGCN_EINVAL : LGCN_OK;
+    const int64_t lim = 0x7fffffff;
+    if (b->n_nodes > lim || b->n_actors > lim / kActorRow || b->n_elem > lim) return LGCN_ESHAPE;
+    const int64_t B = b->n_scenes, G = 2 * (int64_t)b->n_rel * B;
+    if (G > lim || lgcn_store_table_elems(B, b->n_rel) < 0) return LGCN_ESHAPE;
+    if ((s->gt_preds == nullptr) != (s->has_preds == nullptr)) return LGCN_EINVAL;
+    if (s->n_nodes > 0) {
+        LGCN_CHECK_PTR(s->node_ctrs); LGCN_CHECK_PTR(s->node_feats); LGCN_CHECK_PTR(s->turn); LGCN_CHECK_PTR(s->control);
+        LGCN_CHECK_PTR(s->intersect);
+    }
+    if (s->n_actors > 0) { LGCN_CHECK_PTR(s->actor_ctrs); LGCN_CHECK_PTR(s->actor_feats); }
+    if (s->n_scenes > 0) { LGCN_CHECK_PTR(s->rot); LGCN_CHECK_PTR(s->orig); }
+    if (s->n_edges > 0) { LGCN_CHECK_PTR(s->edge_u); LGCN_CHECK_PTR(s->edge_v); }
+    LGCN_CHECK_PTR(b->tab_host); LGCN_CHECK_PTR(b->tab_dev);
+    LGCN_CHECK_PTR(b->node_off); LGCN_CHECK_PTR(b->actor_off); LGCN_CHECK_PTR(b->seg_off);
+    if (G > 0) LGCN_CHECK_PTR(b->seg_base);
+    if (b->n_nodes > 0) {
+        LGCN_CHECK_PTR(b->node_ctrs); LGCN_CHECK_PTR(b->node_feats); LGCN_CHECK_PTR(b->turn); LGCN_CHECK_PTR(b->control);
+        LGCN_CHECK_PTR(b->intersect);
+    }
+    if (b->n_actors > 0) {
+        LGCN_CHECK_PTR(b->actor_ctrs); LGCN_CHECK_PTR(b->actor_feats); LGCN_CHECK_PTR(b->rot); LGCN_CHECK_PTR(b->orig);
+        if (s->gt_preds != nullptr) { LGCN_CHECK_PTR(b->gt_preds); LGCN_CHECK_PTR(b->has_preds); }
+    }
+    if (b->n_elem > 0) LGCN_CHECK_PTR(b->idx_local);
+
+    // the table, read on the host: nothing in it becomes an address before it is known to lie inside the store
+    const StoreTab t = store_tab(b->tab_host, B, G);
+    if (int rc = store_check_runs(t.node_off, t.node_src, B, b->n_nodes, s->n_nodes)) return rc;
+    if (int rc = store_check_runs(t.actor_off, t.actor_src, B, b->n_actors, s->n_actors)) return rc;
+    if (int rc = store_check_runs(t.seg_off, t.seg_src, G, b->n_elem, s->n_edges)) return rc;
+    for (int64_t j = 0; j < B; ++j)
+        if (t.scene[j] < 0 || t.scene[j] >= s->n_scenes) return LGCN_EINVAL;
+
+    const void *quads[] = {s->node_ctrs, s->node_feats, s->turn, s->actor_ctrs, s->rot, s->orig, b->tab_dev, b->node_ctrs,
+                           b->node_feats, b->turn, b->actor_ctrs, b->rot, b->orig, b->idx_local, b->seg_off, b->seg_base};
+    for (const void *q : quads) LGCN_CHECK_ALIGN16(q);
+    const void *words[] = {s->control, s->intersect, s->actor_feats, s->gt_preds, s->edge_u, s->edge_v, b->control,
+                           b->intersect, b->node_off, b->actor_off, b->actor_feats, b->gt_preds};
+    for (const void *q : words)
+        if (reinterpret_cast<uintptr_t>(q) & 3u) return LGCN_EALIGN;
+    if (reinterpret_cast<uintptr_t>(b->tab_host) & 7u) return LGCN_EALIGN;
+
+    const int64_t items[5] = {b->n_nodes, b->n_actors, b->n_actors * kActorRow, b->n_elem, 2 * (B + 1) + 2 * G + 1};
+    int64_t at = 0;
+    for (int k = 0; k < 5; ++k) {
+        grid->first[k] = (uint32_t)at;
+        at += store_blocks(items[k]);
+    }
+    if (at > lim) return LGCN_ESHAPE;
+    grid->first[5] = (uint32_t)at;
+    return LGCN_OK;
+}
+
+}  // namespace lgcn
+
+using namespace lgcn;
+
+extern "C" {
+
+int64_t lgcn_store_table_elems(int64_t n_scenes, int64_t n_rel) {
+    if (n_scenes < 0 || n_rel < 0) return LGCN_EINVAL;
+    const int64_t lim = 0x7fffffff;
+    if (n_scenes > lim / 8 || n_rel > lim / 8) return LGCN_ESHAPE;
+    const int64_t total = store_tab(nullptr, n_scenes, 2 * n_rel * n_scenes).total;
+    return total > lim ? (int64_t)LGCN_ESHAPE : total;
+}
+
+int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream) {
+    StoreGrid grid;
+    if (int rc = store_validate(s, b, &grid)) return rc;
+    if (b->n_scenes == 0) return LGCN_OK;
+    hipLaunchKernelGGL(k_store_gather, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream), *s, *b,
+                       grid);
+    return launch_status();
+}
+
+}  // extern "C"

@@ -12,13 +12,19 @@ Layout (S scenes, R = 2 * num_scales + 2 relations in the order pre0, suc0, ...,
   gt_preds [A,30,2] float32, has_preds [A,30] bool
   edge_off [R, S+1] int64: edges of relation r of scene s are  u[r][edge_off[r,s]:edge_off[r,s+1]]
   edge_u, edge_v [sum E] int32 (scene-local node indices), stored relation-major: rel_off [R+1]
+
+FlatSceneFile cuts a batch on the host.  DeviceSceneStore keeps the arrays in device memory and cuts the same batch
+there with one launch; plan_batch is its host half.
 """
+from dataclasses import dataclass
 from typing import Dict, List, Sequence
 
 import numpy as np
 import torch
 
-from .engine import FlatBatch
+from . import ops
+from ._lib import LgcnError
+from .engine import FlatBatch, _FLAT_ARRAYS
 
 _NODE = ("ctrs", "feats", "turn", "control", "intersect")
 
@@ -131,4 +137,169 @@ class FlatSceneFile:
                   "orig": up(a["orig"][rep]), "sizes": [int(x) for x in n_act]}
         if "gt_preds" in a:
             extras["gt_preds"], extras["has_preds"] = up(a["gt_preds"][arow]), up(a["has_preds"][arow])
+        return fb, extras
+
+
+@dataclass
+class StorePlan:
+    """Everything of one batch that is not an array (the non-array fields of FlatBatch + `sizes`), and the table that
+    lgcn_store_gather reads (include/lgcn.h): int64, node_off [B+1], actor_off [B+1], node_src [B], actor_src [B],
+    scene [B], seg_off [G+1], seg_src [G] with G = 2 * n_rel * B segments ordered (relation, u|v, scene)."""
+    n_scenes: int
+    n_nodes: int
+    n_actors: int
+    num_scales: int
+    rel_slices: List[tuple]
+    n_edges: List[int]
+    cap_a2m: int
+    cap_a2a: int
+    sizes: List[int]
+    n_rel: int
+    n_elem: int
+    table: np.ndarray
+
+    @property
+    def n_seg(self) -> int:
+        return 2 * self.n_rel * self.n_scenes
+
+    @property
+    def node_off(self) -> np.ndarray:
+        return self.table[:self.n_scenes + 1]
+
+    @property
+    def actor_off(self) -> np.ndarray:
+        return self.table[self.n_scenes + 1:2 * self.n_scenes + 2]
+
+    @property
+    def seg_off(self) -> np.ndarray:
+        at = 5 * self.n_scenes + 2
+        return self.table[at:at + self.n_seg + 1]
+
+    @property
+    def seg_base(self) -> np.ndarray:
+        return np.tile(self.node_off[:-1], 2 * self.n_rel)
+
+
+_I32_MAX = 2 ** 31 - 1
+
+
+def plan_batch(node_off, actor_off, edge_off, rel_off, num_scales: int, indices) -> StorePlan:
+    """Host half of DeviceSceneStore.batch: from a store's offset tables (the arrays of the same names in the file) and
+    the picked scenes to a StorePlan.  Vectorised numpy over small tables; needs no GPU."""
+    if len(indices) == 0:
+        raise LgcnError("store: an empty pick has no batch")
+    idx = np.asarray(indices)
+    if idx.ndim != 1 or idx.dtype.kind not in "iu":
+        raise TypeError("store: indices must be a flat sequence of integers")
+    idx = idx.astype(np.int64, copy=False)
+    S = len(node_off) - 1
+    if int(idx.min()) < 0 or int(idx.max()) >= S:
+        raise IndexError("store: scene index outside [0, %d)" % S)
+    B, R = len(idx), int(edge_off.shape[0])
+    G = 2 * R * B
+    tab = np.empty(5 * B + 2 * G + 3, np.int64)
+    t_node_off, t_actor_off = tab[:B + 1], tab[B + 1:2 * B + 2]
+    t_node_src, t_actor_src, t_scene = tab[2 * B + 2:3 * B + 2], tab[3 * B + 2:4 * B + 2], tab[4 * B + 2:5 * B + 2]
+    t_seg_off, t_seg_src = tab[5 * B + 2:5 * B + G + 3], tab[5 * B + G + 3:]
+    t_node_src[:], t_actor_src[:], t_scene[:] = node_off[idx], actor_off[idx], idx
+    n_nodes, n_act = node_off[idx + 1] - t_node_src, actor_off[idx + 1] - t_actor_src
+    t_node_off[0] = t_actor_off[0] = t_seg_off[0] = 0
+    np.cumsum(n_nodes, out=t_node_off[1:])
+    np.cumsum(n_act, out=t_actor_off[1:])
+    lo = edge_off[:, idx]                                               # [R, B]
+    t_seg_src.reshape(R, 2, B)[:] = (lo + np.asarray(rel_off)[:R, None])[:, None, :]
+    np.cumsum(np.broadcast_to((edge_off[:, idx + 1] - lo)[:, None, :], (R, 2, B)).reshape(-1), out=t_seg_off[1:])
+    total_n, total_a, n_elem = int(t_node_off[-1]), int(t_actor_off[-1]), int(t_seg_off[-1])
+    if total_n > _I32_MAX or 60 * total_a > _I32_MAX or n_elem > _I32_MAX or G > _I32_MAX:
+        raise LgcnError("store: a batch of %d nodes, %d actors and %d index elements is past 32-bit offsets"
+                        % (total_n, total_a, n_elem))
+    cut = t_seg_off[::B].tolist()                                       # the 2 R + 1 ends of the u / v blocks
+    rel_slices = [((cut[2 * r], cut[2 * r + 1]), (cut[2 * r + 1], cut[2 * r + 2])) for r in range(R)]
+    return StorePlan(
+        n_scenes=B, n_nodes=total_n, n_actors=total_a, num_scales=int(num_scales), rel_slices=rel_slices,
+        n_edges=[u[1] - u[0] for u, _ in rel_slices], cap_a2m=int(np.dot(n_nodes, n_act)), cap_a2a=int(np.dot(n_act, n_act)),
+        sizes=n_act.tolist(), n_rel=R, n_elem=n_elem, table=tab)
+
+
+def _carve(spec, device):
+    """One device byte buffer that holds the arrays (name, dtype, shape) of `spec` in order, each at a 256-byte aligned
+    offset (the layout of engine.collate_flat_host), and the arrays as views of it."""
+    at, off = [], 0
+    for _, dt, shp in spec:
+        at.append(off)
+        off = (off + int(np.prod(shp)) * dt.itemsize + 255) & ~255
+    buf = torch.empty(max(off, 256), dtype=torch.uint8, device=device)
+    typed, views = {}, {}
+    for (name, dt, shp), o in zip(spec, at):
+        if dt not in typed:
+            typed[dt] = buf.view(dt)
+        strides, step = [], 1
+        for d in reversed(shp):
+            strides.append(step)
+            step *= d
+        # one op per array (a slice, a dtype view and a reshape are three, and sixteen arrays make them the call's cost)
+        views[name] = typed[dt].as_strided(shp, strides[::-1], o // dt.itemsize)
+    return buf, views
+
+
+class DeviceSceneStore:
+    """A flat store resident in device memory: `batch(indices)` assembles the FlatBatch (+ actor tracks) of any list of
+    scenes with one small upload (the offset table of the pick, from pinned memory) and ONE kernel launch
+    (ops.store_gather), on the current stream and without synchronising.  Same results as FlatSceneFile.batch, byte for
+    byte.  The offset tables stay on the host (numpy); `plan(indices)` is the host half and needs no GPU."""
+
+    def __init__(self, source, device=None):
+        a = (source if isinstance(source, FlatSceneFile) else FlatSceneFile(source)).a
+        self.n_scenes = len(a["node_off"]) - 1
+        self.num_scales = int(a["num_scales"])
+        self.node_off, self.actor_off = np.asarray(a["node_off"], np.int64), np.asarray(a["actor_off"], np.int64)
+        self.edge_off, self.rel_off = np.asarray(a["edge_off"], np.int64), np.asarray(a["rel_off"], np.int64)
+        if not torch.cuda.is_available():
+            raise LgcnError("DeviceSceneStore needs a GPU (the HIP hot path has no CPU fallback); plan_batch does not")
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.index is None:
+            self.device = torch.device(self.device.type, torch.cuda.current_device())
+        names = list(ops.STORE_FLOATS) + ["edge_u", "edge_v"] + (["gt_preds", "has_preds"] if "gt_preds" in a else [])
+        host = {k: np.ascontiguousarray(a[k]) for k in names}
+        if "has_preds" in host:
+            host["has_preds"] = host["has_preds"].view(np.uint8)
+        self._job = ops.StoreJob({k: torch.from_numpy(v).to(self.device) for k, v in host.items()})
+        torch.cuda.synchronize(self.device)      # resident before any stream reads it
+        self.nbytes = self._job.nbytes
+
+    def __len__(self):
+        return self.n_scenes
+
+    def plan(self, indices) -> StorePlan:
+        return plan_batch(self.node_off, self.actor_off, self.edge_off, self.rel_off, self.num_scales, indices)
+
+    def batch(self, indices, plan: StorePlan = None):
+        """-> (FlatBatch, extras) as FlatSceneFile.batch(indices, device) returns them.  The FlatBatch arrays are views
+        of one device byte buffer (`buf_view()`) at the 256-byte aligned offsets of engine.HostFlatBatch; the extras are
+        views of a second one.  `plan`: this pick's plan(), if the caller already has it."""
+        p = self.plan(indices) if plan is None else plan
+        B, N, A, E, G = p.n_scenes, p.n_nodes, p.n_actors, p.n_elem, p.n_seg
+        f32, i32, i64 = torch.float32, torch.int32, torch.int64
+        flat = (("node_ctrs", f32, (N, 2)), ("node_feats", f32, (N, 2)), ("turn", f32, (N, 2)), ("control", f32, (N,)),
+                ("intersect", f32, (N,)), ("actor_ctrs", f32, (A, 2)), ("node_off", i32, (B + 1,)),
+                ("actor_off", i32, (B + 1,)), ("idx_local", i64, (E,)), ("seg_off", i64, (G + 1,)), ("seg_base", i64, (G,)))
+        assert tuple(n for n, _, _ in flat) == _FLAT_ARRAYS
+        extra = (("actor_feats", f32, (A, 3, 20)), ("rot", f32, (A, 2, 2)), ("orig", f32, (A, 2)))
+        if self._job.has_gt:
+            extra += (("gt_preds", f32, (A, 30, 2)), ("has_preds", torch.bool, (A, 30)))
+        with torch.cuda.device(self.device):
+            # the table goes through pinned memory of its own: the host allocator hands a block out again only after the
+            # copies queued from it have run, so back-to-back calls never share staging
+            stage = torch.empty(p.table.size, dtype=i64, pin_memory=True)
+            stage.numpy()[:] = p.table
+            tab_dev = torch.empty(p.table.size, dtype=i64, device=self.device)
+            tab_dev.copy_(stage, non_blocking=True)
+            fbuf, out = _carve(flat, self.device)
+            out.update(_carve(extra, self.device)[1])
+            ops.store_gather(self._job, stage, tab_dev, B, p.n_rel, N, A, E, out)
+        fb = FlatBatch(n_scenes=B, n_nodes=N, n_actors=A, num_scales=p.num_scales, rel_slices=p.rel_slices,
+                       cap_a2m=p.cap_a2m, cap_a2a=p.cap_a2a, n_edges=p.n_edges, _buf=fbuf,
+                       **{n: out[n] for n in _FLAT_ARRAYS})
+        extras = {n: out[n] for n, _, _ in extra}
+        extras["sizes"] = list(p.sizes)
         return fb, extras

@@ -1025,6 +1025,11 @@ class Net(nn.Module):
         if m["n_nodes"] == 0 or m["n_edges"][2 * ns - 2] == 0 or m["n_edges"][2 * ns - 1] == 0:
             raise KeyError("node_idcs")
         fb, out = self._replay_or_run(eng, hfb, feats, rot, orig, sizes)
+        return self._finish_inference(eng, fb, out, feats, rot, orig, sizes)
+
+    def _finish_inference(self, eng, fb, out, feats, rot, orig, sizes) -> Dict[str, List[Tensor]]:
+        """The host-side checks behind a whole-Net forward `out` of the device batch `fb` (feats / rot / orig: its actor
+        inputs, on the host or on the device), then the per-scene lists."""
         # one device->host read for the host-side checks: the range guard's flag and the three pair counts
         host = torch.cat([out["nonfinite"].view(1)] + [c.view(1) for c in out["n_pairs"]]).tolist()
         if eng.hot.pair_caps == "tight":
@@ -1055,6 +1060,28 @@ class Net(nn.Module):
         # per-scene views in two calls (a Python slice per scene and tensor costs ~2 us each: 0.13 ms at batch 32)
         sizes = [int(a) for a in sizes]
         return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
+
+    def forward_store(self, store, indices) -> Dict[str, List[Tensor]]:
+        """No-grad forward of the scenes `indices` of a flatfile.DeviceSceneStore: the batch is cut out of the resident
+        store by one launch (no per-scene host work, no scene dicts) and run eagerly through engine.FullNetEngine.
+        Output and error behaviour are those of forward(data) on the same scenes: per-scene lists in world coordinates,
+        KeyError when pre[5] / suc[5] is empty, RuntimeError under Att.strict when a fusion block has no pair."""
+        from .engine import FullNetEngine
+        eng = self.__dict__.get("_engine")
+        if eng is None:
+            eng = FullNetEngine(self)
+            self.__dict__["_engine"] = eng
+        plan = store.plan(indices)
+        ns = plan.num_scales
+        if plan.n_nodes == 0 or plan.n_edges[2 * ns - 2] == 0 or plan.n_edges[2 * ns - 1] == 0:
+            raise KeyError("node_idcs")
+        if plan.n_actors == 0:
+            raise L.LgcnError("forward_store: the picked scenes hold no actor")
+        with torch.no_grad():
+            fb, ex = store.batch(indices, plan=plan)
+            feats, rot, orig, sizes = ex["actor_feats"], ex["rot"], ex["orig"], ex["sizes"]
+            out = eng.forward(fb, feats, rot, orig, sizes, return_pairs=Att.strict)
+            return self._finish_inference(eng, fb, out, feats, rot, orig, sizes)
 
 
 def _tree_cpu(x):

@@ -2094,3 +2094,81 @@ def roi_edge_fill(job: RoiJob, edge_base: torch.Tensor, n_out_edges: int, n_out_
                                               job.a2m_v.data_ptr())
     L.check(L.load().lgcn_roi_edge_fill(C.byref(p), _stream()), "lgcn_roi_edge_fill")
     return job.out_u, job.out_v, job.a2m_v
+
+
+# ------------------------------------------------------------------ device-resident scene store (flatfile.DeviceSceneStore)
+STORE_FLOATS = ("node_ctrs", "node_feats", "turn", "control", "intersect", "actor_ctrs", "actor_feats", "rot", "orig")
+
+
+def store_table_elems(n_scenes: int, n_rel: int) -> int:
+    """int64 entries of the per-batch table of lgcn_store_gather for n_scenes picked scenes and n_rel relations."""
+    n = int(L.load().lgcn_store_table_elems(int(n_scenes), int(n_rel)))
+    if n < 0:
+        L.check(n, "lgcn_store_table_elems")
+    return n
+
+
+class StoreJob:
+    """A flat store's lgcn_store_t with the device tensors it points to.  ``t``: node_ctrs, node_feats, turn [N,2],
+    control, intersect [N], actor_ctrs [A,2], actor_feats [A,20,3], rot [S,2,2], orig [S,2] fp32, edge_u, edge_v [E] int32
+    and, both or neither, gt_preds [A,30,2] fp32 and has_preds [A,30] uint8."""
+
+    def __init__(self, t: dict):
+        kinds = {k: torch.float32 for k in STORE_FLOATS}
+        kinds.update(edge_u=torch.int32, edge_v=torch.int32)
+        if ("gt_preds" in t) != ("has_preds" in t):
+            raise L.LgcnError("store: gt_preds and has_preds come together")
+        if "gt_preds" in t:
+            kinds.update(gt_preds=torch.float32, has_preds=torch.uint8)
+        self.t = {k: _dev(t[k], dt, "store " + k) for k, dt in kinds.items()}
+        N, A_, S = self.t["control"].numel(), self.t["actor_ctrs"].shape[0], self.t["rot"].shape[0]
+        shapes = dict(node_ctrs=(N, 2), node_feats=(N, 2), turn=(N, 2), control=(N,), intersect=(N,), actor_ctrs=(A_, 2),
+                      actor_feats=(A_, 20, 3), rot=(S, 2, 2), orig=(S, 2), edge_v=tuple(self.t["edge_u"].shape),
+                      gt_preds=(A_, 30, 2), has_preds=(A_, 30))
+        for k, v in self.t.items():
+            if k in shapes and tuple(v.shape) != shapes[k]:
+                raise L.LgcnError("store: %s must be %s, got %s" % (k, shapes[k], tuple(v.shape)))
+        p = self.p = L.Store()
+        p.n_scenes, p.n_nodes, p.n_actors, p.n_edges = S, N, A_, self.t["edge_u"].numel()
+        for k, v in self.t.items():
+            setattr(p, k, v.data_ptr() if v.numel() else None)
+        self.has_gt = "gt_preds" in self.t
+        self.device = self.t["rot"].device
+        self.nbytes = sum(v.numel() * v.element_size() for v in self.t.values())
+
+
+def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n_scenes: int, n_rel: int, n_nodes: int,
+                 n_actors: int, n_elem: int, out: dict) -> None:
+    """lgcn_store_gather: one launch on the current stream fills ``out`` (name -> device tensor, the output fields of
+    lgcn_store_batch_t) with the batch that the table describes.  ``tab_host``: the int64 table on the host, validated by
+    the library before the launch; ``tab_dev``: the same words on the device (the caller has queued the copy on the
+    current stream)."""
+    if tab_host.is_cuda or tab_host.dtype != torch.int64 or not tab_host.is_contiguous():
+        raise L.LgcnError("store_gather: tab_host must be a contiguous int64 host tensor")
+    tab_dev = _dev(tab_dev, torch.int64, "store tab_dev")
+    if tab_dev.device != job.device or tab_dev.device.index != torch.cuda.current_device():
+        raise L.LgcnError("store_gather: the store lives on %s, which is not the current device" % (job.device,))
+    if tab_host.numel() != tab_dev.numel() or tab_host.numel() != store_table_elems(n_scenes, n_rel):
+        raise L.LgcnError("store_gather: the table must hold lgcn_store_table_elems(n_scenes, n_rel) entries")
+    b = L.StoreBatch()
+    b.n_scenes, b.n_rel, b.n_nodes, b.n_actors, b.n_elem = n_scenes, n_rel, n_nodes, n_actors, n_elem
+    b.tab_host, b.tab_dev = tab_host.data_ptr(), tab_dev.data_ptr()
+    n_seg = 2 * n_rel * n_scenes
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    want = dict(node_ctrs=(f32, 2 * n_nodes), node_feats=(f32, 2 * n_nodes), turn=(f32, 2 * n_nodes), control=(f32, n_nodes),
+                intersect=(f32, n_nodes), actor_ctrs=(f32, 2 * n_actors), node_off=(i32, n_scenes + 1),
+                actor_off=(i32, n_scenes + 1), idx_local=(i64, n_elem), seg_off=(i64, n_seg + 1), seg_base=(i64, n_seg),
+                actor_feats=(f32, 60 * n_actors), rot=(f32, 4 * n_actors), orig=(f32, 2 * n_actors))
+    if job.has_gt:
+        want.update(gt_preds=(f32, 60 * n_actors), has_preds=(None, 30 * n_actors))
+    if set(out) != set(want):
+        raise L.LgcnError("store_gather: outputs must be %s, got %s" % (sorted(want), sorted(out)))
+    for k, v in out.items():
+        dt, n = want[k]
+        if not v.is_cuda or not v.is_contiguous() or v.device != job.device:
+            raise L.LgcnError("store_gather: %s must be a contiguous CUDA tensor on the store's device (the HIP hot path "
+                              "has no CPU fallback)" % k)
+        if v.numel() != n or (v.dtype != dt if dt is not None else v.element_size() != 1):
+            raise L.LgcnError("store_gather: %s must hold %d elements of %s, got %d of %s" % (k, n, dt or "one byte", v.numel(), v.dtype))
+        setattr(b, k, v.data_ptr() if n else None)
+    L.check(L.load().lgcn_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_store_gather")

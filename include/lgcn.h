@@ -1149,8 +1149,10 @@ int lgcn_roi_loss_bwd(const float *logits, const float *goals, const float *traj
  * Lane-RoI extraction of the fork (reference data_lrcnn.py:620-844, generate_lane_roi) for a BATCH of scenes: the
  * per-agent lane search, the nodes of every RoI and the 14 induced relations, in four calls that share one struct.
  * Integer and exact-fp32 kernels (no FMA, correctly rounded sqrt): index arrays, feats, agent_feat and the distances
- * equal the reference's; lane lengths and step sums are added in numpy's order (pairwise_sum: 8 accumulators; one piece
- * for lanes of more than 128 nodes, where numpy splits), atan2f is the device's.
+ * equal the reference's; lane lengths and step sums are added in numpy's order (pairwise_sum: 8 accumulators up to 128
+ * elements, halves added recursively above, as numpy splits them), atan2f is the device's.
+ * lgcn_roi_lane_length_host runs the kernels' lane-length routine on the host (feats [.,2] fp32, n node ids; NaN for a
+ * negative n or a NULL array): the sum over sqrt(x * x + y * y) of the listed nodes, for comparison with numpy's bits.
  *
  * Inputs (device unless said): the scenes' arrays concatenated, indices LOCAL to their scene, int32.
  *   off_host / off_dev: one table of int32 offsets, the same on the host (validated) and on the device (read by kernels):
@@ -1168,7 +1170,8 @@ int lgcn_roi_loss_bwd(const float *logits, const float *goals, const float *traj
  *   dropped), level-by-level lane search over suc_pairs (horizon v * 3 + horizon_buffer) and pre_pairs (v * 2 + ...), left /
  *   right closure, lane order (search order with every lane at its first occurrence when the closure adds none, else
  *   ascending).  agent_nodes [n_agents + 1]: the RoI's node count, 0 for a dropped agent (speed 0, no anchor, < 6 nodes,
- *   neither a pre[0] nor a suc[0] edge); the last word is a status: bit 0 = an index out of range was skipped, bit 1 = a
+ *   neither a pre[0] nor a suc[0] edge); the last word is a status: bit 0 = an index out of range was skipped (a node, lane
+ *   or pair index of a relation, a lane pair or lane_idcs, whether or not an RoI would have reached it), bit 1 = a
  *   lane search hit lgcn_roi_max_levels() (a cycle of zero-length lanes).  agent_vel [n_agents].
  * lgcn_roi_nodes (1 launch): roi_agent [n_rois], roi_base [n_rois + 1] (node offset of every kept RoI, from the counts
  *   above) -> node_mask [n_out_nodes] int64, out_feats [n_out_nodes,8], agent_feat [n_rois,80], near [n_out_nodes]
@@ -1201,6 +1204,7 @@ typedef struct {
 } lgcn_roi_t;
 int lgcn_roi_max_lanes(void);
 int lgcn_roi_max_levels(void);
+float lgcn_roi_lane_length_host(const float *feats, const int32_t *nodes, int n);
 int64_t lgcn_roi_ws_elems(int64_t n_nodes, int64_t n_lanes, int64_t n_edges, int64_t n_slots, int64_t n_agents);
 int lgcn_roi_search(const lgcn_roi_t *p, void *stream);
 int lgcn_roi_nodes(const lgcn_roi_t *p, void *stream);

@@ -278,6 +278,7 @@ SIGNATURES = {
     "lgcn_roi_loss_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "lgcn_roi_max_lanes": (C.c_int, []),
     "lgcn_roi_max_levels": (C.c_int, []),
+    "lgcn_roi_lane_length_host": (C.c_float, [_P, _P, _I]),
     "lgcn_roi_ws_elems": (C.c_int64, [_L, _L, _L, _L, _L]),
     "lgcn_roi_search": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_roi_nodes": (C.c_int, [C.POINTER(Roi), _P]),

@@ -17,6 +17,9 @@ constexpr int kRoiThreads = 256;
 constexpr int kRoiScanItems = 4;
 constexpr int kRoiScanTile = 1024 * kRoiScanItems;
 constexpr int kStRange = 1, kStLevels = 2;
+constexpr int kRoiSumBlock = 128;             // numpy's PW_BLOCKSIZE: longer sums are split in halves
+constexpr int kRoiSumBuffer = 8192;           // numpy's default reduction buffer: longer sums go piece by piece
+constexpr int kRoiSumDepth = 10;
 
 // regions of the int32 workspace (each a multiple of 4 elements)
 struct RoiWs {
@@ -147,13 +150,13 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_count(const lgcn_roi_t
     w.cnt[w.n_keys + gl] = c;
 }
 
-__device__ __forceinline__ float roi_norm(const float *xy) {
+__host__ __device__ __forceinline__ float roi_norm(const float *xy) {
     const float x = xy[0], y = xy[1];
     return sqrtf(x * x + y * y);      // correctly rounded sqrt; no contraction
 }
 
-// numpy's pairwise_sum of the norms of feats[nodes[0..n)] (8 accumulators, then the remainder in order)
-__device__ __forceinline__ float roi_lane_length(const int32_t *nodes, int n, const float *feats) {
+// numpy's pairwise_sum of the norms of feats[nodes[0..n)] for n <= 128 (8 accumulators, then the remainder in order)
+__host__ __device__ inline float roi_lane_block(const int32_t *nodes, int n, const float *feats) {
     if (n < 8) {
         float r = 0.f;
         for (int k = 0; k < n; ++k) r += roi_norm(feats + 2 * nodes[k]);
@@ -174,6 +177,51 @@ __device__ __forceinline__ float roi_lane_length(const int32_t *nodes, int n, co
     return res;
 }
 
+// numpy's pairwise_sum of up to 8192 elements: above 128 elements numpy halves the range (the left half cut down to a
+// multiple of 8) and adds the two halves' sums, recursively.  The recursion is walked with a stack of frames: a range of m
+// elements leaves at most m / 2 + 8 to its right half, so 8192 elements are down to 128 within 7 levels.
+__host__ __device__ inline float roi_lane_piece(const int32_t *nodes, int n, const float *feats) {
+    if (n <= kRoiSumBlock) return roi_lane_block(nodes, n, feats);
+    int off[kRoiSumDepth], len[kRoiSumDepth], stage[kRoiSumDepth];
+    float left[kRoiSumDepth];
+    int sp = 0;
+    off[0] = 0; len[0] = n; stage[0] = 0; left[0] = 0.f;
+    float ret = 0.f;
+    while (sp >= 0) {
+        const int o = off[sp], m = len[sp];
+        if (m <= kRoiSumBlock || sp + 1 >= kRoiSumDepth) {       // a leaf (the depth bound is never reached, see above)
+            ret = roi_lane_block(nodes + o, m, feats);
+            --sp;
+            continue;
+        }
+        int half = m / 2;
+        half -= half % 8;
+        if (stage[sp] == 0) {
+            stage[sp] = 1;
+            ++sp;
+            off[sp] = o; len[sp] = half; stage[sp] = 0;
+        } else if (stage[sp] == 1) {
+            left[sp] = ret;
+            stage[sp] = 2;
+            ++sp;
+            off[sp] = o + half; len[sp] = m - half; stage[sp] = 0;
+        } else {
+            ret = left[sp] + ret;
+            --sp;
+        }
+    }
+    return ret;
+}
+
+// np.sum of the norms of feats[nodes[0..n)]: numpy reduces through its buffer, 8192 elements at a time (np.getbufsize()'s
+// default), every piece by pairwise_sum, the pieces' sums added in order
+__host__ __device__ inline float roi_lane_length(const int32_t *nodes, int n, const float *feats) {
+    float res = roi_lane_piece(nodes, n < kRoiSumBuffer ? n : kRoiSumBuffer, feats);
+    for (int i = kRoiSumBuffer; i < n; i += kRoiSumBuffer)
+        res += roi_lane_piece(nodes + i, n - i < kRoiSumBuffer ? n - i : kRoiSumBuffer, feats);
+    return res;
+}
+
 __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_fill(const lgcn_roi_t p, const RoiWs w) {
     const int gl = blockIdx.x * kRoiThreads + threadIdx.x;
     if (gl >= p.n_lanes) return;
@@ -182,14 +230,19 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_fill(const lgcn_roi_t 
     const int l = gl - t.lane[s];
     const int32_t *lane_ptr = w.cnt + w.n_keys;
     const int base = lane_ptr[gl] - lane_ptr[0], end = lane_ptr[gl + 1] - lane_ptr[0];
-    const int nb = t.node[s];
+    const int nb = t.node[s], nl = t.lane[s + 1] - t.lane[s];
     int c = base;
-    for (int i = nb; i < t.node[s + 1]; ++i)
-        if (p.lane_idcs[i] == l && c < end) {
+    bool bad = false;       // a node of no lane of its scene: no table holds it, so it is reported, not dropped in silence
+    for (int i = nb; i < t.node[s + 1]; ++i) {
+        const int li = p.lane_idcs[i];
+        bad |= (unsigned)li >= (unsigned)nl;
+        if (li == l && c < end) {
             w.lane_nodes[c] = i - nb;
             w.node_rank[i] = c - base;
             ++c;
         }
+    }
+    if (bad && l == 0) atomicOr(&p.agent_nodes[p.n_agents], kStRange);
     w.lane_len[gl] = roi_lane_length(w.lane_nodes + base, c - base, p.feats + 2 * (int64_t)nb);
 }
 
@@ -705,6 +758,11 @@ extern "C" {
 
 int lgcn_roi_max_lanes(void) { return kRoiMaxLanes; }
 int lgcn_roi_max_levels(void) { return kRoiMaxLevels; }
+
+float lgcn_roi_lane_length_host(const float *feats, const int32_t *nodes, int n) {
+    if (n < 0 || (n > 0 && (feats == nullptr || nodes == nullptr))) return __builtin_nanf("");
+    return roi_lane_length(nodes, n, feats);
+}
 
 int64_t lgcn_roi_ws_elems(int64_t n_nodes, int64_t n_lanes, int64_t n_edges, int64_t n_slots, int64_t n_agents) {
     if (n_nodes < 0 || n_lanes < 0 || n_edges < 0 || n_slots < 0 || n_agents < 0) return LGCN_EINVAL;

@@ -66,8 +66,15 @@ def generate_lane_roi_batch(scenes, horizon_buffer=20., device=False):
     than the horizon, with no left / right neighbour outside the RoI) is kept ONCE, at its first occurrence, where the
     reference emits its nodes twice; and among eligible nodes at exactly the same distance the anchor is the one with the
     smaller index, where the reference's unstable argsort leaves the choice open.  A lane search that does not end within
-    lgcn_roi_max_levels() levels (a cycle of zero-length lanes, on which the reference never returns) and an index out of
-    range raise LgcnError.  At most ops.roi_max_lanes() = 4096 lanes per scene (LgcnError above, nothing is launched).
+    lgcn_roi_max_levels() levels (a cycle of zero-length lanes, on which the reference never returns) raises LgcnError
+    ("did not end").  So does EVERY index out of range ("outside its scene"), whether or not an RoI would have reached it:
+    a node index of one of the 14 relations, a lane index of suc_pairs / pre_pairs (these two are read by the searches, so
+    only in a scene with a moving agent that has an anchor), and a lane_idcs value below 0 or above lane_idcs[-1] (the
+    reference counts lanes as lane_idcs[-1] + 1 and would leave such a node out of every RoI in silence).  The status is
+    per batch: one bad scene fails the call, and the next call starts clean (a batch without any agent launches nothing
+    and checks nothing).  Lane lengths are summed as np.sum does for
+    any number of nodes (pairwise in blocks of 128, through the default 8192-element buffer).
+    At most ops.roi_max_lanes() = 4096 lanes per scene (LgcnError above, nothing is launched).
 
     11 kernel launches, one memset and two zero fills per batch, whatever the number of scenes, agents or RoIs, and two
     size read-backs (node counts, edge counts)."""
@@ -82,7 +89,9 @@ def generate_lane_roi_batch(scenes, horizon_buffer=20., device=False):
     for b, nl in enumerate(n_lanes):
         if nl > cap:
             raise L.LgcnError("generate_lane_roi: scene %d has %d lanes, the lane-RoI kernels take at most %d" % (b, nl, cap))
-    dev = torch.device("cuda", torch.cuda.current_device())
+        if nl <= 0 and len(scenes[b]["graph"]["lane_idcs"]):      # lane_idcs[-1] < 0: no lane for the kernels to check against
+            raise L.LgcnError("generate_lane_roi: a node, lane or pair index lies outside its scene")
+    dev =torch.device("cuda", torch.cuda.current_device())
     graphs = [s["graph"] for s in scenes]
     n_nodes = [len(g["lane_idcs"]) for g in graphs]
     n_agents = [len(s["ctrs"]) for s in scenes]

@@ -1,7 +1,9 @@
 """Scenes for the lane-RoI tests: a builder of small lane graphs with a chosen topology (chains of lanes of 1..20
 nodes, parallel chains joined by left / right edges, branches, lane cycles, clusters of one-node lanes, shuffled node
 order) in the reference's scene schema with pre_pairs / suc_pairs and obs_trajs, and the six random trials of
-tests/test_gpu_lane_roi.py (tests/test_lane_roi_model_host.py checks the same seeds with the model alone)."""
+tests/test_gpu_lane_roi.py (tests/test_lane_roi_model_host.py checks the same seeds with the model alone); the named
+scenes at real sizes of tests/test_gpu_lane_roi_large.py (large_scene) with the properties they must hold; the loaders
+of the two recordings of the reference and the comparison helpers."""
 import numpy as np
 
 from lanegcn_amd import data as gen
@@ -195,13 +197,175 @@ def trial(seed):
     return scenes
 
 
+# ------------------------------------------------------------------ named scenes at real sizes
+# name -> seed.  tests/golden/make_golden_lane_roi_large.py searches the seeds of the recorded scenes (no agent on an
+# edge, no lane listed twice, every property of assert_large_properties) and refuses to write unless they stand here.
+LARGE_SEEDS = dict(wide=1, chain=2, cap=1, mixed=1, crowd=1, longlane=1, fan=1, empty_agents=1)
+LARGE_RECORDED = ("wide", "chain", "cap")      # in tests/golden/lane_roi_large.npz (with mixed it passes 1,000,000 bytes)
+LARGE_NAMES = LARGE_RECORDED + ("mixed", "crowd", "longlane", "fan", "empty_agents")
+
+
+def large_scene(name, seed=None):
+    """One named scene, each the smallest at which one path of csrc/lgcn_roi.hip can go wrong:
+    wide          30 lanes of 20 nodes in 3 copies, shuffled, int16: an RoI of more than 512 nodes (three chunks of 256
+                  in the edge kernels), ascending lanes (the closure grew)
+    chain         700 one-node lanes, 0.5 m each, no neighbours: an RoI of more than 256 lanes in search order
+    cap           4096 one-node lanes in 4 copies: lane ids on both sides of bitset word 64, an RoI of over 1024 lanes
+    mixed         1800 lanes of 1..3 nodes in 2 copies, shuffled: over 256 lanes with lane offsets and node ranks
+    crowd         40 lanes, 72 agents, some standing and some turned: over 40 RoIs in one scene
+    longlane      a chain with one lane of 130 and one of 300 nodes (numpy sums more than 128 elements in blocks)
+    fan           2,020 one-node lanes far away, then a trunk lane with 80 successor chains of 3 lanes, no neighbours: one
+                  search level adds 80 lanes in bitset words 63..70, which go into the search-order list by a popcount
+                  prefix over the words before them, on both sides of word 64
+    empty_agents  a small graph without agents"""
+    rng = np.random.default_rng(LARGE_SEEDS[name] if seed is None else seed)
+    b = Builder(rng)
+    at = lambda new, lane, k=0: int(new[lane[k]])
+    if name == "wide":
+        cp = b.chain((0.0, 0.0), 0.4, [20] * 30, 3, spacing=1.0)
+        g, new = b.graph(np.int16, shuffle=True)
+        return agents(rng, g, [(at(new, cp[0][14], 10), 0.05, 31.0, 0.3), (at(new, cp[1][12], 5), -0.05, 25.5, -0.4),
+                               (at(new, cp[2][20], 3), 0.0, 12.5, 0.2)])
+    if name == "chain":
+        cp = b.chain((0.0, 0.0), 1.0, [1] * 700, 1, spacing=0.5)
+        g, new = b.graph(np.int64)
+        return agents(rng, g, [(at(new, cp[0][300]), 0.02, 31.0, 0.3), (at(new, cp[0][640]), -0.02, 20.5, -0.3)])
+    if name == "cap":
+        cp = b.chain((0.0, 0.0), 0.2, [1] * 1024, 4, spacing=0.5)
+        g, new = b.graph(np.int32)
+        return agents(rng, g, [(at(new, cp[2][500]), 0.02, 31.0, 0.2), (at(new, cp[0][300]), -0.02, 25.5, -0.2),
+                               (at(new, cp[3][900]), 0.0, 28.3, 0.1)])
+    if name == "mixed":
+        cp = b.chain((0.0, 0.0), 2.0, [int(x) for x in rng.integers(1, 4, 900)], 2, spacing=0.5)
+        g, new = b.graph(np.int32, shuffle=True)
+        return agents(rng, g, [(at(new, cp[0][450]), 0.03, 31.0, 0.3), (at(new, cp[1][200]), -0.03, 22.0, -0.3)])
+    if name == "crowd":
+        return random_scene(rng, 40, 72, np.int32, max_size=14)
+    if name == "longlane":
+        cp = b.chain((0.0, 0.0), 0.3, [6, 130, 7, 300, 6], 1, spacing=0.3)
+        g, new = b.graph(np.int64)
+        return agents(rng, g, [(at(new, cp[0][1], 60), 0.02, 9.0, 0.3), (at(new, cp[0][3], 150), -0.02, 14.0, -0.3)])
+    if name == "fan":
+        b.chain((2000.0, 0.0), 0.0, [1] * 2020, 1, spacing=0.5)
+        trunk = b.chain((0.0, 0.0), 0.5, [3], 1, spacing=2.0)[0][0]
+        end = b.ctrs[trunk[-1]] + b.feats[trunk[-1]] / 2.0
+        for off in np.linspace(-0.6, 0.6, 80):
+            b.branch(trunk, b.chain(end, 0.5 + off, [3, 3, 3], 1, spacing=2.0)[0][0])
+        g, new = b.graph(np.int32)
+        return agents(rng, g, [(at(new, trunk, 1), 0.02, 7.0, 0.2)])
+    if name == "empty_agents":
+        b.chain((0.0, 0.0), 0.5, [5, 6, 4], 2)
+        g, _ = b.graph(np.int64)
+        return agents(rng, g, [])
+    raise KeyError(name)
+
+
+def large_scenes(names=LARGE_NAMES):
+    """{name: scene} of the named scenes, deterministic (LARGE_SEEDS)."""
+    return {n: large_scene(n) for n in names}
+
+
+def roi_properties(scene, out):
+    """Per RoI of `out` (a model or reference result for `scene`): agent, node count, lanes in RoI order (each once), the
+    sizes of those lanes, ascending or not, the anchor's lane, whether the left / right closure grew."""
+    import lane_roi_model as M
+    sc = M.Scene(scene)
+    props = []
+    for a, sg in zip(out["valid_agent_ids"].tolist(), out["subgraphs"]):
+        ln = sc.lane_idcs[sg["node_mask"]]
+        lanes = ln[np.sort(np.unique(ln, return_index=True)[1])]
+        props.append(dict(agent=a, nodes=int(sg["num_nodes"]), lanes=lanes, sizes=[len(sc.lane_nodes[l]) for l in lanes],
+                          ascending=bool((np.diff(lanes) > 0).all()), anchor_lane=int(sc.lane_idcs[M.anchor(sc, a)]),
+                          grew=bool(M.roi_lanes(sc, a, M.anchor(sc, a), 20.0)[1])))
+    return props
+
+
+def assert_large_properties(name, scene, out, excluded=()):
+    """The property each named scene is there for, read off a result `out`, carried by an agent outside `excluded`."""
+    import lane_roi_model as M
+    g = scene["graph"]
+    li = np.asarray(g["lane_idcs"], np.int64)
+    lane_sizes = np.bincount(li)
+    props = [p for p in roi_properties(scene, out) if p["agent"] not in set(excluded)]
+    some = lambda f: any(f(p) for p in props)
+    if name == "wide":
+        assert g["lane_idcs"].dtype == np.int16 and (np.diff(li) < 0).any() and len(scene["ctrs"]) == 3
+        assert (M.agent_velocity(scene["feats"]) > 0).all()
+        assert some(lambda p: p["nodes"] > 512 and p["grew"] and p["ascending"]), props
+    elif name == "chain":
+        assert len(lane_sizes) >= 600 and (lane_sizes == 1).all() and len(g["left"]["u"]) == 0 == len(g["right"]["u"])
+
+        def search_order(p):
+            lanes, t = p["lanes"].tolist(), p["anchor_lane"]
+            n_suc = int(np.argmax(np.diff(lanes) < 0))          # lanes[:n_suc + 1] = target and its successors
+            return (len(lanes) > 256 and not p["ascending"] and n_suc >= 1 and len(lanes) - n_suc - 1 >= 1
+                    and lanes == list(range(t, t + n_suc + 1)) + list(range(t - 1, t - len(lanes) + n_suc, -1)))
+        assert some(search_order), props
+    elif name == "cap":
+        assert len(lane_sizes) == 4096 and (lane_sizes == 1).all()
+        assert some(lambda p: p["anchor_lane"] >= 2048 and len(p["lanes"]) > 1024 and p["lanes"].min() < 2048
+                    and p["lanes"].max() >= 2080), props
+        assert some(lambda p: 4095 in p["lanes"]), props
+    elif name == "mixed":
+        assert 1700 <= len(lane_sizes) <= 1900 and set(lane_sizes.tolist()) == {1, 2, 3} and (np.diff(li) < 0).any()
+        assert some(lambda p: len(p["lanes"]) > 256 and {1, 2, 3} <= set(p["sizes"])), props
+    elif name == "crowd":
+        sc = M.Scene(scene)
+        assert len(scene["ctrs"]) >= 70 and 30 <= len(lane_sizes) <= 50 and 200 <= len(li) <= 400
+        assert len(props) >= 40
+        moving = np.flatnonzero(sc.vel > 0)
+        assert len(moving) < len(sc.vel)                          # some stand
+        assert any(M.angle_gap(sc, a)[np.argmin(M.node_dist(sc, a))] > 0.5 * np.pi for a in moving)      # some are turned
+    elif name == "longlane":
+        long_ = np.flatnonzero(lane_sizes >= 300)
+        mid = np.flatnonzero((lane_sizes >= 130) & (lane_sizes < 300))
+        assert len(long_) and len(mid)
+        assert some(lambda p: p["anchor_lane"] in long_) and some(lambda p: p["anchor_lane"] in mid), props
+    elif name == "fan":
+        pairs = np.asarray(g["suc_pairs"], np.int64)
+
+        def fans_out(p):
+            nxt = pairs[pairs[:, 0] == p["anchor_lane"], 1]
+            return (not p["grew"] and not p["ascending"] and {63, 64, 65} <= set((nxt >> 5).tolist())
+                    and set(nxt.tolist()) <= set(p["lanes"].tolist()) and len(p["lanes"]) > 160)
+        assert len(g["left"]["u"]) == 0 and some(fans_out), props
+    elif name == "empty_agents":
+        assert len(scene["ctrs"]) == 0 and len(li) > 0 and len(out["subgraphs"]) == 0
+        assert out["valid_agent_ids"].dtype == np.int16 and out["valid_agent_ids"].shape == (0,)
+    else:
+        raise KeyError(name)
+
+
+def zero_ring_scene(on_ring=True):
+    """A ring of three one-node lanes whose feats are exactly zero (a lane search on it never adds length) beside an
+    ordinary chain, with one agent anchored on the ring (on_ring) or on the chain."""
+    rng = np.random.default_rng(7)
+    b = Builder(rng)
+    ring = b.chain((0.0, 0.0), 0.0, [1, 1, 1], 1, cycle=True, spacing=0.5)
+    ch = b.chain((300.0, 0.0), 0.0, [6, 7, 5], 1, spacing=1.0)
+    g, new = b.graph(np.int64)
+    on = [int(new[l[0]]) for l in ring[0]]
+    g["feats"][on] = 0.0
+    return agents(rng, g, [(on[1] if on_ring else int(new[ch[0][1][3]]), 0.01, 6.0, 0.1)])
+
+
 # ------------------------------------------------------------------ fixture and comparison
+def load_large_fixture():
+    """({name: scene}, {name: want}): the recorded scenes of tests/golden/lane_roi_large.npz and the reference's output,
+    as load_fixture gives them."""
+    return _load("lane_roi_large.npz", named=True)
+
+
 def load_fixture():
     """(scenes, want): the four scenes of tests/golden/lane_roi_b4.npz and the reference's recorded output per scene,
     {"subgraphs": [...], "valid_agent_ids": int16}."""
+    return _load("lane_roi_b4.npz")
+
+
+def _load(file, named=False):
     import os
     from golden_io import load_scenes, unflatten
-    flat = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lane_roi_b4.npz")))
+    flat = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", file)))
     scenes = load_scenes(flat)
     for s in scenes:
         s["theta"] = float(s["theta"])
@@ -211,6 +375,9 @@ def load_fixture():
         for sg in subs:
             sg["num_nodes"], sg["agent_vel"] = int(sg["num_nodes"]), np.float32(sg["agent_vel"])
         want.append({"subgraphs": subs, "valid_agent_ids": flat["want/%d/valid_agent_ids" % b]})
+    if named:
+        names = [str(n) for n in flat["names"]]
+        return dict(zip(names, scenes)), dict(zip(names, want))
     return scenes, want
 
 
@@ -239,3 +406,46 @@ def drop_agents(out, agents):
     """`out` ({"subgraphs", "valid_agent_ids"}) without the RoIs of the listed agents."""
     keep = [i for i, a in enumerate(out["valid_agent_ids"].tolist()) if a not in set(agents)]
     return {"subgraphs": [out["subgraphs"][i] for i in keep], "valid_agent_ids": out["valid_agent_ids"][keep]}
+
+
+def to_tensors(x, move):
+    """numpy leaves -> tensors through `move`, recursively."""
+    import torch
+    if isinstance(x, dict):
+        return {k: to_tensors(v, move) for k, v in x.items()}
+    if isinstance(x, list):
+        return [to_tensors(v, move) for v in x]
+    return move(torch.from_numpy(x)) if isinstance(x, np.ndarray) and x.ndim else x
+
+
+def to_numpy(x):
+    """Tensor leaves -> numpy, recursively."""
+    import torch
+    if isinstance(x, dict):
+        return {k: to_numpy(v) for k, v in x.items()}
+    if isinstance(x, list):
+        return [to_numpy(v) for v in x]
+    return x.cpu().numpy() if torch.is_tensor(x) else x
+
+
+def assert_same_tensors(x, y, path):
+    """Trees of tensors and plain values: keys, lengths, dtypes, devices and values."""
+    import torch
+    if isinstance(x, dict):
+        assert set(x) == set(y), path
+        for k in x:
+            assert_same_tensors(x[k], y[k], path + "/" + str(k))
+    elif isinstance(x, (list, tuple)):
+        assert len(x) == len(y), path
+        for i, (p, q) in enumerate(zip(x, y)):
+            assert_same_tensors(p, q, "%s/%d" % (path, i))
+    elif torch.is_tensor(x):
+        assert x.dtype == y.dtype and x.device == y.device and torch.equal(x, y), path
+    else:
+        assert type(x) is type(y) and x == y, (path, x, y)
+
+
+def device_leaves(sg):
+    """The array leaves of one RoI dict."""
+    leaves = [sg["node_mask"], sg["feats"], sg["agent_feat"], sg["a2m"]["u"], sg["a2m"]["v"]]
+    return leaves + [e[k] for e in sg["pre"] + sg["suc"] + [sg["left"], sg["right"]] for k in "uv"]

@@ -38,18 +38,9 @@ def test_fixture_parity_per_scene_and_batched(fixture):
         C.assert_same(_out(got), want[b], "batch%d" % b, VEL_RTOL)
     # tensor leaves, on the host and on the device, give the same RoIs
     for move in (lambda t: t, lambda t: t.cuda()):
-        tens = [to_tensors(s, move) for s in copy.deepcopy(scenes)]
+        tens = [C.to_tensors(s, move) for s in copy.deepcopy(scenes)]
         for b, got in enumerate(D.generate_lane_roi_batch(tens)):
             C.assert_same(_out(got), want[b], "tensor%d" % b, VEL_RTOL)
-
-
-def to_tensors(x, move):
-    """numpy leaves -> tensors through `move`, recursively."""
-    if isinstance(x, dict):
-        return {k: to_tensors(v, move) for k, v in x.items()}
-    if isinstance(x, list):
-        return [to_tensors(v, move) for v in x]
-    return move(torch.from_numpy(x)) if isinstance(x, np.ndarray) and x.ndim else x
 
 
 @pytest.mark.parametrize("seed", C.TRIAL_SEEDS)
@@ -76,7 +67,7 @@ def test_repeatable_and_device_leaves():
             leaves = [sd["node_mask"], sd["feats"], sd["agent_feat"], sd["a2m"]["u"], sd["a2m"]["v"], sd["left"]["u"], sd["right"]["v"]]
             leaves += [e[k] for k1 in ("pre", "suc") for e in sd[k1] for k in "uv"]
             assert all(torch.is_tensor(x) and x.is_cuda for x in leaves)
-            host = to_tensors(sd, lambda t: t)      # no numpy leaf in it: unchanged
+            host = C.to_tensors(sd, lambda t: t)      # no numpy leaf in it: unchanged
             as_np = lambda x: x.cpu().numpy() if torch.is_tensor(x) else x
             conv = lambda x: ({k: conv(v) for k, v in x.items()} if isinstance(x, dict) else
                               [conv(v) for v in x] if isinstance(x, list) else as_np(x))
@@ -85,21 +76,7 @@ def test_repeatable_and_device_leaves():
     ga = R.subgraph_gather([dev[i]["subgraphs"] for i in keep])
     gb = R.subgraph_gather([first[i]["subgraphs"] for i in keep])
     assert set(ga) == set(gb)
-
-    def same(x, y, path):
-        if isinstance(x, dict):
-            assert set(x) == set(y), path
-            for k in x:
-                same(x[k], y[k], path + "/" + str(k))
-        elif isinstance(x, (list, tuple)):
-            assert len(x) == len(y), path
-            for i, (p, q) in enumerate(zip(x, y)):
-                same(p, q, "%s/%d" % (path, i))
-        elif torch.is_tensor(x):
-            assert x.dtype == y.dtype and x.device == y.device and torch.equal(x, y), path
-        else:
-            assert type(x) is type(y) and x == y, (path, x, y)
-    same(ga, gb, "gather")
+    C.assert_same_tensors(ga, gb, "gather")
 
 
 def test_net_forward_on_device_rois_equals_forward_on_model_rois():

@@ -10,8 +10,8 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("lgcn_roi_max_lanes", "lgcn_roi_max_levels", "lgcn_roi_ws_elems", "lgcn_roi_search", "lgcn_roi_nodes",
-         "lgcn_roi_edge_count", "lgcn_roi_edge_fill")
+NAMES = ("lgcn_roi_max_lanes", "lgcn_roi_max_levels", "lgcn_roi_lane_length_host", "lgcn_roi_ws_elems", "lgcn_roi_search",
+         "lgcn_roi_nodes", "lgcn_roi_edge_count", "lgcn_roi_edge_fill")
 EINVAL, ESHAPE, EALIGN = -1, -2, -3
 
 

@@ -1265,6 +1265,96 @@ typedef struct {
 int64_t lgcn_store_table_elems(int64_t n_scenes, int64_t n_rel);
 int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream);
 
+/*
+ * Scene construction for a BATCH of raw scenes (lanegcn_amd/data_raw.py): tracks to actor arrays
+ * (reference data.py:148-217, ArgoDataset.get_obj_feats) and map lanes to the scale-0 lane graph (data.py:220-361,
+ * ArgoDataset.get_lane_graph up to :353; the dilated scales stay lgcn_bool_square*).
+ *
+ * Arithmetic, the same in both: per scene frame = (orig x, y, rot 00, 01, 10, 11) fp32, computed by the host; a point p
+ * (float64) becomes d = p - (double)orig, x' = r00 * dx + r01 * dy, y' = r10 * dx + r11 * dy in float64, every product
+ * and sum rounded on its own (no FMA).  Order comes from prefix scans (block scan + per-block sums: a scene may span any
+ * number of workgroups); no float atomics: the same inputs give the same bytes.
+ *
+ * lgcn_scene_tracks (2 launches; data.py:162-201): off_host / off_dev = trk_off [n_scenes + 1] (tracks of every scene,
+ *   from 0 to n_tracks; every scene holds at least its agent) then row_off [n_tracks + 1] (rows of every track, to
+ *   n_rows), int32, the same on the host (validated) and on the device; xy [n_rows,2] float64 world positions, step
+ *   [n_rows] int32 (>= 0; values of 50 and above are ignored), frame [n_scenes,6], pred_range = (x_min, x_max, y_min,
+ *   y_max) compared in fp32.  Per track: steps 20..49 go to gt [.,30,2] (world, rounded to fp32) and has [.,30]; the
+ *   track is kept if step 19 is present and its transformed, rounded position lies inside pred_range; its observed part
+ *   is the maximal run of consecutive steps that ends at 19: obs [.,20,3] = (x', y', 1) rounded to fp32, ctrs [.,2] =
+ *   obs[19], feats [.,20,3] = fp32 differences of obs with the run's first step zeroed.  Kept tracks are compacted in
+ *   input order; the outputs hold n_tracks rows, of which the first head[n_scenes] are written.
+ *   head [n_scenes + 2] int32, ZEROED by the caller: head[s] = first output row of scene s, head[n_scenes] = kept tracks,
+ *   head[n_scenes + 1] = 0 or n_tracks - t for the first track t that lists a step below 50 twice (its output row, if
+ *   any, is then unspecified).  ws: lgcn_scene_tracks_ws_elems(n_tracks) int32.
+ *
+ * Lane tables (lgcn_lane_table_t, one per city): topo_host / topo_dev = lgcn_scene_topo_elems(n_lanes, n_pred, n_succ)
+ *   int32, the same on the host (validated by every call) and on the device: pt_off [L + 1], pred_off [L + 1], succ_off
+ *   [L + 1], left [L], right [L], flags [L] (turn | control << 8 | intersect << 16; turn 1 = LEFT, 2 = RIGHT), pred
+ *   [n_pred], succ [n_succ]; neighbours are table rows, -1 = not in the table; pts [n_pts,2] float64 on the device.
+ *
+ * lgcn_scene_lanes_rank (1 memset + 2 launches; data.py:228-241) and lgcn_scene_lanes_fill (2 launches; :243-334) share
+ *   one struct.  tabs_host / tabs_dev [n_tables]: the same structs on the host and on the device.  off_host / off_dev:
+ *   scene_tab [n_scenes] (table of every scene), cand_off [n_scenes + 1] (candidate lanes, to n_cand; at least one per
+ *   scene), rank_off [n_scenes + 1] (prefix sums of the scenes' table sizes, to n_rank), and with explicit_ids != 0 cand
+ *   [n_cand], the candidates as table rows in the caller's order, each row at most once per scene; with explicit_ids == 0
+ *   the candidates of a scene are all rows of its table in table order.  pred_range is compared in float64.
+ *   rank: a candidate is kept if the extent of its transformed centerline overlaps the rectangle; head [4 (n_scenes + 1)]
+ *   = per scene, then in total, the exclusive sums of (kept lanes, their nodes, their pred entries, their succ entries).
+ *   fill: n_nodes = head's node total; nodes in candidate order: ctrs, feats [n_nodes,2] (midpoint and difference of
+ *   consecutive transformed points, formed in float64, rounded once), turn [n_nodes,2], control, intersect [n_nodes],
+ *   lane_idcs [n_nodes] int64 (scene-local lane); pre_u / pre_v [cap_pre], suc_u / suc_v [cap_suc] int64: per lane its
+ *   chain edges, then one edge per kept predecessor / successor in the table's list order (scene-local nodes); pre_pairs,
+ *   suc_pairs, left_pairs, right_pairs [cap_*,2] int64 (scene-local lanes).  A neighbour is looked up in the per-scene
+ *   rank array.  The caps are upper bounds from head (cap_pre >= nodes - lanes + pred entries, ...): a write beyond a cap
+ *   is dropped, never made.  head2 [4 (n_scenes + 1)]: exclusive sums of the kept (pred, succ, left, right) neighbours;
+ *   scene s owns pre edges [(node - lane + pred2)(s), ..(s + 1)) and so on.  ws: lgcn_scene_lanes_ws_elems(n_cand,
+ *   n_rank) int32, kept from rank to fill.
+ *
+ * Checked before anything is launched: NULL struct or required pointer, negative size, NaN in pred_range, an offset table
+ * that does not start at 0, decreases or ends elsewhere than its total, a scene without a track or a candidate, a lane of
+ * fewer than 2 points, a neighbour row outside [-1, n_lanes), a table index or candidate outside its table, rank_off that
+ * does not follow the table sizes (LGCN_EINVAL); misaligned pointers (LGCN_EALIGN: 16 bytes for ws, xy, pts, 8 for int64
+ * arrays and tabs_dev, 4 for the rest); sizes beyond the 32-bit workspace, or a batch whose scenes' tables together hold more
+ * than 2^31 - 1 points and neighbour entries, which the int32 scans could not count (LGCN_ESHAPE).  n_scenes == 0 with all totals 0
+ * returns LGCN_OK without a launch.  The size helpers return LGCN_EINVAL / LGCN_ESHAPE as negative values.
+ */
+typedef struct {
+    int32_t n_scenes, n_tracks, n_rows, pad_;
+    float pred_range[4];
+    const int32_t *off_host, *off_dev;
+    const double *xy;
+    const int32_t *step;
+    const float *frame;
+    int32_t *ws, *head;
+    float *feats, *obs, *ctrs, *gt;
+    unsigned char *has;
+} lgcn_scene_tracks_t;
+int64_t lgcn_scene_tracks_ws_elems(int64_t n_tracks);
+int lgcn_scene_tracks(const lgcn_scene_tracks_t *p, void *stream);
+
+typedef struct {
+    int32_t n_lanes, n_pts, n_pred, n_succ;
+    const int32_t *topo_host, *topo_dev;
+    const double *pts;
+} lgcn_lane_table_t;
+typedef struct {
+    int32_t n_scenes, n_tables, n_cand, n_rank, explicit_ids, pad_;
+    double pred_range[4];
+    const lgcn_lane_table_t *tabs_host, *tabs_dev;
+    const int32_t *off_host, *off_dev;
+    const float *frame;
+    int32_t *ws, *head;                                            /* lgcn_scene_lanes_rank */
+    int64_t n_nodes, cap_pre, cap_suc, cap_pre_pairs, cap_suc_pairs, cap_left_pairs, cap_right_pairs;
+    int32_t *head2;                                                /* lgcn_scene_lanes_fill */
+    float *ctrs, *feats, *turn, *control, *intersect;
+    int64_t *lane_idcs, *pre_u, *pre_v, *suc_u, *suc_v, *pre_pairs, *suc_pairs, *left_pairs, *right_pairs;
+} lgcn_scene_lanes_t;
+int64_t lgcn_scene_topo_elems(int64_t n_lanes, int64_t n_pred, int64_t n_succ);
+int64_t lgcn_scene_lanes_ws_elems(int64_t n_cand, int64_t n_rank);
+int lgcn_scene_lanes_rank(const lgcn_scene_lanes_t *p, void *stream);
+int lgcn_scene_lanes_fill(const lgcn_scene_lanes_t *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,6 +183,39 @@ class StoreBatch(C.Structure):    # lgcn_store_batch_t
     ]
 
 
+class SceneTracks(C.Structure):    # lgcn_scene_tracks_t
+    _fields_ = [
+        ("n_scenes", C.c_int32), ("n_tracks", C.c_int32), ("n_rows", C.c_int32), ("pad_", C.c_int32),
+        ("pred_range", C.c_float * 4),
+        ("off_host", C.c_void_p), ("off_dev", C.c_void_p), ("xy", C.c_void_p), ("step", C.c_void_p), ("frame", C.c_void_p),
+        ("ws", C.c_void_p), ("head", C.c_void_p),
+        ("feats", C.c_void_p), ("obs", C.c_void_p), ("ctrs", C.c_void_p), ("gt", C.c_void_p), ("has", C.c_void_p),
+    ]
+
+
+class LaneTableC(C.Structure):     # lgcn_lane_table_t
+    _fields_ = [
+        ("n_lanes", C.c_int32), ("n_pts", C.c_int32), ("n_pred", C.c_int32), ("n_succ", C.c_int32),
+        ("topo_host", C.c_void_p), ("topo_dev", C.c_void_p), ("pts", C.c_void_p),
+    ]
+
+
+class SceneLanes(C.Structure):     # lgcn_scene_lanes_t
+    _fields_ = [
+        ("n_scenes", C.c_int32), ("n_tables", C.c_int32), ("n_cand", C.c_int32), ("n_rank", C.c_int32),
+        ("explicit_ids", C.c_int32), ("pad_", C.c_int32),
+        ("pred_range", C.c_double * 4),
+        ("tabs_host", C.c_void_p), ("tabs_dev", C.c_void_p), ("off_host", C.c_void_p), ("off_dev", C.c_void_p),
+        ("frame", C.c_void_p), ("ws", C.c_void_p), ("head", C.c_void_p),
+        ("n_nodes", C.c_int64), ("cap_pre", C.c_int64), ("cap_suc", C.c_int64), ("cap_pre_pairs", C.c_int64),
+        ("cap_suc_pairs", C.c_int64), ("cap_left_pairs", C.c_int64), ("cap_right_pairs", C.c_int64),
+        ("head2", C.c_void_p),
+        ("ctrs", C.c_void_p), ("feats", C.c_void_p), ("turn", C.c_void_p), ("control", C.c_void_p), ("intersect", C.c_void_p),
+        ("lane_idcs", C.c_void_p), ("pre_u", C.c_void_p), ("pre_v", C.c_void_p), ("suc_u", C.c_void_p), ("suc_v", C.c_void_p),
+        ("pre_pairs", C.c_void_p), ("suc_pairs", C.c_void_p), ("left_pairs", C.c_void_p), ("right_pairs", C.c_void_p),
+    ]
+
+
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 OPT_KINDS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}
 
@@ -286,6 +319,12 @@ SIGNATURES = {
     "lgcn_roi_edge_fill": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_store_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_gather": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
+    "lgcn_scene_tracks_ws_elems": (C.c_int64, [_L]),
+    "lgcn_scene_tracks": (C.c_int, [C.POINTER(SceneTracks), _P]),
+    "lgcn_scene_topo_elems": (C.c_int64, [_L, _L, _L]),
+    "lgcn_scene_lanes_ws_elems": (C.c_int64, [_L, _L]),
+    "lgcn_scene_lanes_rank": (C.c_int, [C.POINTER(SceneLanes), _P]),
+    "lgcn_scene_lanes_fill": (C.c_int, [C.POINTER(SceneLanes), _P]),
 }
 
 _lib = None

@@ -75,6 +75,8 @@ def _pack(scenes):
     not have the packed layout's fields or the pack fails -- Net.forward then collates the dict-of-lists batch itself."""
     if len(scenes) == 0 or not all(k in scenes[0] for k in ("graph", "feats", "ctrs", "rot", "orig")):
         return None
+    if torch.is_tensor(scenes[0]["feats"]) and scenes[0]["feats"].is_cuda:
+        return None      # scenes built on the device (data_raw.build_scenes): nothing to stage on the host
     try:
         from .engine import collate_flat_host, host_actor_inputs
         # pinned staging only in a process that already talks to the GPU (never initialise it in a loader worker)

@@ -2172,3 +2172,132 @@ def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n
             raise L.LgcnError("store_gather: %s must hold %d elements of %s, got %d of %s" % (k, n, dt or "one byte", v.numel(), v.dtype))
         setattr(b, k, v.data_ptr() if n else None)
     L.check(L.load().lgcn_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_store_gather")
+
+
+# ------------------------------------------------------------------ scene construction (data_raw: get_obj_feats / get_lane_graph)
+def _i32_table(off, what):
+    import numpy as np
+    off = np.asarray(off)
+    if off.size and (off.min() < 0 or off.max() > 0x7fffffff):
+        raise L.LgcnError("%s: the batch is too large for 32-bit offsets" % what)
+    return np.ascontiguousarray(off, np.int32)
+
+
+class SceneTracksJob:
+    """One batch's lgcn_scene_tracks_t (reference data.py:148-217) with the tensors it points to.  xy [R,2] float64, step
+    [R] int32, frame [S,6] fp32 (orig, rot) on the device; off: host int32 trk_off [S + 1] then row_off [T + 1]; head: a
+    ZEROED int32 device tensor [S + 2].  The outputs hold T rows; head[S] of them are written."""
+
+    def __init__(self, xy, step, frame, off, pred_range, head):
+        self.xy, self.step = _dev(xy, torch.float64, "scene xy"), _dev(step, torch.int32, "scene step")
+        self.frame, self.head = _dev(frame, torch.float32, "scene frame"), _dev(head, torch.int32, "scene head")
+        S, R = self.frame.shape[0], self.step.numel()
+        self.off = _i32_table(off, "scene_tracks")
+        T = len(self.off) - (S + 1) - 1
+        if T < 0 or tuple(self.xy.shape) != (R, 2) or tuple(self.frame.shape) != (S, 6) or self.head.numel() != S + 2:
+            raise L.LgcnError("scene_tracks: xy [R,2], step [R], frame [S,6], off [S + T + 2], head [S + 2]")
+        dev = self.frame.device
+        self.S, self.T = S, T
+        n_ws = L.load().lgcn_scene_tracks_ws_elems(T)
+        if n_ws < 0:
+            L.check(int(n_ws), "lgcn_scene_tracks_ws_elems")
+        self.ws = torch.empty(int(n_ws), dtype=torch.int32, device=dev)
+        self.off_dev = torch.from_numpy(self.off).to(dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.feats, self.obs = torch.empty((T, 20, 3), **f32), torch.empty((T, 20, 3), **f32)
+        self.ctrs, self.gt = torch.empty((T, 2), **f32), torch.empty((T, 30, 2), **f32)
+        self.has = torch.empty((T, 30), dtype=torch.bool, device=dev)
+        p = self.p = L.SceneTracks()
+        p.n_scenes, p.n_tracks, p.n_rows = S, T, R
+        p.pred_range[:] = [float(x) for x in pred_range]
+        p.off_host, p.off_dev = self.off.ctypes.data, self.off_dev.data_ptr()
+        p.xy, p.step = (self.xy.data_ptr(), self.step.data_ptr()) if R else (None, None)
+        p.frame, p.ws, p.head = self.frame.data_ptr(), self.ws.data_ptr(), self.head.data_ptr()
+        p.feats, p.obs, p.ctrs, p.gt, p.has = (self.feats.data_ptr(), self.obs.data_ptr(), self.ctrs.data_ptr(),
+                                               self.gt.data_ptr(), self.has.data_ptr())
+
+
+def scene_tracks(job: SceneTracksJob):
+    """lgcn_scene_tracks: two launches fill job.feats, obs, ctrs, gt, has (compacted) and job.head."""
+    L.check(L.load().lgcn_scene_tracks(C.byref(job.p), _stream()), "lgcn_scene_tracks")
+
+
+def scene_topo_elems(n_lanes: int, n_pred: int, n_succ: int) -> int:
+    n = int(L.load().lgcn_scene_topo_elems(int(n_lanes), int(n_pred), int(n_succ)))
+    if n < 0:
+        L.check(n, "lgcn_scene_topo_elems")
+    return n
+
+
+class SceneLanesJob:
+    """One batch's lgcn_scene_lanes_t (reference data.py:220-353).  tables: the batch's lane tables, each with n_lanes,
+    n_pts, n_pred, n_succ, topo_host (numpy int32), topo_dev, pts_dev (device tensors); off: host int32 scene_tab [S],
+    cand_off [S + 1], rank_off [S + 1] and, with explicit=True, cand [n_cand]; frame [S,6] fp32 on the device; head: an
+    int32 device tensor [4 (S + 1)]."""
+
+    def __init__(self, tables, off, explicit, frame, pred_range, head):
+        self.frame, self.head = _dev(frame, torch.float32, "scene frame"), _dev(head, torch.int32, "scene head")
+        S = self.frame.shape[0]
+        self.off = _i32_table(off, "scene_lanes")
+        if len(self.off) < 3 * S + 2 or tuple(self.frame.shape) != (S, 6) or self.head.numel() != 4 * (S + 1):
+            raise L.LgcnError("scene_lanes: frame [S,6], off [3 S + 2 (+ n_cand)], head [4 (S + 1)]")
+        dev = self.frame.device
+        self.S, self.tables = S, list(tables)
+        self.tabs = (L.LaneTableC * max(len(self.tables), 1))()
+        for i, tb in enumerate(self.tables):
+            c = self.tabs[i]
+            c.n_lanes, c.n_pts, c.n_pred, c.n_succ = tb.n_lanes, tb.n_pts, tb.n_pred, tb.n_succ
+            _dev(tb.topo_dev, torch.int32, "lane table topo")
+            _dev(tb.pts_dev, torch.float64, "lane table pts")
+            if tb.topo_dev.device != dev or tb.topo_host.size != tb.topo_dev.numel() or tb.pts_dev.numel() != 2 * tb.n_pts \
+                    or tb.topo_host.size != scene_topo_elems(tb.n_lanes, tb.n_pred, tb.n_succ):
+                raise L.LgcnError("scene_lanes: a lane table does not match its sizes or lives on another device")
+            c.topo_host, c.topo_dev = tb.topo_host.ctypes.data, tb.topo_dev.data_ptr()
+            c.pts = tb.pts_dev.data_ptr() if tb.n_pts else None
+        self.tabs_dev = torch.frombuffer(bytearray(bytes(self.tabs)), dtype=torch.uint8).to(dev)
+        self.off_dev = torch.from_numpy(self.off).to(dev)
+        p = self.p = L.SceneLanes()
+        p.n_scenes, p.n_tables, p.explicit_ids = S, len(self.tables), int(bool(explicit))
+        p.n_cand, p.n_rank = (int(self.off[2 * S]), int(self.off[3 * S + 1])) if S else (0, 0)
+        if len(self.off) != 3 * S + 2 + (p.n_cand if explicit else 0):
+            raise L.LgcnError("scene_lanes: the offset table does not match its candidate count")
+        p.pred_range[:] = [float(x) for x in pred_range]
+        p.tabs_host, p.tabs_dev = C.addressof(self.tabs), self.tabs_dev.data_ptr()
+        p.off_host, p.off_dev = self.off.ctypes.data, self.off_dev.data_ptr()
+        n_ws = L.load().lgcn_scene_lanes_ws_elems(p.n_cand, p.n_rank)
+        if n_ws < 0:
+            L.check(int(n_ws), "lgcn_scene_lanes_ws_elems")
+        self.ws = torch.empty(int(n_ws), dtype=torch.int32, device=dev)
+        p.frame, p.ws, p.head = self.frame.data_ptr(), self.ws.data_ptr(), self.head.data_ptr()
+
+
+def scene_lanes_rank(job: SceneLanesJob):
+    """lgcn_scene_lanes_rank: one memset and two launches fill job.head (per scene, then in total: kept lanes, nodes,
+    pred entries, succ entries, as exclusive sums)."""
+    L.check(L.load().lgcn_scene_lanes_rank(C.byref(job.p), _stream()), "lgcn_scene_lanes_rank")
+
+
+def scene_lanes_fill(job: SceneLanesJob, totals, head2: torch.Tensor) -> dict:
+    """lgcn_scene_lanes_fill: two launches write the nodes, pre[0] / suc[0] and the four pair lists of the whole batch.
+    totals = (kept lanes, nodes, pred entries, succ entries) as read from job.head; head2: int32 device [4 (S + 1)].
+    Returns the output tensors, sized by their upper bounds (head2 tells how much of the edge and pair arrays is used)."""
+    p, dev = job.p, job.frame.device
+    n_l, n_n, n_p, n_s = (int(x) for x in totals)
+    job.head2 = _dev(head2, torch.int32, "scene head2")
+    if job.head2.numel() != 4 * (job.S + 1):
+        raise L.LgcnError("scene_lanes_fill: head2 must hold 4 (S + 1) entries")
+    f32, i64 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int64, device=dev)
+    o = job.out = dict(
+        ctrs=torch.empty((n_n, 2), **f32), feats=torch.empty((n_n, 2), **f32), turn=torch.empty((n_n, 2), **f32),
+        control=torch.empty(n_n, **f32), intersect=torch.empty(n_n, **f32), lane_idcs=torch.empty(n_n, **i64),
+        pre_u=torch.empty(n_n - n_l + n_p, **i64), pre_v=torch.empty(n_n - n_l + n_p, **i64),
+        suc_u=torch.empty(n_n - n_l + n_s, **i64), suc_v=torch.empty(n_n - n_l + n_s, **i64),
+        pre_pairs=torch.empty((n_p, 2), **i64), suc_pairs=torch.empty((n_s, 2), **i64),
+        left_pairs=torch.empty((n_l, 2), **i64), right_pairs=torch.empty((n_l, 2), **i64))
+    p.n_nodes, p.cap_pre, p.cap_suc = n_n, n_n - n_l + n_p, n_n - n_l + n_s
+    p.cap_pre_pairs, p.cap_suc_pairs, p.cap_left_pairs, p.cap_right_pairs = n_p, n_s, n_l, n_l
+    p.head2 = job.head2.data_ptr()
+    for k, v in o.items():
+        setattr(p, k, v.data_ptr() if v.numel() else None)
+    L.check(L.load().lgcn_scene_lanes_fill(C.byref(p), _stream()), "lgcn_scene_lanes_fill")
+    return o

@@ -1244,6 +1244,16 @@ int lgcn_roi_edge_fill(const lgcn_roi_t *p, void *stream);
  * (LGCN_ESHAPE); pointers not aligned to 16 bytes ([.,2] arrays, rot, orig, the int64 arrays, tab_dev), 8 bytes (tab_host)
  * or 4 bytes (the rest but has_preds) (LGCN_EALIGN).  n_scenes == 0 with all totals 0 returns LGCN_OK without a launch.
  * lgcn_store_table_elems: LGCN_EINVAL for a negative argument, LGCN_ESHAPE beyond 2^31 - 1 elements.
+ *
+ * lgcn_store_gather_aug: the same launch (the same kernel body, its other instantiation) with the reference's training
+ * rotation (data.py:45-63) applied on the way through.  aug_host / aug_dev: [B, 8] fp32, the same words on the host
+ * (validated) and on the device (read by the kernel, 16-byte aligned); per picked scene Rm row-major, then rot'
+ * row-major.  Every row (x, y) of node_ctrs, node_feats, actor_ctrs and of channels 0 / 1 of actor_feats becomes
+ * (x Rm00 + y Rm10, x Rm01 + y Rm11): two fp32 products, each rounded, one fp32 add, no FMA.  rot [n_actors,2,2] is rot'
+ * of the actor's pick instead of the store's; a scene picked twice is turned by the angle of each pick.  Everything
+ * else is lgcn_store_gather's output, byte for byte.  Checked first: all that lgcn_store_gather checks, with the same
+ * codes; then aug_host or aug_dev NULL, a non-finite entry of aug_host (LGCN_EINVAL), aug_dev not 16-byte aligned
+ * (LGCN_EALIGN).  n_scenes == 0 returns as lgcn_store_gather does, without looking at the tables.
  */
 typedef struct {
     int64_t n_scenes, n_nodes, n_actors, n_edges;
@@ -1264,6 +1274,8 @@ typedef struct {
 } lgcn_store_batch_t;
 int64_t lgcn_store_table_elems(int64_t n_scenes, int64_t n_rel);
 int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream);
+int lgcn_store_gather_aug(const lgcn_store_t *s, const lgcn_store_batch_t *b, const float *aug_host, const float *aug_dev,
+                          void *stream);
 
 /*
  * Scene construction for a BATCH of raw scenes (lanegcn_amd/data_raw.py): tracks to actor arrays

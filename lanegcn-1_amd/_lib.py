@@ -319,6 +319,7 @@ SIGNATURES = {
     "lgcn_roi_edge_fill": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_store_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_gather": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
+    "lgcn_store_gather_aug": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P, _P, _P]),
     "lgcn_scene_tracks_ws_elems": (C.c_int64, [_L]),
     "lgcn_scene_tracks": (C.c_int, [C.POINTER(SceneTracks), _P]),
     "lgcn_scene_topo_elems": (C.c_int64, [_L, _L, _L]),

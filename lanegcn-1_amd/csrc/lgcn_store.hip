@@ -5,6 +5,11 @@
 // finds the picked scene / index segment of its item by binary search in the per-batch table, so neither the number
 // of scenes nor the number of segments is bounded by a wave or an LDS array.  Every source run is contiguous per scene
 // and threads of a wave hold consecutive items: reads and writes are coalesced but for the run boundaries.
+//
+// lgcn_store_gather_aug is the same kernel body (k_store_gather<true>) with the reference's training rotation on the way
+// through: coordinates are turned by the pick's Rm, rot comes from the per-batch table instead of the store.
+#include <cmath>
+
 #include "lgcn_common.hpp"
 
 namespace lgcn {
@@ -51,8 +56,21 @@ __device__ __forceinline__ int store_find(const int64_t *__restrict__ off, int n
     return lo;
 }
 
+// one picked scene's entry of the augmentation table: Rm row-major, then rot' row-major (include/lgcn.h)
+struct StoreAug {
+    float4 rm, rot;
+};
+
+// (x, y) Rm as the project fixes it: two fp32 products, each rounded, one fp32 add, never fused
+__device__ __forceinline__ float2 store_turn(float2 p, float4 rm) {
+    return make_float2(__fadd_rn(__fmul_rn(p.x, rm.x), __fmul_rn(p.y, rm.z)),
+                       __fadd_rn(__fmul_rn(p.x, rm.y), __fmul_rn(p.y, rm.w)));
+}
+
+// AUG = false is lgcn_store_gather (aug is not read); AUG = true turns the picked scene j by aug[j] on the way through
+template <bool AUG>
 __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store_t s, const lgcn_store_batch_t b,
-                                                                const StoreGrid g) {
+                                                                const StoreGrid g, const StoreAug *__restrict__ aug) {
     const int B = b.n_scenes;
     const int64_t G = 2 * (int64_t)b.n_rel * B;
     const StoreTab t = store_tab(b.tab_dev, B, G);
@@ -65,8 +83,14 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         if (i >= b.n_nodes) return;
         const int j = store_find(t.node_off, B, i);
         const int64_t r = t.node_src[j] + (i - t.node_off[j]);
-        reinterpret_cast<float2 *>(b.node_ctrs)[i] = reinterpret_cast<const float2 *>(s.node_ctrs)[r];
-        reinterpret_cast<float2 *>(b.node_feats)[i] = reinterpret_cast<const float2 *>(s.node_feats)[r];
+        if constexpr (AUG) {
+            const float4 rm = aug[j].rm;
+            reinterpret_cast<float2 *>(b.node_ctrs)[i] = store_turn(reinterpret_cast<const float2 *>(s.node_ctrs)[r], rm);
+            reinterpret_cast<float2 *>(b.node_feats)[i] = store_turn(reinterpret_cast<const float2 *>(s.node_feats)[r], rm);
+        } else {
+            reinterpret_cast<float2 *>(b.node_ctrs)[i] = reinterpret_cast<const float2 *>(s.node_ctrs)[r];
+            reinterpret_cast<float2 *>(b.node_feats)[i] = reinterpret_cast<const float2 *>(s.node_feats)[r];
+        }
         reinterpret_cast<float2 *>(b.turn)[i] = reinterpret_cast<const float2 *>(s.turn)[r];
         b.control[i] = s.control[r];
         b.intersect[i] = s.intersect[r];
@@ -75,8 +99,13 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         const int j = store_find(t.actor_off, B, i);
         const int64_t r = t.actor_src[j] + (i - t.actor_off[j]);
         const int64_t sc = t.scene[j];
-        reinterpret_cast<float2 *>(b.actor_ctrs)[i] = reinterpret_cast<const float2 *>(s.actor_ctrs)[r];
-        reinterpret_cast<float4 *>(b.rot)[i] = reinterpret_cast<const float4 *>(s.rot)[sc];
+        if constexpr (AUG) {
+            reinterpret_cast<float2 *>(b.actor_ctrs)[i] = store_turn(reinterpret_cast<const float2 *>(s.actor_ctrs)[r], aug[j].rm);
+            reinterpret_cast<float4 *>(b.rot)[i] = aug[j].rot;
+        } else {
+            reinterpret_cast<float2 *>(b.actor_ctrs)[i] = reinterpret_cast<const float2 *>(s.actor_ctrs)[r];
+            reinterpret_cast<float4 *>(b.rot)[i] = reinterpret_cast<const float4 *>(s.rot)[sc];
+        }
         reinterpret_cast<float2 *>(b.orig)[i] = reinterpret_cast<const float2 *>(s.orig)[sc];
     } else if (kind == 2) {               // one of an actor's 60 floats: actor_feats [20,3] -> [3,20], gt_preds, has_preds
         if (i >= b.n_actors * kActorRow) return;
@@ -85,7 +114,13 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         const int j = store_find(t.actor_off, B, a);
         const int64_t r = t.actor_src[j] + (a - t.actor_off[j]);
         const int c = e / 20, step = e - c * 20;
-        b.actor_feats[i] = s.actor_feats[r * kActorRow + step * 3 + c];
+        if (AUG && c < 2) {                // channels 0 / 1 are the step's (x, y): both are read, one component is written
+            const float *xy = s.actor_feats + r * kActorRow + step * 3;
+            const float2 q = store_turn(make_float2(xy[0], xy[1]), aug[j].rm);
+            b.actor_feats[i] = c == 0 ? q.x : q.y;
+        } else {
+            b.actor_feats[i] = s.actor_feats[r * kActorRow + step * 3 + c];
+        }
         if (s.gt_preds != nullptr) {
             b.gt_preds[i] = s.gt_preds[r * kActorRow + e];
             if (e < kHasRow) b.has_preds[a * kHasRow + e] = s.has_preds[r * kHasRow + e];
@@ -198,8 +233,22 @@ int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *
     StoreGrid grid;
     if (int rc = store_validate(s, b, &grid)) return rc;
     if (b->n_scenes == 0) return LGCN_OK;
-    hipLaunchKernelGGL(k_store_gather, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream), *s, *b,
-                       grid);
+    hipLaunchKernelGGL(k_store_gather<false>, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
+                       *s, *b, grid, static_cast<const StoreAug *>(nullptr));
+    return launch_status();
+}
+
+int lgcn_store_gather_aug(const lgcn_store_t *s, const lgcn_store_batch_t *b, const float *aug_host, const float *aug_dev,
+                          void *stream) {
+    StoreGrid grid;
+    if (int rc = store_validate(s, b, &grid)) return rc;
+    if (b->n_scenes == 0) return LGCN_OK;
+    LGCN_CHECK_PTR(aug_host); LGCN_CHECK_PTR(aug_dev);
+    for (int64_t k = 0; k < 8 * (int64_t)b->n_scenes; ++k)
+        if (!std::isfinite(aug_host[k])) return LGCN_EINVAL;
+    LGCN_CHECK_ALIGN16(aug_dev);
+    hipLaunchKernelGGL(k_store_gather<true>, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
+                       *s, *b, grid, reinterpret_cast<const StoreAug *>(aug_dev));
     return launch_status();
 }
 

@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from . import lanegcn as M
+from ._lib import LgcnError
 
 
 @dataclass
@@ -42,9 +43,25 @@ class FlatBatch:
     cap_a2a: int                # sum_i a_i * a_i
     n_edges: List[int]
     _buf: Optional[torch.Tensor] = None     # the one device byte buffer the arrays are views of (collate_flat)
+    node_sizes: Optional[List[int]] = None  # nodes per scene, on the host (what flat_graph splits by)
 
     def buf_view(self) -> Optional[torch.Tensor]:
         return self._buf
+
+
+def flat_graph(fb: FlatBatch) -> Dict:
+    """The dict lanegcn.graph_gather returns (idcs, ctrs per scene; feats, turn, control, intersect; pre, suc, left,
+    right with int64 global u / v), out of a FlatBatch: one lgcn_graph_gather launch over idx_local, then views.  No
+    per-segment host work, no upload and no read-back -- the per-scene sizes are the batch's host-side node_sizes."""
+    if fb.node_sizes is None:
+        raise LgcnError("flat_graph: the FlatBatch carries no node_sizes (collate_flat and the scene stores set it)")
+    g64, _ = ops.graph_gather_indices(fb.idx_local, fb.seg_off, fb.seg_base)
+    sizes, ns = list(fb.node_sizes), fb.num_scales
+    rel = [{"u": g64[a:b], "v": g64[c:d]} for (a, b), (c, d) in fb.rel_slices]
+    return {"idcs": list(torch.split(torch.arange(fb.n_nodes, device=fb.node_ctrs.device), sizes)),
+            "ctrs": list(torch.split(fb.node_ctrs, sizes)), "feats": fb.node_feats, "turn": fb.turn, "control": fb.control,
+            "intersect": fb.intersect, "pre": rel[0:2 * ns:2], "suc": rel[1:2 * ns:2], "left": rel[2 * ns],
+            "right": rel[2 * ns + 1]}
 
 
 _FLAT_ARRAYS = ("node_ctrs", "node_feats", "turn", "control", "intersect", "actor_ctrs", "node_off", "actor_off",
@@ -142,7 +159,7 @@ def collate_flat_host(scenes: List[Dict], pin: Optional[bool] = None) -> HostFla
         view[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
     meta = dict(n_scenes=B, n_nodes=int(node_off[-1]), n_actors=int(actor_off[-1]), num_scales=ns,
                 rel_slices=rel_slices, cap_a2m=int(np.dot(n_nodes, n_act)), cap_a2a=int(np.dot(n_act, n_act)),
-                n_edges=n_edges)
+                n_edges=n_edges, node_sizes=n_nodes.tolist())
     return HostFlatBatch(buf, layout, meta)
 
 

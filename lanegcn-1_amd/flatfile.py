@@ -10,11 +10,13 @@ Layout (S scenes, R = 2 * num_scales + 2 relations in the order pre0, suc0, ...,
   node_ctrs, node_feats, turn [N,2]; control, intersect [N]     float32
   actor_ctrs [A,2], actor_feats [A,20,3], rot [S,2,2], orig [S,2]   float32
   gt_preds [A,30,2] float32, has_preds [A,30] bool
+  theta [S] float64, only with write_scenes(..., theta=True): the scenes' headings, for the rotation augmentation
   edge_off [R, S+1] int64: edges of relation r of scene s are  u[r][edge_off[r,s]:edge_off[r,s+1]]
   edge_u, edge_v [sum E] int32 (scene-local node indices), stored relation-major: rel_off [R+1]
 
 FlatSceneFile cuts a batch on the host.  DeviceSceneStore keeps the arrays in device memory and cuts the same batch
-there with one launch; plan_batch is its host half.
+there with one launch; plan_batch is its host half.  With `rot_dt` both turn the picked scenes as the
+reference's rot_aug does (data.py:39-65), the device store inside that same launch.
 """
 from dataclasses import dataclass
 from typing import Dict, List, Sequence
@@ -40,8 +42,9 @@ def _relations(graph) -> List[Dict]:
     return rels + [graph["left"], graph["right"]]
 
 
-def write_scenes(path: str, scenes: Sequence[Dict]) -> None:
-    """Write scene dicts (reference schema) as one flat store."""
+def write_scenes(path: str, scenes: Sequence[Dict], theta: bool = False) -> None:
+    """Write scene dicts (reference schema) as one flat store.  theta: also keep every scene's heading `theta` [S]
+    float64, which the training rotation (rot_aug_tables) starts from."""
     S = len(scenes)
     graphs = [s["graph"] for s in scenes]
     R = 2 * len(graphs[0]["pre"]) + 2
@@ -74,7 +77,51 @@ def write_scenes(path: str, scenes: Sequence[Dict]) -> None:
     if "gt_preds" in scenes[0]:
         out["gt_preds"] = cat([_npy(s["gt_preds"]) for s in scenes], np.float32)
         out["has_preds"] = cat([_npy(s["has_preds"]) for s in scenes], bool)
+    if theta:
+        out["theta"] = np.array([float(s["theta"]) for s in scenes], np.float64)
     np.savez(path, **out)
+
+
+def rot_aug_tables(theta, dt):
+    """The reference's training rotation (data.py:45-54) of B picked scenes with headings `theta`, turned by `dt` (both
+    float64 [B]) -> (theta' = theta + dt float64 [B], aug float32 [B, 8]): per scene Rm = the rotation by -dt, row-major,
+    then rot' = the rotation by theta', row-major -- each entry a float64 cos / sin rounded to float32, as the reference
+    forms them.  The table lgcn_store_gather_aug reads."""
+    theta, dt = np.asarray(theta, np.float64).reshape(-1), np.asarray(dt, np.float64).reshape(-1)
+    new = theta + dt
+    aug = np.empty((len(dt), 8), np.float32)
+    aug[:, 0], aug[:, 1], aug[:, 2], aug[:, 3] = np.cos(-dt), -np.sin(-dt), np.sin(-dt), np.cos(-dt)
+    aug[:, 4], aug[:, 5], aug[:, 6], aug[:, 7] = np.cos(new), -np.sin(new), np.sin(new), np.cos(new)
+    return new, aug
+
+
+def draw_rot_dt(n: int, rot_size: float, rng=None) -> np.ndarray:
+    """`n` angles rand() * rot_size (data.py:45), one per picked scene in pick order.  rng=None draws from np.random, one
+    np.random.rand() per scene: a seeded global generator gives the reference's sequence for scenes visited in that
+    order.  Otherwise `rng` is a np.random.Generator."""
+    if rng is None:
+        return np.array([np.random.rand() * rot_size for _ in range(int(n))], np.float64)
+    return rng.random(int(n)) * rot_size
+
+
+def _pick_aug(theta, idx, rot_dt):
+    """The rot_dt rules of both batch() methods, before anything is launched -> rot_aug_tables of the pick."""
+    try:
+        dt = np.asarray(rot_dt, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("store: rot_dt must be a sequence of finite floats") from None
+    if dt.ndim != 1 or len(dt) != len(idx) or not np.isfinite(dt).all():
+        raise ValueError("store: rot_dt must hold one finite angle per picked scene (%d)" % len(idx))
+    if theta is None:
+        raise LgcnError("store: rot_dt needs the scenes' theta; write the store with write_scenes(..., theta=True)")
+    return rot_aug_tables(theta[np.asarray(idx, np.int64)], dt)
+
+
+def _turn(xy: np.ndarray, rm: np.ndarray) -> np.ndarray:
+    """Rows (x, y) of float32 `xy` [..., 2] times Rm (`rm` [..., 4] row-major, broadcast): two rounded float32 products
+    and one float32 add per output -- the arithmetic of the gather kernel, bit for bit."""
+    x, y = xy[..., 0], xy[..., 1]
+    return np.stack([x * rm[..., 0] + y * rm[..., 2], x * rm[..., 1] + y * rm[..., 3]], -1)
 
 
 class FlatSceneFile:
@@ -85,6 +132,7 @@ class FlatSceneFile:
             self.a = {k: z[k] for k in z.files}
         self.n_scenes = len(self.a["node_off"]) - 1
         self.num_scales = int(self.a["num_scales"])
+        self.theta = np.asarray(self.a["theta"], np.float64) if "theta" in self.a else None
 
     def __len__(self):
         return self.n_scenes
@@ -92,11 +140,14 @@ class FlatSceneFile:
     def _rows(self, off, idx):
         return np.concatenate([np.arange(off[i], off[i + 1]) for i in idx]) if len(idx) else np.zeros(0, np.int64)
 
-    def batch(self, indices: Sequence[int], device=None):
+    def batch(self, indices: Sequence[int], device=None, rot_dt=None):
         """-> (FlatBatch, extras) with extras = {actor_feats [A,3,20], rot [A,2,2], orig [A,2], sizes,
-        gt_preds, has_preds}: everything FullNetEngine / HotPathEngine need, no per-scene dicts."""
+        gt_preds, has_preds}: everything FullNetEngine / HotPathEngine need, no per-scene dicts.
+        rot_dt: one angle per picked scene; the scenes come out turned as the reference's rot_aug turns them
+        (rot_aug_tables, _turn), rot is rot' and extras["theta"] holds the new headings (host float64 [B])."""
         a = self.a
         idx = list(indices)
+        theta_new, aug = (None, None) if rot_dt is None else _pick_aug(self.theta, idx, rot_dt)
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
         n_nodes = np.array([a["node_off"][i + 1] - a["node_off"][i] for i in idx], np.int64)
@@ -124,19 +175,30 @@ class FlatSceneFile:
             n_edges.append(spans[0][1] - spans[0][0])
         seg_off = np.zeros(len(seg_len) + 1, np.int64)
         np.cumsum(seg_len, out=seg_off[1:])
+        rep = np.repeat(np.asarray(idx), n_act)
+        node_ctrs, node_feats, actor_ctrs = a["node_ctrs"][nrow], a["node_feats"][nrow], a["actor_ctrs"][arow]
+        actor_feats, rot = a["actor_feats"][arow], a["rot"][rep]
+        if aug is not None:
+            by_node, by_actor = np.repeat(aug, n_nodes, 0), np.repeat(aug, n_act, 0)
+            node_ctrs, node_feats = _turn(node_ctrs, by_node[:, :4]), _turn(node_feats, by_node[:, :4])
+            actor_ctrs = _turn(actor_ctrs, by_actor[:, :4])
+            actor_feats[:, :, :2] = _turn(actor_feats[:, :, :2], by_actor[:, None, :4])     # (fancy indexing made a copy)
+            rot = by_actor[:, 4:].reshape(-1, 2, 2)
         fb = FlatBatch(
             n_scenes=len(idx), n_nodes=int(node_off[-1]), n_actors=int(actor_off[-1]), num_scales=self.num_scales,
-            node_ctrs=up(a["node_ctrs"][nrow]), node_feats=up(a["node_feats"][nrow]), turn=up(a["turn"][nrow]),
-            control=up(a["control"][nrow]), intersect=up(a["intersect"][nrow]), actor_ctrs=up(a["actor_ctrs"][arow]),
+            node_ctrs=up(node_ctrs), node_feats=up(node_feats), turn=up(a["turn"][nrow]),
+            control=up(a["control"][nrow]), intersect=up(a["intersect"][nrow]), actor_ctrs=up(actor_ctrs),
             node_off=up(node_off.astype(np.int32)), actor_off=up(actor_off.astype(np.int32)),
             idx_local=up(np.concatenate(pieces) if pieces else np.zeros(0, np.int64)), seg_off=up(seg_off),
             seg_base=up(np.asarray(seg_base, np.int64)), rel_slices=rel_slices,
-            cap_a2m=int(np.dot(n_nodes, n_act)), cap_a2a=int(np.dot(n_act, n_act)), n_edges=n_edges)
-        rep = np.repeat(np.asarray(idx), n_act)
-        extras = {"actor_feats": up(a["actor_feats"][arow].transpose(0, 2, 1)), "rot": up(a["rot"][rep]),
+            cap_a2m=int(np.dot(n_nodes, n_act)), cap_a2a=int(np.dot(n_act, n_act)), n_edges=n_edges,
+            node_sizes=n_nodes.tolist())
+        extras = {"actor_feats": up(actor_feats.transpose(0, 2, 1)), "rot": up(rot),
                   "orig": up(a["orig"][rep]), "sizes": [int(x) for x in n_act]}
         if "gt_preds" in a:
             extras["gt_preds"], extras["has_preds"] = up(a["gt_preds"][arow]), up(a["has_preds"][arow])
+        if aug is not None:
+            extras["theta"] = theta_new
         return fb, extras
 
 
@@ -249,7 +311,8 @@ class DeviceSceneStore:
     byte.  The offset tables stay on the host (numpy); `plan(indices)` is the host half and needs no GPU."""
 
     def __init__(self, source, device=None):
-        a = (source if isinstance(source, FlatSceneFile) else FlatSceneFile(source)).a
+        source = source if isinstance(source, FlatSceneFile) else FlatSceneFile(source)
+        a, self.theta = source.a, source.theta       # theta stays on the host, next to the offset tables
         self.n_scenes = len(a["node_off"]) - 1
         self.num_scales = int(a["num_scales"])
         self.node_off, self.actor_off = np.asarray(a["node_off"], np.int64), np.asarray(a["actor_off"], np.int64)
@@ -270,15 +333,22 @@ class DeviceSceneStore:
     def __len__(self):
         return self.n_scenes
 
+    @property
+    def has_gt(self) -> bool:
+        """Whether the store holds gt_preds / has_preds (a training step needs them)."""
+        return self._job.has_gt
+
     def plan(self, indices) -> StorePlan:
         return plan_batch(self.node_off, self.actor_off, self.edge_off, self.rel_off, self.num_scales, indices)
 
-    def batch(self, indices, plan: StorePlan = None):
-        """-> (FlatBatch, extras) as FlatSceneFile.batch(indices, device) returns them.  The FlatBatch arrays are views
-        of one device byte buffer (`buf_view()`) at the 256-byte aligned offsets of engine.HostFlatBatch; the extras are
-        views of a second one.  `plan`: this pick's plan(), if the caller already has it."""
+    def batch(self, indices, plan: StorePlan = None, rot_dt=None):
+        """-> (FlatBatch, extras) as FlatSceneFile.batch(indices, device, rot_dt) returns them.  The FlatBatch arrays are
+        views of one device byte buffer (`buf_view()`) at the 256-byte aligned offsets of engine.HostFlatBatch; the extras
+        are views of a second one.  `plan`: this pick's plan(), if the caller already has it.  `rot_dt`: one angle per
+        picked scene; the rotation happens inside the same launch, and its table rides in the offset table's upload."""
         p = self.plan(indices) if plan is None else plan
         B, N, A, E, G = p.n_scenes, p.n_nodes, p.n_actors, p.n_elem, p.n_seg
+        theta_new, aug = (None, None) if rot_dt is None else _pick_aug(self.theta, p.table[4 * B + 2:5 * B + 2], rot_dt)
         f32, i32, i64 = torch.float32, torch.int32, torch.int64
         flat = (("node_ctrs", f32, (N, 2)), ("node_feats", f32, (N, 2)), ("turn", f32, (N, 2)), ("control", f32, (N,)),
                 ("intersect", f32, (N,)), ("actor_ctrs", f32, (A, 2)), ("node_off", i32, (B + 1,)),
@@ -290,16 +360,29 @@ class DeviceSceneStore:
         with torch.cuda.device(self.device):
             # the table goes through pinned memory of its own: the host allocator hands a block out again only after the
             # copies queued from it have run, so back-to-back calls never share staging
-            stage = torch.empty(p.table.size, dtype=i64, pin_memory=True)
-            stage.numpy()[:] = p.table
-            tab_dev = torch.empty(p.table.size, dtype=i64, device=self.device)
+            # the rotation table, 8 floats = 4 int64 words per scene, rides behind the offset table (from an even word on:
+            # 16-byte aligned): still one upload and one launch per batch
+            T = p.table.size
+            at = T + (T & 1)
+            words = T if aug is None else at + 4 * B
+            stage = torch.empty(words, dtype=i64, pin_memory=True)
+            stage.numpy()[:T] = p.table
+            tab_dev = torch.empty(words, dtype=i64, device=self.device)
+            tabs = (stage, tab_dev, None, None)
+            if aug is not None:
+                stage.numpy()[T:at] = 0
+                tabs = (stage[:T], tab_dev[:T], stage[at:].view(f32), tab_dev[at:].view(f32))
+                tabs[2].numpy()[:] = aug.reshape(-1)
             tab_dev.copy_(stage, non_blocking=True)
             fbuf, out = _carve(flat, self.device)
             out.update(_carve(extra, self.device)[1])
-            ops.store_gather(self._job, stage, tab_dev, B, p.n_rel, N, A, E, out)
+            ops.store_gather(self._job, tabs[0], tabs[1], B, p.n_rel, N, A, E, out, tabs[2], tabs[3])
         fb = FlatBatch(n_scenes=B, n_nodes=N, n_actors=A, num_scales=p.num_scales, rel_slices=p.rel_slices,
                        cap_a2m=p.cap_a2m, cap_a2a=p.cap_a2a, n_edges=p.n_edges, _buf=fbuf,
+                       node_sizes=np.diff(p.node_off).tolist(),
                        **{n: out[n] for n in _FLAT_ARRAYS})
         extras = {n: out[n] for n, _, _ in extra}
         extras["sizes"] = list(p.sizes)
+        if aug is not None:
+            extras["theta"] = theta_new
         return fb, extras

@@ -1083,6 +1083,48 @@ class Net(nn.Module):
             out = eng.forward(fb, feats, rot, orig, sizes, return_pairs=Att.strict)
             return self._finish_inference(eng, fb, out, feats, rot, orig, sizes)
 
+    def forward_store_train(self, store, indices, rot_dt=None):
+        """Training forward of the scenes `indices` of a flatfile.DeviceSceneStore -> (out, data): the modules of
+        forward(data)'s grad branch in the same order, fed with the flat tensors of the store's batch (one launch; with
+        `rot_dt`, one angle per pick, turned inside it as the reference's rot_aug turns a scene) -- no scene dicts, no
+        actor_gather / graph_gather / utils.gpu.  `out`: per-scene cls / reg lists in world coordinates, recorded by
+        autograd.  `data`: what Loss.forward reads (gt_preds, has_preds: per-scene lists of device views) and the frame
+        (rot, orig per scene -- None for a scene without actors, which has no row in the batch -- and ctrs).  Errors as
+        forward_store's, decided from the plan before any launch; a store without gt_preds raises LgcnError."""
+        from .engine import flat_graph
+        plan = store.plan(indices)
+        ns = plan.num_scales
+        if plan.n_nodes == 0 or plan.n_edges[2 * ns - 2] == 0 or plan.n_edges[2 * ns - 1] == 0:
+            raise KeyError("node_idcs")
+        if plan.n_actors == 0:
+            raise L.LgcnError("forward_store_train: the picked scenes hold no actor")
+        if not store.has_gt:
+            raise L.LgcnError("forward_store_train: the store holds no gt_preds / has_preds to train against")
+        fb, ex = store.batch(indices, plan=plan, rot_dt=rot_dt)
+        sizes = ex["sizes"]
+        actor_idcs = list(torch.split(torch.arange(fb.n_actors, device=fb.actor_ctrs.device), sizes))
+        actor_ctrs = list(torch.split(fb.actor_ctrs, sizes))
+        actors = self.actor_net(ex["actor_feats"])
+        graph = flat_graph(fb)
+        nodes, node_idcs, node_ctrs = self.map_net(graph)
+        nodes = self.a2m(nodes, graph, actors, actor_idcs, actor_ctrs)
+        nodes = self.m2m(nodes, graph)
+        actors = self.m2a(actors, actor_idcs, actor_ctrs, nodes, node_idcs, node_ctrs)
+        actors = self.a2a(actors, actor_idcs, actor_ctrs)
+        out = self.pred_net(actors, actor_idcs, actor_ctrs)
+        # the scene's rot / orig: the row of its first actor (the batch holds them per actor)
+        first = plan.actor_off[:-1].tolist()
+        rot = [ex["rot"][o] if n else None for o, n in zip(first, sizes)]
+        orig = [ex["orig"][o] if n else None for o, n in zip(first, sizes)]
+        for i in range(len(out["reg"])):        # back to world coordinates, as forward(data) does
+            if sizes[i]:
+                out["reg"][i] = torch.matmul(out["reg"][i], rot[i]) + orig[i].view(1, 1, 1, -1)
+        data = {"gt_preds": list(torch.split(ex["gt_preds"], sizes)), "has_preds": list(torch.split(ex["has_preds"], sizes)),
+                "rot": rot, "orig": orig, "ctrs": actor_ctrs}
+        if "theta" in ex:
+            data["theta"] = ex["theta"]
+        return out, data
+
 
 def _tree_cpu(x):
     if isinstance(x, dict):

@@ -2138,13 +2138,23 @@ class StoreJob:
 
 
 def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n_scenes: int, n_rel: int, n_nodes: int,
-                 n_actors: int, n_elem: int, out: dict) -> None:
+                 n_actors: int, n_elem: int, out: dict, aug_host: torch.Tensor = None, aug_dev: torch.Tensor = None) -> None:
     """lgcn_store_gather: one launch on the current stream fills ``out`` (name -> device tensor, the output fields of
     lgcn_store_batch_t) with the batch that the table describes.  ``tab_host``: the int64 table on the host, validated by
     the library before the launch; ``tab_dev``: the same words on the device (the caller has queued the copy on the
-    current stream)."""
+    current stream).  ``aug_host`` / ``aug_dev``: both or neither; the [n_scenes, 8] fp32 rotation table of
+    lgcn_store_gather_aug on the host and on the device -- the same launch, with the scenes turned on the way through."""
     if tab_host.is_cuda or tab_host.dtype != torch.int64 or not tab_host.is_contiguous():
         raise L.LgcnError("store_gather: tab_host must be a contiguous int64 host tensor")
+    if (aug_host is None) != (aug_dev is None):
+        raise L.LgcnError("store_gather: aug_host and aug_dev come together")
+    if aug_host is not None:
+        if aug_host.is_cuda or aug_host.dtype != torch.float32 or not aug_host.is_contiguous():
+            raise L.LgcnError("store_gather: aug_host must be a contiguous float32 host tensor")
+        aug_dev = _dev(aug_dev, torch.float32, "store aug_dev")
+        if aug_dev.device != job.device or aug_host.numel() != 8 * n_scenes or aug_dev.numel() != 8 * n_scenes:
+            raise L.LgcnError("store_gather: the rotation table must hold [n_scenes, 8] floats on the host and on the "
+                              "store's device")
     tab_dev = _dev(tab_dev, torch.int64, "store tab_dev")
     if tab_dev.device != job.device or tab_dev.device.index != torch.cuda.current_device():
         raise L.LgcnError("store_gather: the store lives on %s, which is not the current device" % (job.device,))
@@ -2171,7 +2181,11 @@ def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n
         if v.numel() != n or (v.dtype != dt if dt is not None else v.element_size() != 1):
             raise L.LgcnError("store_gather: %s must hold %d elements of %s, got %d of %s" % (k, n, dt or "one byte", v.numel(), v.dtype))
         setattr(b, k, v.data_ptr() if n else None)
-    L.check(L.load().lgcn_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_store_gather")
+    if aug_host is None:
+        L.check(L.load().lgcn_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_store_gather")
+    else:
+        L.check(L.load().lgcn_store_gather_aug(C.byref(job.p), C.byref(b), aug_host.data_ptr(), aug_dev.data_ptr(), _stream()),
+                "lgcn_store_gather_aug")
 
 
 # ------------------------------------------------------------------ scene construction (data_raw: get_obj_feats / get_lane_graph)

@@ -41,6 +41,22 @@ def batches(dataset, collate_fn, batch_size, rank, world, seed, epoch, shuffle=T
         yield collate_fn([dataset[j] for j in idx[i:i + batch_size]])
 
 
+def store_picks(n_scenes, batch_size, rank, world, seed, epoch):
+    """The scene indices of every batch of `batches` (the same D.shard schedule), for a resident store of n_scenes."""
+    idx = D.shard(n_scenes, rank, world, seed=seed, epoch=epoch, shuffle=True, drop_last=True)
+    for i in range(0, len(idx) - batch_size + 1, batch_size):
+        yield idx[i:i + batch_size]
+
+
+def first_rows_on_host(data):
+    """What PostProcess reads of a store batch: the first actor row per scene of gt_preds / has_preds (device views), each
+    copied to the host once per step -> per-scene lists of host tensors (an empty one for a scene without actors)."""
+    counts = [min(len(x), 1) for x in data["gt_preds"]]
+    gt = torch.cat([x[0:1] for x in data["gt_preds"]]).cpu()
+    has = torch.cat([x[0:1] for x in data["has_preds"]]).cpu()
+    return {"gt_preds": list(torch.split(gt, counts)), "has_preds": list(torch.split(has, counts))}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="LaneGCN training on MI355X (RCCL data parallel)")
     ap.add_argument("-m", "--model", default="lanegcn_mi355x", type=str, metavar="MODEL", help="model plugin module")
@@ -51,6 +67,11 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=0, help="override config['batch_size']")
     ap.add_argument("--save-dir", default="", help="override config['save_dir']")
     ap.add_argument("--dataset-len", type=int, default=0, help="synthetic dataset length override")
+    ap.add_argument("--store", default="", type=str, metavar="PATH",
+                    help="train from this flat store (flatfile.write_scenes), resident on the device; validation keeps the dataset")
+    ap.add_argument("--rot-size", type=float, default=None, metavar="X",
+                    help="turn every picked scene by rand() * X per step (needs a store written with theta=True); default: "
+                         "config['rot_size'] when config['rot_aug'] is set, else no augmentation")
     args = ap.parse_args(argv)
 
     rank, world, local_rank = D.env_ranks()
@@ -80,6 +101,14 @@ def main(argv=None):
 
     kw = {"length": args.dataset_len} if args.dataset_len else {}
     dataset = Dataset(config.get("train_split"), config, train=True, **kw)
+    store, rot_size = None, None
+    if args.store and not args.eval:
+        from lanegcn_amd.flatfile import DeviceSceneStore, draw_rot_dt
+        store = DeviceSceneStore(args.store)
+        if args.rot_size is not None:
+            rot_size = args.rot_size
+        elif config.get("rot_aug"):
+            rot_size = config["rot_size"]
     if args.eval:
         net.eval()
         with torch.no_grad():
@@ -114,7 +143,7 @@ def main(argv=None):
     # The shard drops the tail that does not divide by the world size and by the batch size (the reference's
     # DistributedSampler pads the shard by repeating samples, train.py:119-131; its DataLoader then drops the last
     # partial batch): every rank sees the same number of full batches either way.
-    per_rank = len(dataset) // world
+    per_rank = len(store if store is not None else dataset) // world
     num_batches = max(per_rank // config["batch_size"], 1)
     save_iters = int(np.ceil(config["save_freq"] * num_batches))                       # train.py:166-171
     display_iters = max(int(config["display_iters"] / (world * config["batch_size"])), 1)
@@ -125,11 +154,21 @@ def main(argv=None):
     last_path, done = None, False
     bucket = D.GradBucket(net.parameters())                        # persistent flat gradient buffer (p.grad = views of it)
     for ep in range(int(epoch + 0.5 / num_batches), config["num_epochs"]):
-        for data in batches(dataset, collate_fn, config["batch_size"], rank, world, seed=0, epoch=ep):
+        if store is not None:
+            feed = store_picks(len(store), config["batch_size"], rank, world, seed=0, epoch=ep)
+        else:
+            feed = batches(dataset, collate_fn, config["batch_size"], rank, world, seed=0, epoch=ep)
+        for data in feed:
             epoch += 1.0 / num_batches
-            out = net(data)
-            loss_out = loss(out, data)
-            post_out = post_process(out, data)
+            if store is not None:                                  # `data` is the pick: one launch cuts (and turns) the batch
+                rot_dt = None if rot_size is None else draw_rot_dt(len(data), rot_size)
+                out, data = net.forward_store_train(store, data, rot_dt=rot_dt)
+                loss_out = loss(out, data)
+                post_out = post_process(out, first_rows_on_host(data))
+            else:
+                out = net(data)
+                loss_out = loss(out, data)
+                post_out = post_process(out, data)
             post_process.append(metrics, loss_out, post_out)
             bucket.zero()                                          # the reference's opt.zero_grad(): one fill of the flat bucket
             loss_out["loss"].backward()                            # accumulates into the bucket's views

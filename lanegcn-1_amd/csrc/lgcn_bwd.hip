@@ -1,7 +1,7 @@
 // Backward building blocks of the LaneGCN hot path (fp32): GroupNorm/ReLU backward rows, the
 // deterministic column reductions behind dgamma/dbeta, and a row gather.  The row-GEMMs of the
 // backward are lgcn_agg_mlp launches (transposed plan / transposed weights); the weight
-// gradients live next to the forward gather code in lgcn_rowmlp.hip (lgcn_wgrad).
+// gradients live in lgcn_rowmlp_bwd.hip (lgcn_wgrad), on the forward's gather code (lgcn_rowmlp.hpp).
 #include "lgcn_common.hpp"
 #include "lgcn_tile.hpp"
 

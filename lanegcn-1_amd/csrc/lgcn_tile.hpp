@@ -210,40 +210,6 @@ struct PairParams {
     float *m;
 };
 
-// lgcn_pool_pairs: the pair stage of the fork's LanePooling (see include/lgcn.h)
-struct PoolParams {
-    const float *ctx_pose, *tgt_pose;
-    const int32_t *ti, *ci, *n_pairs;
-    int64_t cap;
-    const float *wp, *bp, *wpc0h, *U, *g, *bt;
-    float eps;
-    float *m;
-};
-
-// lgcn_att_pairs_bwd: the forward's inputs, what it saved and the gradient outputs (see include/lgcn.h)
-struct PairBwdParams {
-    PairParams f;
-    const float *wptd2, *wptc0e;      // transposed images of W_d2 and W_c0[:, 0:128]
-    const uint4 *masks;
-    const float *dS;
-    float *dc, *rec;
-    int want_d, want_wc;              // anything upstream of e (the dist parameters) / dW_c0e
-};
-
-struct PairBwdOut { float *dwd2, *dwc0e, *dgc, *dbc, *dgd, *dbd, *dbd0, *dwd0; };
-
-// lgcn_pool_pairs_bwd: the forward's inputs, what it saved and the gradient outputs (see include/lgcn.h)
-struct PoolBwdParams {
-    PoolParams f;
-    const float *wptc0h;              // transposed image of W_0[:, 128:256]
-    const uint4 *masks;
-    const float *dS;
-    float *dz, *rec;
-    int want_p, want_w;               // anything upstream of h (relpose.0's parameters) / dW_0h
-};
-
-struct PoolBwdOut { float *dw0h, *dwp, *dbp, *dg, *dbt; };
-
 // split-bf16 implementations (lgcn_rowmlp_bf.hip)
 int agg_mlp_bf(const lgcn_agg_mlp_t &p, bool lane_conv, hipStream_t st);
 int agg_mlp_pair_bf(const lgcn_agg_mlp_t &a, const lgcn_agg_mlp_t &b, hipStream_t st);

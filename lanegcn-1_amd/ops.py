@@ -1278,12 +1278,37 @@ def _pool_args(what, ps, ctx_pose, tgt_pose, wp, bp, w_c0, U):
     return ctx_pose, tgt_pose, _dev(wp.detach(), torch.float32, "wp"), _dev(bp.detach(), torch.float32, "bp"), U
 
 
-def _pool_buf(what, name, t, rows, cols, dtype, device):
-    if t is None:
-        return torch.empty((max(rows, 1), cols), dtype=dtype, device=device)
-    if t.shape[0] < rows or not t.is_contiguous() or t.dtype != dtype:
-        raise L.LgcnError("%s: %s must be a contiguous [>= cap, %d] tensor" % (what, name, cols))
-    return t
+def _row_buf(buf, rows, cols, dtype, device, err, min_rows=0):
+    """A caller's output buffer of at least `rows` rows, checked (err: the message of a misfit), or a new one."""
+    if buf is None:
+        return torch.empty((max(rows, min_rows), cols), dtype=dtype, device=device)
+    if buf.shape[0] < rows or not buf.is_contiguous() or buf.dtype != dtype or not buf.is_cuda:
+        raise L.LgcnError(err)
+    return buf
+
+
+def _bwd_chunks(n_chunks, rows, cap, dev):
+    """Workgroups of a fused backward launch.  Default: one per CU, never more than a quarter of the 32-row tiles of `rows`
+    (a workgroup then walks at least four); always within what `cap` rows and the library allow."""
+    if n_chunks is None:
+        n_chunks = min(cu_count(dev), (rows + 127) // 128)
+    return max(1, min(int(n_chunks), (cap + 31) // 32, 1024))
+
+
+def _bwd_ws(fn, what, *args, dev):
+    """The workspace of a fused backward's chunk records.  fn: the library's *_ws_elems, called with args = (rows,
+    n_chunks, ...); what: "<op>: <name of the row count>", for the error."""
+    n_ws = fn(*args)
+    if n_ws < 0:
+        raise L.LgcnError("%s = %d / n_chunks = %d not supported" % (what, args[0], args[1]))
+    return torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+
+
+def _pair_masks(masks, P, k):
+    """bool [P,k,128] of the first P rows of a pair kernel's k masks of 4 words each (att_pair_masks, pool_pair_masks)."""
+    w = masks[:P].reshape(P, k, 4, 1).to(torch.int64) & 0xFFFFFFFF
+    bits = (w >> torch.arange(32, device=masks.device)) & 1
+    return bits.reshape(P, k, C_FEAT).bool()
 
 
 def pool_pairs(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=None, cap=None, eps=EPS, tag="pool_pairs"):
@@ -1323,8 +1348,9 @@ def pool_pairs_train(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=Non
     with exact_mma():
         wpc0h = packed(w_c0, C_FEAT, C_FEAT)
     cap = ps.cap if cap is None else min(int(cap), ps.cap)
-    m = _pool_buf("pool_pairs_train", "m", m, cap, C_FEAT, torch.float32, U.device)
-    masks = _pool_buf("pool_pairs_train", "masks", masks, cap, POOL_MASK_WORDS, torch.int32, U.device)
+    err = "pool_pairs_train: %s must be a contiguous [>= cap, %d] tensor"
+    m = _row_buf(m, cap, C_FEAT, torch.float32, U.device, err % ("m", C_FEAT), 1)
+    masks = _row_buf(masks, cap, POOL_MASK_WORDS, torch.int32, U.device, err % ("masks", POOL_MASK_WORDS), 1)
     with _Timed(tag):
         rc = lib.lgcn_pool_pairs_train(_ptr(ctx_pose), _ptr(tgt_pose), _ptr(ps.hi), _ptr(ps.wi), _ptr(ps.n_pairs), cap,
                                        _ptr(wp), _ptr(bp), _ptr(wpc0h), _ptr(U), _ptr(gn[0]), _ptr(gn[1]), eps, _ptr(m),
@@ -1336,9 +1362,7 @@ def pool_pairs_train(ps: PairSet, ctx_pose, tgt_pose, wp, bp, w_c0, U, gn, m=Non
 def pool_pair_masks(masks: torch.Tensor, P: int) -> torch.Tensor:
     """bool [P,2,128] of the first P rows of pool_pairs_train's masks: [p, k, c] = mask k of channel c of pair p, k = 0:
     W_p d + b_p > 0, 1: m > 0.  Layout: word 4 k + j of a row holds channels 32 j .. 32 j + 31, bit b = channel 32 j + b."""
-    w = masks[:P].reshape(P, 2, 4, 1).to(torch.int64) & 0xFFFFFFFF
-    bits = (w >> torch.arange(32, device=masks.device)) & 1
-    return bits.reshape(P, 2, C_FEAT).bool()
+    return _pair_masks(masks, P, 2)
 
 
 POOL_BWD_OUTS = ("d_w0h", "d_wp", "d_bp", "d_g", "d_bt")
@@ -1362,10 +1386,7 @@ def pool_pairs_bwd(ps: PairSet, dS, masks, ctx_pose, tgt_pose, wp, bp, w_c0, U, 
     cap = ps.cap if cap is None else min(int(cap), ps.cap)
     if masks.shape[0] < cap or not masks.is_contiguous() or masks.dtype != torch.int32:
         raise L.LgcnError("pool_pairs_bwd: masks must be a contiguous int32 [>= cap, 8] tensor")
-    if n_chunks is None:
-        rows = cap if ps._p_host is None else min(ps._p_host, cap)
-        n_chunks = min(cu_count(dev), (rows + 127) // 128)
-    n_chunks = max(1, min(int(n_chunks), (cap + 31) // 32, 1024))
+    n_chunks = _bwd_chunks(n_chunks, cap if ps._p_host is None else min(ps._p_host, cap), cap, dev)
     out = {"dz": None}
     q = L.PoolPairsBwd()
     q.ctx_pose, q.tgt_pose, q.ti, q.ci, q.n_pairs = (t.data_ptr() for t in (ctx_pose, tgt_pose, ps.hi, ps.wi, ps.n_pairs))
@@ -1373,7 +1394,7 @@ def pool_pairs_bwd(ps: PairSet, dS, masks, ctx_pose, tgt_pose, wp, bp, w_c0, U, 
     q.wp, q.bp, q.wpc0h, q.U, q.g, q.bt = (t.data_ptr() for t in (wp, bp, wpc0h, U, gn[0], gn[1]))
     q.wptc0h, q.masks, q.dS = wptc0h.data_ptr(), masks.data_ptr(), dS.data_ptr()
     if want_dz:
-        out["dz"] = _pool_buf("pool_pairs_bwd", "dz", dz, cap, C_FEAT, torch.float32, dev)
+        out["dz"] = _row_buf(dz, cap, C_FEAT, torch.float32, dev, "pool_pairs_bwd: dz must be a contiguous [>= cap, 128] tensor", 1)
         q.dz = out["dz"].data_ptr()
     shapes = {"d_w0h": (C_FEAT, C_FEAT), "d_wp": (C_FEAT, 4)}
     for name in want:
@@ -1381,12 +1402,8 @@ def pool_pairs_bwd(ps: PairSet, dS, masks, ctx_pose, tgt_pose, wp, bp, w_c0, U, 
             raise L.LgcnError("pool_pairs_bwd: unknown output %r" % (name,))
         out[name] = torch.empty(shapes.get(name, (C_FEAT,)), dtype=torch.float32, device=dev)
         setattr(q, name, out[name].data_ptr())
-    ws = None
     if want:
-        n_ws = lib.lgcn_pool_pairs_bwd_ws_elems(cap, n_chunks)
-        if n_ws < 0:
-            raise L.LgcnError("pool_pairs_bwd: cap = %d / n_chunks = %d not supported" % (cap, n_chunks))
-        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        ws = _bwd_ws(lib.lgcn_pool_pairs_bwd_ws_elems, "pool_pairs_bwd: cap", cap, n_chunks, dev=dev)
         q.ws = ws.data_ptr()
     q.eps, q.n_chunks = eps, n_chunks
     with _Timed(tag):
@@ -1399,9 +1416,7 @@ def att_pair_masks(masks: torch.Tensor, P: int) -> torch.Tensor:
     """bool [P,3,128] of the first P rows of att_pairs_train's masks: [p, k, c] = mask k of channel c of pair p, k = 0:
     W_d0 d + b_d0 > 0, 1: e > 0, 2: m > 0.  Layout: word 4 k + j of a row holds channels 32 j .. 32 j + 31, bit b =
     channel 32 j + b."""
-    w = masks[:P].reshape(P, 3, 4, 1).to(torch.int64) & 0xFFFFFFFF
-    bits = (w >> torch.arange(32, device=masks.device)) & 1
-    return bits.reshape(P, 3, C_FEAT).bool()
+    return _pair_masks(masks, P, 3)
 
 
 PAIR_BWD_OUTS = ("d_wd2", "d_wc0e", "d_wd0", "d_bd0", "d_gd", "d_btd", "d_gc", "d_btc")
@@ -1421,10 +1436,7 @@ def att_pairs_bwd(ps: PairSet, dS, masks, wd0, bd0, w_d2, gn_d, w_c0, U, V, gn_c
     with exact_mma():
         wpd2, wpc0e = packed(w_d2, 0, C_FEAT), packed(w_c0, 0, C_FEAT)
         wptd2, wptc0e = packed_t(w_d2, 0), packed_t(w_c0, 0)
-    if n_chunks is None:
-        rows = ps.cap if ps._p_host is None else ps._p_host
-        n_chunks = min(cu_count(dev), (rows + 127) // 128)
-    n_chunks = max(1, min(int(n_chunks), (ps.cap + 31) // 32, 1024))
+    n_chunks = _bwd_chunks(n_chunks, ps.cap if ps._p_host is None else ps._p_host, ps.cap, dev)
     out = {"dc": None}
     q = L.AttPairsBwd()
     q.agt_ctrs, q.ctx_ctrs, q.hi, q.wi, q.n_pairs = (t.data_ptr() for t in (ps.agt_ctrs, ps.ctx_ctrs, ps.hi, ps.wi, ps.n_pairs))
@@ -1439,12 +1451,8 @@ def att_pairs_bwd(ps: PairSet, dS, masks, wd0, bd0, w_d2, gn_d, w_c0, U, V, gn_c
     for name in want:
         out[name] = torch.empty(shapes.get(name, (C_FEAT,)), dtype=torch.float32, device=dev)
         setattr(q, name, out[name].data_ptr())
-    ws = None
     if want:
-        n_ws = lib.lgcn_att_pairs_bwd_ws_elems(ps.cap, n_chunks)
-        if n_ws < 0:
-            raise L.LgcnError("att_pairs_bwd: cap = %d / n_chunks = %d not supported" % (ps.cap, n_chunks))
-        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        ws = _bwd_ws(lib.lgcn_att_pairs_bwd_ws_elems, "att_pairs_bwd: cap", ps.cap, n_chunks, dev=dev)
         q.ws = ws.data_ptr()
     q.eps, q.n_chunks = eps, n_chunks
     with _Timed(tag):
@@ -1626,22 +1634,15 @@ def laneconv_bwd(d_out, out, Z, Y, T, gn1_w, w2, gn2_w, *, x=None, w1=None, want
         q.dX = 0 if res["dX"] is None else res["dX"].data_ptr()
     else:
         for name, buf, on in (("dT", dT, True), ("g2", g2, want_dx)):
-            if on and buf is not None and (buf.shape[0] < N or not buf.is_contiguous() or buf.dtype != torch.float32):
-                raise L.LgcnError("laneconv_bwd: %s must be a contiguous float32 [>= %d, 128]" % (name, N))
-            res[name] = None if not on else buf if buf is not None else torch.empty((N, C_FEAT), dtype=torch.float32, device=dev)
+            err = "laneconv_bwd: %s must be a contiguous float32 [>= %d, 128]" % (name, N)
+            res[name] = _row_buf(buf, N, C_FEAT, torch.float32, dev, err) if on else None
             setattr(q, name, 0 if res[name] is None else res[name].data_ptr())
     for name in want:
         res[name] = torch.empty((C_FEAT, C_FEAT) if name in ("d_w2", "d_w1") else (C_FEAT,), dtype=torch.float32, device=dev)
         setattr(q, name, res[name].data_ptr())
-    if n_chunks is None:
-        n_chunks = min(cu_count(dev), (N + 127) // 128)
-    n_chunks = max(1, min(int(n_chunks), (N + 31) // 32, 1024))
-    ws = None
+    n_chunks = _bwd_chunks(n_chunks, N, N, dev)
     if want:
-        n_ws = lib.lgcn_laneconv_bwd_ws_elems(N, n_chunks, int(ident1))
-        if n_ws < 0:
-            raise L.LgcnError("laneconv_bwd: n_rows = %d / n_chunks = %d not supported" % (N, n_chunks))
-        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        ws = _bwd_ws(lib.lgcn_laneconv_bwd_ws_elems, "laneconv_bwd: n_rows", N, n_chunks, int(ident1), dev=dev)
         q.ws = ws.data_ptr()
     q.n_rows, q.eps, q.n_chunks, q.ident1 = N, eps, n_chunks, int(ident1)
     with _Timed(tag):
@@ -1702,20 +1703,14 @@ def rowblock_bwd(d_out, out, pre, gn_w, rels, *, want_src=None, want_w=None, wan
         w_index.append(k)
     res = {"d_src": [None] * n_rel, "d_w": [None] * len(ws_of), "w_index": w_index, "d_gamma": None, "d_beta": None,
            "d_res": None}
-    rows = lambda: torch.empty((N, C_FEAT), dtype=torch.float32, device=dev)
-
-    def given(buf, name):
-        if buf.shape[0] < N or not buf.is_contiguous() or buf.dtype != torch.float32 or not buf.is_cuda:
-            raise L.LgcnError("rowblock_bwd: %s must be a contiguous float32 [>= %d, 128]" % (name, N))
-        return buf
-
+    rows = lambda buf, name: _row_buf(buf, N, C_FEAT, torch.float32, dev,
+                                      "rowblock_bwd: %s must be a contiguous float32 [>= %d, 128]" % (name, N))
     for r in range(n_rel):
         if want_src[r]:
-            buf = None if d_src is None else d_src[r]
-            res["d_src"][r] = rows() if buf is None else given(buf, "d_src[%d]" % r)
+            res["d_src"][r] = rows(None if d_src is None else d_src[r], "d_src[%d]" % r)
             q.d_src[r] = res["d_src"][r].data_ptr()
     if want_res:
-        res["d_res"] = rows() if d_res is None else given(d_res, "d_res")
+        res["d_res"] = rows(d_res, "d_res")
         q.d_res = res["d_res"].data_ptr()
     for k, w in enumerate(ws_of):
         cols = sorted(rels[r][2] for r in range(n_rel) if w_index[r] == k and want_w[r])
@@ -1734,14 +1729,9 @@ def rowblock_bwd(d_out, out, pre, gn_w, rels, *, want_src=None, want_w=None, wan
         res["d_gamma"] = torch.empty(C_FEAT, dtype=torch.float32, device=dev)
         res["d_beta"] = torch.empty(C_FEAT, dtype=torch.float32, device=dev)
         q.d_gamma, q.d_beta = res["d_gamma"].data_ptr(), res["d_beta"].data_ptr()
-    if n_chunks is None:
-        n_chunks = min(cu_count(dev), (N + 127) // 128)
-    n_chunks = max(1, min(int(n_chunks), (N + 31) // 32, 1024))
+    n_chunks = _bwd_chunks(n_chunks, N, N, dev)
     if want_gn or any(want_w):
-        n_ws = lib.lgcn_rowblock_bwd_ws_elems(N, n_chunks, n_rel)
-        if n_ws < 0:
-            raise L.LgcnError("rowblock_bwd: n_rows = %d / n_chunks = %d not supported" % (N, n_chunks))
-        ws = torch.empty(max(n_ws, 1), dtype=torch.float32, device=dev)
+        ws = _bwd_ws(lib.lgcn_rowblock_bwd_ws_elems, "rowblock_bwd: n_rows", N, n_chunks, n_rel, dev=dev)
         keep.append(ws)
         q.ws = ws.data_ptr()
     q.n_rows, q.eps, q.n_rel, q.n_chunks = N, eps, n_rel, n_chunks

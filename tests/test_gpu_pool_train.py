@@ -303,6 +303,14 @@ def test_absent_gradients(mods):
         for i, k in enumerate(NAMES):
             assert (part[1 + i] is None) == (k not in only), (only, k)
             assert k not in only or same_bits(full[1 + i], part[1 + i]), (only, k)
+    # the interleaved output alone: d_wp [128,4] takes the record's last four rows, and every output next to them is absent
+    ps, inp, _, _ = make_case(ops, 33)
+    x = {k: inp[k].cuda() for k in NAMES}
+    _, masks = ops.pool_pairs_train(ps, *op_args(inp, x), eps=EPS)
+    bwd = lambda **kw: ops.pool_pairs_bwd(ps, inp["dS"].cuda(), masks, *op_args(inp, x), eps=EPS, n_chunks=2, **kw)
+    whole, alone = bwd(), bwd(want=("d_wp",), want_dz=False)
+    assert set(alone) == {"dz", "d_wp"} and alone["dz"] is None and bool(whole["d_wp"].abs().max() > 0)
+    assert same_bits(whole["d_wp"], alone["d_wp"])
 
 
 def test_no_upstream_gradient_returns_none(mods):

@@ -373,6 +373,16 @@ def test_absent_gradients(mods, shape):
         for k in full:
             assert (part[k] is None) == (k in gone), (kw, k)
             assert k in gone or same_bits(full[k], part[k]), (kw, k)
+    # a column block of a wider weight gradient (row stride 256) next to an absent one: shape "e" with one relation's dW
+    # left out writes the other's 128 columns with the bits of the full run and leaves the rest of the [128,256] tensor zero
+    inp = block_inputs(33, "e")
+    pre, out = hip_forward(mods, inp, "e")
+    whole = entry(mods, inp, "e", pre, out, n_chunks=2)["d w0"]
+    assert whole.shape == (C, 2 * C) and bool(whole[:, :C].abs().max() > 0) and bool(whole[:, C:].abs().max() > 0)
+    for r in range(2):
+        half = entry(mods, inp, "e", pre, out, n_chunks=2, want_w=[i == r for i in range(2)])["d w0"]
+        assert same_bits(half[:, r * C:(r + 1) * C].contiguous(), whole[:, r * C:(r + 1) * C].contiguous()), r
+        assert bool((half[:, (1 - r) * C:(2 - r) * C] == 0).all()), r
 
 
 def test_no_parameter_gradient_needs_no_workspace(mods):

@@ -41,7 +41,7 @@ def test_version_and_strerror(lib):
 def test_struct_layout_matches_header(lib):
     _, mod = lib
     # lgcn_rel_t: 2 pointers + 2 int32; lgcn_agg_mlp_t: 32-byte head, 16 rels, 16 + 7 pointers (the library
-    # static_asserts the same number: csrc/lgcn_rowmlp.hip)
+    # static_asserts the same number: csrc/lgcn_rowmlp.hpp)
     assert C.sizeof(mod.Rel) == 24
     assert mod.AggMlp.rel.offset == 32
     assert C.sizeof(mod.AggMlp) == 32 + 16 * 24 + 23 * 8

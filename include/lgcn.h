@@ -550,6 +550,21 @@ int lgcn_agg_mlp_pair(const lgcn_agg_mlp_t *a_host, const lgcn_agg_mlp_t *b_host
 int lgcn_agg_mlp_multi(const lgcn_agg_mlp_t *const *ps_host, int n, void *stream);
 
 /*
+ * Context heads of an Att block whose context rows are not its targets (M2A: the lane nodes; lanegcn.py:696-699):
+ *   out[j] = x W_j^T   for j < n_w, n_w = 1 or 2
+ * in ONE weight-stationary launch: a workgroup reads a 48-row tile of x once, each of its 8 waves keeps a 32-channel
+ * slice of one weight in registers over the full K, and the results are stored straight from the accumulators.
+ *   x, out[j]: fp32 [n_rows,128];  w[j]: lgcn_pack_weight image (k = 128) of W_j for `mma`;  w, out: HOST arrays of n_w
+ *   device pointers.
+ * Bit-identical to lgcn_agg_mlp with one LGCN_REL_IDENT relation (src = x, wp = w[j]) and flags = 0: same operand roles,
+ * one fp32 accumulator per element, K-steps and plane products in the same order.
+ * LGCN_MMA_F16X2 and LGCN_MMA_BF16 only (others: LGCN_ESHAPE, checked first -- use lgcn_agg_mlp there).  n_rows < 0, n_w
+ * outside 1..2, a NULL array or, with n_rows > 0, a NULL x / w[j] / out[j]: LGCN_EINVAL; n_rows > 2^31 - 1: LGCN_ESHAPE;
+ * pointers not 16-byte aligned: LGCN_EALIGN.  n_rows == 0 returns LGCN_OK without a launch.
+ */
+int lgcn_ctx_heads(const float *x, int64_t n_rows, const void *const *w, int n_w, int mma, float *const *out, void *stream);
+
+/*
  * MapNet input stage, lanegcn.py:324-327:
  *   out = ReLU( GN_a(W_a2 ReLU(W_a1 ctr + b_a1)) + GN_s(W_s2 ReLU(W_s1 seg + b_s1)) )
  * ctrs, feats: [N,2]; w1: [128,2] + b1 [128] (nn.Linear(2,128)); wp2: packed.

@@ -272,8 +272,10 @@ class HotPathEngine:
             out["map_net"] = feat
         # A2M (lanegcn.py:385-407)
         fold = side is None and M._fold_ok(actors) and fb.n_nodes > 0
-        if fold:      # launches folded across the Att layers of the three blocks (lanegcn.att_block): 8 row-block launches
-            feat = self.a2m.run(feat, fb.turn, fb.control, fb.intersect, actors, pairs[0])
+        if fold:      # launches folded across the Att layers of the three blocks (lanegcn.att_block): 7 row-block launches + M2A's ctx-heads
+            # M2A's U of layer 0 depends on `actors` alone: it rides in A2M's first launch, off M2A's critical path
+            feat, u_m2a = self.a2m.run(feat, fb.turn, fb.control, fb.intersect, actors, pairs[0],
+                                       extra=self.m2a.att[0].u_kw(actors))
         else:
             feat = self.a2m.fuse_meta(feat, fb.turn, fb.control, fb.intersect)
             if side is not None:
@@ -290,7 +292,8 @@ class HotPathEngine:
         act = actors
         if fold:
             # M2A's last tail also emits U / V of A2A's first layer (its targets and context are M2A's output rows)
-            act, uv = M.att_block(self.m2a.att, act, feat, pairs[1], next_att=self.a2a.att[0], next_ctx_is_out=True)
+            # (it starts with the V rows of both layers: one weight-stationary launch over the lane nodes)
+            act, uv = M.att_block(self.m2a.att, act, feat, pairs[1], next_att=self.a2a.att[0], next_ctx_is_out=True, u0=u_m2a)
             if stages:
                 out["m2a"] = act
             act, _ = M.att_block(self.a2a.att, act, act, pairs[2], uv=uv, ctx_is_agts=True)
@@ -371,8 +374,12 @@ class HotPathEngine:
             st["nodes"] = M.lane_conv(self.map_net.fuse, self.map_net.stem(fb.node_ctrs, fb.node_feats), st["plan"],
                                       fb.num_scales, impl=self.lane_impl)
 
-        def a2m():
-            st["nodes_a2m"] = self.a2m.run(st["nodes"], fb.turn, fb.control, fb.intersect, actors, st["pairs"][0])
+        def a2m():      # as in forward(): the first launch also emits M2A's U of layer 0
+            args = (st["nodes"], fb.turn, fb.control, fb.intersect, actors, st["pairs"][0])
+            if M._fold_ok(actors) and fb.n_nodes > 0:
+                st["nodes_a2m"], st["u_m2a"] = self.a2m.run(*args, extra=self.m2a.att[0].u_kw(actors))
+            else:
+                st["nodes_a2m"], st["u_m2a"] = self.a2m.run(*args), None
 
         def m2m():
             st["nodes_m2m"] = M.lane_conv(self.m2m.fuse, st["nodes_a2m"], st["plan"], fb.num_scales, impl=self.lane_impl)
@@ -380,7 +387,7 @@ class HotPathEngine:
         def m2a():      # as in forward(): the last tail also emits A2A's first U / V
             if M._fold_ok(st["nodes_m2m"]):
                 st["actors_m2a"], st["uv_a2a"] = M.att_block(self.m2a.att, actors, st["nodes_m2m"], st["pairs"][1],
-                                                             next_att=self.a2a.att[0], next_ctx_is_out=True)
+                                                             next_att=self.a2a.att[0], next_ctx_is_out=True, u0=st.get("u_m2a"))
                 return
             act = actors
             for att in self.m2a.att:

@@ -478,7 +478,8 @@ class Att(nn.Module):
 
 
 def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: Optional[dict] = None, uv=None,
-              ctx_is_agts: bool = False, next_att: Optional["Att"] = None, next_ctx_is_out: bool = False):
+              ctx_is_agts: bool = False, next_att: Optional["Att"] = None, next_ctx_is_out: bool = False,
+              u0: Optional[Tensor] = None, extra: Optional[dict] = None):
     """The Att layers of one fusion block (reference lanegcn.py:397-406, 506-512, 537-544) with the row-block launches
     folded: a layer's tail also emits the next layer's U (and V, when the context rows are the targets: A2A) from its
     output rows before they leave the CU, the V rows of every layer whose context does not change are computed up
@@ -487,26 +488,46 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
       head: agg_mlp keywords of a row block whose output is the block's target rows (agts is then ignored);
       uv: (U, V) of layer 0 when a previous block's tail has already emitted them;
       next_att: first Att of the FOLLOWING block when this block's output rows are its targets (and, with
-                next_ctx_is_out, its context rows): the last tail emits its U (and V).
-    Returns (out, uv_next) -- uv_next is None without next_att."""
+                next_ctx_is_out, its context rows): the last tail emits its U (and V);
+      u0: U of layer 0 when an earlier launch has computed it (it depends on the targets alone: HotPathEngine puts M2A's
+          into A2M's first launch); the block then starts with its V rows;
+      extra: one more agg_mlp problem for the block's first launch (A2M carrying M2A's U of layer 0); its output is
+             returned as a third value.
+    V rows that are still missing once U of layer 0 is known (context rows that are not the targets) come from one
+    weight-stationary launch that reads the context rows once (ops.ctx_heads: f16x2 / bf16) or, in the other modes,
+    from a multi-problem row-block launch.
+    Returns (out, uv_next) -- uv_next is None without next_att -- or (out, uv_next, extra's output)."""
     n = len(atts)
     Vs = [None] * n
+    x_out = None
     if uv is not None:
         U, Vs[0] = uv
+    elif u0 is not None:
+        U = u0
     else:
         first = dict(head, chain_u=atts[0].chain_u()) if head is not None else atts[0].u_kw(agts)
         probs = [first] + [atts[i].v_kw(ctx) for i in range(1 if ctx_is_agts else n)]
-        res = ops.agg_mlp_multi(probs, tag="att_head")
+        res = ops.agg_mlp_multi(probs + ([extra] if extra is not None else []), tag="att_head")
+        if extra is not None:
+            x_out, extra = res[-1], None
         if head is not None:
             agts, U = res[0]
         else:
             U = res[0]
         for i in range(len(probs) - 1):
             Vs[i] = res[1 + i]
-    if not ctx_is_agts and any(v is None for v in Vs):      # layer 0's V came with uv: the later layers' V on their own
+    if extra is not None:
+        x_out = ops.agg_mlp(**extra)
+    if not ctx_is_agts and any(v is None for v in Vs):      # U of layer 0 came with uv / u0: the V rows on their own
         todo = [i for i in range(n) if Vs[i] is None]
-        for i, v in zip(todo, ops.agg_mlp_multi([atts[i].v_kw(ctx) for i in todo], tag="att_head")):
-            Vs[i] = v
+        if ops.ctx_heads_ok():
+            for k in range(0, len(todo), 2):
+                part = todo[k:k + 2]
+                for i, v in zip(part, ops.ctx_heads(ctx, [atts[i].chain_v() for i in part])):
+                    Vs[i] = v
+        else:
+            for i, v in zip(todo, ops.agg_mlp_multi([atts[i].v_kw(ctx) for i in todo], tag="att_head")):
+                Vs[i] = v
     uv_next = None
     for i, att in enumerate(atts):
         nxt = atts[i + 1] if i + 1 < n else next_att
@@ -522,7 +543,7 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
                 Vs[i + 1] = res[2]
         else:
             agts, uv_next = res[0], (res[1], res[2] if want_v else None)
-    return agts, uv_next
+    return (agts, uv_next) if x_out is None else (agts, uv_next, x_out)
 
 
 def _fold_ok(ctx: Tensor) -> bool:
@@ -555,14 +576,19 @@ class A2M(nn.Module):
         return dict(n_rows=feat.shape[0], rels=[ops.RelSpec(feat, ops.packed(w, 0, 128))], flags=L.F_GN1 | L.F_RELU1,
                     x4=(turn, control, intersect), w4=ops.cols4(w, 128), gn1=_gn(self.meta.norm), eps=self.meta.norm.eps)
 
-    def run(self, feat: Tensor, turn: Tensor, control: Tensor, intersect: Tensor, actors: Tensor, ps: ops.PairSet) -> Tensor:
-        """meta + both Att layers for given pairs, launches folded (att_block): inference only."""
+    def run(self, feat: Tensor, turn: Tensor, control: Tensor, intersect: Tensor, actors: Tensor, ps: ops.PairSet,
+            extra: Optional[dict] = None):
+        """meta + both Att layers for given pairs, launches folded (att_block): inference only.
+        extra: one more agg_mlp problem that rides in the first launch (meta + chained U0 | V0 | V1 | extra: the four
+        problems of lgcn_agg_mlp_multi) -- a row block that depends on the forward's inputs alone, such as M2A's U of
+        layer 0 over the actors; the result is then (feat, extra's output)."""
         if not _fold_ok(actors):
             feat = self.fuse_meta(feat, turn, control, intersect)
             for att in self.att:
                 feat = att.run(feat, actors, ps)
-            return feat
-        return att_block(self.att, None, actors, ps, head=self.meta_kw(feat, turn, control, intersect))[0]
+            return feat if extra is None else (feat, ops.agg_mlp(**extra))
+        res = att_block(self.att, None, actors, ps, head=self.meta_kw(feat, turn, control, intersect), extra=extra)
+        return res[0] if extra is None else (res[0], res[2])
 
     def forward(self, feat: Tensor, graph: Dict, actors: Tensor, actor_idcs: List[Tensor],
                 actor_ctrs: List[Tensor]) -> Tensor:

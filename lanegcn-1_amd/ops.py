@@ -1008,6 +1008,32 @@ def agg_mlp_multi(problems: Sequence[dict], tag=None):
     return [b[2] for b in built]
 
 
+def ctx_heads_ok() -> bool:
+    """lgcn_ctx_heads implements the current matrix-core mode (f16x2, bf16); the others take agg_mlp."""
+    return _mma in (L.MMA_F16X2, L.MMA_BF16)
+
+
+def ctx_heads(x: torch.Tensor, wps: Sequence[torch.Tensor], outs: Optional[Sequence[torch.Tensor]] = None, tag="ctx_heads"):
+    """[x W_j^T for j] for one or two packed [128,128] weights over the same rows, one weight-stationary launch
+    (lgcn_ctx_heads): bit for bit what agg_mlp gives with one IDENT relation and flags = 0.  f16x2 / bf16 only
+    (ctx_heads_ok(); the library refuses the other modes)."""
+    lib = L.load()
+    x = _dev(x, torch.float32, "x")
+    if x.dim() != 2 or x.shape[1] != C_FEAT or not 1 <= len(wps) <= 2:
+        raise L.LgcnError("ctx_heads: x must be [N,128], with one or two weights")
+    n = x.shape[0]
+    if outs is None:
+        outs = [torch.empty((n, C_FEAT), dtype=torch.float32, device=x.device) for _ in wps]
+    if len(outs) != len(wps) or any(o.shape != (n, C_FEAT) or o.dtype != torch.float32 or not o.is_contiguous()
+                                    or o.device != x.device for o in outs):
+        raise L.LgcnError("ctx_heads: every output must be a contiguous fp32 [N,128] tensor on x's device")
+    w = (C.c_void_p * len(wps))(*[t.data_ptr() for t in wps])
+    o = (C.c_void_p * len(wps))(*[t.data_ptr() for t in outs])
+    with _Timed(tag):
+        L.check(lib.lgcn_ctx_heads(_ptr(x), n, w, len(wps), _mma, o, _stream()), "lgcn_ctx_heads")
+    return list(outs)
+
+
 # ------------------------------------------------------------------ LaneConv (gather-free, weight-stationary)
 @dataclass
 class LcPlan:

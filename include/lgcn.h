@@ -1382,6 +1382,74 @@ int64_t lgcn_scene_lanes_ws_elems(int64_t n_cand, int64_t n_rank);
 int lgcn_scene_lanes_rank(const lgcn_scene_lanes_t *p, void *stream);
 int lgcn_scene_lanes_fill(const lgcn_scene_lanes_t *p, void *stream);
 
+/*
+ * Graph construction for a BATCH of scenes (csrc/lgcn_graphbatch.hip): what lgcn_bool_square* and
+ * lgcn_cross_edges do for one scene, from flat arrays plus per-scene offset tables, in a number of launches that does not
+ * depend on the number of scenes.  Every output is an integer array and equals the per-scene entries' element for element
+ * (the per-row bodies are shared, csrc/lgcn_graphops.hpp).  All offset tables are int32 [n_scenes + 1], start at 0, never
+ * decrease and end at their total; off_host / off_dev hold the same tables, back to back, on the host (validated before
+ * anything is launched) and on the device (read by the kernels).
+ *
+ * Dilation (reference data.py:520-534).  Tables: node_off, pre_off, suc_off.  pre_u / pre_v [n_pre], suc_u / suc_v [n_suc]:
+ *   the scale-0 edges of every scene, int64, scene-local node indices (row u, column v); an edge with an end outside its
+ *   scene's [0, n) is ignored.  ws: lgcn_dilate_batch_ws_elems(n_nodes, n_pre + n_suc) int32.
+ *   lgcn_dilate_batch_csr   (1 launch + lgcn_csr_build): rowptr [lgcn_csr_rowptr_elems(2 n_nodes, 1)], col [n_pre + n_suc,
+ *                            at least 1] = one CSR over the stacked rows (relation * n_nodes + scene base + node), columns
+ *                            scene base + node.
+ *   lgcn_dilate_batch_count (2 launches): out_rowptr [2 n_nodes + 1] = row pointer of A * A (exact, duplicate-free row
+ *                            lengths; both relations and all scenes in one squaring); bounds [2][n_scenes + 1] = its value
+ *                            where the scenes of the pre rows, then of the suc rows, begin and end.  Read bounds back:
+ *                            bounds[1][n_scenes] = nnz, and bounds[r][s] - bounds[r][0] are the edge offsets of relation r.
+ *   lgcn_dilate_batch_fill  (1 launch): out_col [nnz] (the next scale's col, with out_rowptr as its rowptr) and out_u /
+ *                            out_v [nnz] int64, scene-local: rows ascending, columns ascending within a row, every edge
+ *                            once; relation r owns [bounds[r][0], bounds[r][n_scenes]).  A row never writes beyond the
+ *                            room out_rowptr gives it.
+ *   The nnz of a scale must fit 31 bits.
+ *
+ * Left / right (reference preprocess_data.py:287-392, cross_angle = None).  Tables: node_off, lane_off, pre_off, suc_off,
+ *   left_off, right_off (pairs per scene), then mask_off (sums of lanes^2), left_work_off and right_work_off (sums of
+ *   side pairs * (pre pairs + suc pairs + 1)), which must be what the first six imply.  ctrs, feats [n_nodes,2] fp32,
+ *   lane_idcs [n_nodes] int64 (scene-local lanes), the four pair lists [.,2] int64 (scene-local lanes); mat: 2 * mask_off[S]
+ *   bytes (at most 0x7ffffff0, LGCN_ESHAPE beyond); ws: lgcn_cross_edges_batch_ws_elems(n_nodes) int32.
+ *   lgcn_cross_edges_batch (1 memset + 4 launches, both sides together): out_u / out_v [2 n_nodes] int16 = the low 16 bits
+ *   of the scene-local edge (u, partner of u), left side first, scenes in order, u ascending; counts [2][n_scenes + 1]:
+ *   side d's edges of scene s are [counts[d][s], counts[d][s + 1]).  A scene whose side list is empty has no edge there.
+ *
+ * Refused before anything is launched: NULL struct or required pointer, negative size, NaN cross_dist, a bad offset table
+ * (LGCN_EINVAL); pointers not aligned to 16 bytes (ws), 8 (int64 and float2 arrays), 4 (int32) or 2 (int16) (LGCN_EALIGN);
+ * sizes beyond the 32-bit workspace or the mask limit (LGCN_ESHAPE).  n_scenes == 0 with all totals 0 returns LGCN_OK
+ * without a launch.  The size helpers return LGCN_EINVAL / LGCN_ESHAPE as negative values.
+ */
+typedef struct {
+    int32_t n_scenes, pad_;
+    int64_t n_nodes, n_pre, n_suc;
+    const int32_t *off_host, *off_dev;
+    const int64_t *pre_u, *pre_v, *suc_u, *suc_v;                  /* lgcn_dilate_batch_csr */
+    int32_t *ws, *rowptr, *col;
+    int32_t *out_rowptr, *bounds;                                  /* lgcn_dilate_batch_count */
+    int64_t nnz;                                                   /* lgcn_dilate_batch_fill */
+    int32_t *out_col;
+    int64_t *out_u, *out_v;
+} lgcn_dilate_batch_t;
+int64_t lgcn_dilate_batch_ws_elems(int64_t n_nodes, int64_t n_edges);
+int lgcn_dilate_batch_csr(const lgcn_dilate_batch_t *p, void *stream);
+int lgcn_dilate_batch_count(const lgcn_dilate_batch_t *p, void *stream);
+int lgcn_dilate_batch_fill(const lgcn_dilate_batch_t *p, void *stream);
+
+typedef struct {
+    int32_t n_scenes;
+    float cross_dist;
+    int64_t n_nodes, n_lanes, n_pre, n_suc, n_left, n_right;
+    const int32_t *off_host, *off_dev;
+    const float *ctrs, *feats;
+    const int64_t *lane_idcs, *pre_pairs, *suc_pairs, *left_pairs, *right_pairs;
+    uint8_t *mat;
+    int32_t *ws, *counts;
+    int16_t *out_u, *out_v;
+} lgcn_cross_batch_t;
+int64_t lgcn_cross_edges_batch_ws_elems(int64_t n_nodes);
+int lgcn_cross_edges_batch(const lgcn_cross_batch_t *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

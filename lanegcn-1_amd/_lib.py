@@ -216,6 +216,28 @@ class SceneLanes(C.Structure):     # lgcn_scene_lanes_t
     ]
 
 
+class DilateBatch(C.Structure):    # lgcn_dilate_batch_t
+    _fields_ = [
+        ("n_scenes", C.c_int32), ("pad_", C.c_int32), ("n_nodes", C.c_int64), ("n_pre", C.c_int64), ("n_suc", C.c_int64),
+        ("off_host", C.c_void_p), ("off_dev", C.c_void_p),
+        ("pre_u", C.c_void_p), ("pre_v", C.c_void_p), ("suc_u", C.c_void_p), ("suc_v", C.c_void_p),
+        ("ws", C.c_void_p), ("rowptr", C.c_void_p), ("col", C.c_void_p), ("out_rowptr", C.c_void_p), ("bounds", C.c_void_p),
+        ("nnz", C.c_int64), ("out_col", C.c_void_p), ("out_u", C.c_void_p), ("out_v", C.c_void_p),
+    ]
+
+
+class CrossBatch(C.Structure):     # lgcn_cross_batch_t
+    _fields_ = [
+        ("n_scenes", C.c_int32), ("cross_dist", C.c_float),
+        ("n_nodes", C.c_int64), ("n_lanes", C.c_int64), ("n_pre", C.c_int64), ("n_suc", C.c_int64), ("n_left", C.c_int64),
+        ("n_right", C.c_int64),
+        ("off_host", C.c_void_p), ("off_dev", C.c_void_p), ("ctrs", C.c_void_p), ("feats", C.c_void_p),
+        ("lane_idcs", C.c_void_p), ("pre_pairs", C.c_void_p), ("suc_pairs", C.c_void_p), ("left_pairs", C.c_void_p),
+        ("right_pairs", C.c_void_p),
+        ("mat", C.c_void_p), ("ws", C.c_void_p), ("counts", C.c_void_p), ("out_u", C.c_void_p), ("out_v", C.c_void_p),
+    ]
+
+
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 OPT_KINDS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}
 
@@ -327,6 +349,12 @@ SIGNATURES = {
     "lgcn_scene_lanes_ws_elems": (C.c_int64, [_L, _L]),
     "lgcn_scene_lanes_rank": (C.c_int, [C.POINTER(SceneLanes), _P]),
     "lgcn_scene_lanes_fill": (C.c_int, [C.POINTER(SceneLanes), _P]),
+    "lgcn_dilate_batch_ws_elems": (C.c_int64, [_L, _L]),
+    "lgcn_dilate_batch_csr": (C.c_int, [C.POINTER(DilateBatch), _P]),
+    "lgcn_dilate_batch_count": (C.c_int, [C.POINTER(DilateBatch), _P]),
+    "lgcn_dilate_batch_fill": (C.c_int, [C.POINTER(DilateBatch), _P]),
+    "lgcn_cross_edges_batch_ws_elems": (C.c_int64, [_L]),
+    "lgcn_cross_edges_batch": (C.c_int, [C.POINTER(CrossBatch), _P]),
 }
 
 _lib = None

@@ -4,6 +4,7 @@
 // -ffp-contract=off so the pair-search distance is evaluated exactly like
 // ATen's sub / pow(2) / sum / sqrt / le chain (no FMA).
 #include "lgcn_common.hpp"
+#include "lgcn_graphops.hpp"
 
 namespace lgcn {
 
@@ -500,7 +501,7 @@ __global__ __launch_bounds__(256) void k_index_sort(const IndexParams p) {
 // adjacency, formed by repeated squaring (mat = mat * mat).  One squaring of a CSR matrix with sorted or unsorted
 // rows (duplicates allowed: they only repeat candidates):
 //   bound  : cand_ptr[u] = exclusive scan of sum_{v in A[u]} |A[v]|
-//   expand : row u's candidates {w : w in A[v], v in A[u]} -> sorted, duplicates removed in place, count kept
+//   expand : row u's candidates {w : w in A[v], v in A[u]} -> sorted, each once (sq_merge_row), count kept
 //   compact: rows packed to the scanned counts (+ the COO row index of every entry)
 // One thread per row: lane graphs branch rarely, a row of A^32 has a handful of entries.
 __global__ __launch_bounds__(256) void k_sq_bound(const int32_t *rowptr, const int32_t *col, int64_t n, int32_t *ub) {
@@ -520,22 +521,8 @@ __global__ __launch_bounds__(256) void k_sq_expand(const int32_t *rowptr, const 
     const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (u > n) return;
     if (u == n) { cnt[n] = 0; return; }
-    int32_t *c = cand + cand_ptr[u];
-    int k = 0;
-    for (int e = rowptr[u]; e < rowptr[u + 1]; ++e) {
-        const int v = col[e];
-        if (v < 0 || v >= n) continue;
-        for (int f = rowptr[v]; f < rowptr[v + 1]; ++f) {      // insertion into the sorted, duplicate-free prefix
-            const int w = col[f];
-            int q = k - 1;
-            while (q >= 0 && c[q] > w) --q;
-            if (q >= 0 && c[q] == w) continue;
-            for (int r = k; r > q + 1; --r) c[r] = c[r - 1];
-            c[q + 1] = w;
-            ++k;
-        }
-    }
-    cnt[u] = k;
+    const auto row_of = [n](int v) { return v >= 0 && v < n ? v : -1; };
+    cnt[u] = sq_merge_row(rowptr, col, rowptr[u], rowptr[u + 1], row_of, cand + cand_ptr[u], cand_ptr[u + 1] - cand_ptr[u]);
 }
 
 __global__ __launch_bounds__(256) void k_sq_compact(const int32_t *cand_ptr, const int32_t *cand, const int32_t *out_rowptr,
@@ -550,72 +537,21 @@ __global__ __launch_bounds__(256) void k_sq_compact(const int32_t *cand_ptr, con
     }
 }
 
-// Left / right node adjacency (reference preprocess_data.py:287-392, cross_angle = None).
-// Lane-level mask (:318-327 / :356-360): mat = (S pre + S suc + S) > 0.5 with S, pre, suc the 0/1 matrices of the side
-// pairs and the predecessor / successor lane pairs: mat[a][b] = S[a][b] or exists c: S[a][c] and (pre[c][b] or suc[c][b]).
+// Left / right node adjacency (reference preprocess_data.py:287-392, cross_angle = None); the bodies are in
+// lgcn_graphops.hpp.
 __global__ __launch_bounds__(256) void k_lane_mask(const int64_t *side, int64_t n_side, const int64_t *pre, int64_t n_pre,
                                                    const int64_t *suc, int64_t n_suc, int num_lanes, uint8_t *mat) {
-    const int64_t per = n_pre + n_suc + 1;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_side * per) return;
-    const int64_t i = t / per, j = t % per;
-    const int64_t a = side[2 * i], c = side[2 * i + 1];
-    if (a < 0 || a >= num_lanes || c < 0 || c >= num_lanes) return;
-    int64_t b = c;
-    if (j > 0) {
-        const int64_t *pp = j - 1 < n_pre ? pre + 2 * (j - 1) : suc + 2 * (j - 1 - n_pre);
-        if (pp[0] != c) return;
-        b = pp[1];
-        if (b < 0 || b >= num_lanes) return;
-    }
-    mat[a * num_lanes + b] = 1;
+    lane_mask_item(side, n_side, pre, n_pre, suc, n_suc, num_lanes, mat, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
 }
 
-// One wave per node h (:329-347): over the nodes w whose lane is allowed for h's lane, the nearest centre (fp32
-// sub / mul / add / sqrt as ATen evaluates sqrt(((a - b) ** 2).sum(2)); the FIRST w among equals, as a CPU min(1)
-// returns); kept when the distance is < cross_dist and the two segments' headings differ by < pi / 4.
 __global__ __launch_bounds__(256) void k_cross_edges(const float2 *ctrs, const float2 *feats, const int64_t *lane_idcs,
                                                      int n, const uint8_t *mat, int num_lanes, float cross_dist,
                                                      int32_t *partner) {
     const int lane = threadIdx.x & 63;
     const int h = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (h >= n) return;
-    const float2 a = ctrs[h];
-    const int64_t la = lane_idcs[h];
-    const bool la_ok = la >= 0 && la < num_lanes;
-    float best = 3.0e38f;
-    int bw = 0x7fffffff;
-    for (int w0 = 0; w0 < n; w0 += 64) {
-        const int w = w0 + lane;
-        if (w < n) {
-            const int64_t lb = lane_idcs[w];
-            const bool ok = la_ok && lb >= 0 && lb < num_lanes && mat[la * num_lanes + lb] != 0;
-            float d = 1e6f;                                     // :332 masked entries
-            if (ok) {
-                const float2 c = ctrs[w];
-                const float dx = __fsub_rn(a.x, c.x), dy = __fsub_rn(a.y, c.y);
-                d = __fsqrt_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-            }
-            if (d < best) { best = d; bw = w; }                 // ascending w per lane: the first of equals stays
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64);
-        const int ow = __shfl_xor(bw, off, 64);
-        if (ob < best || (ob == best && ow < bw)) { best = ob; bw = ow; }
-    }
-    if (lane == 0) {
-        int out = -1;
-        if (best < cross_dist && bw < n) {
-            const float2 f1 = feats[h], f2 = feats[bw];
-            const float t1 = atan2f(f1.y, f1.x), t2 = atan2f(f2.y, f2.x);
-            float dt = fabsf(__fsub_rn(t1, t2));
-            if (dt > 3.14159274101257324f) dt = fabsf(__fsub_rn(dt, 6.28318548202514648f));      // float32(pi), float32(2 pi)
-            if (dt < 0.785398185253143311f) out = bw;                                            // float32(pi / 4)
-        }
-        partner[h] = out;
-    }
+    const int out = cross_partner(ctrs, feats, lane_idcs, n, mat, num_lanes, cross_dist, h, lane);
+    if (lane == 0) partner[h] = out;
 }
 
 // rowptr and cursor of the CSR plan zeroed in one launch (two memset nodes cost a launch boundary each)

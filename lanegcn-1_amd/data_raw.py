@@ -1,6 +1,7 @@
 """Front end of the data path: raw tracks and map lanes to scenes, on the device for a whole batch (csrc/lgcn_scene.hip,
-DESIGN.md section 3.11).  The reference does this per scene in Python: ArgoDataset.get_obj_feats (data.py:148-217) and
-ArgoDataset.get_lane_graph (data.py:220-361).
+and with batched=True csrc/lgcn_graphbatch.hip for the dilated scales and left / right).  The
+reference does this per scene in Python: ArgoDataset.get_obj_feats (data.py:148-217) and ArgoDataset.get_lane_graph
+(data.py:220-361).
 
 Neither routine needs argoverse-api once its inputs are plain arrays:
   a raw scene   {"city", "trajs": [[n_i,2] float64], "steps": [[n_i] int64]}, the agent first: what the reference's
@@ -210,13 +211,18 @@ def _split(x, off, device):
     return np.split(x.cpu().numpy(), off[1:-1])
 
 
+def _cuts(h, h2):
+    """Per-scene offsets [S + 1] of the batch's scale-0 edge arrays and pair lists, from the two read-back heads."""
+    h2 = h2.reshape(len(h), 4).astype(np.int64)
+    chain = h[:, 1] - h[:, 0]
+    return dict(pre=chain + h2[:, 0], suc=chain + h2[:, 1], pre_pairs=h2[:, 0], suc_pairs=h2[:, 1], left_pairs=h2[:, 2],
+                right_pairs=h2[:, 3])
+
+
 def _graphs(out, h, h2, device):
     """Per-scene graph dicts (scale 0) cut out of the batch's arrays."""
     S = len(h) - 1
-    h2 = h2.reshape(S + 1, 4).astype(np.int64)
-    chain = h[:, 1] - h[:, 0]
-    cuts = dict(pre=chain + h2[:, 0], suc=chain + h2[:, 1], pre_pairs=h2[:, 0], suc_pairs=h2[:, 1], left_pairs=h2[:, 2],
-                right_pairs=h2[:, 3])
+    cuts = _cuts(h, h2)
     used = {k: int(v[-1]) for k, v in cuts.items()}
     parts = {k: _split(out[k], h[:, 1], device) for k in ("ctrs", "feats", "turn", "control", "intersect", "lane_idcs")}
     for k in ("pre", "suc"):
@@ -242,6 +248,27 @@ def _dilate(graph, dev_graph, num_scales, device):
         if not device:
             more = [{"u": e["u"].cpu().numpy(), "v": e["v"].cpu().numpy()} for e in more]
         graph[k] = graph[k] + more
+
+
+def _batched_tail(graphs, out, h, h2, num_scales, cross_dist, device):
+    """Scales 1 .. num_scales - 1 of pre / suc and, with cross_dist given, left / right for the whole batch from the flat
+    arrays _lane_fill left on the device (ops.dilate_batch, ops.cross_edges_batch): no per-scene call, no concatenation,
+    one host read per scale and one for the left / right counts."""
+    cuts = _cuts(h, h2)
+    flat = lambda k, cut=None: out[k][:int(cuts[cut or k][-1])]      # the used part of an array sized by its upper bound
+    scales = ops.dilate_batch(flat("pre_u", "pre"), flat("pre_v", "pre"), flat("suc_u", "suc"), flat("suc_v", "suc"), h[:, 1],
+                              cuts["pre"], cuts["suc"], num_scales)
+    for sc in scales:
+        for k in ("pre", "suc"):
+            us, vs = _split(sc[k + "_u"], sc[k + "_off"], device), _split(sc[k + "_v"], sc[k + "_off"], device)
+            for g, u, v in zip(graphs, us, vs):
+                g[k] = g[k] + [{"u": u, "v": v}]
+    if cross_dist is not None:
+        edges, offs = ops.cross_edges_batch(out["ctrs"], out["feats"], out["lane_idcs"], flat("pre_pairs"), flat("suc_pairs"),
+                                            flat("left_pairs"), flat("right_pairs"), h[:, 1], h[:, 0], cuts["pre_pairs"],
+                                            cuts["suc_pairs"], cuts["left_pairs"], cuts["right_pairs"], cross_dist)
+        for g, side in zip(graphs, preprocess_data.split_cross(edges, offs, range(len(graphs)), device)):
+            g["left"], g["right"] = side["left"], side["right"]
 
 
 def get_obj_feats(data, config, theta=None):
@@ -281,11 +308,13 @@ def get_lane_graph(data, table, config, lane_ids=None):
     return graph
 
 
-def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None):
+def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None, batched=False):
     """Raw scenes to scene dicts in the reference's schema, the whole batch at once: the track kernels and the lane
     kernels run once (6 launches, one memset and one zero fill whatever the number of scenes, 2 size read-backs), then per
     scene the existing device ops: preprocess_data.dilated_nbrs for scales 1 .. num_scales - 1 and, with cross=True,
-    preprocess_data.preprocess for graph["left"] / graph["right"] (config["cross_dist"], default 6).
+    preprocess_data.preprocess for graph["left"] / graph["right"] (config["cross_dist"], default 6).  batched=True replaces
+    the per-scene ops by ops.dilate_batch and ops.cross_edges_batch on the batch's flat arrays: the same leaves from a
+    number of launches and host reads (num_scales - 1, plus 1 with cross=True) that does not depend on the number of scenes.
 
     raws: raw scenes; tables: {city: LaneTable} (uploaded on first use if .to(device) was not called; a batch may mix
     cities); lane_ids: optional per-scene candidate lists (None = the whole table).  Returns new dicts with city, idx (the
@@ -322,19 +351,25 @@ def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None):
     actors = {k: _split(v[:n_a], a_off, device) for k, v in (("feats", tjob.feats), ("obs_trajs", tjob.obs), ("ctrs", tjob.ctrs),
                                                              ("gt_preds", tjob.gt), ("has_preds", tjob.has))}
     graphs = _graphs(out, h, h2, device)
-    dev_graphs = graphs if device else _graphs(out, h, h2, True)
+    cross_dist = float(config.get("cross_dist", 6.0))
+    if batched:
+        _batched_tail(graphs, out, h, h2, int(config["num_scales"]), cross_dist if cross else None, device)
+    else:
+        dev_graphs = graphs if device else _graphs(out, h, h2, True)
     if device:
         orig_l, rot_l = frame[:, :2].unbind(0), frame[:, 2:].reshape(S, 2, 2).unbind(0)
     else:
         orig_l, rot_l = list(orig), list(rot)
     scenes = []
     for b, r in enumerate(raws):
-        g, dg = graphs[b], dev_graphs[b]
-        _dilate(g, dg, int(config["num_scales"]), device)
-        if cross:
-            side = preprocess_data.preprocess(dict(dg, idx=b), float(config.get("cross_dist", 6.0)))
-            for k in ("left", "right"):
-                g[k] = {c: torch.from_numpy(side[k][c]).to(dev) for c in "uv"} if device else side[k]
+        g = graphs[b]
+        if not batched:
+            dg = dev_graphs[b]
+            _dilate(g, dg, int(config["num_scales"]), device)
+            if cross:
+                side = preprocess_data.preprocess(dict(dg, idx=b), cross_dist)
+                for k in ("left", "right"):
+                    g[k] = {c: torch.from_numpy(side[k][c]).to(dev) for c in "uv"} if device else side[k]
         s = {"city": r["city"], "idx": b, "orig": orig_l[b], "theta": float(theta[b]), "rot": rot_l[b], "graph": g}
         s.update({k: v[b] for k, v in actors.items()})
         scenes.append(s)

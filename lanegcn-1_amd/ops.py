@@ -745,6 +745,123 @@ def cross_edges(ctrs: torch.Tensor, feats: torch.Tensor, lane_idcs: torch.Tensor
     return u, partner[u].long()
 
 
+# ------------------------------------------------------------------ graph construction, a batch of scenes (lgcn_graphbatch.hip)
+def read_back(t: torch.Tensor):
+    """The one place where the batched graph ops copy a device tensor to the host (numpy), so that the copies can be
+    counted: each is a synchronisation."""
+    return t.cpu().numpy()
+
+
+def _off_tables(tables, what):
+    """Offset tables [S + 1] as one contiguous int32 host array (rows) after the checks the library repeats."""
+    import numpy as np
+    rows = [np.asarray(t, np.int64).reshape(-1) for t in tables]
+    if any(len(r) != len(rows[0]) or len(r) < 1 for r in rows):
+        raise L.LgcnError("%s: every offset table must hold S + 1 entries" % what)
+    return _i32_table(np.stack(rows), what)
+
+
+def dilate_batch(pre_u, pre_v, suc_u, suc_v, node_off, pre_off, suc_off, num_scales: int):
+    """Scales 1 .. num_scales - 1 of pre and suc for a whole batch of scenes (lgcn_dilate_batch_*): what dilated_nbrs
+    gives per scene and relation, from flat arrays.  pre_u / pre_v, suc_u / suc_v: int64 device tensors, the scenes'
+    scale-0 edges back to back with scene-local node indices; node_off, pre_off, suc_off: host offset tables [S + 1].
+    Returns one dict per scale: pre_u, pre_v, suc_u, suc_v (flat int64 device tensors, scene-local, (u, v)-sorted inside
+    a scene) and pre_off, suc_off (numpy int64 [S + 1]).  Each scale squares both relations of all scenes at once: three
+    launches and ONE read-back (the scene boundaries of the new row pointer, whose ends are the sizes to allocate)."""
+    import numpy as np
+    lib = L.load()
+    off = _off_tables([node_off, pre_off, suc_off], "dilate_batch")
+    S = off.shape[1] - 1
+    n_nodes, n_pre, n_suc = (int(x) for x in off[:, -1])
+    if [int(t.numel()) for t in (pre_u, pre_v, suc_u, suc_v)] != [n_pre, n_pre, n_suc, n_suc]:
+        raise L.LgcnError("dilate_batch: the edge offset tables do not end at the edge counts")
+    e = [_dev(t.reshape(-1), torch.int64, "dilate_batch edges") for t in (pre_u, pre_v, suc_u, suc_v)]
+    dev = e[0].device
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    empty = lambda: {"pre_u": torch.empty(0, **i64), "pre_v": torch.empty(0, **i64), "suc_u": torch.empty(0, **i64),
+                     "suc_v": torch.empty(0, **i64), "pre_off": np.zeros(S + 1, np.int64), "suc_off": np.zeros(S + 1, np.int64)}
+    if S == 0 or n_nodes == 0 or num_scales <= 1:
+        return [empty() for _ in range(1, num_scales)]
+    n_ws = int(lib.lgcn_dilate_batch_ws_elems(n_nodes, n_pre + n_suc))
+    if n_ws < 0:
+        L.check(n_ws, "lgcn_dilate_batch_ws_elems")
+    n_rp = int(lib.lgcn_csr_rowptr_elems(2 * n_nodes, 1))
+    ws, off_dev = torch.empty(n_ws, **i32), torch.from_numpy(off).to(dev)
+    p = L.DilateBatch()
+    p.n_scenes, p.n_nodes, p.n_pre, p.n_suc = S, n_nodes, n_pre, n_suc
+    p.off_host, p.off_dev, p.ws = off.ctypes.data, off_dev.data_ptr(), ws.data_ptr()
+    p.pre_u, p.pre_v, p.suc_u, p.suc_v = (t.data_ptr() if t.numel() else None for t in e)
+    rowptr, col = torch.empty(n_rp, **i32), torch.empty(max(n_pre + n_suc, 1), **i32)
+    p.rowptr, p.col = rowptr.data_ptr(), col.data_ptr()
+    L.check(lib.lgcn_dilate_batch_csr(C.byref(p), _stream()), "lgcn_dilate_batch_csr")
+    out = []
+    for _ in range(1, num_scales):
+        out_rowptr, bounds = torch.empty(n_rp, **i32), torch.empty((2, S + 1), **i32)
+        p.out_rowptr, p.bounds = out_rowptr.data_ptr(), bounds.data_ptr()
+        L.check(lib.lgcn_dilate_batch_count(C.byref(p), _stream()), "lgcn_dilate_batch_count")
+        b = read_back(bounds).astype(np.int64)
+        nnz = int(b[1, S])
+        out_col = torch.empty(max(nnz, 1), **i32)
+        out_u, out_v = torch.empty(max(nnz, 1), **i64), torch.empty(max(nnz, 1), **i64)
+        p.nnz, p.out_col, p.out_u, p.out_v = nnz, out_col.data_ptr(), out_u.data_ptr(), out_v.data_ptr()
+        L.check(lib.lgcn_dilate_batch_fill(C.byref(p), _stream()), "lgcn_dilate_batch_fill")
+        cut = int(b[0, S])
+        out.append({"pre_u": out_u[:cut], "pre_v": out_v[:cut], "suc_u": out_u[cut:nnz], "suc_v": out_v[cut:nnz],
+                    "pre_off": b[0] - b[0, 0], "suc_off": b[1] - b[1, 0]})
+        rowptr, col = out_rowptr, out_col
+        p.rowptr, p.col = rowptr.data_ptr(), col.data_ptr()
+    return out
+
+
+def cross_edges_batch(ctrs, feats, lane_idcs, pre_pairs, suc_pairs, left_pairs, right_pairs, node_off, lane_off, pre_off,
+                      suc_off, left_off, right_off, cross_dist: float):
+    """Left and right node adjacency of a whole batch of scenes (lgcn_cross_edges_batch): what cross_edges gives per scene
+    and side, from flat arrays.  ctrs, feats [N,2] fp32, lane_idcs [N] int64 (scene-local lanes), the pair lists [k,2]
+    int64 (scene-local lanes), all on the device, the scenes back to back; the offset tables are host arrays [S + 1].
+    Returns {"left_u", "left_v", "right_u", "right_v"} (flat int16 device tensors, scene-local, u ascending inside a
+    scene) and {"left_off", "right_off"} (numpy int64 [S + 1]).  One memset and four launches; ONE read-back (the counts)."""
+    import numpy as np
+    lib = L.load()
+    six = _off_tables([node_off, lane_off, pre_off, suc_off, left_off, right_off], "cross_edges_batch").astype(np.int64)
+    S = six.shape[1] - 1
+    n_lane, per = np.diff(six[1]), np.diff(six[2]) + np.diff(six[3]) + 1
+    csum = lambda x: np.concatenate([[0], np.cumsum(x, dtype=np.int64)])
+    off = _i32_table(np.concatenate([six, np.stack([csum(n_lane * n_lane), csum(np.diff(six[4]) * per),
+                                                    csum(np.diff(six[5]) * per)])]), "cross_edges_batch")
+    ctrs, feats = _dev(ctrs, torch.float32, "ctrs"), _dev(feats, torch.float32, "feats")
+    lane_idcs = _dev(lane_idcs, torch.int64, "lane_idcs")
+    pairs = [_dev(t.reshape(-1, 2), torch.int64, "pairs") for t in (pre_pairs, suc_pairs, left_pairs, right_pairs)]
+    n_nodes = int(six[0, -1])
+    if ctrs.numel() != 2 * n_nodes or feats.numel() != 2 * n_nodes or lane_idcs.numel() != n_nodes or \
+            [t.shape[0] for t in pairs] != [int(x) for x in six[2:, -1]]:
+        raise L.LgcnError("cross_edges_batch: the offset tables do not end at the array sizes")
+    dev = ctrs.device
+    i16 = dict(dtype=torch.int16, device=dev)
+    if S == 0:
+        z = torch.empty(0, **i16)
+        return {"left_u": z, "left_v": z, "right_u": z, "right_v": z}, {"left_off": np.zeros(1, np.int64),
+                                                                         "right_off": np.zeros(1, np.int64)}
+    n_ws = int(lib.lgcn_cross_edges_batch_ws_elems(n_nodes))
+    if n_ws < 0:
+        L.check(n_ws, "lgcn_cross_edges_batch_ws_elems")
+    ws, off_dev = torch.empty(max(n_ws, 1), dtype=torch.int32, device=dev), torch.from_numpy(off).to(dev)
+    mat = torch.empty(max(2 * int(off[6, -1]), 1), dtype=torch.uint8, device=dev)
+    counts = torch.empty((2, S + 1), dtype=torch.int32, device=dev)
+    out_u, out_v = torch.empty(max(2 * n_nodes, 1), **i16), torch.empty(max(2 * n_nodes, 1), **i16)
+    p = L.CrossBatch()
+    p.n_scenes, p.cross_dist = S, float(cross_dist)
+    p.n_nodes, p.n_lanes, p.n_pre, p.n_suc, p.n_left, p.n_right = (int(x) for x in six[:, -1])
+    p.off_host, p.off_dev = off.ctypes.data, off_dev.data_ptr()
+    p.ctrs, p.feats, p.lane_idcs = (t.data_ptr() if n_nodes else None for t in (ctrs, feats, lane_idcs))
+    p.pre_pairs, p.suc_pairs, p.left_pairs, p.right_pairs = (t.data_ptr() if t.numel() else None for t in pairs)
+    p.mat, p.ws, p.counts, p.out_u, p.out_v = mat.data_ptr(), ws.data_ptr(), counts.data_ptr(), out_u.data_ptr(), out_v.data_ptr()
+    L.check(lib.lgcn_cross_edges_batch(C.byref(p), _stream()), "lgcn_cross_edges_batch")
+    c = read_back(counts).astype(np.int64)
+    (l0, l1), (r0, r1) = (int(c[0, 0]), int(c[0, S])), (int(c[1, 0]), int(c[1, S]))
+    return ({"left_u": out_u[l0:l1], "left_v": out_v[l0:l1], "right_u": out_u[r0:r1], "right_v": out_v[r0:r1]},
+            {"left_off": c[0] - c[0, 0], "right_off": c[1] - c[1, 0]})
+
+
 # ------------------------------------------------------------------ weight packing
 def _cached(weight: torch.Tensor, key, make):
     """Per-tensor-object cache, valid while (data_ptr, _version) are unchanged.  Living on the

@@ -11,6 +11,9 @@ Argoverse-like sizes: one city table of 13,200 lane segments of 10 points each (
   full_ms            ... plus the per-scene preprocess for left / right (the default call)
   full_prefiltered_ms  the default call with explicit lane_ids: the lanes within the reference's query radius, found on
                      the host outside the timed region (the map query itself is out of scope)
+  dilated_batched_ms, full_batched_ms  dilated_ms and full_ms with batched=True: the scales and left / right from
+                     ops.dilate_batch and ops.cross_edges_batch on the whole batch (same raws, same process); the tool
+                     asserts that every pre / suc / left / right leaf of full_batched equals full's
 and the host model's scale-0 time per scene (median over --model-scenes scenes)."""
 import argparse
 import json
@@ -26,6 +29,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 # lgcn_scene_tracks: 2 kernels; lgcn_scene_lanes_rank: 1 memset + 2 kernels; lgcn_scene_lanes_fill: 2 kernels; one zero
 # fill (the head buffer)
 DEVICE_OPS = {"kernels": 6, "memsets": 1, "fills": 1, "size_readbacks": 2}
+# batched=True adds, whatever the number of scenes: lgcn_dilate_batch_csr: 1 kernel + lgcn_csr_build's 5 to 6; per scale
+# lgcn_dilate_batch_count: 2, lgcn_dilate_batch_fill: 1 and one read-back; lgcn_cross_edges_batch: 1 memset + 4 kernels and
+# one read-back (num_scales = 6: 25 to 26 kernels, 1 memset, 6 read-backs, besides torch's allocations and table uploads)
+BATCHED_TAIL_OPS = {"kernels": 26, "memsets": 1, "size_readbacks": 6}
 
 
 def city(n_x=120, n_y=110, cell=15.0, n_pts=10):
@@ -74,11 +81,13 @@ def main():
     lane_ids = [table.lane_id[n].tolist() for n in near]
     cfg = dict(C.CONFIG)
     out = {"scenes": args.scenes, "table_lanes": table.n_lanes, "table_points": table.n_pts, "tracks_per_scene": 40,
-           "candidates_prefiltered_per_scene": int(np.mean([len(n) for n in near])), "device_ops_per_batch": DEVICE_OPS}
+           "candidates_prefiltered_per_scene": int(np.mean([len(n) for n in near])), "device_ops_per_batch": DEVICE_OPS,
+           "batched_tail_ops_per_batch": BATCHED_TAIL_OPS}
 
-    scenes = None
+    scenes, kept = None, {}
     for name, kw in (("scale0_ms", dict(config=dict(cfg, num_scales=1), cross=False)), ("dilated_ms", dict(cross=False)),
-                     ("full_ms", dict()), ("full_prefiltered_ms", dict(lane_ids=lane_ids))):
+                     ("full_ms", dict()), ("full_prefiltered_ms", dict(lane_ids=lane_ids)),
+                     ("dilated_batched_ms", dict(cross=False, batched=True)), ("full_batched_ms", dict(batched=True))):
         times = []
         for _ in range(args.runs + 3):
             torch.cuda.synchronize()
@@ -87,6 +96,17 @@ def main():
             torch.cuda.synchronize()
             times.append((time.perf_counter() - t0) * 1e3)
         out[name] = round(statistics.median(times[3:]), 3)
+        kept[name] = scenes
+    # faster and different is not faster: at the timed size, every graph leaf of the batched call equals the per-scene call's
+    for a, b in zip(kept["full_batched_ms"], kept["full_ms"]):
+        for k in ("pre", "suc"):
+            assert len(a["graph"][k]) == len(b["graph"][k])
+            for x, y in zip(a["graph"][k], b["graph"][k]):
+                assert torch.equal(x["u"], y["u"]) and torch.equal(x["v"], y["v"]), k
+        for k in ("left", "right"):
+            for c in "uv":
+                assert a["graph"][k][c].dtype == b["graph"][k][c].dtype and torch.equal(a["graph"][k][c], b["graph"][k][c]), k
+    out["batched_equals_per_scene"] = True
     out["nodes_per_scene"] = int(np.mean([s["graph"]["num_nodes"] for s in scenes]))
     out["actors_per_scene"] = int(np.mean([len(s["ctrs"]) for s in scenes]))
     times = []

@@ -565,6 +565,21 @@ int lgcn_agg_mlp_multi(const lgcn_agg_mlp_t *const *ps_host, int n, void *stream
 int lgcn_ctx_heads(const float *x, int64_t n_rows, const void *const *w, int n_w, int mma, float *const *out, void *stream);
 
 /*
+ * Node-side tail of an Att block whose targets outnumber its context rows (A2M: the lane nodes; lanegcn.py:702-709),
+ * weight-stationary: the lgcn_agg_mlp problem
+ *   rel = {LGCN_REL_IDENT(a, W_agt), LGCN_REL_RANGE(m, W_c1)} with rowptr [N+1], flags = GN1 | RELU1 | GEMM2 | GN2 | RES |
+ *   RELU2, gn1, wp2, gn2, res, out, and optionally the chained U output (ch_wq, ch_gq_*, ch_wu, ch_u_out)
+ * on 48-row tiles whose 8 waves each keep a 16-channel slice of every weight in registers over the full K, each slice
+ * requested a GEMM or more before it is used.  Bit-identical to lgcn_agg_mlp on the same problem: the same accumulation
+ * order (relation 0 then 1, K-steps and plane products in order), the same GroupNorm sums, the segment sum in pair order.
+ * Exactly that shape: LGCN_MMA_F32 / LGCN_MMA_BF16X3 (checked first), any other relation list or flags, a chained V
+ * output, w4, out_pre / out_mid / out_pre2 or a tile_rb: LGCN_ESHAPE -- use lgcn_agg_mlp there.  n_rows < 0 or a NULL
+ * required pointer: LGCN_EINVAL; n_rows > 2^31 - 1: LGCN_ESHAPE; pointers (but rowptr) not 16-byte aligned: LGCN_EALIGN.
+ * n_rows == 0 returns LGCN_OK without a launch.
+ */
+int lgcn_node_tail(const lgcn_agg_mlp_t *p_host, void *stream);
+
+/*
  * MapNet input stage, lanegcn.py:324-327:
  *   out = ReLU( GN_a(W_a2 ReLU(W_a1 ctr + b_a1)) + GN_s(W_s2 ReLU(W_s1 seg + b_s1)) )
  * ctrs, feats: [N,2]; w1: [128,2] + b1 [128] (nn.Linear(2,128)); wp2: packed.

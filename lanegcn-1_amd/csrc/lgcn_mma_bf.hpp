@@ -108,8 +108,9 @@ struct Tile {
 
 // acc[rb][cb] (16 x 16 blocks: rows 16rb.., channels 32w + 16cb..) += A(planes) * W
 // A operand of 16x16x32: lane l holds A[l & 15][k = 8 (l >> 4) + j]; B operand B[k][col = l & 15].
-template <int F>
-struct BFrag { uint4 v[Fmt<F>::NP][2]; };
+// NCB: 16-column blocks of the fragment (2: a wave's 32 channels; 1: the 16-channel slices of lgcn_nodetail.hip)
+template <int F, int NCB = 2>
+struct BFrag { uint4 v[Fmt<F>::NP][NCB]; };
 
 template <int F>
 __device__ __forceinline__ void load_b(BFrag<F> &b, const uint4 *__restrict__ Bw, int wave, int lane, int s) {
@@ -120,8 +121,8 @@ __device__ __forceinline__ void load_b(BFrag<F> &b, const uint4 *__restrict__ Bw
             b.v[p][cb] = Bw[((((p * 4 + wave) * 4 + s) * 2 + cb) << 6) + lane];
 }
 
-template <int RB, int F>
-__device__ __forceinline__ void kstep(const uint16_t *__restrict__ arow, int s, const BFrag<F> &b, f32x4 (&acc)[RB][2]) {
+template <int RB, int F, int NCB>
+__device__ __forceinline__ void kstep(const uint16_t *__restrict__ arow, int s, const BFrag<F, NCB> &b, f32x4 (&acc)[RB][NCB]) {
     constexpr int PLANE = Tile<RB, F>::PLANE;
     uint4 a[Fmt<F>::NP][RB];
 #pragma unroll
@@ -132,7 +133,7 @@ __device__ __forceinline__ void kstep(const uint16_t *__restrict__ arow, int s, 
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
+        for (int cb = 0; cb < NCB; ++cb) {
             f32x4 c = acc[rb][cb];
 #pragma unroll
             for (int q = 0; q < Fmt<F>::NPROD; ++q)   // smallest terms first
@@ -230,12 +231,12 @@ __device__ __forceinline__ void acc_store(float *T, const f32x4 (&acc)[RB][2], i
         }
 }
 
-template <int RB>
-__device__ __forceinline__ void acc_zero(f32x4 (&acc)[RB][2]) {
+template <int RB, int NCB>
+__device__ __forceinline__ void acc_zero(f32x4 (&acc)[RB][NCB]) {
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
 template <int F>

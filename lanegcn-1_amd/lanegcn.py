@@ -472,9 +472,11 @@ class Att(nn.Module):
         # ctx.1 is linear: apply it to the per-target segment sum instead of every pair
         rels = [ops.RelSpec(agts, ops.packed(self.agt.weight)),
                 ops.RelSpec(m, ops.packed(self.ctx[1].weight), L.REL_RANGE16 if seg else L.REL_RANGE)]
-        return ops.agg_mlp(T, rels, _FULL, rowptr=ps.rowptr, gn1=_gn(self.norm),
-                           wp2=ops.packed(lin.linear.weight), gn2=_gn(lin.norm), res=agts, eps=self.norm.eps,
-                           tag="att_post", chain_u=chain_u, chain_v=chain_v)
+        # many targets (A2M: the lane nodes), no V to emit: the weight-stationary launch, same bits
+        tail = ops.node_tail if seg == 0 and chain_v is None and ops.node_tail_ok() else ops.agg_mlp
+        return tail(T, rels, _FULL, rowptr=ps.rowptr, gn1=_gn(self.norm),
+                    wp2=ops.packed(lin.linear.weight), gn2=_gn(lin.norm), res=agts, eps=self.norm.eps,
+                    tag="att_post", chain_u=chain_u, chain_v=chain_v)
 
 
 def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: Optional[dict] = None, uv=None,

@@ -1151,6 +1151,22 @@ def ctx_heads(x: torch.Tensor, wps: Sequence[torch.Tensor], outs: Optional[Seque
     return list(outs)
 
 
+def node_tail_ok() -> bool:
+    """lgcn_node_tail is in the library and implements the current matrix-core mode (f16x2, bf16); the others take agg_mlp."""
+    return _mma in (L.MMA_F16X2, L.MMA_BF16) and hasattr(L.load(), "lgcn_node_tail")
+
+
+def node_tail(n_rows: int, rels: Sequence[RelSpec], flags: int, *, tag="node_tail", **kw):
+    """An Att tail over many target rows -- rels = [IDENT(agts, W_agt), RANGE(m, W_c1)], every flag, gn1, wp2, gn2, res,
+    optionally chain_u -- in one weight-stationary launch (lgcn_node_tail): bit for bit what agg_mlp gives with the same
+    arguments.  The library refuses every other shape and the f32 / bf16x3 modes (node_tail_ok())."""
+    lib = L.load()
+    p, keep, out = _agg_params(n_rows, rels, flags, **kw)
+    with _Timed(tag):
+        L.check(lib.lgcn_node_tail(C.byref(p), _stream()), "lgcn_node_tail")
+    return out
+
+
 # ------------------------------------------------------------------ LaneConv (gather-free, weight-stationary)
 @dataclass
 class LcPlan:

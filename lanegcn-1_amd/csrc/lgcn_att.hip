@@ -170,7 +170,7 @@ void k_att_pairs_ws(const PairParams p, const int seg) {
         // ---- e = ReLU(GN_d(e1)) -> A planes
         {
             RowVals r = row_load(T, tidv);
-            row_gn<F == 0>(r, tidv, l_gd, l_btd, p.eps);
+            row_gn<F != 1>(r, tidv, l_gd, l_btd, p.eps);
             row_relu(r);
             row_split_store<F>(A, TL::PLANE, rowv, tidv, r);
         }
@@ -199,7 +199,7 @@ void k_att_pairs_ws(const PairParams p, const int seg) {
         // ---- m_p = ReLU(GN_c(t))
         {
             RowVals r = row_load(T, tidv);
-            row_gn<F == 0>(r, tidv, l_gc, l_btc, p.eps);
+            row_gn<F != 1>(r, tidv, l_gc, l_btc, p.eps);
             row_relu(r);
             const int64_t pr = pr0 + rowv;
             if (seg == 0) {

@@ -640,7 +640,7 @@ void k_lc_tile(const LcTileParams p) {
                     if ((int64_t)b * M + row < p.n_rows)
                         row_store_global(p.part + (((int64_t)b * p.n_groups + g) * M + row) * kC, tid, r);
                 } else {
-                    row_gn<F == 0>(r, tid, p.gn1_g, p.gn1_b, p.eps);
+                    row_gn<F != 1>(r, tid, p.gn1_g, p.gn1_b, p.eps);
                     row_relu(r);
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
@@ -677,7 +677,7 @@ void k_lc_tile(const LcTileParams p) {
                 const int64_t n = (int64_t)b * M + ph * HR + hrow;
                 if (hrow < HR) {
                     RowVals r = tile_row(sweep);
-                    row_gn<F == 0>(r, tid, p.gn2_g, p.gn2_b, p.eps);
+                    row_gn<F != 1>(r, tid, p.gn2_g, p.gn2_b, p.eps);
                     row_add(r, resv[sweep]);
                     row_relu(r);
                     if (n < p.n_rows) row_store_global(p.out + n * kC, tid, r);
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(256) void k_lc_combine(const LcCombParams p, int n_
 #pragma unroll
         for (int j = 0; j < 4; ++j) r.v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    row_gn<F == 0>(r, tid, p.gn1_g, p.gn1_b, p.eps);
+    row_gn<F != 1>(r, tid, p.gn1_g, p.gn1_b, p.eps);
     row_relu(r);
     row_split_store<F>(A, TL::PLANE, row, tid, r);
     lds_barrier();
@@ -761,7 +761,7 @@ __global__ __launch_bounds__(256) void k_lc_combine(const LcCombParams p, int n_
     acc_store<2>(T, acc, lane, wave);
     lds_barrier();
     r = row_load(T, tid);
-    row_gn<F == 0>(r, tid, p.gn2_g, p.gn2_b, p.eps);
+    row_gn<F != 1>(r, tid, p.gn2_g, p.gn2_b, p.eps);
     row_add(r, resv);
     row_relu(r);
     if (live_row) row_store_global(p.out + n * kC, tid, r);

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     const bool live = has_row && n < p.n_rows;
     if (has_row) {
         RowVals r = row_load(T, tid);
-        row_gn<F == 0>(r, tid, gnp, gnp + kC, p.eps);
+        row_gn<F != 1>(r, tid, gnp, gnp + kC, p.eps);
         row_relu(r);
         row_split_store<F>(A0, TL::PLANE, row, tid, r);      // A0's readers passed the barrier above
     }
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     lds_barrier();
     if (has_row) {
         RowVals r = row_load(T, tid);
-        row_gn<F == 0>(r, tid, gnp + 2 * kC, gnp + 3 * kC, p.eps);
+        row_gn<F != 1>(r, tid, gnp + 2 * kC, gnp + 3 * kC, p.eps);
         row_add(r, resv);
         row_relu(r);
         if (live) row_store_global(p.out + n * kC, tid, r);
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     lds_barrier();
     if (has_row) {
         RowVals r = row_load(T, tid);
-        row_gn<F == 0>(r, tid, gnp + 4 * kC, gnp + 5 * kC, p.eps);
+        row_gn<F != 1>(r, tid, gnp + 4 * kC, gnp + 5 * kC, p.eps);
         row_relu(r);
         row_split_store<F>(A0, TL::PLANE, row, tid, r);
     }

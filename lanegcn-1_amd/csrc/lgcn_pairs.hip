@@ -224,7 +224,26 @@ __global__ __launch_bounds__(64 * kPairWaves) __attribute__((amdgpu_waves_per_eu
         float q = q0 + q1;
         q += xlane(q, a16);
         q += xlane(q, a32);
-        rstd = 1.0f / sqrtf(q * (1.0f / kC) + p.eps);
+        const float var = q * (1.0f / kC);
+        rstd = 1.0f / sqrtf(var + p.eps);
+        // bf16 has fp32's exponent range: the squares of a row beyond ~2^60 leave fp32, and the row would come out as beta.
+        // row_rstd_wide (lgcn_tile.hpp) restated for this layout; the four lanes of a row hold the same bits of var, so they
+        // take the branch together and the exchanges find their partners.  fp16 planes cannot get there (lgcn_tile.hpp).
+        if constexpr (F != 1)
+            if (__builtin_expect(!(var <= 3.4028234e38f), 0)) {
+                constexpr float k = 0x1p-68f;
+                float w0 = 0.f, w1 = 0.f;
+#pragma unroll
+                for (int cb = 0; cb < 8; ++cb) {
+                    const f32x4 c = a[cb] * k;
+                    w0 = fmaf(c[0], c[0], w0); w1 = fmaf(c[1], c[1], w1);
+                    w0 = fmaf(c[2], c[2], w0); w1 = fmaf(c[3], c[3], w1);
+                }
+                float w = w0 + w1;
+                w += xlane(w, a16);
+                w += xlane(w, a32);
+                rstd = k / sqrtf(w * (1.0f / kC) + p.eps * (k * k));
+            }
     };
 
     for (int base = first; base < nblk; base += rstride) {   // rounds of 8 blocks, uniform per workgroup

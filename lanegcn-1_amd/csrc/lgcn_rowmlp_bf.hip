@@ -451,7 +451,7 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
         lds_barrier();
         if (my_has_row) {
             RowVals r = row_load(T + (upper ? 32 : 0) * kLDA, my_rt);
-            row_gn<F == 0>(r, my_rt, gnp + 4 * kC, gnp + 5 * kC, p.eps);
+            row_gn<F != 1>(r, my_rt, gnp + 4 * kC, gnp + 5 * kC, p.eps);
             row_relu(r);
             row_split_store<F>(Yp, TL::PLANE, my_row, my_rt, r);      // Yp's readers passed the barrier above
         }
@@ -477,7 +477,7 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
 #ifndef LGCN_STAMPS
         if (my_live && p.out_pre) row_store_global(p.out_pre + my_n * kC, my_rt, r);
 #endif
-        if (flags & LGCN_F_GN1) row_gn<F == 0>(r, my_rt, gnp, gnp + kC, p.eps);
+        if (flags & LGCN_F_GN1) row_gn<F != 1>(r, my_rt, gnp, gnp + kC, p.eps);
         if (!two && my_live && (flags & LGCN_F_RES)) row_add(r, resv);
         if (flags & LGCN_F_RELU1) row_relu(r);
         if (two && my_live && p.out_mid) row_store_global(p.out_mid + my_n * kC, my_rt, r);
@@ -503,7 +503,7 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
     if (my_has_row) {
         RowVals r = row_load(T + (upper ? 32 : 0) * kLDA, my_rt);
         if (my_live && p.out_pre2) row_store_global(p.out_pre2 + my_n * kC, my_rt, r);
-        if (flags & LGCN_F_GN2) row_gn<F == 0>(r, my_rt, gnp + 2 * kC, gnp + 3 * kC, p.eps);
+        if (flags & LGCN_F_GN2) row_gn<F != 1>(r, my_rt, gnp + 2 * kC, gnp + 3 * kC, p.eps);
         if (my_live && (flags & LGCN_F_RES)) row_add(r, resv);
         if (flags & LGCN_F_RELU2) row_relu(r);
         if (my_live) row_store_global(p.out + my_n * kC, my_rt, r);
@@ -593,7 +593,7 @@ __global__ __launch_bounds__(256) void k_mapnet_input_bf(const InputParams p, in
             const int row = c0 + (tid >> 3);
             if (row < ROWS) {
                 RowVals r = row_load(T + c0 * kLDA, tid);
-                row_gn<F == 0>(r, tid, g, bt, p.eps);
+                row_gn<F != 1>(r, tid, g, bt, p.eps);
                 if (br == 0) {
                     keep[c0 / 32] = r;
                 } else {

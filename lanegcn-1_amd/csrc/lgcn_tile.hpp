@@ -44,20 +44,26 @@ __device__ __forceinline__ float sum8(float x) {
 // and the row would come out as beta): the same sum over the centred values scaled by 2^-68 (exact), rstd scaled back.
 // Rare path behind one compare; a row that holds a NaN or an inf takes it too and comes out NaN as before.  The eight
 // lanes of a row share var, so they take the branch together and sum8 finds its partners.
-// row_gn compiles it in with WIDE (the default): the f32 kernels and the split kernels of the range-safe three-plane
-// mode (Fmt<0>) do.  The fp16-plane kernels pass WIDE = false: their GEMM outputs cannot pass 128 * 15 * 65520^2 < 2^50,
+// row_gn compiles it in with WIDE (the default): the f32 kernels and the split kernels of every format with fp32's
+// exponent range do -- the three-plane mode (Fmt<0>) and the single bf16 plane (Fmt<2>), whose rows reach a GroupNorm at
+// 2^100 as readily as fp32's (the pair kernel of lgcn_pairs.hip restates the same path for its own layout).
+// The fp16-plane kernels (Fmt<1>) pass WIDE = false: their GEMM outputs cannot pass 128 * 15 * 65520^2 < 2^50,
 // whose squares fit (what else reaches a GroupNorm there -- U + V of the pair stage, the rank-4 meta update -- are such
 // outputs or O(1) inputs in this network), and they keep the register budget that lets two workgroups share a CU.
 // row_gn_hat, the backward's recomputation, and k_gn_bwd take the same path: with rstd ~ 2^-70 the gradients of such a row
 // (dx ~ rstd dy, dW = dT^T x ~ dy) stay inside fp32, and a backward that returned rstd = 0 where the forward did not
 // would hand back silent zeros.
+// The squares are added one at a time (two live temporaries, not the pairwise tree of row_gn's first pass): the bf16
+// LaneConv tile kernel sits at its 128-VGPR limit and takes no more without scratch.
 __device__ __forceinline__ float row_rstd_wide(const RowVals &r, float mean, float eps) {
     constexpr float k = 0x1p-68f;
     float q = 0.f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float a = (r.v[j].x - mean) * k, bb = (r.v[j].y - mean) * k, c = (r.v[j].z - mean) * k, d = (r.v[j].w - mean) * k;
-        q += (a * a + bb * bb) + (c * c + d * d);
+        float t = (r.v[j].x - mean) * k; q += t * t;
+        t = (r.v[j].y - mean) * k; q += t * t;
+        t = (r.v[j].z - mean) * k; q += t * t;
+        t = (r.v[j].w - mean) * k; q += t * t;
     }
     return k / sqrtf(sum8(q) * (1.0f / kC) + eps * (k * k));
 }

@@ -23,7 +23,8 @@ EPS = 1e-5
 #            below 65520 (the first value that rounds to fp16's infinity), and within 1e-4 while a block's max |W| >= 2^-9
 #            (2e-3) and max |x| >= 2^-10 with the other operand O(1); below it the fp16 planes run out of bits (1e-3 at
 #            max |W| = 2^-13, 1e-2 at 2^-17: DESIGN.md "Operand scale"; tools/check_weight_scale.py lists such blocks)
-#   "bf16"   single bf16 product (BASELINE config "bf16"; not within 1e-4)
+#   "bf16"   single bf16 product (BASELINE config "bf16"; not within 1e-4: 8 significand bits, 1e-3 .. 1e-2 against float64
+#            at any operand scale -- fp32's exponent range, like bf16x3)
 _mma = L.MMA_NAMES[os.environ.get("LGCN_MMA", "f16x2")]
 
 

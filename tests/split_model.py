@@ -18,8 +18,9 @@ EPS = 1e-5
 FORMATS = {
     "bf16x3": ("bf16", 3, (2, 0, 1, 1, 0, 0), (0, 2, 1, 0, 1, 0)),
     "f16x2": ("f16", 2, (1, 0, 0), (0, 1, 0)),
+    "bf16": ("bf16", 1, (0,), (0,)),
 }
-MODES = ("f32", "bf16x3", "f16x2")
+MODES = ("f32", "bf16x3", "f16x2", "bf16")
 
 
 def arr(a, dtype=None):

@@ -18,8 +18,8 @@ order of their own (two independent noises of the oracle's size, and the tail of
 
 Cases (hot_path_cases): f16x2 at s_w = 2^{0, -2, -4, -6, -8, -10}, every 128-column block at max |W| = 2^-9 (the
 threshold of tools/check_weight_scale.py), the wide state, and the one-scene S0 batch at 2^0 and
-2^-6; bf16x3 and f32 at 2^{0, -10, -20} and the wide state; HotPathEngine (forward_guarded and one captured replay) in
-f16x2 at 2^0, 2^-8 and the wide state, with the same bars and bitwise the module path.  Fresh modules per case (no packed
+2^-6; bf16x3, f32 and the single-product bf16 mode at 2^{0, -10, -20} and the wide state; HotPathEngine
+(forward_guarded and one captured replay) in f16x2 at 2^0, 2^-8 and the wide state, with the same bars and bitwise the module path.  Fresh modules per case (no packed
 image is reused), ops.set_guard("raise") throughout: a silent bf16x3 re-run must not satisfy an f16x2 bar.
 Measured figures: DESIGN.md section 5c, "whole hot path"."""
 import numpy as np
@@ -35,6 +35,7 @@ pytestmark = pytest.mark.gpu
 U = lambda e: ("uniform", e)
 CASES = [("f16x2", "b4", st) for st in H.F16_GRID + [("blocks", -9), H.WIDE]] + [("f16x2", "s0", U(0)), ("f16x2", "s0", U(-6))]
 CASES += [(m, "b4", st) for m in ("bf16x3", "f32") for st in H.EXACT_GRID + [H.WIDE]]
+CASES += [("bf16", "b4", st) for st in H.EXACT_GRID + [H.WIDE]]
 ENGINE_STATES = [U(0), U(-8), H.WIDE]
 
 

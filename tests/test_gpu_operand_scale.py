@@ -17,12 +17,15 @@ their rows from [n, 2] inputs -- att_pairs, mapnet_input -- to those inputs and 
 rows exactly), s_w to every 128-wide weight (and, for att_pairs, to U and V).
   f16x2:        s_w in 2^{4, 0, -4, -8, -12, -16} at s_x = 1;  s_x in 2^{12, -8, -14} at s_w = 1
   bf16x3, f32:  (s_x, s_w) = (2^-100, 2^80), (2^60, 2^40), (2^-8, 2^-8)
+  bf16:         the same three -- one bf16 plane, one product (Fmt<2>): fp32's exponent range at 8 significand bits, so
+                its model stands at 1e-3 .. 5e-3 whatever the scale, and the bar is twice that
 Rows: n = 1, 33, 130 (a single row, a ragged second tile, several tiles).  Each case prints, per tensor, the model's and the
 kernel's error before anything is asserted.
 
 At (2^60, 2^40) and (2^-100, 2^80) the values that reach a GroupNorm are ~2^100 / ~2^80 and their squares leave fp32: these
 cases are what row_gn's wide path (csrc/lgcn_tile.hpp: row_rstd_wide) exists for -- without it the rows come out as beta
-(error 0.3 .. 1 against float64).  Measured figures: DESIGN.md section 5c.
+(error 0.3 .. 1 against float64), in every mode whose operands have fp32's exponent range: f32, bf16x3 and bf16.
+Measured figures: DESIGN.md section 5c.
 """
 import functools
 import types
@@ -41,6 +44,7 @@ ROWS = (1, 33, 130)
 F16_GRID = [(0, 4), (0, 0), (0, -4), (0, -8), (0, -12), (0, -16), (12, 0), (-8, 0), (-14, 0)]
 WIDE_GRID = [(-100, 80), (60, 40), (-8, -8)]
 CASES = [("f16x2", ex, ew) for ex, ew in F16_GRID] + [(m, ex, ew) for m in ("bf16x3", "f32") for ex, ew in WIDE_GRID]
+CASES += [("bf16", ex, ew) for ex, ew in WIDE_GRID]
 IDS = ["%s-x2^%d-w2^%d" % c for c in CASES]
 T_AGT, S_CTX, P_PAIRS = 9, 11, 33
 
@@ -216,13 +220,13 @@ def pair_set(ops, agt, ctx):
     return ps, hi, wi
 
 
-ATT_IMPLS = {"f32": ["stream"], "bf16x3": ["ws"], "f16x2": ["wi", "ws"]}
+ATT_IMPLS = {"f32": ["stream"], "bf16x3": ["ws"], "f16x2": ["wi", "ws"], "bf16": ["wi", "ws"]}
 
 
 @pytest.mark.parametrize("mode,ex,ew", CASES, ids=IDS)
 def test_att_pairs(mods, mode, ex, ew):
-    """lgcn_att_pairs (f32, "stream"), lgcn_att_pairs_ws (bf16x3; f16x2 "ws") and lgcn_att_pairs_wi (f16x2 "wi": the
-    K-permuted images of packed_kperm), P = 33."""
+    """lgcn_att_pairs (f32, "stream"), lgcn_att_pairs_ws (bf16x3; f16x2 and bf16 "ws") and lgcn_att_pairs_wi (f16x2 and
+    bf16 "wi": the K-permuted images of packed_kperm), P = 33."""
     M, ops, L = mods
     d = draw()
     agt, ctx, bd0 = p2(d["agt"], ex), p2(d["ctx"], ex), p2(d["b1"][0], ex)
@@ -286,7 +290,10 @@ def conv_draw(shape):
 @pytest.mark.parametrize("shape", CONV_SHAPES, ids=["%d-%d-k%d-s%d" % s for s in CONV_SHAPES])
 def test_conv1d_unit(mods, shape, ex, ew):
     """lgcn_conv1d_gn_train: the two-plane units (exact=False) against the f16x2 model, the exact units (exact=True) at the
-    floor at every scale; y (the convolution) and out (behind the GroupNorm over the actor's lout x cout values)."""
+    floor at every scale; y (the convolution) and out (behind the GroupNorm over the actor's lout x cout values).
+    The conv units take no matrix mode: ops.conv1d_gn / conv1d_gn_train run lgcn_conv1d_gn (two fp16 planes) or, with
+    exact=True, lgcn_conv1d_gn_f32 whatever ops.set_mma() says, and no bf16 product is ever formed here -- so "bf16" adds
+    no case to this test."""
     M, ops, L = mods
     x0, w0, gamma, beta = conv_draw(shape)
     x, w, stride = p2(x0, ex), p2(w0, ew), shape[3]

@@ -107,6 +107,20 @@ def test_bf16x3_model_is_scale_free(state):
     assert max(got.values()) <= 3e-7         # fp32 holds between the GEMMs (2^-24 each), no plane effect
 
 
+def test_bf16_model_is_scale_free():
+    """The single-product mode (one bf16 plane: fp32's exponent range, 8 significand bits) over EXACT_GRID: 4e-3 .. 8e-3
+    per stage at s_w = 2^0, inside the 2e-2 the project allows that mode, and -- unlike f16x2, whose error grows like
+    1 / s_w -- no larger at 2^-10 and 2^-20 (it shrinks there: the float64 function's GroupNorms meet eps and the
+    residuals take over)."""
+    errs = {st: H.model_err("b4", st, "bf16") for st in H.EXACT_GRID}
+    for st, e in errs.items():
+        print("HOTPATH model b4 %s bf16: %s" % (H.case_id(st), " ".join("%.2e" % e[k] for k in H.STAGES)))
+    base = errs[U(0)]
+    assert all(1e-3 <= base[k] <= 2e-2 for k in H.STAGES)               # the model really rounds to 8 bits
+    for st, e in errs.items():
+        assert all(e[k] <= 1.5 * base[k] for k in H.STAGES), (st, e)
+
+
 def test_bar():
     assert H.bar(0.0, 0.0) == 1e-6 and H.bar(0.0, 5e-7) == pytest.approx(2e-6)
     assert H.bar(2e-5, 5e-7) == pytest.approx(4e-5) and H.bar(5e-5, 1e-6) == pytest.approx(1e-4)

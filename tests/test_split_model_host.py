@@ -58,6 +58,32 @@ def test_bf16x3_is_scale_free(draw):
     assert max(errs.values()) <= 2e-8
 
 
+def test_bf16_is_one_rne_plane_and_one_product(draw):
+    """LGCN_MMA_BF16 (Fmt<2>): NP = 1, PA = PB = {0} -- the one plane is the RNE rounding itself, nothing is left over."""
+    assert S.FORMATS["bf16"] == ("bf16", 1, (0,), (0,)) and "bf16" in S.MODES
+    x, w = draw
+    v = np.concatenate([x.ravel(), w.ravel(), np.array([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, 1.2345678 * 2.0 ** -100, 2.0 ** -130],
+                                                       np.float32)])
+    p = S.planes(v, "bf16")
+    assert len(p) == 1 and np.array_equal(p[0], S.round16(v, "bf16").astype(np.float64))
+    assert p[0][-4:-2].tolist() == [1.0, 1.0 + 2.0 ** -6] and p[0][-1] == 2.0 ** -130       # ties to even; a bf16 subnormal survives
+    assert abs(p[0][-2] / (1.2345678 * 2.0 ** -100) - 1) <= 2.0 ** -9 and p[0][-2] * 2.0 ** 100 * 128 % 1 == 0     # 8 bits at 2^-100
+    # the product is that of the rounded operands, in float64
+    want = S.round16(x, "bf16").astype(np.float64) @ S.round16(w, "bf16").astype(np.float64).T
+    assert np.array_equal(S.mm(x, w, "bf16"), want)
+
+
+def test_bf16_is_scale_free(draw):
+    """One bf16 plane has fp32's exponent range: the model's error (8 significand bits per operand) does not move with a
+    power-of-two scale on either operand, as bf16x3's does not."""
+    x, w = draw
+    base = model_err(x, w, "bf16")
+    errs = {(ex, ew): model_err(scaled(x, ex), scaled(w, ew), "bf16") for ex, ew in ((0, 0), (-100, 80), (-8, -8))}
+    print("bf16 model: %s" % " ".join("%.3e" % e for e in errs.values()))
+    assert 5e-4 <= base <= 1e-2                            # 2^-9 per operand over a 128-term sum of mixed signs
+    assert all(abs(e - base) <= 1e-12 * base for e in errs.values())
+
+
 def test_planes_are_rne_with_fp32_residual_and_subnormals():
     # fp16: 2049 is a tie (2048 | 2050) -> even 2048, residual 1; 2^-20 is subnormal in fp16 and must survive;
     # 2^-25 rounds to zero in the first plane (half the smallest subnormal: tie to even) and is gone

@@ -1465,6 +1465,41 @@ typedef struct {
 int64_t lgcn_cross_edges_batch_ws_elems(int64_t n_nodes);
 int lgcn_cross_edges_batch(const lgcn_cross_batch_t *p, void *stream);
 
+/* ------------------------------------------------------------------ */
+/* Forecasting metrics of a whole split (reference test.py:60-100)    */
+/* ------------------------------------------------------------------ */
+
+/*
+ * lgcn_eval_scenes: one launch per batch, one wave per scene; no atomics, no host read.
+ *   reg [A, M, T, 2] (world frame), cls [A, M], gt [A, T, 2] fp32; has [A, T] bytes; actor_off [B+1] int32
+ *   (FlatBatch.actor_off); slot [B] int64: the row of each scene in the split-wide buffers, which the caller owns and
+ *   zero-fills once: rec [n_slots, 32] fp32 and, both or neither, traj [n_slots, M, T, 2], score [n_slots, M].
+ * Only the first actor row a = actor_off[b] of scene b is read (test.py:86).  rec[slot[b]]:
+ *   [0] flag: 0 = not evaluated (no actor, or has[a, :horizon] not all set), 1 = evaluated, 2 = a non-finite value in
+ *       reg[a, :, :horizon], cls[a] or gt[a, :horizon] (the has test comes first)
+ *   [1] M, [2] horizon, [3] 0
+ *   [4 + 3 (k - 1) + 0 / 1 / 2] = minFDE_k, minADE_k, p_k for k = 1..M, over the first k modes as they come:
+ *       j* = first j < k of the smallest |reg[a, j, horizon - 1] - gt[a, horizon - 1]|; minADE_k = that mode's mean
+ *       displacement over t < horizon (Argoverse: pick by FDE, report its ADE); p_k = softmax(cls[a, :k])[j*]
+ *   every other float is 0; a record of flag 0 or 2 is 0 behind [0].  traj / score [slot[b]] = reg[a] / cls[a] for flag 1
+ *   and 2.  A slot that no launch names is not touched.  The record depends on the scene's rows alone (not on B, the
+ *   scene's place in the batch or the grid).
+ *   err [1] int32: set to 1 when a slot[b] lies outside [0, n_slots); nothing is written for that scene.
+ * lgcn_eval_reduce: one launch per summary, float64 in a fixed order (a strided pass, then a tree): bitwise repeatable.
+ *   cnt [3] int64 = the slots with flag 0, 1, 2; out [8, 6] float64: row k - 1 = sums over the flag-1 records with
+ *   M >= k of minADE_k, minFDE_k, [minFDE_k > miss_thr], (1 - p_k)^2 + minFDE_k, (1 - p_k)^2 + minADE_k,
+ *   min(-log p_k, -log 0.05) + minADE_k (the numerators of Argoverse's minADE, minFDE, MR, brier-minFDE, brier-minADE,
+ *   p-minADE).  err [1] int32: written 1 when two flag-1 records differ in [1] or [2], else 0.
+ * Checked before any launch: LGCN_EINVAL (null pointer, negative size, M / T / horizon < 1, horizon > T, one of traj /
+ * score alone), LGCN_ESHAPE (M > 8, T > 64, B or n_slots > 2^31 - 1), LGCN_EALIGN (any pointer but `has` not 16-byte
+ * aligned).  B == 0 / n_slots == 0: LGCN_OK, nothing launched, nothing written.
+ */
+int lgcn_eval_scenes(const float *reg, const float *cls, const float *gt, const unsigned char *has,
+                     const int32_t *actor_off, const int64_t *slot, int64_t n_scenes, int n_mod, int n_t, int horizon,
+                     int64_t n_slots, float *rec, float *traj, float *score, int32_t *err, void *stream);
+int lgcn_eval_reduce(const float *rec, int64_t n_slots, double miss_thr, double *out, int64_t *cnt, int32_t *err,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

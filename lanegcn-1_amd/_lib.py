@@ -356,6 +356,8 @@ SIGNATURES = {
     "lgcn_dilate_batch_fill": (C.c_int, [C.POINTER(DilateBatch), _P]),
     "lgcn_cross_edges_batch_ws_elems": (C.c_int64, [_L]),
     "lgcn_cross_edges_batch": (C.c_int, [C.POINTER(CrossBatch), _P]),
+    "lgcn_eval_scenes": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
+    "lgcn_eval_reduce": (C.c_int, [_P, _L, _D, _P, _P, _P, _P]),
 }
 
 _lib = None

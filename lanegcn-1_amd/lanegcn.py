@@ -1058,6 +1058,14 @@ class Net(nn.Module):
     def _finish_inference(self, eng, fb, out, feats, rot, orig, sizes) -> Dict[str, List[Tensor]]:
         """The host-side checks behind a whole-Net forward `out` of the device batch `fb` (feats / rot / orig: its actor
         inputs, on the host or on the device), then the per-scene lists."""
+        out = self._check_inference(eng, fb, out, feats, rot, orig, sizes)
+        # per-scene views in two calls (a Python slice per scene and tensor costs ~2 us each: 0.13 ms at batch 32)
+        sizes = [int(a) for a in sizes]
+        return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
+
+    def _check_inference(self, eng, fb, out, feats, rot, orig, sizes) -> Dict:
+        """The host-side checks of _finish_inference (one device->host read; the pair-capacity regrow and the range
+        guard run the forward again) -> the flat engine output that passed them: cls [A, M], reg [A, M, T, 2]."""
         # one device->host read for the host-side checks: the range guard's flag and the three pair counts
         host = torch.cat([out["nonfinite"].view(1)] + [c.view(1) for c in out["n_pairs"]]).tolist()
         if eng.hot.pair_caps == "tight":
@@ -1085,21 +1093,27 @@ class Net(nn.Module):
             host = [0] + torch.stack(out["n_pairs"]).flatten().tolist()
         if Att.strict and any(int(c) == 0 for c in host[1:]):
             raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
-        # per-scene views in two calls (a Python slice per scene and tensor costs ~2 us each: 0.13 ms at batch 32)
-        sizes = [int(a) for a in sizes]
-        return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
+        return out
 
     def forward_store(self, store, indices) -> Dict[str, List[Tensor]]:
         """No-grad forward of the scenes `indices` of a flatfile.DeviceSceneStore: the batch is cut out of the resident
         store by one launch (no per-scene host work, no scene dicts) and run eagerly through engine.FullNetEngine.
         Output and error behaviour are those of forward(data) on the same scenes: per-scene lists in world coordinates,
         KeyError when pre[5] / suc[5] is empty, RuntimeError under Att.strict when a fusion block has no pair."""
+        fb, ex, out = self.forward_store_flat(store, indices)
+        sizes = [int(a) for a in ex["sizes"]]
+        return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
+
+    def forward_store_flat(self, store, indices, plan=None):
+        """forward_store before its outputs are cut into per-scene lists -> (fb, ex, out): the FlatBatch and the extras of
+        store.batch(indices), and the flat engine output behind the host-side checks (out["cls"] [A, M], out["reg"]
+        [A, M, T, 2] in world coordinates, actor rows in batch order).  Errors as forward_store's."""
         from .engine import FullNetEngine
         eng = self.__dict__.get("_engine")
         if eng is None:
             eng = FullNetEngine(self)
             self.__dict__["_engine"] = eng
-        plan = store.plan(indices)
+        plan = store.plan(indices) if plan is None else plan
         ns = plan.num_scales
         if plan.n_nodes == 0 or plan.n_edges[2 * ns - 2] == 0 or plan.n_edges[2 * ns - 1] == 0:
             raise KeyError("node_idcs")
@@ -1109,7 +1123,7 @@ class Net(nn.Module):
             fb, ex = store.batch(indices, plan=plan)
             feats, rot, orig, sizes = ex["actor_feats"], ex["rot"], ex["orig"], ex["sizes"]
             out = eng.forward(fb, feats, rot, orig, sizes, return_pairs=Att.strict)
-            return self._finish_inference(eng, fb, out, feats, rot, orig, sizes)
+            return fb, ex, self._check_inference(eng, fb, out, feats, rot, orig, sizes)
 
     def forward_store_train(self, store, indices, rot_dt=None):
         """Training forward of the scenes `indices` of a flatfile.DeviceSceneStore -> (out, data): the modules of

@@ -2465,3 +2465,77 @@ def scene_lanes_fill(job: SceneLanesJob, totals, head2: torch.Tensor) -> dict:
         setattr(p, k, v.data_ptr() if v.numel() else None)
     L.check(L.load().lgcn_scene_lanes_fill(C.byref(p), _stream()), "lgcn_scene_lanes_fill")
     return o
+
+
+# ------------------------------------------------------------------ forecasting metrics of a split (lanegcn_amd.evaluate)
+EVAL_REC = 32          # floats of one scene's record (include/lgcn.h, lgcn_eval_scenes)
+EVAL_MAX_MOD = 8
+
+
+def _eval_arg(t, dtype, shape, name):
+    """A contiguous device tensor of `dtype` and `shape` whose first byte is 16-byte aligned (a copy where a view is not)."""
+    t = _dev(t, dtype, name)
+    if tuple(t.shape) != tuple(shape):
+        raise L.LgcnError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _eval_out(t, dtype, shape, name):
+    if t is None:
+        return None
+    if not t.is_cuda or not t.is_contiguous() or t.dtype != dtype or tuple(t.shape) != tuple(shape) or t.data_ptr() % 16:
+        raise L.LgcnError("%s must be a contiguous, 16-byte aligned CUDA tensor of %s %s" % (name, dtype, tuple(shape)))
+    return t
+
+
+def eval_scenes(reg, cls, gt, has, actor_off, slot, horizon: int, rec, traj=None, score=None, err=None) -> None:
+    """lgcn_eval_scenes: one launch on the current stream, no host read.  reg [A, M, T, 2], cls [A, M], gt [A, T, 2] fp32,
+    has [A, T] bool / uint8, actor_off [B+1] int32, slot [B] int64; writes rec [n_slots, 32] (and traj [n_slots, M, T, 2],
+    score [n_slots, M], both or neither) at the rows `slot` names.  err: int32 [1], set to 1 by a slot outside the table."""
+    if reg.dim() != 4 or reg.shape[3] != 2:
+        raise L.LgcnError("eval_scenes: reg must be [A, M, T, 2], got %s" % (tuple(reg.shape),))
+    A, M, T, _ = reg.shape
+    B = slot.numel()
+    reg = _eval_arg(reg, torch.float32, (A, M, T, 2), "eval_scenes reg")
+    cls = _eval_arg(cls, torch.float32, (A, M), "eval_scenes cls")
+    gt = _eval_arg(gt, torch.float32, (A, T, 2), "eval_scenes gt")
+    if has.dtype not in (torch.bool, torch.uint8):
+        raise L.LgcnError("eval_scenes: has must be bool or uint8, got %s" % has.dtype)
+    has = _eval_arg(has, has.dtype, (A, T), "eval_scenes has")
+    actor_off = _eval_arg(actor_off, torch.int32, (B + 1,), "eval_scenes actor_off")
+    slot = _eval_arg(slot, torch.int64, (B,), "eval_scenes slot")
+    if rec.dim() != 2:
+        raise L.LgcnError("eval_scenes: rec must be [n_slots, %d]" % EVAL_REC)
+    n_slots = rec.shape[0]
+    rec = _eval_out(rec, torch.float32, (n_slots, EVAL_REC), "eval_scenes rec")
+    traj = _eval_out(traj, torch.float32, (n_slots, M, T, 2), "eval_scenes traj")
+    score = _eval_out(score, torch.float32, (n_slots, M), "eval_scenes score")
+    err = _eval_out(err, torch.int32, (1,), "eval_scenes err")
+    if err is None:
+        raise L.LgcnError("eval_scenes: err (int32 [1] on the device) is required")
+    if any(t is not None and t.device != reg.device for t in (cls, gt, has, actor_off, slot, rec, traj, score, err)):
+        raise L.LgcnError("eval_scenes: every tensor must live on %s" % (reg.device,))
+    if A == 0 and B > 0:          # no row to point at: every scene of the batch is empty; the kernel reads no row
+        reg, cls, gt, has = rec, rec, rec, rec
+    L.check(L.load().lgcn_eval_scenes(_ptr(reg), _ptr(cls), _ptr(gt), _ptr(has), _ptr(actor_off), _ptr(slot), B, M, T, int(horizon),
+                                      n_slots, _ptr(rec), _ptr(traj), _ptr(score), _ptr(err), _stream()), "lgcn_eval_scenes")
+
+
+def eval_reduce(rec, miss_thr: float, out, cnt, err) -> None:
+    """lgcn_eval_reduce: one launch on the current stream: out [8, 6] float64 (row k - 1: the six sums at K = k), cnt [3]
+    int64 (slots of flag 0, 1, 2), err int32 [1] (set to 1 when evaluated records disagree on M or the horizon)."""
+    if rec.dim() != 2:
+        raise L.LgcnError("eval_reduce: rec must be [n_slots, %d]" % EVAL_REC)
+    n_slots = rec.shape[0]
+    rec = _eval_out(rec, torch.float32, (n_slots, EVAL_REC), "eval_reduce rec")
+    out = _eval_out(out, torch.float64, (EVAL_MAX_MOD, 6), "eval_reduce out")
+    cnt = _eval_out(cnt, torch.int64, (3,), "eval_reduce cnt")
+    err = _eval_out(err, torch.int32, (1,), "eval_reduce err")
+    if out is None or cnt is None or err is None:
+        raise L.LgcnError("eval_reduce: out, cnt and err are required")
+    if n_slots == 0:
+        out.zero_()
+        cnt.zero_()
+        return
+    L.check(L.load().lgcn_eval_reduce(_ptr(rec), n_slots, float(miss_thr), _ptr(out), _ptr(cnt), _ptr(err), _stream()),
+            "lgcn_eval_reduce")

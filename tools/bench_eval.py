@@ -1,0 +1,149 @@
+"""Evaluating a split: lanegcn_amd.evaluate.evaluate_store against the loop a user had to write without it, and the two
+evaluation launches alone.
+
+    python tools/bench_eval.py [--scenes 256] [--batch 32] [--rounds 30] [--warmup 5] [--reps 3] [--slots 39472]
+
+The store and the protocol of tools/bench_store.py: `scenes` synthetic scenes of S2's per-scene size (324 nodes, 50
+actors), batches of `batch`; one process measures, the two loops alternating, `reps` times over.
+  (a) scenes_per_s_evaluate  evaluate_store over `rounds` batches + summary() (one reduce launch, one read)
+  (b) scenes_per_s_manual    the same batches through Net.forward_store, PostProcess.forward's per-scene host copies of
+                             reg[i][0:1] / gt_preds / has_preds, and pred_metrics at the end
+      each window starts and ends with a synchronise; scenes/s = rounds * batch / window
+  (c) eval_scenes_us         lgcn_eval_scenes for one batch between device events
+  (d) eval_reduce_us         lgcn_eval_reduce over `slots` records (39,472: the Argoverse validation split) between events
+  (c) and (d) are medians over `rounds` launches after `warmup`, each behind a queued 256 MB fill (the stream is busy while
+  the host enqueues, so the interval is the launch and not the host's call).  Per figure the JSON line carries the median of the `reps`
+values and their lowest and highest (the spread between repetitions)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scenes", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--rounds", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--slots", type=int, default=39472)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import lanegcn_amd  # noqa: F401
+    from lanegcn_amd import data as gen
+    from lanegcn_amd import lanegcn as M
+    from lanegcn_amd import ops
+    from lanegcn_amd.evaluate import Evaluator, evaluate_store
+    from lanegcn_amd.flatfile import DeviceSceneStore, write_scenes
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_eval.py measures on the GPU; none found")
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "split.npz")
+        write_scenes(path, gen.synth_batch("S2", seed=0, n_scenes=args.scenes))
+        store = DeviceSceneStore(path)
+    torch.manual_seed(0)
+    net = M.Net(M.config).cuda().eval()
+    post = M.PostProcess(M.config)
+    cfg = M.config
+    sync = torch.cuda.synchronize
+    rng = np.random.default_rng(1)
+    n_batches = args.warmup + args.rounds
+
+    def picks():
+        """The scene indices of one window: `n_batches` batches without a repeat inside a batch."""
+        return [rng.permutation(args.scenes)[:args.batch].astype(np.int64) for _ in range(n_batches)]
+
+    def evaluate_rate(window):
+        ev = Evaluator(len(store), cfg["num_mods"], cfg["num_preds"])
+        evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[:args.warmup]))
+        sync()
+        t0 = time.perf_counter()
+        evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[args.warmup:]))
+        res = ev.summary()
+        sync()
+        return args.rounds * args.batch / (time.perf_counter() - t0), res
+
+    def manual_rate(window):
+        """forward_store + PostProcess.forward's host copies + pred_metrics: what scoring a split took without the evaluator."""
+        first = store.actor_off[:-1]
+        gt_all, has_all = store._job.t["gt_preds"], store._job.t["has_preds"].bool()
+        metrics = {"preds": [], "gt_preds": [], "has_preds": []}
+        with torch.no_grad():
+            for i, pick in enumerate(window):
+                if i == args.warmup:
+                    metrics = {"preds": [], "gt_preds": [], "has_preds": []}
+                    sync()
+                    t0 = time.perf_counter()
+                out = net.forward_store(store, pick)
+                rows = torch.from_numpy(first[pick]).cuda()          # one gather + one copy per tensor, as train_dp.first_rows_on_host
+                data = {"gt_preds": list(gt_all[rows].cpu().split(1)), "has_preds": list(has_all[rows].cpu().split(1))}
+                po = post(out, data)
+                for k in metrics:
+                    metrics[k] += po[k]
+            ade1, fde1, ade, fde, _ = M.pred_metrics(np.concatenate(metrics["preds"], 0), np.concatenate(metrics["gt_preds"], 0),
+                                                     np.concatenate(metrics["has_preds"], 0))
+            sync()
+        return args.rounds * args.batch / (time.perf_counter() - t0), (ade1, fde1, ade, fde)
+
+    busy = torch.empty(1 << 28, dtype=torch.uint8, device="cuda")
+
+    def launch_us(fn):
+        """Median device time of fn() between two events, in microseconds.  A 256 MB fill is queued first, so the stream is
+        still busy while the host enqueues event, launch, event: the interval holds the launch, not the host's call."""
+        ts = []
+        for i in range(n_batches):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            busy.zero_()
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            if i >= args.warmup:
+                ts.append(a.elapsed_time(b) * 1e3)
+        return statistics.median(ts)
+
+    reps = {"scenes_per_s_evaluate": [], "scenes_per_s_manual": [], "eval_scenes_us": [], "eval_reduce_us": []}
+    agree = None
+    for r in range(args.reps):
+        window = picks()
+        got = {}
+        for name in (("evaluate", "manual") if r % 2 else ("manual", "evaluate")):
+            rate, got[name] = (evaluate_rate if name == "evaluate" else manual_rate)(window)
+            reps["scenes_per_s_" + name].append(rate)
+        # the two loops scored the same scenes: K = 1 / K = num_mods minADE, minFDE against ade1, fde1, ade, fde
+        s, m = got["evaluate"], got["manual"]
+        mine = (s[1]["minADE"], s[1]["minFDE"], s[cfg["num_mods"]]["minADE"], s[cfg["num_mods"]]["minFDE"])
+        # (a scene picked in several batches counts once in the table and once per batch in the manual loop: a loose check)
+        agree = max(abs(a - float(b)) / abs(float(b)) for a, b in zip(mine, m))
+        # the launches alone, on one batch of this store
+        pick = window[0]
+        with torch.no_grad():
+            fb, ex, out = net.forward_store_flat(store, pick)
+        ev = Evaluator(len(store), cfg["num_mods"], cfg["num_preds"])
+        slot = torch.from_numpy(pick).cuda()
+        reps["eval_scenes_us"].append(launch_us(lambda: ops.eval_scenes(
+            out["reg"], out["cls"], ex["gt_preds"], ex["has_preds"], fb.actor_off, slot, ev.horizon, ev.rec, None, None, ev._err_slot)))
+        big = Evaluator(args.slots, cfg["num_mods"], cfg["num_preds"])
+        big.rec[:, 0] = 1.0
+        big.rec[:, 1], big.rec[:, 2] = cfg["num_mods"], cfg["num_preds"]
+        big.rec[:, 4:4 + 3 * cfg["num_mods"]] = torch.rand((args.slots, 3 * cfg["num_mods"]), device="cuda")
+        reps["eval_reduce_us"].append(launch_us(lambda: ops.eval_reduce(big.rec, 2.0, big._out, big._cnt, big._err_mix)))
+    res = {"scenes": args.scenes, "batch": args.batch, "rounds": args.rounds, "warmup": args.warmup, "reps": args.reps,
+           "reduce_slots": args.slots, "metrics_rel_diff_between_loops": float("%.3g" % agree)}
+    for k, v in reps.items():
+        digits = 1 if k.startswith("scenes") else 2
+        res[k] = {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

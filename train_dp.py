@@ -10,6 +10,9 @@ dict {"epoch", "state_dict" (CPU tensors), "opt_state"} named "%3.3f.ckpt" (:230
 metrics reset every display_iters; a validation pass every val_iters and at the end (:189-208).  The gradient average
 is ONE flat all-reduce (lanegcn_amd.dist.allreduce_mean_grads).  Difference: the sampler drops the shard's tail
 where the reference's DistributedSampler pads it.
+
+The reference's test.py (:60-100) is `--eval --eval-store PATH`: the whole store, every scene once over all ranks, through
+lanegcn_amd.evaluate (Argoverse's forecasting metrics for K = num_mods and K = 1; `--save-preds` writes the predictions).
 """
 import argparse
 import os
@@ -57,6 +60,16 @@ def first_rows_on_host(data):
     return {"gt_preds": list(torch.split(gt, counts)), "has_preds": list(torch.split(has, counts))}
 
 
+def store_eval_picks(n_scenes, rank, world):
+    """This rank's scenes of a store under evaluation: r, r + world, ... -- every scene once, no tail dropped."""
+    return np.arange(rank, n_scenes, world, dtype=np.int64)
+
+
+def metric_lines(summary, ks):
+    """One line per K of an Evaluator.summary(), the metrics in Argoverse's key order."""
+    return ["K=%d " % k + ", ".join("%s %.4f" % (m, v) for m, v in summary[k].items()) for k in ks]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="LaneGCN training on MI355X (RCCL data parallel)")
     ap.add_argument("-m", "--model", default="lanegcn_mi355x", type=str, metavar="MODEL", help="model plugin module")
@@ -68,7 +81,14 @@ def main(argv=None):
     ap.add_argument("--save-dir", default="", help="override config['save_dir']")
     ap.add_argument("--dataset-len", type=int, default=0, help="synthetic dataset length override")
     ap.add_argument("--store", default="", type=str, metavar="PATH",
-                    help="train from this flat store (flatfile.write_scenes), resident on the device; validation keeps the dataset")
+                    help="train from this flat store (flatfile.write_scenes), resident on the device; validation keeps the dataset "
+                         "unless --eval-store is given")
+    ap.add_argument("--eval-store", default="", type=str, metavar="PATH",
+                    help="a flat store with gt_preds (the validation split), resident on the device: with --eval the whole store "
+                         "is evaluated (Argoverse's forecasting metrics for K = num_mods and K = 1); without it, validation "
+                         "runs from this store instead of the dataset")
+    ap.add_argument("--save-preds", default="", type=str, metavar="FILE.npz",
+                    help="with --eval --eval-store: write index, preds [n, num_mods, num_preds, 2] and scores [n, num_mods]")
     ap.add_argument("--rot-size", type=float, default=None, metavar="X",
                     help="turn every picked scene by rand() * X per step (needs a store written with theta=True); default: "
                          "config['rot_size'] when config['rot_aug'] is set, else no augmentation")
@@ -109,6 +129,26 @@ def main(argv=None):
             rot_size = args.rot_size
         elif config.get("rot_aug"):
             rot_size = config["rot_size"]
+    ks = sorted({config["num_mods"], 1}, reverse=True)
+    if args.eval and args.eval_store:                              # the reference's test.py: the whole split, every scene once
+        from lanegcn_amd.evaluate import Evaluator, evaluate_store
+        from lanegcn_amd.flatfile import DeviceSceneStore
+        eval_store = DeviceSceneStore(args.eval_store)
+        ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"], keep_preds=bool(args.save_preds))
+        net.eval()
+        evaluate_store(net, eval_store, config["val_batch_size"], ev, indices=store_eval_picks(len(eval_store), rank, world))
+        ev.merge()
+        summary = ev.summary(ks=ks)
+        if rank == 0:
+            print("\n".join(metric_lines(summary, ks)))
+            print("evaluated %d scenes, skipped %d, non-finite %d"
+                  % (summary["n_evaluated"], summary["n_skipped"], summary["n_nonfinite"]))
+            if args.save_preds:
+                index, preds, scores = ev.predictions()
+                np.savez(args.save_preds, index=index, preds=preds, scores=scores)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return 0
     if args.eval:
         net.eval()
         with torch.no_grad():
@@ -127,7 +167,41 @@ def main(argv=None):
         torch.autograd.set_multithreading_enabled(False)
     val_set = Dataset(config.get("val_split"), config, train=False, **kw)
 
+    eval_store = None
+    if args.eval_store:
+        from lanegcn_amd.evaluate import Evaluator, evaluate_store
+        from lanegcn_amd.flatfile import DeviceSceneStore
+        eval_store = DeviceSceneStore(args.eval_store)
+
+    def validate_store(epoch):
+        """validate() from the resident store: ADE / FDE from the evaluator's records (K = 1 and K = num_mods), the loss
+        from loss(out, data) per batch on the store's gt_preds / has_preds; the reference's validation line."""
+        net.eval()
+        t_val, vm = time.time(), dict()
+        ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"])
+
+        def batch_loss(out, fb, ex):
+            data = {"gt_preds": [ex["gt_preds"]], "has_preds": [ex["has_preds"]]}
+            post_process.append(vm, loss({"cls": [out["cls"]], "reg": [out["reg"]]}, data), {})
+
+        evaluate_store(net, eval_store, config["val_batch_size"], ev, indices=store_eval_picks(len(eval_store), rank, world),
+                       on_batch=batch_loss)
+        ev.merge()
+        summary = ev.summary(ks=ks)
+        vm = D.gather_metrics(vm)
+        if rank == 0 and vm:
+            print("************************* Validation, time %3.2f *************************" % (time.time() - t_val))
+            cls = vm["cls_loss"] / (vm["num_cls"] + 1e-10)
+            reg = vm["reg_loss"] / (vm["num_reg"] + 1e-10)
+            print("loss %2.4f %2.4f %2.4f, ade1 %2.4f, fde1 %2.4f, ade %2.4f, fde %2.4f"
+                  % (cls + reg, cls, reg, summary[1]["minADE"], summary[1]["minFDE"], summary[ks[0]]["minADE"],
+                     summary[ks[0]]["minFDE"]))
+            print()
+        net.train()
+
     def validate(epoch):                                             # train.py:200-216
+        if eval_store is not None:
+            return validate_store(epoch)
         net.eval()
         t_val, vm = time.time(), dict()
         with torch.no_grad():

@@ -580,6 +580,26 @@ int lgcn_ctx_heads(const float *x, int64_t n_rows, const void *const *w, int n_w
 int lgcn_node_tail(const lgcn_agg_mlp_t *p_host, void *stream);
 
 /*
+ * Head of an Att block whose targets are the lane nodes (A2M's first launch; lanegcn.py:387-406, 696-699),
+ * weight-stationary: 1 <= n <= LGCN_MAX_MULTI lgcn_agg_mlp problems of one LGCN_REL_IDENT relation each in ONE launch, on
+ * 48-row tiles whose 8 waves each keep a 16-channel slice of every weight in registers over the full K.  A problem is a
+ *   head   : flags = GN1 | RELU1, gn1, out, optionally the rank-4 update (w4, x4_*) and the chained U output (ch_wq,
+ *            ch_gq_*, ch_wu, ch_u_out);
+ *   u-chain: flags = GN1 | RELU1 | GEMM2, gn1, wp2, out;
+ *   plain  : flags = 0, out.
+ * Problems with the same src and n_rows, the head apart, share their tiles (the rows are read once): up to two plain ones
+ * and a u-chain per tile range.
+ * Bit-identical to lgcn_agg_mlp_multi on the same problems: one fp32 accumulator per element, K-steps and plane products
+ * in the same order, the same rank-4 arithmetic and GroupNorm sums.
+ * LGCN_MMA_F32 / LGCN_MMA_BF16X3 or problems of different modes (checked first), any other relation list or flags, a
+ * chained V output, w4 or a chained U outside a head, out_pre / out_mid / out_pre2 or a tile_rb: LGCN_ESHAPE -- use
+ * lgcn_agg_mlp_multi there.  n out of range, a NULL problem, n_rows < 0 or a NULL required pointer: LGCN_EINVAL; n_rows >
+ * 2^31 - 1: LGCN_ESHAPE; pointers (but x4_*) not 16-byte aligned: LGCN_EALIGN.  A problem with n_rows == 0 adds no tiles
+ * and its pointers are not looked at; if every problem is empty the call returns LGCN_OK without a launch.
+ */
+int lgcn_node_head(const lgcn_agg_mlp_t *const *ps_host, int n, void *stream);
+
+/*
  * MapNet input stage, lanegcn.py:324-327:
  *   out = ReLU( GN_a(W_a2 ReLU(W_a1 ctr + b_a1)) + GN_s(W_s2 ReLU(W_s1 seg + b_s1)) )
  * ctrs, feats: [N,2]; w1: [128,2] + b1 [128] (nn.Linear(2,128)); wp2: packed.

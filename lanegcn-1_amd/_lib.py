@@ -269,6 +269,7 @@ SIGNATURES = {
     "lgcn_agg_mlp_multi": (C.c_int, [C.POINTER(C.POINTER(AggMlp)), _I, _P]),
     "lgcn_ctx_heads": (C.c_int, [_P, _L, C.POINTER(_P), _I, _I, C.POINTER(_P), _P]),
     "lgcn_node_tail": (C.c_int, [C.POINTER(AggMlp), _P]),
+    "lgcn_node_head": (C.c_int, [C.POINTER(C.POINTER(AggMlp)), _I, _P]),
     "lgcn_gn_bwd": (C.c_int, [_P, _P, _P, _P, _L, _F, _P, _P, _P, _P, _P, _P]),
     "lgcn_gn_fwd": (C.c_int, [_P, _P, _P, _P, _L, _F, _I, _P, _P]),
     "lgcn_gn_cl": (C.c_int, [_P, _L, _I, _I, _P, _P, _F, _P, _I, _I, _I, _P, _P]),

@@ -239,6 +239,14 @@ __device__ __forceinline__ void acc_zero(f32x4 (&acc)[RB][NCB]) {
         for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// Rank-4 fp32 update of one accumulator element (the 4 meta channels of A2M.meta: turn (2), control, intersect against
+// the weight's columns 128..131), shared by the row block and lgcn_nodehead.hip so that both round alike: four products,
+// summed left to right, then added to the accumulator -- five roundings, no FMA (the library is built with
+// -ffp-contract=off).
+__device__ __forceinline__ float rank4_update(float acc, float2 tu, float b, float c, float4 wc) {
+    return acc + (((tu.x * wc.x + tu.y * wc.y) + b * wc.z) + c * wc.w);
+}
+
 template <int F>
 __device__ __forceinline__ void row_split_store(uint16_t *planes, int plane_elems, int row, int t, const RowVals &r) {
 #pragma unroll

@@ -20,10 +20,9 @@
 // block's two barriers per GEMM; the rows go back to LDS as operand planes (split_store).
 #include "lgcn_common.hpp"
 #include "lgcn_mma_bf.hpp"
+#include "lgcn_wslice.hpp"
 
 namespace lgcn {
-
-constexpr int kNtRB = 3;            // 48-row tiles
 
 template <int F>
 struct NodeTailSmem {
@@ -34,38 +33,6 @@ struct NodeTailSmem {
     static constexpr int GN = T + TL::T_BYTES;             // gn1 g|b, gn2 g|b, chained query g|b
     static constexpr int BYTES = GN + 6 * kC * 4;
 };
-
-// One weight's slice of a wave: K-step s -> the fragment of channels [16 wave, 16 wave + 16) (packed image of
-// lgcn_pack_weight: channel quarter wave >> 1, 16-column block wave & 1).
-template <int F>
-struct WSlice { BFrag<F, 1> s[4]; };
-
-template <int F>
-__device__ __forceinline__ void load_slice(WSlice<F> &w, const float *__restrict__ wp, int wave, int lane) {
-    const uint4 *__restrict__ Bw = reinterpret_cast<const uint4 *>(wp);
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int p = 0; p < Fmt<F>::NP; ++p)
-            w.s[s].v[p][0] = Bw[((((p * 4 + (wave >> 1)) * 4 + s) * 2 + (wave & 1)) << 6) + lane];
-}
-
-template <int F>
-__device__ __forceinline__ void gemm_slice(const uint16_t *__restrict__ A, const WSlice<F> &w, int lane, f32x4 (&acc)[kNtRB][1]) {
-    const uint16_t *arow = A + (lane & 15) * kLDB + 8 * (lane >> 4);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) kstep<kNtRB, F>(arow, s, w.s[s], acc);
-}
-
-// C/D layout of 16x16: col = lane & 15, row = 4 (lane >> 4) + reg
-__device__ __forceinline__ void acc_to_tile(float *T, const f32x4 (&acc)[kNtRB][1], int lane, int wave) {
-#pragma unroll
-    for (int rb = 0; rb < kNtRB; ++rb) {
-        float *p = T + (16 * rb + 4 * (lane >> 4)) * kLDA + 16 * wave + (lane & 15);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) p[i * kLDA] = acc[rb][0][i];
-    }
-}
 
 // <= 128 VGPRs: a second workgroup, or another forward's kernel, shares the CU.
 template <int F>
@@ -206,13 +173,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
     lds_barrier();
     acc_zero(acc);
     gemm_slice<F>(A0, w0, lane, acc);
-#pragma unroll
-    for (int rb = 0; rb < kNtRB; ++rb)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int64_t nn = row0 + 16 * rb + 4 * (lane >> 4) + i;
-            if (nn < p.n_rows) p.ch_u_out[nn * kC + 16 * wave + (lane & 15)] = acc[rb][0][i];
-        }
+    acc_to_global(p.ch_u_out, acc, row0, p.n_rows, lane, wave);
 }
 
 }  // namespace lgcn

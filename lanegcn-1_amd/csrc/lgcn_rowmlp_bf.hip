@@ -395,7 +395,7 @@ __device__ __forceinline__ void agg_body(const lgcn_agg_mlp_t &p, int n_tiles, i
                         const int64_t n = row0 + 16 * rb + 4 * (lane >> 4) + i;
                         if (n < p.n_rows) {
                             const float2 tu = reinterpret_cast<const float2 *>(p.x4_a)[n];
-                            acc[rb][cb][i] += tu.x * wc.x + tu.y * wc.y + p.x4_b[n] * wc.z + p.x4_c[n] * wc.w;
+                            acc[rb][cb][i] = rank4_update(acc[rb][cb][i], tu, p.x4_b[n], p.x4_c[n], wc);
                         }
                     }
             }

@@ -486,7 +486,8 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
     folded: a layer's tail also emits the next layer's U (and V, when the context rows are the targets: A2A) from its
     output rows before they leave the CU, the V rows of every layer whose context does not change are computed up
     front, and the block's first launch carries them together with U of layer 0 -- chained onto `head`, the row block
-    that produces the targets (A2M.meta), when there is one.  Same arithmetic as Att.run per layer.
+    that produces the targets (A2M.meta), when there is one (that launch is then the weight-stationary ops.node_head in
+    f16x2 / bf16, the multi-problem row block otherwise).  Same arithmetic as Att.run per layer.
       head: agg_mlp keywords of a row block whose output is the block's target rows (agts is then ignored);
       uv: (U, V) of layer 0 when a previous block's tail has already emitted them;
       next_att: first Att of the FOLLOWING block when this block's output rows are its targets (and, with
@@ -509,7 +510,10 @@ def att_block(atts, agts: Optional[Tensor], ctx: Tensor, ps: ops.PairSet, head: 
     else:
         first = dict(head, chain_u=atts[0].chain_u()) if head is not None else atts[0].u_kw(agts)
         probs = [first] + [atts[i].v_kw(ctx) for i in range(1 if ctx_is_agts else n)]
-        res = ops.agg_mlp_multi(probs + ([extra] if extra is not None else []), tag="att_head")
+        probs_all = probs + ([extra] if extra is not None else [])
+        # targets produced by `head` (A2M: the lane nodes): the weight-stationary launch, same bits
+        ws = head is not None and ops.node_head_ok() and all(ops.node_head_form(kw) is not None for kw in probs_all)
+        res = (ops.node_head if ws else ops.agg_mlp_multi)(probs_all, tag="att_head")
         if extra is not None:
             x_out, extra = res[-1], None
         if head is not None:

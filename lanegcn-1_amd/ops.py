@@ -1168,6 +1168,39 @@ def node_tail(n_rows: int, rels: Sequence[RelSpec], flags: int, *, tag="node_tai
     return out
 
 
+def node_head_ok() -> bool:
+    """lgcn_node_head is in the library and implements the current matrix-core mode (f16x2, bf16); the others take
+    agg_mlp_multi."""
+    return _mma in (L.MMA_F16X2, L.MMA_BF16) and hasattr(L.load(), "lgcn_node_head")
+
+
+def node_head_form(kw: dict) -> Optional[str]:
+    """The form lgcn_node_head runs an agg_mlp problem (keyword dict) as -- "head", "u-chain" or "plain" -- or None."""
+    rels, flags = kw.get("rels", ()), kw.get("flags")
+    if len(rels) != 1 or rels[0].mode != L.REL_IDENT or kw.get("chain_v") is not None or kw.get("tile_rb", 0) != 0:
+        return None
+    if any(kw.get(k) is not None for k in ("out_pre", "out_mid", "out_pre2")):
+        return None
+    if flags == L.F_GN1 | L.F_RELU1:
+        return "head"
+    if kw.get("w4") is not None or kw.get("chain_u") is not None:
+        return None
+    return {L.F_GN1 | L.F_RELU1 | L.F_GEMM2: "u-chain", 0: "plain"}.get(flags)
+
+
+def node_head(problems: Sequence[dict], tag="att_head"):
+    """Up to 4 row-chain problems over one IDENT relation each -- a head (GN1 | RELU1, optionally w4 / x4 and chain_u), a
+    u-chain (GN1 | RELU1 | GEMM2) or a plain GEMM (flags 0) -- in one weight-stationary launch (lgcn_node_head): bit for bit
+    what agg_mlp_multi gives on the same list, outputs returned alike.  The library refuses every other shape and the
+    f32 / bf16x3 modes (node_head_ok(), node_head_form())."""
+    lib = L.load()
+    built = [_agg_params(**kw) for kw in problems]
+    arr = (C.POINTER(L.AggMlp) * len(built))(*[C.pointer(b[0]) for b in built])
+    with _Timed(tag):
+        L.check(lib.lgcn_node_head(arr, len(built), _stream()), "lgcn_node_head")
+    return [b[2] for b in built]
+
+
 # ------------------------------------------------------------------ LaneConv (gather-free, weight-stationary)
 @dataclass
 class LcPlan:

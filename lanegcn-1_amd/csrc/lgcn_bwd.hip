@@ -165,6 +165,18 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// rstd of an item whose fp32 sum of squares overflowed (centred values beyond ~2^58 at 2,560 elements: var = inf, rstd = 0,
+// and the item would come out as beta): row_rstd_wide (lgcn_tile.hpp) for one wave per item -- qs is the wave's sum of the
+// squares of the centred values scaled by kGnClWide (exact), rstd is scaled back.  2^-72: the largest item (16,384
+// elements) at fp32's largest values still sums to 2^124, and an item that overflowed holds a centred value of 2^57 or
+// more, whose scaled square is far from underflow.  The lanes of a wave share var, so they take the rare branch together;
+// an item that holds a NaN or an inf takes it too and comes out NaN as before.
+constexpr float kGnClWide = 0x1p-72f;
+__device__ __forceinline__ bool gn_cl_overflowed(float sumsq) { return __builtin_expect(!(sumsq <= 3.4028234e38f), 0); }
+__device__ __forceinline__ float gn_cl_rstd_wide(float qs, int n, float eps) {
+    return kGnClWide / sqrtf(wave_sum(qs) / (float)n + eps * (kGnClWide * kGnClWide));
+}
+
 __global__ __launch_bounds__(256) void k_gn_cl(const float *__restrict__ x, int64_t n_items, int C, int L,
                                                const float *__restrict__ gamma, const float *__restrict__ beta, float eps,
                                                const float *__restrict__ res, int res_up2, int relu, int cl,
@@ -179,7 +191,13 @@ __global__ __launch_bounds__(256) void k_gn_cl(const float *__restrict__ x, int6
     const float mean = wave_sum(s) / (float)n;
     float q = 0.f;
     for (int i = lane; i < n; i += 64) { const float d = xi[i] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)n + eps);
+    q = wave_sum(q);
+    float rstd = 1.0f / sqrtf(q / (float)n + eps);
+    if (gn_cl_overflowed(q)) {
+        float qs = 0.f;
+        for (int i = lane; i < n; i += 64) { const float d = (xi[i] - mean) * kGnClWide; qs += d * d; }
+        rstd = gn_cl_rstd_wide(qs, n, eps);
+    }
     const int Lh = L >> 1;
     const float *ri = res ? res + item * (res_up2 ? C * Lh : n) : nullptr;
     float *oi = out + item * n;
@@ -230,7 +248,20 @@ __global__ __launch_bounds__(256) void k_gn_cl_vec(const float *__restrict__ x, 
             q += (a * a + b * b) + (c * c + d * d);
         }
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)n + eps);
+    q = wave_sum(q);
+    float rstd = 1.0f / sqrtf(q / (float)n + eps);
+    if (gn_cl_overflowed(q)) {
+        float qs = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            if (lane + 64 * k < nq) {
+                const float a = (v[k].x - mean) * kGnClWide, b = (v[k].y - mean) * kGnClWide, c = (v[k].z - mean) * kGnClWide,
+                            d = (v[k].w - mean) * kGnClWide;
+                qs += (a * a + b * b) + (c * c + d * d);
+            }
+        }
+        rstd = gn_cl_rstd_wide(qs, n, eps);
+    }
     const int Lh = L >> 1;
     const float *ri = res ? res + item * (res_up2 ? C * Lh : n) : nullptr;
     float4 *oi = reinterpret_cast<float4 *>(out + item * n);
@@ -290,7 +321,13 @@ __global__ __launch_bounds__(256) void k_gn_cl_bwd(const float *__restrict__ dy,
     const float rest = wave_sum(e) / (float)n;
     float q = 0.f;
     for (int i = lane; i < n; i += 64) { const float d = (xi[i] - mean) - rest; q += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)n + eps);
+    q = wave_sum(q);
+    float rstd = 1.0f / sqrtf(q / (float)n + eps);
+    if (gn_cl_overflowed(q)) {                                 // the forward's wide path (k_gn_cl): no silent zeros here
+        float qs = 0.f;
+        for (int i = lane; i < n; i += 64) { const float d = ((xi[i] - mean) - rest) * kGnClWide; qs += d * d; }
+        rstd = gn_cl_rstd_wide(qs, n, eps);
+    }
     float s1 = 0.f, s2 = 0.f;
     for (int i = lane; i < n; i += 64) {
         const float gv = (pi == nullptr || pi[i] > 0.f) ? di[i] : 0.f;

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(512) void k_conv_gn(const ConvParams p) {
     conv_tile_load(T, ldt, m, v);
     const float4 g = *reinterpret_cast<const float4 *>(p.gamma + c), bt = *reinterpret_cast<const float4 *>(p.beta + c);
     float mean, rstd;
-    conv_gn_stats(v, m, s_red, p.eps, mean, rstd);
+    conv_gn_stats<F32>(v, m, s_red, p.eps, mean, rstd);        // the exact units: with the wide path
     if (a < p.n_act) {
 #pragma unroll
         for (int k = 0; k < 5; ++k) {

@@ -254,6 +254,16 @@ __device__ __forceinline__ float conv_half_sum(float s) {
 // The per-actor statistics of the values the actor's threads hold (absent ones are zero), two passes as ATen's GroupNorm:
 // mean, then the variance about it.  They meet through 32-lane shuffles and one LDS word per half-wave, summed in
 // ascending order.  Contains two barriers; s_red: 2 x 16 words.
+// WIDE: the exact units (fp32 operands, fp32's exponent range) and the backward that recomputes their statistics.  Centred
+// values beyond ~2^58 (lout x cout <= 2,560 squares) take the sum of squares out of fp32: var = inf, rstd = 0, and the
+// actor would come out as beta.  Then the same sum is formed over the centred values scaled by 2^-70 (exact) and rstd is
+// scaled back -- row_rstd_wide (lgcn_tile.hpp) for this layout.  The workgroup's actors do not share var and the second
+// sum needs barriers, so every thread forms every actor's sum from s_red (the same additions in the same order as the
+// owner's) and the workgroup takes the branch together; only the actors whose own sum left fp32 replace their rstd, so
+// every other actor keeps its bits.  An actor that holds a NaN or an inf takes the branch too and comes out NaN as before.
+// The two-plane kernels pass WIDE = false and keep their code: their convolution outputs cannot pass
+// 3 * 128 * 3 * 65520^2 < 2^43, whose squares fit.
+template <bool WIDE = false>
 __device__ __forceinline__ void conv_gn_stats(const float4 (&v)[5], const ConvGnMap &m, float (*s_red)[16], float eps,
                                               float &mean, float &rstd) {
     float s = 0.f;
@@ -279,6 +289,33 @@ __device__ __forceinline__ void conv_gn_stats(const float4 (&v)[5], const ConvGn
     float var = 0.f;
     for (int k = 0; k < m.ng; ++k) var += s_red[1][m.g0 + k];
     rstd = 1.0f / sqrtf(var / m.per + eps);
+    if constexpr (WIDE) {
+        bool any = false;                                       // workgroup-uniform: every actor's sum, as its owner formed it
+        for (int g = 0; g < 16; g += m.ng) {
+            float t = 0.f;
+            for (int k = 0; k < m.ng; ++k) t += s_red[1][g + k];
+            any |= !(t <= 3.4028234e38f);
+        }
+        if (__builtin_expect(any, 0)) {
+            constexpr float ks = 0x1p-70f;
+            float qs = 0.f;
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                if (m.has(k)) {
+                    const float d0 = (v[k].x - mean) * ks, d1 = (v[k].y - mean) * ks, d2 = (v[k].z - mean) * ks,
+                                d3 = (v[k].w - mean) * ks;
+                    qs += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+                }
+            }
+            qs = conv_half_sum(qs);
+            lds_barrier();                                      // every thread has read the first sums
+            if ((m.tid & 31) == 0) s_red[1][m.tid >> 5] = qs;
+            lds_barrier();
+            float vs = 0.f;
+            for (int k = 0; k < m.ng; ++k) vs += s_red[1][m.g0 + k];
+            if (!(var <= 3.4028234e38f)) rstd = ks / sqrtf(vs / m.per + eps * (ks * ks));
+        }
+    }
 }
 
 // a thread's <= 5 float4 of the fp32 tile

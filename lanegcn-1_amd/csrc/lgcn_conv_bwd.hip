@@ -74,7 +74,7 @@ __global__ __launch_bounds__(512) void k_conv_gn_bwd(const ConvBwdParams p) {
         }
     }
     float mean, rstd;
-    conv_gn_stats(yv, m, s_red, p.eps, mean, rstd);
+    conv_gn_stats<true>(yv, m, s_red, p.eps, mean, rstd);      // y may come from the exact units: their wide path too
     // corrected two-pass, as row_gn_hat (lgcn_tile.hpp): the mean of the centred values is what the fp32 mean left behind.
     // s_red[0] is free again: its readers passed the second barrier of conv_gn_stats.
     float rest = 0.f;

@@ -776,7 +776,10 @@ class ActorNet(nn.Module):
         # lgcn_conv1d_gn / lgcn_res1d_gn take no matrix-mode argument: they always split operands into two fp16 planes.
         # In the exact-f32 and bf16x3 modes (and inside the range guard's bf16x3 re-run, which must cure an overflow that
         # starts in ActorNet too) the MIOpen channels-last path runs instead -- unless ActorNet.exact is set: the fp32
-        # units (lgcn_conv1d_gn_f32) have no operand range and serve every matrix mode.
+        # units (lgcn_conv1d_gn_f32) take fp32's whole operand range and serve every matrix mode.  Their GroupNorm (and
+        # lgcn_gn_cl's, the norm of the MIOpen path) follows convolutions of any finite size: where the squares of the
+        # centred values leave fp32 (beyond ~2^58) the variance is summed over scaled values (conv_gn_stats<true>,
+        # gn_cl_rstd_wide; measured at 2^100, DESIGN.md 5c "ActorNet").  Before that path they returned beta there.
         if ActorNet.impl != "hip" or not (ActorNet.exact or ops.get_mma() == "f16x2") or not self._channels_last_shape_ok(actors):
             return False
         if not ActorNet.train_hip and ops.wants_grad(actors, *ops.module_params(self)):

@@ -244,16 +244,32 @@ def hot_path(graph, actors, actor_ctrs, sd, mode, model=True, cfg=None):
     return {k: arr(v, np.float64) for k, v in out.items()}
 
 
-def conv1d_unit(x, w, stride, gamma, beta, mode, eps=EPS, relu=False, model=True):
+def up2_linear(r):
+    """F.interpolate(scale_factor=2, mode="linear", align_corners=False) along axis 1 of r [A, n, c] in float64 (up2_taps of
+    csrc/lgcn_conv.hpp): source coordinate (j + 0.5) / 2 - 0.5 clamped at 0, so out[2i] = 0.25 r[i - 1] + 0.75 r[i] and
+    out[2i + 1] = 0.75 r[i] + 0.25 r[i + 1], the two ends clamped (out[0] = r[0], out[2n - 1] = r[n - 1])."""
+    r = arr(r, np.float64)
+    n = r.shape[1]
+    src = np.maximum((np.arange(2 * n) + 0.5) * 0.5 - 0.5, 0.0)
+    i0 = np.floor(src).astype(np.int64)
+    i1 = np.minimum(i0 + 1, n - 1)
+    w1 = (src - i0)[None, :, None]
+    return (1.0 - w1) * r[:, i0] + w1 * r[:, i1]
+
+
+def conv1d_unit(x, w, stride, gamma, beta, mode, eps=EPS, relu=False, res=None, res_up2=False, model=True):
     """lgcn_conv1d_gn_train on channels-last x [A, L, cin], w [cout, cin, ks] (ks 1 / 3, padding (ks - 1) / 2, no bias):
-    (out, y), y the convolution, out = act(GN(y)) with the statistics over an actor's lout x cout values.
+    (out, y), y the convolution, out = act(GN(y) + residual) with the statistics over an actor's lout x cout values.
+    res [A, lout, cout], or [A, lout / 2, cout] with res_up2 (upsampled x2, up2_linear); the model takes it as fp32, as
+    the kernel holds it, and adds it in float64.
     mode "f16x2": the two-plane units; "f32": the exact units."""
-    x, w = arr(x, np.float32), arr(w, np.float32)
+    dt = np.float32 if model else np.float64
+    x, w = arr(x).astype(dt), arr(w, np.float32)
     A_, lin, cin = x.shape
     cout, _, ks = w.shape
     pad = (ks - 1) // 2
     lout = (lin + 2 * pad - ks) // stride + 1
-    xp = np.zeros((A_, lin + 2 * pad, cin), np.float32)
+    xp = np.zeros((A_, lin + 2 * pad, cin), dt)
     xp[:, pad:pad + lin] = x
     y = np.zeros((A_ * lout, cout))
     for t in range(ks):
@@ -263,7 +279,70 @@ def conv1d_unit(x, w, stride, gamma, beta, mode, eps=EPS, relu=False, model=True
     mu = y.mean((1, 2), keepdims=True)
     var = ((y - mu) ** 2).mean((1, 2), keepdims=True)
     out = (y - mu) / np.sqrt(var + eps) * arr(gamma, np.float64) + arr(beta, np.float64)
+    if res is not None:
+        r = arr(_hold(res, model), np.float64)
+        assert r.shape == ((A_, lout // 2, cout) if res_up2 else (A_, lout, cout)) and not (res_up2 and lout % 2)
+        out = out + (up2_linear(r) if res_up2 else r)
     return (np.maximum(out, 0.0) if relu else out), y
+
+
+def res1d_block(x, blk, mode, second=None, model=True):
+    """layers.Res1d on channels-last x [A, L, cin] as the composition of conv1d_unit calls that ops.res1d_gn stands for
+    (lgcn_res1d_gn; with `second`, a C -> C block with the identity shortcut chained behind, lgcn_res1d_pair_gn):
+        out = act( GN2(conv2( relu(GN1(conv1 x)) )) + r ),   r = x, or GN_d(conv_d x) with conv_d k = 1 at conv1's stride.
+    blk: dict(w1, stride, gn1 = (gamma, beta), w2, gn2, wd = None, gnd = None, eps, act = True).  What one unit hands to
+    the next -- the intermediate rows the fused launches keep in LDS, the shortcut's rows, the first block's output -- is
+    an fp32 value that is split again: _hold.  Mode "f32" rounds nothing anywhere (no operand format to model), so its
+    model is the reference and its error 0, as hot_path_cases.model_err has it."""
+    hold = model = model and mode != "f32"
+    kw = dict(eps=blk.get("eps", EPS), model=model)
+    x = _hold(x, hold)
+    mid = _hold(conv1d_unit(x, blk["w1"], blk["stride"], *blk["gn1"], mode, relu=True, **kw)[0], hold)
+    skip = x
+    if blk.get("wd") is not None:
+        skip = _hold(conv1d_unit(x, blk["wd"], blk["stride"], *blk["gnd"], mode, **kw)[0], hold)
+    out = conv1d_unit(mid, blk["w2"], 1, *blk["gn2"], mode, relu=blk.get("act", True), res=skip, **kw)[0]
+    if second is None:
+        return out
+    assert second.get("wd") is None and second["stride"] == 1
+    return res1d_block(_hold(out, hold), second, mode, model=model)
+
+
+def actor_blocks(state, eps=EPS):
+    """ActorNet's state dict (groups.g.b.{conv1, bn1, conv2, bn2, downsample.0, downsample.1}, lateral.i.{conv, norm},
+    output.*) as res1d_block's dicts: (groups [[blk, blk]] x 3, lateral [(w, gamma, beta)] x 3, output blk).  The strides
+    are the architecture's (the first block of groups 1 and 2 halves the length)."""
+    W = lambda name: arr(state[name], np.float32)
+    G = lambda name: (W(name + ".weight"), W(name + ".bias"))
+
+    def blk(p, stride):
+        d = dict(w1=W(p + ".conv1.weight"), stride=stride, gn1=G(p + ".bn1"), w2=W(p + ".conv2.weight"), gn2=G(p + ".bn2"), eps=eps)
+        if p + ".downsample.0.weight" in state:
+            d.update(wd=W(p + ".downsample.0.weight"), gnd=G(p + ".downsample.1"))
+        return d
+    groups = [[blk("groups.%d.0" % g, 1 if g == 0 else 2), blk("groups.%d.1" % g, 1)] for g in range(3)]
+    lateral = [(W("lateral.%d.conv.weight" % i),) + G("lateral.%d.norm" % i) for i in range(3)]
+    return groups, lateral, blk("output", 1)
+
+
+def actor_net(x, state, mode, model=True):
+    """ActorNet on x [A, 3, L] (the module's input; L = 20): the FPN walk of ActorNet._forward_hip over conv1d_unit /
+    res1d_block -- three groups of two Res1d blocks (lengths L, L / 2, L / 4), the coarsest lateral, two top-down steps
+    (lateral conv + GN + the x2-upsampled coarser level, no ReLU), the output block -- returning its last step [A, 128].
+    Every unit's output is held in fp32 (the launches hand fp32 tensors on; the fused launches' LDS rows are fp32 values
+    too); mode "f32": nothing is rounded (res1d_block)."""
+    groups, lateral, output = actor_blocks(state)
+    hold = model = model and mode != "f32"
+    out, pyramid = arr(x).transpose(0, 2, 1), []
+    for g in groups:
+        out = _hold(res1d_block(out, g[0], mode, second=g[1], model=model), hold)
+        pyramid.append(out)
+    w, gamma, beta = lateral[2]
+    out = _hold(conv1d_unit(pyramid[2], w, 1, gamma, beta, mode, model=model)[0], hold)
+    for i in (1, 0):
+        w, gamma, beta = lateral[i]
+        out = _hold(conv1d_unit(pyramid[i], w, 1, gamma, beta, mode, res=out, res_up2=True, model=model)[0], hold)
+    return arr(res1d_block(out, output, mode, model=model)[:, -1, :], np.float64)
 
 
 def bar(e_model):

@@ -1513,12 +1513,42 @@ int lgcn_cross_edges_batch(const lgcn_cross_batch_t *p, void *stream);
  * Checked before any launch: LGCN_EINVAL (null pointer, negative size, M / T / horizon < 1, horizon > T, one of traj /
  * score alone), LGCN_ESHAPE (M > 8, T > 64, B or n_slots > 2^31 - 1), LGCN_EALIGN (any pointer but `has` not 16-byte
  * aligned).  B == 0 / n_slots == 0: LGCN_OK, nothing launched, nothing written.
+ *
+ * lgcn_eval_actors: the same record for EVERY actor row of the batch, partial futures included (the rule of PredLoss,
+ * reference lanegcn.py:740-807): one launch per batch, one wave per actor row; no atomics, no host read.
+ *   reg, cls, gt, has, actor_off as above; n_actors = A; slot_base [B] int64: the split-wide row of each scene's first
+ *   actor (the split's actor_off[scene]); the tables hold one row per actor of the split.  Row a belongs to the scene b
+ *   with actor_off[b] <= a < actor_off[b + 1] (scenes without actors are stepped over), i = a - actor_off[b], and its
+ *   record goes to rec[slot_base[b] + i].  With O = {t < horizon : has[a, t]}, n_obs = |O|, t_last = max O:
+ *   [0] flag: 0 = n_obs == 0; 2 = a non-finite value in reg[a, :, :horizon], cls[a] or gt[a, t] for t in O (an
+ *       unobserved gt step is never looked at); 1 otherwise
+ *   [1] M, [2] horizon (flag 1), [3] (float) i (every flag)
+ *   [4 + 3 (k - 1) ...] as above with horizon - 1 -> t_last, the sum over t < horizon -> the sum over O, and the mean's
+ *       divisor -> n_obs
+ *   [28] horizon - n_obs (missing steps), [29] horizon - 1 - t_last (steps cut off the end) (flag 1)
+ *   every other float is 0; a record of flag 0 or 2 is 0 in [1], [2], [4..31].  A fully observed first actor's record is,
+ *   in all 32 floats, the one lgcn_eval_scenes writes for its scene.  traj / score rows: written for flag 1 and 2.
+ *   err [1] int32: set to 1 when a row's slot lies outside [0, n_slots) or the row lies outside [actor_off[0],
+ *   actor_off[B]); nothing is written for that row.
+ *   Checks as lgcn_eval_scenes; LGCN_ESHAPE also for n_actors > 2^24 (a local index must be exact in fp32).
+ *   n_actors == 0 / B == 0: LGCN_OK, nothing launched.
+ * lgcn_eval_reduce_sel: lgcn_eval_reduce over the records a selection keeps -- the same thread-to-slot mapping, prefetch
+ *   and tree, so out is bit for bit lgcn_eval_reduce's on a copy of the table whose excluded rows are zeroed.
+ *   who: 0 all, 1 local index [3] == 0, 2 local index > 0 (any flag); max_missing: a flag-1 record counts only if
+ *   [28] <= max_missing.  cnt [4] int64 = kept slots of flag 0, 1, 2, and the slots the selection excluded; err as in
+ *   lgcn_eval_reduce, over the kept records.  LGCN_EINVAL also for who outside 0..2 or max_missing < 0.
  */
 int lgcn_eval_scenes(const float *reg, const float *cls, const float *gt, const unsigned char *has,
                      const int32_t *actor_off, const int64_t *slot, int64_t n_scenes, int n_mod, int n_t, int horizon,
                      int64_t n_slots, float *rec, float *traj, float *score, int32_t *err, void *stream);
 int lgcn_eval_reduce(const float *rec, int64_t n_slots, double miss_thr, double *out, int64_t *cnt, int32_t *err,
                      void *stream);
+int lgcn_eval_actors(const float *reg, const float *cls, const float *gt, const unsigned char *has,
+                     const int32_t *actor_off, const int64_t *slot_base, int64_t n_actors, int64_t n_scenes, int n_mod,
+                     int n_t, int horizon, int64_t n_slots, float *rec, float *traj, float *score, int32_t *err,
+                     void *stream);
+int lgcn_eval_reduce_sel(const float *rec, int64_t n_slots, double miss_thr, int who, int max_missing, double *out,
+                         int64_t *cnt, int32_t *err, void *stream);
 
 #ifdef __cplusplus
 }

@@ -359,6 +359,8 @@ SIGNATURES = {
     "lgcn_cross_edges_batch": (C.c_int, [C.POINTER(CrossBatch), _P]),
     "lgcn_eval_scenes": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     "lgcn_eval_reduce": (C.c_int, [_P, _L, _D, _P, _P, _P, _P]),
+    "lgcn_eval_actors": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
+    "lgcn_eval_reduce_sel": (C.c_int, [_P, _L, _D, _I, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

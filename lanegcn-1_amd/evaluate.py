@@ -8,7 +8,13 @@ Per batch: one launch of lgcn_eval_scenes behind the forward writes a 32-float r
 row) into a table that holds one row per scene of the split -- no host read, no synchronise.  Per summary: one launch of
 lgcn_eval_reduce sums the table in float64 in a fixed order and one device-to-host read brings the sums back.  The table
 makes the result independent of the batch size, the order of the batches and the number of ranks: every slot is written
-by one wave from that scene's rows alone."""
+by one wave from that scene's rows alone.
+
+    ev = evaluate_store(net, store, batch_size=32, actors=True)       # an ActorEvaluator: one row per ACTOR of the split
+    ev.summary(who="others", min_obs=10)
+
+scores every actor with at least one observed future step by PredLoss's rule (final displacement at the last observed
+step, mean over the observed steps): lgcn_eval_actors per batch, lgcn_eval_reduce_sel per summary."""
 from typing import Dict, Optional, Sequence
 
 import numpy as np
@@ -19,7 +25,8 @@ from ._lib import LgcnError
 
 METRICS = ("minADE", "minFDE", "MR", "p-minADE", "brier-minADE", "brier-minFDE")      # Argoverse's key order
 _COLUMN = {"minADE": 0, "minFDE": 1, "MR": 2, "brier-minFDE": 3, "brier-minADE": 4, "p-minADE": 5}      # of lgcn_eval_reduce's out
-# one byte buffer behind summary()'s single read: out [8, 6] float64 | cnt [3] int64 | slot error int32 | mixed-records error int32
+# one byte buffer behind summary()'s single read: out [8, 6] float64 | cnt [3] int64 ([4] with a selection) | slot error int32 |
+# mixed-records error int32
 _AT_CNT, _AT_ERR_SLOT, _AT_ERR_MIX, _STATUS_BYTES = 384, 416, 432, 448
 
 
@@ -37,13 +44,20 @@ class Evaluator:
         self.n_scenes, self.num_mods, self.num_preds, self.horizon = int(n_scenes), int(num_mods), int(num_preds), int(horizon)
         self.miss_thr, self.keep_preds = float(miss_thr), bool(keep_preds)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._tables(self._n_rows())
+
+    def _n_rows(self) -> int:
+        return self.n_scenes
+
+    def _tables(self, n_rows: int) -> None:
         f32 = dict(dtype=torch.float32, device=self.device)
-        self.rec = torch.zeros((self.n_scenes, ops.EVAL_REC), **f32)
-        self.traj = torch.zeros((self.n_scenes, self.num_mods, self.num_preds, 2), **f32) if keep_preds else None
-        self.score = torch.zeros((self.n_scenes, self.num_mods), **f32) if keep_preds else None
+        self.rec = torch.zeros((n_rows, ops.EVAL_REC), **f32)
+        self.traj = torch.zeros((n_rows, self.num_mods, self.num_preds, 2), **f32) if self.keep_preds else None
+        self.score = torch.zeros((n_rows, self.num_mods), **f32) if self.keep_preds else None
         st = self._status = torch.zeros(_STATUS_BYTES, dtype=torch.uint8, device=self.device)
         self._out = st[:_AT_CNT].view(torch.float64).view(ops.EVAL_MAX_MOD, 6)
         self._cnt = st[_AT_CNT:_AT_CNT + 24].view(torch.int64)
+        self._cnt4 = st[_AT_CNT:_AT_CNT + 32].view(torch.int64)
         self._err_slot = st[_AT_ERR_SLOT:_AT_ERR_SLOT + 4].view(torch.int32)
         self._err_mix = st[_AT_ERR_MIX:_AT_ERR_MIX + 4].view(torch.int32)
 
@@ -81,25 +95,33 @@ class Evaluator:
         """One reduce launch and one device-to-host read -> {k: {metric: mean over the evaluated scenes}} for every k of
         `ks`, plus n_evaluated / n_skipped / n_nonfinite (scenes of flag 1 / 0 / 2).  strict: LgcnError unless every scene
         of the split was evaluated (the reference's `assert has_preds.all()`)."""
+        return self._summarise(ks, strict, lambda: ops.eval_reduce(self.rec, self.miss_thr, self._out, self._cnt, self._err_mix), 3,
+                               "a scene index outside [0, %d) was passed to update(); its scene was not recorded" % self.n_scenes,
+                               "%d scenes were not evaluated (no agent, or its future is not fully observed)")
+
+    def _summarise(self, ks, strict, reduce, n_cnt, slot_msg, skipped_msg) -> Dict:
+        """`reduce()` (one launch into the status buffer) and the one read behind every summary; n_cnt: counts it writes."""
+        name = type(self).__name__
         ks = [int(k) for k in ks]
         if any(not 1 <= k <= self.num_mods for k in ks):
             raise LgcnError("summary: K must lie in 1..%d, got %s" % (self.num_mods, ks))
         with torch.cuda.device(self.device):
-            ops.eval_reduce(self.rec, self.miss_thr, self._out, self._cnt, self._err_mix)
+            reduce()
         host = self._status.cpu().numpy()
         if int(host[_AT_ERR_SLOT:_AT_ERR_SLOT + 4].view(np.int32)[0]) != 0:
-            raise LgcnError("Evaluator: a scene index outside [0, %d) was passed to update(); its scene was not recorded" % self.n_scenes)
+            raise LgcnError("%s: %s" % (name, slot_msg))
         if int(host[_AT_ERR_MIX:_AT_ERR_MIX + 4].view(np.int32)[0]) != 0:
-            raise LgcnError("Evaluator: the table holds records of different num_mods / horizon")
+            raise LgcnError("%s: the table holds records of different num_mods / horizon" % name)
         out = host[:_AT_CNT].view(np.float64).reshape(ops.EVAL_MAX_MOD, 6)
-        n_skip, n_eval, n_bad = (int(c) for c in host[_AT_CNT:_AT_CNT + 24].view(np.int64))
+        n_skip, n_eval, n_bad, *rest = (int(c) for c in host[_AT_CNT:_AT_CNT + 8 * n_cnt].view(np.int64))
         if strict and (n_skip or n_bad):
-            raise LgcnError("Evaluator: %d scenes were not evaluated (no agent, or its future is not fully observed) and %d hold "
-                            "non-finite values" % (n_skip, n_bad))
+            raise LgcnError(("%s: " + skipped_msg + " and %d hold non-finite values") % (name, n_skip, n_bad))
         res = {}
         for k in ks:
             res[k] = {m: (float(out[k - 1, _COLUMN[m]]) / n_eval if n_eval else float("nan")) for m in METRICS}
         res.update(n_evaluated=n_eval, n_skipped=n_skip, n_nonfinite=n_bad)
+        if rest:
+            res.update(n_excluded=rest[0])
         return res
 
     def records(self) -> np.ndarray:
@@ -115,21 +137,96 @@ class Evaluator:
         return index.cpu().numpy(), self.traj[index].cpu().numpy(), self.score[index].cpu().numpy()
 
 
-def evaluate_store(net, store, batch_size: int, evaluator: Optional[Evaluator] = None, indices=None, on_batch=None) -> Evaluator:
+class ActorEvaluator(Evaluator):
+    """The record table of every actor of a split: row actor_off[s] + i is the i-th actor of scene s (`actor_off`: the
+    split's int64 [S + 1] prefix sums, DeviceSceneStore.actor_off).  An actor with at least one observed step t < horizon is
+    evaluated over its observed steps (lgcn_eval_actors; include/lgcn.h has the record).  Other arguments as Evaluator."""
+
+    def __init__(self, actor_off, num_mods: int, num_preds: int, horizon: Optional[int] = None, miss_thr: float = 2.0,
+                 keep_preds: bool = False, device=None):
+        off = np.ascontiguousarray(actor_off, dtype=np.int64).reshape(-1)
+        if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+            raise LgcnError("ActorEvaluator: actor_off must be prefix sums [S + 1] that start at 0")
+        if off.size > 1 and int(np.diff(off).max()) > 1 << 24:
+            raise LgcnError("ActorEvaluator: a scene of more than 2^24 actors (the record holds the local index in fp32)")
+        self.actor_off, self.n_slots = off, int(off[-1])
+        Evaluator.__init__(self, off.size - 1, num_mods, num_preds, horizon, miss_thr, keep_preds, device)
+
+    def _n_rows(self) -> int:
+        return self.n_slots
+
+    @classmethod
+    def for_store(cls, store, config, **kw):
+        """The evaluator of every actor of a flatfile.DeviceSceneStore, sized by `config` (num_mods, num_preds)."""
+        kw.setdefault("device", store.device)
+        return cls(store.actor_off, config["num_mods"], config["num_preds"], **kw)
+
+    def update(self, out_reg_flat, out_cls_flat, fb, ex: Dict, indices) -> None:
+        """One launch on the current stream: the records of every actor of the batch `fb` / `ex` whose scenes are the rows
+        `indices` of the split.  Arguments as Evaluator.update."""
+        if "gt_preds" not in ex or "has_preds" not in ex:
+            raise LgcnError("ActorEvaluator.update: the batch holds no gt_preds / has_preds to evaluate against")
+        idx = np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        if idx.size != fb.n_scenes:
+            raise LgcnError("ActorEvaluator.update: %d indices for a batch of %d scenes" % (idx.size, fb.n_scenes))
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= self.n_scenes):
+            raise LgcnError("ActorEvaluator.update: a scene index outside [0, %d)" % self.n_scenes)
+        A = fb.n_actors
+        if tuple(out_reg_flat.shape) != (A, self.num_mods, self.num_preds, 2):
+            raise LgcnError("ActorEvaluator.update: reg must be %s, got %s"
+                            % ((A, self.num_mods, self.num_preds, 2), tuple(out_reg_flat.shape)))
+        if A != int((self.actor_off[idx + 1] - self.actor_off[idx]).sum()):
+            raise LgcnError("ActorEvaluator.update: the batch holds %d actors, the split's table has %d for these scenes"
+                            % (A, int((self.actor_off[idx + 1] - self.actor_off[idx]).sum())))
+        with torch.cuda.device(self.device):
+            stage = torch.empty(idx.size, dtype=torch.int64, pin_memory=True)
+            stage.numpy()[:] = self.actor_off[idx]
+            base = stage.to(self.device, non_blocking=True)
+            ops.eval_actors(out_reg_flat, out_cls_flat, ex["gt_preds"], ex["has_preds"], fb.actor_off, base, self.horizon,
+                            self.rec, self.traj, self.score, self._err_slot)
+
+    def summary(self, ks: Sequence[int] = (6, 1), who: str = "all", min_obs: int = 1, strict: bool = False) -> Dict:
+        """One reduce launch and one device-to-host read -> Evaluator.summary's dict over the actors the selection keeps,
+        plus n_excluded.  who: "all", "agent" (the first actor of each scene) or "others"; min_obs: an evaluated actor
+        counts only with at least that many observed steps (1..horizon; horizon: fully observed futures only).  strict:
+        LgcnError unless no kept actor was skipped or non-finite."""
+        if who not in ops.EVAL_WHO:
+            raise LgcnError("summary: who must be one of %s, got %r" % (sorted(ops.EVAL_WHO), who))
+        if not 1 <= int(min_obs) <= self.horizon:
+            raise LgcnError("summary: min_obs must lie in 1..%d, got %s" % (self.horizon, min_obs))
+        return self._summarise(ks, strict, lambda: ops.eval_reduce_sel(self.rec, self.miss_thr, ops.EVAL_WHO[who],
+                                                                       self.horizon - int(min_obs), self._out, self._cnt4, self._err_mix),
+                               4, "update() was given a batch whose actor rows do not match the split's table; some actors were "
+                               "not recorded", "%d actors were not evaluated (no observed step, or never recorded)")
+
+    def actor_index(self):
+        """(scene [n], local [n]) int64: the scene and the index inside it of every row of the table."""
+        scene = np.repeat(np.arange(self.n_scenes, dtype=np.int64), np.diff(self.actor_off))
+        return scene, np.arange(self.n_slots, dtype=np.int64) - self.actor_off[scene]
+
+
+def evaluate_store(net, store, batch_size: int, evaluator: Optional[Evaluator] = None, indices=None, on_batch=None,
+                   actors: bool = False) -> Evaluator:
     """Run `net` over the scenes `indices` (default: all) of a flatfile.DeviceSceneStore in batches of `batch_size` (the
     last one may be shorter) and record every scene in `evaluator` (default: a new one for the whole store, sized by
     net.config).  Per batch: store.plan, store.batch, the whole-Net forward of Net.forward_store with its one host read
     and its error behaviour (KeyError / RuntimeError, the pair-capacity regrow, the range guard's re-run), one
     Evaluator.update.  A batch whose scenes hold no actor at all is skipped: its slots stay `not evaluated`.
-    `on_batch(out, fb, ex)`, if given, sees every evaluated batch's flat outputs (train_dp.py takes the validation loss there)."""
+    `on_batch(out, fb, ex)`, if given, sees every evaluated batch's flat outputs (train_dp.py takes the validation loss there).
+    actors=True: the default evaluator is an ActorEvaluator.for_store (every actor of the split); an evaluator passed in, of
+    either class, is used as it is."""
     if not store.has_gt:
         raise LgcnError("evaluate_store: the store holds no gt_preds / has_preds to evaluate against")
     if batch_size < 1:
         raise LgcnError("evaluate_store: batch_size must be positive")
+    if evaluator is None and actors:
+        evaluator = ActorEvaluator.for_store(store, net.config)
     if evaluator is None:
         evaluator = Evaluator(len(store), net.config["num_mods"], net.config["num_preds"], device=store.device)
     if evaluator.n_scenes != len(store):
         raise LgcnError("evaluate_store: the evaluator holds %d slots for a store of %d scenes" % (evaluator.n_scenes, len(store)))
+    if isinstance(evaluator, ActorEvaluator) and not np.array_equal(evaluator.actor_off, store.actor_off):
+        raise LgcnError("evaluate_store: the evaluator's actor_off is not the store's")
     idx = np.arange(len(store), dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
     with torch.no_grad():
         for i in range(0, len(idx), batch_size):

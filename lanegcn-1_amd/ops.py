@@ -2521,33 +2521,40 @@ def _eval_out(t, dtype, shape, name):
     return t
 
 
+def _eval_batch_args(name, reg, cls, gt, has, actor_off, slot, rec, traj, score, err):
+    """The checks eval_scenes and eval_actors share -> (the tensors in that order, A, B, M, T, n_slots)."""
+    if reg.dim() != 4 or reg.shape[3] != 2:
+        raise L.LgcnError("%s: reg must be [A, M, T, 2], got %s" % (name, tuple(reg.shape)))
+    A, M, T, _ = reg.shape
+    B = slot.numel()
+    reg = _eval_arg(reg, torch.float32, (A, M, T, 2), name + " reg")
+    cls = _eval_arg(cls, torch.float32, (A, M), name + " cls")
+    gt = _eval_arg(gt, torch.float32, (A, T, 2), name + " gt")
+    if has.dtype not in (torch.bool, torch.uint8):
+        raise L.LgcnError("%s: has must be bool or uint8, got %s" % (name, has.dtype))
+    has = _eval_arg(has, has.dtype, (A, T), name + " has")
+    actor_off = _eval_arg(actor_off, torch.int32, (B + 1,), name + " actor_off")
+    slot = _eval_arg(slot, torch.int64, (B,), name + " slot")
+    if rec.dim() != 2:
+        raise L.LgcnError("%s: rec must be [n_slots, %d]" % (name, EVAL_REC))
+    n_slots = rec.shape[0]
+    rec = _eval_out(rec, torch.float32, (n_slots, EVAL_REC), name + " rec")
+    traj = _eval_out(traj, torch.float32, (n_slots, M, T, 2), name + " traj")
+    score = _eval_out(score, torch.float32, (n_slots, M), name + " score")
+    err = _eval_out(err, torch.int32, (1,), name + " err")
+    if err is None:
+        raise L.LgcnError("%s: err (int32 [1] on the device) is required" % name)
+    if any(t is not None and t.device != reg.device for t in (cls, gt, has, actor_off, slot, rec, traj, score, err)):
+        raise L.LgcnError("%s: every tensor must live on %s" % (name, reg.device))
+    return (reg, cls, gt, has, actor_off, slot, rec, traj, score, err), A, B, M, T, n_slots
+
+
 def eval_scenes(reg, cls, gt, has, actor_off, slot, horizon: int, rec, traj=None, score=None, err=None) -> None:
     """lgcn_eval_scenes: one launch on the current stream, no host read.  reg [A, M, T, 2], cls [A, M], gt [A, T, 2] fp32,
     has [A, T] bool / uint8, actor_off [B+1] int32, slot [B] int64; writes rec [n_slots, 32] (and traj [n_slots, M, T, 2],
     score [n_slots, M], both or neither) at the rows `slot` names.  err: int32 [1], set to 1 by a slot outside the table."""
-    if reg.dim() != 4 or reg.shape[3] != 2:
-        raise L.LgcnError("eval_scenes: reg must be [A, M, T, 2], got %s" % (tuple(reg.shape),))
-    A, M, T, _ = reg.shape
-    B = slot.numel()
-    reg = _eval_arg(reg, torch.float32, (A, M, T, 2), "eval_scenes reg")
-    cls = _eval_arg(cls, torch.float32, (A, M), "eval_scenes cls")
-    gt = _eval_arg(gt, torch.float32, (A, T, 2), "eval_scenes gt")
-    if has.dtype not in (torch.bool, torch.uint8):
-        raise L.LgcnError("eval_scenes: has must be bool or uint8, got %s" % has.dtype)
-    has = _eval_arg(has, has.dtype, (A, T), "eval_scenes has")
-    actor_off = _eval_arg(actor_off, torch.int32, (B + 1,), "eval_scenes actor_off")
-    slot = _eval_arg(slot, torch.int64, (B,), "eval_scenes slot")
-    if rec.dim() != 2:
-        raise L.LgcnError("eval_scenes: rec must be [n_slots, %d]" % EVAL_REC)
-    n_slots = rec.shape[0]
-    rec = _eval_out(rec, torch.float32, (n_slots, EVAL_REC), "eval_scenes rec")
-    traj = _eval_out(traj, torch.float32, (n_slots, M, T, 2), "eval_scenes traj")
-    score = _eval_out(score, torch.float32, (n_slots, M), "eval_scenes score")
-    err = _eval_out(err, torch.int32, (1,), "eval_scenes err")
-    if err is None:
-        raise L.LgcnError("eval_scenes: err (int32 [1] on the device) is required")
-    if any(t is not None and t.device != reg.device for t in (cls, gt, has, actor_off, slot, rec, traj, score, err)):
-        raise L.LgcnError("eval_scenes: every tensor must live on %s" % (reg.device,))
+    (reg, cls, gt, has, actor_off, slot, rec, traj, score, err), A, B, M, T, n_slots = _eval_batch_args(
+        "eval_scenes", reg, cls, gt, has, actor_off, slot, rec, traj, score, err)
     if A == 0 and B > 0:          # no row to point at: every scene of the batch is empty; the kernel reads no row
         reg, cls, gt, has = rec, rec, rec, rec
     L.check(L.load().lgcn_eval_scenes(_ptr(reg), _ptr(cls), _ptr(gt), _ptr(has), _ptr(actor_off), _ptr(slot), B, M, T, int(horizon),
@@ -2572,3 +2579,41 @@ def eval_reduce(rec, miss_thr: float, out, cnt, err) -> None:
         return
     L.check(L.load().lgcn_eval_reduce(_ptr(rec), n_slots, float(miss_thr), _ptr(out), _ptr(cnt), _ptr(err), _stream()),
             "lgcn_eval_reduce")
+
+
+def eval_actors(reg, cls, gt, has, actor_off, slot_base, horizon: int, rec, traj=None, score=None, err=None) -> None:
+    """lgcn_eval_actors: one launch on the current stream, no host read: the record of EVERY actor row of the batch, partial
+    futures included.  Tensors as eval_scenes; slot_base [B] int64 is the table row of each scene's first actor, the tables
+    hold one row per actor of the split (row slot_base[b] + i for the i-th actor of scene b).  err is also set by a row that
+    actor_off does not cover."""
+    (reg, cls, gt, has, actor_off, slot_base, rec, traj, score, err), A, B, M, T, n_slots = _eval_batch_args(
+        "eval_actors", reg, cls, gt, has, actor_off, slot_base, rec, traj, score, err)
+    L.check(L.load().lgcn_eval_actors(_ptr(reg), _ptr(cls), _ptr(gt), _ptr(has), _ptr(actor_off), _ptr(slot_base), A, B, M, T,
+                                      int(horizon), n_slots, _ptr(rec), _ptr(traj), _ptr(score), _ptr(err), _stream()),
+            "lgcn_eval_actors")
+
+
+EVAL_WHO = {"all": 0, "agent": 1, "others": 2}      # lgcn_eval_reduce_sel's `who`: every actor, local index 0, local index > 0
+
+
+def eval_reduce_sel(rec, miss_thr: float, who: int, max_missing: int, out, cnt, err) -> None:
+    """lgcn_eval_reduce_sel: eval_reduce over the records a selection keeps (who: 0 all, 1 the first actor of a scene, 2 the
+    others; a flag-1 record counts only with at most max_missing unobserved steps).  cnt [4] int64: kept slots of flag
+    0, 1, 2 and the excluded ones."""
+    if rec.dim() != 2:
+        raise L.LgcnError("eval_reduce_sel: rec must be [n_slots, %d]" % EVAL_REC)
+    n_slots = rec.shape[0]
+    rec = _eval_out(rec, torch.float32, (n_slots, EVAL_REC), "eval_reduce_sel rec")
+    out = _eval_out(out, torch.float64, (EVAL_MAX_MOD, 6), "eval_reduce_sel out")
+    cnt = _eval_out(cnt, torch.int64, (4,), "eval_reduce_sel cnt")
+    err = _eval_out(err, torch.int32, (1,), "eval_reduce_sel err")
+    if out is None or cnt is None or err is None:
+        raise L.LgcnError("eval_reduce_sel: out, cnt and err are required")
+    if int(who) not in (0, 1, 2) or int(max_missing) < 0:
+        raise L.LgcnError("eval_reduce_sel: who must be 0, 1 or 2 and max_missing >= 0, got %s" % ((who, max_missing),))
+    if n_slots == 0:
+        out.zero_()
+        cnt.zero_()
+        return
+    L.check(L.load().lgcn_eval_reduce_sel(_ptr(rec), n_slots, float(miss_thr), int(who), int(max_missing), _ptr(out), _ptr(cnt),
+                                          _ptr(err), _stream()), "lgcn_eval_reduce_sel")

@@ -2,6 +2,7 @@
 evaluation launches alone.
 
     python tools/bench_eval.py [--scenes 256] [--batch 32] [--rounds 30] [--warmup 5] [--reps 3] [--slots 39472]
+    python tools/bench_eval.py --actors [--actor-slots 631552]
 
 The store and the protocol of tools/bench_store.py: `scenes` synthetic scenes of S2's per-scene size (324 nodes, 50
 actors), batches of `batch`; one process measures, the two loops alternating, `reps` times over.
@@ -13,7 +14,14 @@ actors), batches of `batch`; one process measures, the two loops alternating, `r
   (d) eval_reduce_us         lgcn_eval_reduce over `slots` records (39,472: the Argoverse validation split) between events
   (c) and (d) are medians over `rounds` launches after `warmup`, each behind a queued 256 MB fill (the stream is busy while
   the host enqueues, so the interval is the launch and not the host's call).  Per figure the JSON line carries the median of the `reps`
-values and their lowest and highest (the spread between repetitions)."""
+values and their lowest and highest (the spread between repetitions).
+
+--actors: the same store and protocol for the evaluation of EVERY actor (evaluate.ActorEvaluator; every actor of the
+synthetic store is fully observed, the most work a row can be):
+  (e) scenes_per_s_actors    evaluate_store(actors=True) + summary(), alternating with (a) in the same process
+  (f) eval_actors_us         lgcn_eval_actors for one batch (1,600 actor rows) next to (c) on the same batch
+  (g) eval_reduce_sel_us     lgcn_eval_reduce_sel (who = others, every evaluated record kept) over `actor-slots` records
+                             (631,552 = 16 per scene of (d)'s split), next to lgcn_eval_reduce over the same table"""
 import argparse
 import json
 import os
@@ -34,6 +42,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--slots", type=int, default=39472)
+    ap.add_argument("--actors", action="store_true", help="measure the evaluation of every actor against the agent-only one")
+    ap.add_argument("--actor-slots", type=int, default=16 * 39472)
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -41,7 +51,7 @@ def main():
     from lanegcn_amd import data as gen
     from lanegcn_amd import lanegcn as M
     from lanegcn_amd import ops
-    from lanegcn_amd.evaluate import Evaluator, evaluate_store
+    from lanegcn_amd.evaluate import ActorEvaluator, Evaluator, evaluate_store
     from lanegcn_amd.flatfile import DeviceSceneStore, write_scenes
 
     if not torch.cuda.is_available():
@@ -62,8 +72,8 @@ def main():
         """The scene indices of one window: `n_batches` batches without a repeat inside a batch."""
         return [rng.permutation(args.scenes)[:args.batch].astype(np.int64) for _ in range(n_batches)]
 
-    def evaluate_rate(window):
-        ev = Evaluator(len(store), cfg["num_mods"], cfg["num_preds"])
+    def evaluate_rate(window, actors=False):
+        ev = ActorEvaluator.for_store(store, cfg) if actors else Evaluator(len(store), cfg["num_mods"], cfg["num_preds"])
         evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[:args.warmup]))
         sync()
         t0 = time.perf_counter()
@@ -110,6 +120,50 @@ def main():
             if i >= args.warmup:
                 ts.append(a.elapsed_time(b) * 1e3)
         return statistics.median(ts)
+
+    def filled(n):
+        """A record table of n evaluated records (an ActorEvaluator of one scene), every third one a first actor."""
+        big = ActorEvaluator(np.array([0, n], np.int64), cfg["num_mods"], cfg["num_preds"])
+        big.rec[:, 0] = 1.0
+        big.rec[:, 1], big.rec[:, 2] = cfg["num_mods"], cfg["num_preds"]
+        big.rec[:, 3] = (torch.arange(n, device="cuda") % 3).float()
+        big.rec[:, 4:4 + 3 * cfg["num_mods"]] = torch.rand((n, 3 * cfg["num_mods"]), device="cuda")
+        return big
+
+    if args.actors:
+        reps = {"scenes_per_s_evaluate": [], "scenes_per_s_actors": [], "eval_scenes_us": [], "eval_actors_us": [],
+                "eval_reduce_us": [], "eval_reduce_sel_us": []}
+        agree = None
+        for r in range(args.reps):
+            window = picks()
+            got = {}
+            for name in (("evaluate", "actors") if r % 2 else ("actors", "evaluate")):
+                rate, got[name] = evaluate_rate(window, actors=name == "actors")
+                reps["scenes_per_s_" + name].append(rate)
+            n_mod = cfg["num_mods"]
+            agree = (got["evaluate"][n_mod]["minFDE"], got["actors"][n_mod]["minFDE"], got["actors"]["n_evaluated"])
+            pick = window[0]
+            with torch.no_grad():
+                fb, ex, out = net.forward_store_flat(store, pick)
+            ev, av = Evaluator(len(store), n_mod, cfg["num_preds"]), ActorEvaluator.for_store(store, cfg)
+            slot = torch.from_numpy(pick).cuda()
+            base = torch.from_numpy(store.actor_off[pick]).cuda()
+            reps["eval_scenes_us"].append(launch_us(lambda: ops.eval_scenes(
+                out["reg"], out["cls"], ex["gt_preds"], ex["has_preds"], fb.actor_off, slot, ev.horizon, ev.rec, None, None, ev._err_slot)))
+            reps["eval_actors_us"].append(launch_us(lambda: ops.eval_actors(
+                out["reg"], out["cls"], ex["gt_preds"], ex["has_preds"], fb.actor_off, base, av.horizon, av.rec, None, None, av._err_slot)))
+            big = filled(args.actor_slots)
+            reps["eval_reduce_us"].append(launch_us(lambda: ops.eval_reduce(big.rec, 2.0, big._out, big._cnt, big._err_mix)))
+            reps["eval_reduce_sel_us"].append(launch_us(lambda: ops.eval_reduce_sel(
+                big.rec, 2.0, ops.EVAL_WHO["others"], big.horizon - 1, big._out, big._cnt4, big._err_mix)))
+        res = {"scenes": args.scenes, "batch": args.batch, "rounds": args.rounds, "warmup": args.warmup, "reps": args.reps,
+               "actor_rows_per_batch": int(fb.n_actors), "reduce_slots": args.actor_slots,
+               "minFDE_agents": float("%.6g" % agree[0]), "minFDE_all_actors": float("%.6g" % agree[1]), "actors_evaluated": agree[2]}
+        for k, v in reps.items():
+            digits = 1 if k.startswith("scenes") else 2
+            res[k] = {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
+        print(json.dumps(res))
+        return
 
     reps = {"scenes_per_s_evaluate": [], "scenes_per_s_manual": [], "eval_scenes_us": [], "eval_reduce_us": []}
     agree = None

@@ -12,7 +12,8 @@ is ONE flat all-reduce (lanegcn_amd.dist.allreduce_mean_grads).  Difference: the
 where the reference's DistributedSampler pads it.
 
 The reference's test.py (:60-100) is `--eval --eval-store PATH`: the whole store, every scene once over all ranks, through
-lanegcn_amd.evaluate (Argoverse's forecasting metrics for K = num_mods and K = 1; `--save-preds` writes the predictions).
+lanegcn_amd.evaluate (Argoverse's forecasting metrics for K = num_mods and K = 1; `--save-preds` writes the predictions);
+`--eval-actors [--min-obs N]` scores every actor with an observed future step and prints all / agent / others.
 """
 import argparse
 import os
@@ -89,6 +90,12 @@ def main(argv=None):
                          "runs from this store instead of the dataset")
     ap.add_argument("--save-preds", default="", type=str, metavar="FILE.npz",
                     help="with --eval --eval-store: write index, preds [n, num_mods, num_preds, 2] and scores [n, num_mods]")
+    ap.add_argument("--eval-actors", action="store_true",
+                    help="with --eval --eval-store: score every actor with an observed future step, not the agents alone; prints "
+                         "the summaries of all actors, the agents and the others; --save-preds then also writes scene and local "
+                         "and holds every actor")
+    ap.add_argument("--min-obs", type=int, default=1, metavar="N",
+                    help="with --eval-actors: an actor counts only with at least N observed future steps")
     ap.add_argument("--rot-size", type=float, default=None, metavar="X",
                     help="turn every picked scene by rand() * X per step (needs a store written with theta=True); default: "
                          "config['rot_size'] when config['rot_aug'] is set, else no augmentation")
@@ -134,10 +141,29 @@ def main(argv=None):
         from lanegcn_amd.evaluate import Evaluator, evaluate_store
         from lanegcn_amd.flatfile import DeviceSceneStore
         eval_store = DeviceSceneStore(args.eval_store)
-        ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"], keep_preds=bool(args.save_preds))
+        if args.eval_actors:
+            from lanegcn_amd.evaluate import ActorEvaluator
+            ev = ActorEvaluator.for_store(eval_store, config, keep_preds=bool(args.save_preds))
+        else:
+            ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"], keep_preds=bool(args.save_preds))
         net.eval()
         evaluate_store(net, eval_store, config["val_batch_size"], ev, indices=store_eval_picks(len(eval_store), rank, world))
         ev.merge()
+        if args.eval_actors:
+            for who in ("all", "agent", "others"):
+                summary = ev.summary(ks=ks, who=who, min_obs=args.min_obs)
+                if rank == 0:
+                    print("actors: %s, at least %d observed steps" % (who, args.min_obs))
+                    print("\n".join(metric_lines(summary, ks)))
+                    print("evaluated %d actors, skipped %d, non-finite %d, excluded %d"
+                          % (summary["n_evaluated"], summary["n_skipped"], summary["n_nonfinite"], summary["n_excluded"]))
+            if rank == 0 and args.save_preds:
+                index, preds, scores = ev.predictions()
+                scene, local = ev.actor_index()
+                np.savez(args.save_preds, index=index, scene=scene[index], local=local[index], preds=preds, scores=scores)
+            if world > 1:
+                torch.distributed.destroy_process_group()
+            return 0
         summary = ev.summary(ks=ks)
         if rank == 0:
             print("\n".join(metric_lines(summary, ks)))

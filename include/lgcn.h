@@ -1328,6 +1328,46 @@ int lgcn_store_gather_aug(const lgcn_store_t *s, const lgcn_store_batch_t *b, co
                           void *stream);
 
 /*
+ * lgcn_store_pack: the write side of the store.  ONE launch packs G = n_seg index runs, each a contiguous piece of one
+ * of K = n_src source arrays, back to back into dst [n_dst] int32, and (n_scenes > 0) cuts a batch's frame rows
+ * [n_scenes,6] fp32 (orig, then rot row-major) into orig [n_scenes,2] and rot [n_scenes,2,2].  A source holds int16,
+ * int32 or int64 elements; the conversion is numpy's astype(int32): int16 sign-extends, int64 keeps its low 32 bits.
+ * It is how data_raw.build_store turns the builder's flat edge arrays (int64 scales, int16 left / right) into a store's
+ * edge_u / edge_v, and how DeviceSceneStore.concat merges the edge arrays of P stores relation-major (P x 2R runs).
+ *
+ *   tab_host / tab_dev: lgcn_store_pack_table_elems(G, K) = 3 G + 1 + 3 K int64, the same on the host (validated) and
+ *   on the device (read by the kernel; the source addresses live there, so K is not bounded by a kernel argument):
+ *       seg_off [G + 1]   prefix sums of the destination words, from 0 to n_dst (empty runs allowed anywhere)
+ *       seg_src [G]       the run's source, in [0, K)
+ *       seg_at  [G]       first element of the run in its source
+ *       src_ptr [K]       device address of the source (0 allowed for an empty source)
+ *       src_kind [K]      bytes per element: 2, 4 or 8
+ *       src_len [K]       elements of the source
+ *   Words of dst beyond n_dst are not written.
+ *
+ * The grid lies over output words (then one thread per scene for the frame rows); a thread finds its run by binary
+ * search in seg_off, so neither G nor a run's length is bounded by a wave, a workgroup or LDS.  No atomics, no
+ * allocation, no host synchronisation.
+ *
+ * Checked before anything is launched: NULL struct, a negative size, n_seg == 0 next to a non-zero n_dst / n_scenes, a
+ * NULL pointer next to a non-zero size, a kind other than 2 / 4 / 8, a negative source length, seg_off that does not
+ * start at 0, decreases or ends elsewhere than n_dst, a source index outside [0, K), a run that begins or ends outside
+ * its source (LGCN_EINVAL); n_dst, n_scenes, a source length or the table beyond 2^31 - 1 (LGCN_ESHAPE); tab_dev or rot
+ * not 16-byte aligned, tab_host, frame or orig not 8-byte aligned, dst not 4-byte aligned, a source not aligned to its
+ * element (LGCN_EALIGN).  n_seg == 0 returns LGCN_OK without a launch and without looking at the tables.
+ * lgcn_store_pack_table_elems: LGCN_EINVAL for a negative argument, LGCN_ESHAPE beyond 2^31 - 1 elements.
+ */
+typedef struct {
+    int64_t n_seg, n_src, n_dst, n_scenes;
+    const int64_t *tab_host, *tab_dev;
+    int32_t *dst;
+    const float *frame;
+    float *rot, *orig;
+} lgcn_store_pack_t;
+int64_t lgcn_store_pack_table_elems(int64_t n_seg, int64_t n_src);
+int lgcn_store_pack(const lgcn_store_pack_t *p, void *stream);
+
+/*
  * Scene construction for a BATCH of raw scenes (lanegcn_amd/data_raw.py): tracks to actor arrays
  * (reference data.py:148-217, ArgoDataset.get_obj_feats) and map lanes to the scale-0 lane graph (data.py:220-361,
  * ArgoDataset.get_lane_graph up to :353; the dilated scales stay lgcn_bool_square*).

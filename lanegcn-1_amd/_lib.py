@@ -183,6 +183,14 @@ class StoreBatch(C.Structure):    # lgcn_store_batch_t
     ]
 
 
+class StorePack(C.Structure):     # lgcn_store_pack_t
+    _fields_ = [
+        ("n_seg", C.c_int64), ("n_src", C.c_int64), ("n_dst", C.c_int64), ("n_scenes", C.c_int64),
+        ("tab_host", C.c_void_p), ("tab_dev", C.c_void_p), ("dst", C.c_void_p), ("frame", C.c_void_p),
+        ("rot", C.c_void_p), ("orig", C.c_void_p),
+    ]
+
+
 class SceneTracks(C.Structure):    # lgcn_scene_tracks_t
     _fields_ = [
         ("n_scenes", C.c_int32), ("n_tracks", C.c_int32), ("n_rows", C.c_int32), ("pad_", C.c_int32),
@@ -345,6 +353,8 @@ SIGNATURES = {
     "lgcn_store_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_gather": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
     "lgcn_store_gather_aug": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P, _P, _P]),
+    "lgcn_store_pack_table_elems": (C.c_int64, [_L, _L]),
+    "lgcn_store_pack": (C.c_int, [C.POINTER(StorePack), _P]),
     "lgcn_scene_tracks_ws_elems": (C.c_int64, [_L]),
     "lgcn_scene_tracks": (C.c_int, [C.POINTER(SceneTracks), _P]),
     "lgcn_scene_topo_elems": (C.c_int64, [_L, _L, _L]),

@@ -8,6 +8,10 @@
 //
 // lgcn_store_gather_aug is the same kernel body (k_store_gather<true>) with the reference's training rotation on the way
 // through: coordinates are turned by the pick's Rm, rot comes from the per-batch table instead of the store.
+//
+// lgcn_store_pack (k_store_pack) is the write side: one launch packs index runs of int16 / int32 / int64 sources into the
+// store's int32 edge arrays and cuts rot / orig out of a batch's frame rows.  Same shape of kernel: the grid lies over
+// output words, a thread finds its run by binary search, the source descriptors are read from the device table.
 #include <cmath>
 
 #include "lgcn_common.hpp"
@@ -143,6 +147,55 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
     }
 }
 
+// ------------------------------------------------------------------ lgcn_store_pack
+// the table of one pack, int64 (G runs, K sources)
+struct PackTab {
+    const int64_t *seg_off;     // [G + 1] prefix sums of the destination words
+    const int64_t *seg_src;     // [G] the run's source
+    const int64_t *seg_at;      // [G] first element of the run in its source
+    const int64_t *src_ptr;     // [K] device address of the source
+    const int64_t *src_kind;    // [K] bytes per element: 2, 4 or 8
+    const int64_t *src_len;     // [K] elements of the source
+};
+
+__host__ __device__ inline PackTab pack_tab(const int64_t *t, int64_t G, int64_t K) {
+    PackTab s;
+    s.seg_off = t;
+    s.seg_src = s.seg_off + G + 1;
+    s.seg_at = s.seg_src + G;
+    s.src_ptr = s.seg_at + G;
+    s.src_kind = s.src_ptr + K;
+    s.src_len = s.src_kind + K;           // 3 G + 1 + 3 K words in all (lgcn_store_pack_table_elems)
+    return s;
+}
+
+// blocks [0, frame_first) own the destination words, the rest one scene's frame row each thread
+__global__ __launch_bounds__(kStoreThreads) void k_store_pack(const lgcn_store_pack_t p, const uint32_t frame_first) {
+    const uint32_t blk = blockIdx.x;
+    if (blk < frame_first) {              // one destination word: the run's element, narrowed or sign-extended to int32
+        const int64_t i = (int64_t)blk * kStoreThreads + threadIdx.x;
+        if (i >= p.n_dst) return;
+        const PackTab t = pack_tab(p.tab_dev, p.n_seg, p.n_src);
+        const int k = store_find(t.seg_off, (int)p.n_seg, i);
+        const int64_t s = t.seg_src[k];
+        const int64_t r = t.seg_at[k] + (i - t.seg_off[k]);
+        const int64_t kind = t.src_kind[s];
+        const uintptr_t base = (uintptr_t)t.src_ptr[s];
+        int32_t v;
+        if (kind == 8) v = (int32_t)reinterpret_cast<const int64_t *>(base)[r];          // the low 32 bits
+        else if (kind == 4) v = reinterpret_cast<const int32_t *>(base)[r];
+        else v = (int32_t)reinterpret_cast<const int16_t *>(base)[r];
+        p.dst[i] = v;
+    } else {                              // one scene: frame row (orig, rot row-major) -> orig [2], rot [2,2]
+        const int64_t j = (int64_t)(blk - frame_first) * kStoreThreads + threadIdx.x;
+        if (j >= p.n_scenes) return;
+        const float2 *f = reinterpret_cast<const float2 *>(p.frame) + 3 * j;
+        const float2 o = f[0], r0 = f[1], r1 = f[2];
+        reinterpret_cast<float2 *>(p.orig)[j] = o;
+        reinterpret_cast<float4 *>(p.rot)[j] = make_float4(r0.x, r0.y, r1.x, r1.y);
+    }
+}
+
 // ------------------------------------------------------------------ host side
 // prefix sums off[0..n] from 0 to total; src[i] + (off[i + 1] - off[i]) inside [0, limit]
 static int store_check_runs(const int64_t *off, const int64_t *src, int64_t n, int64_t total, int64_t limit) {
@@ -215,6 +268,43 @@ static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, St
     return LGCN_OK;
 }
 
+// everything lgcn_store_pack reads from the host table becomes an address only after it is known to lie inside a source
+static int pack_validate(const lgcn_store_pack_t *p, uint32_t *frame_first, uint32_t *n_blocks) {
+    if (p == nullptr) return LGCN_EINVAL;
+    if (p->n_seg < 0 || p->n_src < 0 || p->n_dst < 0 || p->n_scenes < 0) return LGCN_EINVAL;
+    if (p->n_seg == 0) return (p->n_dst | p->n_scenes) ? LGCN_EINVAL : LGCN_OK;
+    const int64_t lim = 0x7fffffff;
+    if (p->n_dst > lim || p->n_scenes > lim || lgcn_store_pack_table_elems(p->n_seg, p->n_src) < 0) return LGCN_ESHAPE;
+    LGCN_CHECK_PTR(p->tab_host); LGCN_CHECK_PTR(p->tab_dev);
+    if (p->n_dst > 0) LGCN_CHECK_PTR(p->dst);
+    if (p->n_scenes > 0) { LGCN_CHECK_PTR(p->frame); LGCN_CHECK_PTR(p->rot); LGCN_CHECK_PTR(p->orig); }
+    if (reinterpret_cast<uintptr_t>(p->tab_host) & 7u) return LGCN_EALIGN;
+    LGCN_CHECK_ALIGN16(p->tab_dev);
+    LGCN_CHECK_ALIGN16(p->rot);
+    if ((reinterpret_cast<uintptr_t>(p->frame) & 7u) || (reinterpret_cast<uintptr_t>(p->orig) & 7u)) return LGCN_EALIGN;
+    if (reinterpret_cast<uintptr_t>(p->dst) & 3u) return LGCN_EALIGN;
+
+    const PackTab t = pack_tab(p->tab_host, p->n_seg, p->n_src);
+    for (int64_t s = 0; s < p->n_src; ++s) {
+        const int64_t kind = t.src_kind[s], len = t.src_len[s];
+        if ((kind != 2 && kind != 4 && kind != 8) || len < 0) return LGCN_EINVAL;
+        if (len > lim) return LGCN_ESHAPE;
+        if (len > 0 && t.src_ptr[s] == 0) return LGCN_EINVAL;
+        if ((uint64_t)t.src_ptr[s] & (uint64_t)(kind - 1)) return LGCN_EALIGN;
+    }
+    if (t.seg_off[0] != 0) return LGCN_EINVAL;
+    for (int64_t k = 0; k < p->n_seg; ++k) {
+        if (t.seg_off[k + 1] < t.seg_off[k]) return LGCN_EINVAL;      // (so every entry is >= 0 and the difference holds)
+        const int64_t len = t.seg_off[k + 1] - t.seg_off[k], s = t.seg_src[k], at = t.seg_at[k];
+        if (s < 0 || s >= p->n_src) return LGCN_EINVAL;
+        if (at < 0 || at > t.src_len[s] || len > t.src_len[s] - at) return LGCN_EINVAL;
+    }
+    if (t.seg_off[p->n_seg] != p->n_dst) return LGCN_EINVAL;
+    *frame_first = (uint32_t)store_blocks(p->n_dst);
+    *n_blocks = *frame_first + (uint32_t)store_blocks(p->n_scenes);
+    return LGCN_OK;
+}
+
 }  // namespace lgcn
 
 using namespace lgcn;
@@ -249,6 +339,21 @@ int lgcn_store_gather_aug(const lgcn_store_t *s, const lgcn_store_batch_t *b, co
     LGCN_CHECK_ALIGN16(aug_dev);
     hipLaunchKernelGGL(k_store_gather<true>, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
                        *s, *b, grid, reinterpret_cast<const StoreAug *>(aug_dev));
+    return launch_status();
+}
+
+int64_t lgcn_store_pack_table_elems(int64_t n_seg, int64_t n_src) {
+    if (n_seg < 0 || n_src < 0) return LGCN_EINVAL;
+    const int64_t lim = 0x7fffffff;
+    if (n_seg > lim / 8 || n_src > lim / 8) return LGCN_ESHAPE;
+    return 3 * n_seg + 1 + 3 * n_src;            // the words that pack_tab lays out
+}
+
+int lgcn_store_pack(const lgcn_store_pack_t *p, void *stream) {
+    uint32_t frame_first = 0, n_blocks = 0;
+    if (int rc = pack_validate(p, &frame_first, &n_blocks)) return rc;
+    if (n_blocks == 0) return LGCN_OK;
+    hipLaunchKernelGGL(k_store_pack, dim3(n_blocks), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream), *p, frame_first);
     return launch_status();
 }
 

@@ -1,7 +1,8 @@
 """Front end of the data path: raw tracks and map lanes to scenes, on the device for a whole batch (csrc/lgcn_scene.hip,
 and with batched=True csrc/lgcn_graphbatch.hip for the dilated scales and left / right).  The
 reference does this per scene in Python: ArgoDataset.get_obj_feats (data.py:148-217) and ArgoDataset.get_lane_graph
-(data.py:220-361).
+(data.py:220-361).  build_scenes returns scene dicts; build_store packs the same batch straight into a resident
+flatfile.DeviceSceneStore (one more launch, no scene dicts, nothing through the host).
 
 Neither routine needs argoverse-api once its inputs are plain arrays:
   a raw scene   {"city", "trajs": [[n_i,2] float64], "steps": [[n_i] int64]}, the agent first: what the reference's
@@ -250,24 +251,35 @@ def _dilate(graph, dev_graph, num_scales, device):
         graph[k] = graph[k] + more
 
 
-def _batched_tail(graphs, out, h, h2, num_scales, cross_dist, device):
+def _flat_tail(out, h, h2, num_scales, cross_dist):
     """Scales 1 .. num_scales - 1 of pre / suc and, with cross_dist given, left / right for the whole batch from the flat
     arrays _lane_fill left on the device (ops.dilate_batch, ops.cross_edges_batch): no per-scene call, no concatenation,
-    one host read per scale and one for the left / right counts."""
+    one host read per scale and one for the left / right counts -> (scale 0 as such a scale dict: the used parts of
+    pre_u .. suc_v with pre_off / suc_off, the scales above it, (edges, offs) of cross_edges_batch or None)."""
     cuts = _cuts(h, h2)
     flat = lambda k, cut=None: out[k][:int(cuts[cut or k][-1])]      # the used part of an array sized by its upper bound
-    scales = ops.dilate_batch(flat("pre_u", "pre"), flat("pre_v", "pre"), flat("suc_u", "suc"), flat("suc_v", "suc"), h[:, 1],
-                              cuts["pre"], cuts["suc"], num_scales)
+    first = {"pre_u": flat("pre_u", "pre"), "pre_v": flat("pre_v", "pre"), "suc_u": flat("suc_u", "suc"),
+             "suc_v": flat("suc_v", "suc"), "pre_off": cuts["pre"], "suc_off": cuts["suc"]}
+    scales = ops.dilate_batch(first["pre_u"], first["pre_v"], first["suc_u"], first["suc_v"], h[:, 1], cuts["pre"], cuts["suc"],
+                              num_scales)
+    cross = None
+    if cross_dist is not None:
+        cross = ops.cross_edges_batch(out["ctrs"], out["feats"], out["lane_idcs"], flat("pre_pairs"), flat("suc_pairs"),
+                                      flat("left_pairs"), flat("right_pairs"), h[:, 1], h[:, 0], cuts["pre_pairs"],
+                                      cuts["suc_pairs"], cuts["left_pairs"], cuts["right_pairs"], cross_dist)
+    return first, scales, cross
+
+
+def _batched_tail(graphs, out, h, h2, num_scales, cross_dist, device):
+    """_flat_tail's results cut into the per-scene leaves of `graphs`."""
+    _, scales, cross = _flat_tail(out, h, h2, num_scales, cross_dist)
     for sc in scales:
         for k in ("pre", "suc"):
             us, vs = _split(sc[k + "_u"], sc[k + "_off"], device), _split(sc[k + "_v"], sc[k + "_off"], device)
             for g, u, v in zip(graphs, us, vs):
                 g[k] = g[k] + [{"u": u, "v": v}]
-    if cross_dist is not None:
-        edges, offs = ops.cross_edges_batch(out["ctrs"], out["feats"], out["lane_idcs"], flat("pre_pairs"), flat("suc_pairs"),
-                                            flat("left_pairs"), flat("right_pairs"), h[:, 1], h[:, 0], cuts["pre_pairs"],
-                                            cuts["suc_pairs"], cuts["left_pairs"], cuts["right_pairs"], cross_dist)
-        for g, side in zip(graphs, preprocess_data.split_cross(edges, offs, range(len(graphs)), device)):
+    if cross is not None:
+        for g, side in zip(graphs, preprocess_data.split_cross(cross[0], cross[1], range(len(graphs)), device)):
             g["left"], g["right"] = side["left"], side["right"]
 
 
@@ -308,25 +320,11 @@ def get_lane_graph(data, table, config, lane_ids=None):
     return graph
 
 
-def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None, batched=False):
-    """Raw scenes to scene dicts in the reference's schema, the whole batch at once: the track kernels and the lane
-    kernels run once (6 launches, one memset and one zero fill whatever the number of scenes, 2 size read-backs), then per
-    scene the existing device ops: preprocess_data.dilated_nbrs for scales 1 .. num_scales - 1 and, with cross=True,
-    preprocess_data.preprocess for graph["left"] / graph["right"] (config["cross_dist"], default 6).  batched=True replaces
-    the per-scene ops by ops.dilate_batch and ops.cross_edges_batch on the batch's flat arrays: the same leaves from a
-    number of launches and host reads (num_scales - 1, plus 1 with cross=True) that does not depend on the number of scenes.
-
-    raws: raw scenes; tables: {city: LaneTable} (uploaded on first use if .to(device) was not called; a batch may mix
-    cities); lane_ids: optional per-scene candidate lists (None = the whole table).  Returns new dicts with city, idx (the
-    position in the batch), feats, obs_trajs, ctrs, orig, theta, rot, gt_preds, has_preds and graph; leaves are device
-    tensors, which data.collate_fn and Net.forward take as they come, or numpy arrays with device=False.  num_nodes is an
-    int and theta a float.  Errors (LgcnError, nothing launched afterwards): an agent track under 20 rows (before any
-    launch), a step listed twice in a track, a scene in which no lane survives."""
-    dev = _need_gpu("build_scenes")
-    raws = list(raws)
+def _front(raws, tables, config, lane_ids, dev):
+    """The front half that build_scenes and build_store share: the frames, the track and lane launches and the two size
+    read-backs of a non-empty batch -> (orig, theta, rot on the host, frame [S,6] on the device, the track job, a_off
+    [S + 1], the lane fill's flat outputs, h, h2).  Raises the batch's LgcnErrors."""
     S = len(raws)
-    if S == 0:
-        return []
     orig, theta, rot = scene_frames(raws)
     cities, tabs, scene_tab = {}, [], []
     for r in raws:
@@ -347,6 +345,29 @@ def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None, b
     a_off = _track_status(tjob, hh[:S + 2], trk_off)
     out, head2, h = _lane_fill(ljob, hh[S + 2:], dev)
     h2 = head2.cpu().numpy()                                  # read-back 2: kept neighbours
+    return orig, theta, rot, frame, tjob, a_off, out, h, h2
+
+
+def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None, batched=False):
+    """Raw scenes to scene dicts in the reference's schema, the whole batch at once: the track kernels and the lane
+    kernels run once (6 launches, one memset and one zero fill whatever the number of scenes, 2 size read-backs), then per
+    scene the existing device ops: preprocess_data.dilated_nbrs for scales 1 .. num_scales - 1 and, with cross=True,
+    preprocess_data.preprocess for graph["left"] / graph["right"] (config["cross_dist"], default 6).  batched=True replaces
+    the per-scene ops by ops.dilate_batch and ops.cross_edges_batch on the batch's flat arrays: the same leaves from a
+    number of launches and host reads (num_scales - 1, plus 1 with cross=True) that does not depend on the number of scenes.
+
+    raws: raw scenes; tables: {city: LaneTable} (uploaded on first use if .to(device) was not called; a batch may mix
+    cities); lane_ids: optional per-scene candidate lists (None = the whole table).  Returns new dicts with city, idx (the
+    position in the batch), feats, obs_trajs, ctrs, orig, theta, rot, gt_preds, has_preds and graph; leaves are device
+    tensors, which data.collate_fn and Net.forward take as they come, or numpy arrays with device=False.  num_nodes is an
+    int and theta a float.  Errors (LgcnError, nothing launched afterwards): an agent track under 20 rows (before any
+    launch), a step listed twice in a track, a scene in which no lane survives."""
+    dev = _need_gpu("build_scenes")
+    raws = list(raws)
+    S = len(raws)
+    if S == 0:
+        return []
+    orig, theta, rot, frame, tjob, a_off, out, h, h2 = _front(raws, tables, config, lane_ids, dev)
     n_a = int(a_off[-1])
     actors = {k: _split(v[:n_a], a_off, device) for k, v in (("feats", tjob.feats), ("obs_trajs", tjob.obs), ("ctrs", tjob.ctrs),
                                                              ("gt_preds", tjob.gt), ("has_preds", tjob.has))}
@@ -374,3 +395,44 @@ def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None, b
         s.update({k: v[b] for k, v in actors.items()})
         scenes.append(s)
     return scenes
+
+
+def build_store(raws, tables, config, lane_ids=None):
+    """Raw scenes to a flatfile.DeviceSceneStore that holds them, without leaving the device: the launches and host
+    reads of build_scenes(..., device=True, cross=True, batched=True) (2 size read-backs, ops.read_back num_scales - 1
+    times for the dilation and once for left / right) and then ONE more launch, ops.store_pack, which writes the store's
+    int32 relation-major edge_u / edge_v from the builder's flat edge arrays and rot / orig from the frame rows.  No scene
+    dict and no per-scene view is made: inside one relation the builder's flat arrays already hold the scenes back to
+    back, as the store wants them, so a relation's u (or v) is one run, and the node and actor arrays are the builder's
+    own tensors, adopted as they are (the actor arrays as the first n_a rows of tensors sized for every track).
+    The offset tables come from the tables the builder already holds, theta from scene_frames.
+
+    The store equals DeviceSceneStore(path) after write_scenes(path, build_scenes(..., device=False), theta=True), byte for
+    byte; plan, batch (with and without rot_dt), Net.forward_store*, evaluate_store, concat and save work on it.
+    raws, tables, lane_ids and the errors: as build_scenes; an empty batch is an LgcnError."""
+    from .flatfile import DeviceSceneStore
+    dev = _need_gpu("build_store")
+    raws = list(raws)
+    S = len(raws)
+    if S == 0:
+        raise L.LgcnError("build_store: no scene to build a store from")
+    _, theta, _, frame, tjob, a_off, out, h, h2 = _front(raws, tables, config, lane_ids, dev)
+    num_scales = int(config["num_scales"])
+    first, scales, (edges, offs) = _flat_tail(out, h, h2, num_scales, float(config.get("cross_dist", 6.0)))
+    # the store's relations in its order: pre0, suc0, pre1, ..., left, right
+    rels = [{"u": sc[k + "_u"], "v": sc[k + "_v"], "off": sc[k + "_off"]} for sc in [first] + scales for k in ("pre", "suc")]
+    rels += [{"u": edges[k + "_u"], "v": edges[k + "_v"], "off": offs[k + "_off"]} for k in ("left", "right")]
+    R = len(rels)
+    edge_off = np.stack([np.asarray(r["off"], np.int64) for r in rels])
+    rel_off = _csum(edge_off[:, -1])
+    E = int(rel_off[-1])
+    packed = torch.empty(2 * E, dtype=torch.int32, device=dev)
+    rot, orig = torch.empty((S, 2, 2), dtype=torch.float32, device=dev), torch.empty((S, 2), dtype=torch.float32, device=dev)
+    # run k < R is relation k's u of every scene, run R + k its v: 2 R runs, one source each
+    ops.store_pack([r["u"] for r in rels] + [r["v"] for r in rels], np.arange(2 * R), np.zeros(2 * R, np.int64),
+                   np.tile(edge_off[:, -1], 2), packed, frame, rot, orig)
+    n_a = int(a_off[-1])
+    arrays = dict(node_ctrs=out["ctrs"], node_feats=out["feats"], turn=out["turn"], control=out["control"],
+                  intersect=out["intersect"], actor_ctrs=tjob.ctrs[:n_a], actor_feats=tjob.feats[:n_a], rot=rot, orig=orig,
+                  gt_preds=tjob.gt[:n_a], has_preds=tjob.has[:n_a], edge_u=packed[:E], edge_v=packed[E:])
+    return DeviceSceneStore.from_arrays(arrays, h[:, 1], a_off, edge_off, rel_off, num_scales, theta)

@@ -17,6 +17,10 @@ Layout (S scenes, R = 2 * num_scales + 2 relations in the order pre0, suc0, ...,
 FlatSceneFile cuts a batch on the host.  DeviceSceneStore keeps the arrays in device memory and cuts the same batch
 there with one launch; plan_batch is its host half.  With `rot_dt` both turn the picked scenes as the
 reference's rot_aug does (data.py:39-65), the device store inside that same launch.
+
+A DeviceSceneStore is also made on the device: from_arrays wraps existing device tensors (data_raw.build_store ends
+there), concat merges stores (merge_tables is its host half; one ops.store_pack launch merges the edge arrays), and save
+writes the file that write_scenes would write for the store's scenes.
 """
 from dataclasses import dataclass
 from typing import Dict, List, Sequence
@@ -283,6 +287,47 @@ def plan_batch(node_off, actor_off, edge_off, rel_off, num_scales: int, indices)
         sizes=n_act.tolist(), n_rel=R, n_elem=n_elem, table=tab)
 
 
+def merge_tables(parts) -> Dict:
+    """Host half of DeviceSceneStore.concat: the tables of the store that holds the scenes of `parts` in part order.
+    A part is anything with node_off, actor_off, edge_off, rel_off, num_scales and (optionally, None = absent) theta as
+    keys or as attributes: a DeviceSceneStore, FlatSceneFile(path).a, a loaded `.npz`.  Returns node_off, actor_off,
+    edge_off, rel_off, num_scales, theta (None if the parts have none) and the runs that merge the parts' edge_u (or
+    edge_v, the same runs) relation-major: seg_part, seg_at, seg_len [R * P] int64 in the order (relation, part) -- run k is
+    edge_u of part seg_part[k] from seg_at[k] on.  LgcnError for an empty list, parts that differ in num_scales or in
+    having theta.  Plain numpy; needs no GPU."""
+    def get(p, k):
+        if isinstance(p, dict) or hasattr(p, "files"):
+            return p[k] if k in p else None
+        return getattr(p, k, None)
+    parts = list(parts)
+    if not parts:
+        raise LgcnError("store: concat of an empty list")
+    scales = [int(get(p, "num_scales")) for p in parts]
+    if len(set(scales)) != 1:
+        raise LgcnError("store: concat of parts with different num_scales: %s" % sorted(set(scales)))
+    thetas = [get(p, "theta") for p in parts]
+    if len({t is None for t in thetas}) != 1:
+        raise LgcnError("store: concat of parts with and without theta")
+    R = 2 * scales[0] + 2
+    i64 = lambda p, k: np.asarray(get(p, k), np.int64)
+    for p in parts:
+        if i64(p, "edge_off").shape[0] != R or i64(p, "rel_off").shape != (R + 1,):
+            raise LgcnError("store: a part's edge tables do not hold 2 * num_scales + 2 relations")
+    ends = {k: np.stack([i64(p, k)[..., -1] for p in parts]) for k in ("node_off", "actor_off", "edge_off")}    # [P] / [P, R]
+    bases = {k: np.cumsum(v, 0) - v for k, v in ends.items()}
+    chain = lambda k: np.concatenate([[0]] + [i64(p, k)[1:] + base for p, base in zip(parts, bases[k])])
+    node_off, actor_off = chain("node_off"), chain("actor_off")
+    edge_off = np.concatenate([np.zeros((R, 1), np.int64)] + [i64(p, "edge_off")[:, 1:] + b[:, None]
+                                                             for p, b in zip(parts, bases["edge_off"])], 1)
+    rel_off = np.zeros(R + 1, np.int64)
+    np.cumsum(edge_off[:, -1], out=rel_off[1:])
+    rel = np.stack([i64(p, "rel_off") for p in parts], 1)                  # [R + 1, P]
+    return dict(node_off=node_off, actor_off=actor_off, edge_off=edge_off, rel_off=rel_off, num_scales=scales[0],
+                theta=None if thetas[0] is None else np.concatenate([np.asarray(t, np.float64).reshape(-1) for t in thetas]),
+                seg_part=np.tile(np.arange(len(parts), dtype=np.int64), R), seg_at=rel[:-1].reshape(-1).copy(),
+                seg_len=np.diff(rel, axis=0).reshape(-1))
+
+
 def _carve(spec, device):
     """One device byte buffer that holds the arrays (name, dtype, shape) of `spec` in order, each at a 256-byte aligned
     offset (the layout of engine.collate_flat_host), and the arrays as views of it."""
@@ -329,6 +374,71 @@ class DeviceSceneStore:
         self._job = ops.StoreJob({k: torch.from_numpy(v).to(self.device) for k, v in host.items()})
         torch.cuda.synchronize(self.device)      # resident before any stream reads it
         self.nbytes = self._job.nbytes
+
+    @classmethod
+    def from_arrays(cls, arrays, node_off, actor_off, edge_off, rel_off, num_scales: int, theta=None):
+        """A store over device tensors that already exist (nothing is copied; data_raw.build_store and concat end here).
+        arrays: the tensors ops.StoreJob takes (has_preds may be bool); node_off, actor_off [S + 1], edge_off [R, S + 1],
+        rel_off [R + 1]: the host tables of the file layout; theta: the scenes' headings [S] or None.  The tensors may be
+        views of larger allocations: `nbytes` counts the storages they keep alive, once each."""
+        self = object.__new__(cls)
+        i64 = lambda x: np.ascontiguousarray(x, np.int64)
+        self.node_off, self.actor_off, self.edge_off, self.rel_off = i64(node_off), i64(actor_off), i64(edge_off), i64(rel_off)
+        self.n_scenes, self.num_scales = len(self.node_off) - 1, int(num_scales)
+        self.theta = None if theta is None else np.ascontiguousarray(theta, np.float64).reshape(-1)
+        arrays = dict(arrays)
+        if "has_preds" in arrays and arrays["has_preds"].dtype == torch.bool:
+            arrays["has_preds"] = arrays["has_preds"].view(torch.uint8)
+        self._job = job = ops.StoreJob(arrays)
+        self.device = job.device
+        R, S, p = 2 * self.num_scales + 2, self.n_scenes, job.p
+        if self.edge_off.shape != (R, S + 1) or self.actor_off.shape != (S + 1,) or self.rel_off.shape != (R + 1,) \
+                or (self.theta is not None and self.theta.shape != (S,)) or p.n_scenes != S \
+                or int(self.node_off[-1]) != p.n_nodes or int(self.actor_off[-1]) != p.n_actors \
+                or int(self.rel_off[-1]) != p.n_edges or not np.array_equal(np.diff(self.rel_off), self.edge_off[:, -1]):
+            raise LgcnError("store: the offset tables do not describe the arrays")
+        held = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes() for t in job.t.values() if t.numel()}
+        self.nbytes = sum(held.values())
+        return self
+
+    @classmethod
+    def concat(cls, stores):
+        """One store that holds the scenes of `stores` in part order: the store of all those scenes written at once.  The
+        edge arrays are merged relation-major by ONE ops.store_pack launch over P x 2R runs, every other array by one
+        concatenation, the tables on the host (merge_tables).  LgcnError, before any launch: an empty list, parts on
+        different devices, with different num_scales, or that differ in having gt_preds or in having theta."""
+        stores = list(stores)
+        if not stores:
+            raise LgcnError("store: concat of an empty list")
+        if len({str(s.device) for s in stores}) != 1:
+            raise LgcnError("store: concat of parts on different devices")
+        if len({bool(s.has_gt) for s in stores}) != 1:
+            raise LgcnError("store: concat of parts with and without gt_preds")
+        m = merge_tables(stores)
+        P, dev = len(stores), stores[0].device
+        parts = [s._job.t for s in stores]
+        with torch.cuda.device(dev):
+            arrays = {k: torch.cat([t[k] for t in parts]) for k in parts[0] if k not in ("edge_u", "edge_v")}
+            E = int(m["rel_off"][-1])
+            edges = torch.empty(2 * E, dtype=torch.int32, device=dev)
+            ops.store_pack([t["edge_u"].reshape(-1) for t in parts] + [t["edge_v"].reshape(-1) for t in parts],
+                           np.concatenate([m["seg_part"], m["seg_part"] + P]), np.tile(m["seg_at"], 2), np.tile(m["seg_len"], 2), edges)
+        arrays["edge_u"], arrays["edge_v"] = edges[:E], edges[E:]
+        return cls.from_arrays(arrays, m["node_off"], m["actor_off"], m["edge_off"], m["rel_off"], m["num_scales"], m["theta"])
+
+    def save(self, path: str) -> None:
+        """Write the store as the `.npz` that write_scenes(path, scenes, theta=...) writes for its scenes: same keys, dtypes,
+        shapes and bytes (theta if the store has it).  One device->host copy per array."""
+        t = self._job.t
+        out = dict(num_scales=np.int64(self.num_scales), node_off=self.node_off, actor_off=self.actor_off, edge_off=self.edge_off,
+                   rel_off=self.rel_off)
+        for k, v in t.items():
+            out[k] = v.cpu().numpy()
+        if "has_preds" in out:
+            out["has_preds"] = out["has_preds"].view(bool)
+        if self.theta is not None:
+            out["theta"] = self.theta
+        np.savez(path, **out)
 
     def __len__(self):
         return self.n_scenes

@@ -1111,6 +1111,15 @@ class Net(nn.Module):
         sizes = [int(a) for a in ex["sizes"]]
         return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
 
+    def forward_raw(self, raws, tables, lane_ids=None) -> Dict[str, List[Tensor]]:
+        """No-grad forward of raw scenes (data_raw's raw-scene dicts and {city: LaneTable}): data_raw.build_store with
+        this net's config (pred_range, num_scales, cross_dist), then forward_store over all its scenes -- raw tracks to
+        predictions without a scene dict and without a trip through the host.  Output and errors are forward_store's,
+        after build_store's own."""
+        from . import data_raw
+        store = data_raw.build_store(raws, tables, self.config, lane_ids=lane_ids)
+        return self.forward_store(store, np.arange(len(store)))
+
     def forward_store_flat(self, store, indices, plan=None):
         """forward_store before its outputs are cut into per-scene lists -> (fb, ex, out): the FlatBatch and the extras of
         store.batch(indices), and the flat engine output behind the host-side checks (out["cls"] [A, M], out["reg"]

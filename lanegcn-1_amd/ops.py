@@ -2371,6 +2371,85 @@ def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n
                 "lgcn_store_gather_aug")
 
 
+def store_pack_table_elems(n_seg: int, n_src: int) -> int:
+    """int64 entries of the table of lgcn_store_pack for n_seg runs out of n_src sources."""
+    n = int(L.load().lgcn_store_pack_table_elems(int(n_seg), int(n_src)))
+    if n < 0:
+        L.check(n, "lgcn_store_pack_table_elems")
+    return n
+
+
+_PACK_KINDS = {torch.int16: 2, torch.int32: 4, torch.int64: 8}
+
+
+class StorePackJob:
+    """One lgcn_store_pack_t with its table (host and device copy) and the tensors it points to; store_pack's arguments.
+    Building it validates what the wrapper can see and uploads the table; nothing is launched."""
+
+    def __init__(self, sources, seg_src, seg_at, seg_len, dst: torch.Tensor, frame: torch.Tensor = None,
+                 rot: torch.Tensor = None, orig: torch.Tensor = None):
+        import numpy as np
+        seg_src, seg_at, seg_len = (np.asarray(x).reshape(-1) for x in (seg_src, seg_at, seg_len))
+        G, K = len(seg_len), len(sources)
+        if len(seg_src) != G or len(seg_at) != G or any(x.size and x.dtype.kind not in "iu" for x in (seg_src, seg_at, seg_len)):
+            raise L.LgcnError("store_pack: seg_src, seg_at and seg_len must be integer sequences of one length")
+        if not dst.is_contiguous():
+            raise L.LgcnError("store_pack: dst must be contiguous")
+        dst = _dev(dst, torch.int32, "store_pack dst")
+        dev = dst.device
+        if dev.index != torch.cuda.current_device():
+            raise L.LgcnError("store_pack: dst lives on %s, which is not the current device" % (dev,))
+        tab = np.empty(store_pack_table_elems(G, K), np.int64)
+        tab[0] = 0
+        np.cumsum(seg_len, dtype=np.int64, out=tab[1:G + 1])
+        tab[G + 1:2 * G + 1], tab[2 * G + 1:3 * G + 1] = seg_src, seg_at
+        at = 3 * G + 1
+        for i, t in enumerate(sources):
+            if not torch.is_tensor(t) or t.dtype not in _PACK_KINDS or not t.is_cuda or t.device != dev or not t.is_contiguous():
+                raise L.LgcnError("store_pack: source %d must be a contiguous int16 / int32 / int64 tensor on %s (the HIP hot "
+                                  "path has no CPU fallback)" % (i, dev))
+            n = t.numel()
+            tab[at + i], tab[at + K + i], tab[at + 2 * K + i] = (t.data_ptr() if n else 0), _PACK_KINDS[t.dtype], n
+        n_dst = int(tab[G])
+        if G and (int(np.min(seg_len)) < 0 or n_dst > dst.numel()):
+            raise L.LgcnError("store_pack: the runs hold %d words, dst %d" % (n_dst, dst.numel()))
+        p = L.StorePack()
+        p.n_seg, p.n_src, p.n_dst = G, K, n_dst
+        if (frame is None) != (rot is None) or (frame is None) != (orig is None):
+            raise L.LgcnError("store_pack: frame, rot and orig come together")
+        if frame is not None:
+            if not (rot.is_contiguous() and orig.is_contiguous()):
+                raise L.LgcnError("store_pack: rot and orig must be contiguous")
+            frame, rot, orig = (_dev(t, torch.float32, "store_pack " + k) for t, k in ((frame, "frame"), (rot, "rot"), (orig, "orig")))
+            S = frame.shape[0] if frame.dim() == 2 else -1
+            if tuple(frame.shape) != (S, 6) or rot.numel() != 4 * S or orig.numel() != 2 * S or {frame.device, rot.device, orig.device} != {dev}:
+                raise L.LgcnError("store_pack: frame [S,6], rot [S,2,2] and orig [S,2] on dst's device")
+            p.n_scenes = S
+            p.frame, p.rot, p.orig = (t.data_ptr() if S else None for t in (frame, rot, orig))
+        if G == 0 and p.n_scenes:
+            raise L.LgcnError("store_pack: frame rows need at least one run")
+        tab_dev = torch.from_numpy(tab).to(dev) if G else None
+        p.tab_host, p.tab_dev, p.dst = tab.ctypes.data, (tab_dev.data_ptr() if G else None), (dst.data_ptr() if n_dst else None)
+        self.p, self.n_dst, self.keep = p, n_dst, (tab, tab_dev, dst, list(sources), frame, rot, orig)
+
+
+def store_pack_launch(job: StorePackJob) -> int:
+    """The launch of a StorePackJob on the current stream (n_seg == 0: none); returns the words written."""
+    L.check(L.load().lgcn_store_pack(C.byref(job.p), _stream()), "lgcn_store_pack")
+    return job.n_dst
+
+
+def store_pack(sources, seg_src, seg_at, seg_len, dst: torch.Tensor, frame: torch.Tensor = None, rot: torch.Tensor = None,
+               orig: torch.Tensor = None) -> int:
+    """lgcn_store_pack: one launch on the current stream writes dst[:n] (int32 device tensor, n = sum(seg_len)) with the
+    runs sources[seg_src[k]][seg_at[k] : seg_at[k] + seg_len[k]] back to back, converted as numpy's astype(int32)
+    converts them, and leaves the rest of dst alone.  sources: flat contiguous int16 / int32 / int64 device tensors (views
+    of one array are fine); seg_src, seg_at, seg_len: host integer sequences of one length.  frame [S,6] fp32 with rot
+    [S,2,2] and orig [S,2] (all three or none): the same launch cuts the frame rows (orig, rot) into them.  Returns n.
+    The table is validated by the library on the host before the launch; a table that does not fit raises LgcnError."""
+    return store_pack_launch(StorePackJob(sources, seg_src, seg_at, seg_len, dst, frame, rot, orig))
+
+
 # ------------------------------------------------------------------ scene construction (data_raw: get_obj_feats / get_lane_graph)
 def _i32_table(off, what):
     import numpy as np

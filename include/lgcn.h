@@ -1215,7 +1215,8 @@ int lgcn_roi_loss_bwd(const float *logits, const float *goals, const float *traj
  *   ws: lgcn_roi_ws_elems(n_nodes, n_lanes, n_edges, n_slots, n_agents) int32 (negative: LGCN_EINVAL for a negative size,
  *       LGCN_ESHAPE beyond 2^31 - 1 elements), kept from lgcn_roi_search to lgcn_roi_edge_fill.
  *
- * lgcn_roi_search (1 memset + 8 launches): lanes -> nodes tables, the relations as CSR rows, then one workgroup per agent:
+ * lgcn_roi_search (1 memset + 8 launches, 7 where one scan tile holds every row count): lanes -> nodes tables, the
+ *   relations as CSR rows, then one workgroup per agent:
  *   speed (0: dropped), anchor node (closest node within pi/4 of the agent's heading, else pi/2, ties: smaller index; none:
  *   dropped), level-by-level lane search over suc_pairs (horizon v * 3 + horizon_buffer) and pre_pairs (v * 2 + ...), left /
  *   right closure, lane order (search order with every lane at its first occurrence when the closure adds none, else

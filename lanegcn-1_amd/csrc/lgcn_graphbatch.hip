@@ -17,7 +17,7 @@ namespace lgcn {
 __device__ __forceinline__ void gb_bounds(const int32_t *node_off, int S, int n, int i, int value, int32_t *bounds) {
     if (i < 2 * n) {
         const int r = i >= n ? 1 : 0, g = i - r * n;
-        for (int s = sc_find_seg(node_off, S, g); s >= 0 && node_off[s] == g; --s) bounds[r * (S + 1) + s] = value;
+        for (int s = find_seg(node_off, S, g); s >= 0 && node_off[s] == g; --s) bounds[r * (S + 1) + s] = value;
     }
     if (i == n || i == 2 * n) {
         const int r = i / n - 1;
@@ -34,11 +34,11 @@ struct GbDilWs {
 __host__ __device__ inline GbDilWs gb_dil_ws(int32_t *ws, int64_t n_nodes, int64_t n_edges, int64_t n_csr) {
     GbDilWs w;
     int64_t o = 0;
-    w.loc = ws + o; o += sc_up4(2 * n_nodes + 1);
-    w.sums = ws + o; o += sc_up4(sc_blocks(2 * n_nodes + 1));
-    w.csr = ws + o; o += sc_up4(n_csr);
-    w.u = reinterpret_cast<int64_t *>(ws + o); o += sc_up4(2 * n_edges);
-    w.v = reinterpret_cast<int64_t *>(ws + o); o += sc_up4(2 * n_edges);
+    w.loc = ws + o; o += up4(2 * n_nodes + 1);
+    w.sums = ws + o; o += up4(sc_blocks(2 * n_nodes + 1));
+    w.csr = ws + o; o += up4(n_csr);
+    w.u = reinterpret_cast<int64_t *>(ws + o); o += up4(2 * n_edges);
+    w.v = reinterpret_cast<int64_t *>(ws + o); o += up4(2 * n_edges);
     w.total = o;
     return w;
 }
@@ -51,7 +51,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_rebase(const lgcn_dilate_batc
     const int S = p.n_scenes, r = e >= p.n_pre ? 1 : 0;
     const int le = (int)(e - (r ? p.n_pre : 0));
     const int32_t *node_off = p.off_dev, *edge_off = p.off_dev + (1 + r) * (S + 1);
-    const int s = sc_find_seg(edge_off, S, le);
+    const int s = find_seg(edge_off, S, le);
     const int lo = node_off[s], n = node_off[s + 1] - lo;
     const int64_t u = (r ? p.suc_u : p.pre_u)[le], v = (r ? p.suc_v : p.pre_v)[le];
     const bool ok = u >= 0 && u < n && v >= 0 && v < n;
@@ -68,7 +68,7 @@ __device__ __forceinline__ GbRow gb_row(const lgcn_dilate_batch_t &p, int i) {
     GbRow q;
     q.rel_base = i >= N ? N : 0;
     q.g = i - q.rel_base;
-    const int s = sc_find_seg(p.off_dev, p.n_scenes, q.g);
+    const int s = find_seg(p.off_dev, p.n_scenes, q.g);
     q.lo = p.off_dev[s];
     q.hi = p.off_dev[s + 1];
     return q;
@@ -76,7 +76,7 @@ __device__ __forceinline__ GbRow gb_row(const lgcn_dilate_batch_t &p, int i) {
 
 // One thread per row (see sq_merge_row): the exact length of the row of A * A, scanned inside the block.
 __global__ __launch_bounds__(kScThreads) void k_gb_sq_count(const lgcn_dilate_batch_t p, const GbDilWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int NR = 2 * (int)p.n_nodes;
     const int i = blockIdx.x * kScThreads + threadIdx.x;
     int v[1] = {0};
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_sq_count(const lgcn_dilate_ba
 
 // The new row pointer, and its value at the scene boundaries of both relations (what the host reads back).
 __global__ __launch_bounds__(kScThreads) void k_gb_sq_rowptr(const lgcn_dilate_batch_t p, const GbDilWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int N = (int)p.n_nodes;
     const int i = blockIdx.x * kScThreads + threadIdx.x;
     int base[1];
@@ -128,9 +128,9 @@ struct GbCrossWs {
 __host__ __device__ inline GbCrossWs gb_cross_ws(int32_t *ws, int64_t n_nodes) {
     GbCrossWs w;
     int64_t o = 0;
-    w.partner = ws + o; o += sc_up4(2 * n_nodes);
-    w.loc = ws + o; o += sc_up4(2 * n_nodes + 1);
-    w.sums = ws + o; o += sc_up4(sc_blocks(2 * n_nodes + 1));
+    w.partner = ws + o; o += up4(2 * n_nodes);
+    w.loc = ws + o; o += up4(2 * n_nodes + 1);
+    w.sums = ws + o; o += up4(sc_blocks(2 * n_nodes + 1));
     w.total = o;
     return w;
 }
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_lane_mask(const lgcn_cross_ba
     const int32_t *work = p.off_dev + (7 + side) * (S + 1);
     const int64_t t = (int64_t)blockIdx.x * kScThreads + threadIdx.x;
     if (t >= work[S]) return;
-    const int s = sc_find_seg(work, S, (int)t);
+    const int s = find_seg(work, S, (int)t);
     const GbScene q = gb_scene(p, s, side);
     lane_mask_item(q.side, q.n_side, q.pre, q.n_pre, q.suc, q.n_suc, q.num_lanes, q.mat, t - work[s]);
 }
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_partner(const lgcn_cross_batc
     const int side = blockIdx.y, lane = threadIdx.x & 63;
     const int64_t h = (int64_t)blockIdx.x * (kScThreads >> 6) + (threadIdx.x >> 6);
     if (h >= p.n_nodes) return;
-    const GbScene q = gb_scene(p, sc_find_seg(p.off_dev, p.n_scenes, (int)h), side);
+    const GbScene q = gb_scene(p, find_seg(p.off_dev, p.n_scenes, (int)h), side);
     int out = -1;
     if (q.n_side > 0)
         out = cross_partner(reinterpret_cast<const float2 *>(p.ctrs) + q.node_lo, reinterpret_cast<const float2 *>(p.feats) + q.node_lo,
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_partner(const lgcn_cross_batc
 
 // The compaction that torch.nonzero did per scene: kept nodes in (side, scene, node) order.
 __global__ __launch_bounds__(kScThreads) void k_gb_cross_flag(const lgcn_cross_batch_t p, const GbCrossWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int i = blockIdx.x * kScThreads + threadIdx.x;
     int v[1] = {i < 2 * (int)p.n_nodes && w.partner[i] >= 0 ? 1 : 0};
     int excl[1];
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_cross_flag(const lgcn_cross_b
 }
 
 __global__ __launch_bounds__(kScThreads) void k_gb_cross_fill(const lgcn_cross_batch_t p, const GbCrossWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int N = (int)p.n_nodes;
     const int i = blockIdx.x * kScThreads + threadIdx.x;
     int base[1];
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(kScThreads) void k_gb_cross_fill(const lgcn_cross_b
     gb_bounds(p.off_dev, p.n_scenes, N, i, o, p.counts);
     if (i == 2 * N || w.partner[i] < 0 || o >= 2 * N) return;
     const int h = i >= N ? i - N : i;
-    const int lo = p.off_dev[sc_find_seg(p.off_dev, p.n_scenes, h)];
+    const int lo = p.off_dev[find_seg(p.off_dev, p.n_scenes, h)];
     p.out_u[o] = (int16_t)(h - lo);          // the low 16 bits, as .astype(np.int16) keeps them
     p.out_v[o] = (int16_t)w.partner[i];
 }
@@ -224,9 +224,9 @@ static int gb_dilate_validate(const lgcn_dilate_batch_t *p, int stage) {
         return LGCN_ESHAPE;
     LGCN_CHECK_PTR(p->off_host);
     const int S = p->n_scenes;
-    if (int rc = sc_check_table(p->off_host, S, p->n_nodes)) return rc;
-    if (int rc = sc_check_table(p->off_host + (S + 1), S, p->n_pre)) return rc;
-    if (int rc = sc_check_table(p->off_host + 2 * (S + 1), S, p->n_suc)) return rc;
+    if (int rc = check_table(p->off_host, S, p->n_nodes)) return rc;
+    if (int rc = check_table(p->off_host + (S + 1), S, p->n_pre)) return rc;
+    if (int rc = check_table(p->off_host + 2 * (S + 1), S, p->n_suc)) return rc;
     LGCN_CHECK_PTR(p->off_dev); LGCN_CHECK_PTR(p->ws); LGCN_CHECK_PTR(p->rowptr); LGCN_CHECK_PTR(p->col);
     if (stage == 0) {
         if (p->n_pre > 0) { LGCN_CHECK_PTR(p->pre_u); LGCN_CHECK_PTR(p->pre_v); }
@@ -242,10 +242,10 @@ static int gb_dilate_validate(const lgcn_dilate_batch_t *p, int stage) {
     LGCN_CHECK_ALIGN16(p->ws);
     const void *words[] = {p->off_dev, p->rowptr, p->col, p->out_rowptr, p->bounds, p->out_col};
     for (const void *q : words)
-        if (sc_misaligned(q, 3u)) return LGCN_EALIGN;
+        if (misaligned(q, 3u)) return LGCN_EALIGN;
     const void *dwords[] = {p->pre_u, p->pre_v, p->suc_u, p->suc_v, p->out_u, p->out_v};
     for (const void *q : dwords)
-        if (sc_misaligned(q, 7u)) return LGCN_EALIGN;
+        if (misaligned(q, 7u)) return LGCN_EALIGN;
     return LGCN_OK;
 }
 
@@ -268,7 +268,7 @@ static int gb_cross_validate(const lgcn_cross_batch_t *p) {
     const int S = p->n_scenes, S1 = S + 1;
     const int32_t *off = p->off_host;
     for (int k = 0; k < 6; ++k)
-        if (int rc = sc_check_table(off + k * S1, S, totals[k])) return rc;
+        if (int rc = check_table(off + k * S1, S, totals[k])) return rc;
     // the mask and work tables must be what the first six imply: a bad entry never becomes an address
     int64_t mask = 0, work[2] = {0, 0};
     for (int s = 0; s <= S; ++s) {
@@ -294,8 +294,8 @@ static int gb_cross_validate(const lgcn_cross_batch_t *p) {
     LGCN_CHECK_ALIGN16(p->ws);
     const void *dwords[] = {p->ctrs, p->feats, p->lane_idcs, p->pre_pairs, p->suc_pairs, p->left_pairs, p->right_pairs};
     for (const void *q : dwords)
-        if (sc_misaligned(q, 7u)) return LGCN_EALIGN;
-    if (sc_misaligned(p->off_dev, 3u) || sc_misaligned(p->counts, 3u) || sc_misaligned(p->out_u, 1u) || sc_misaligned(p->out_v, 1u))
+        if (misaligned(q, 7u)) return LGCN_EALIGN;
+    if (misaligned(p->off_dev, 3u) || misaligned(p->counts, 3u) || misaligned(p->out_u, 1u) || misaligned(p->out_v, 1u))
         return LGCN_EALIGN;
     return LGCN_OK;
 }

@@ -2,129 +2,13 @@
 // plan, distance-gated pair search.  Everything here is bit-exact against the
 // reference (lanegcn.py:171-209, 672-689); this file is compiled with
 // -ffp-contract=off so the pair-search distance is evaluated exactly like
-// ATen's sub / pow(2) / sum / sqrt / le chain (no FMA).
+// ATen's sub / pow(2) / sum / sqrt / le chain (no FMA).  The scans and the
+// segment search are those of lgcn_blockscan.hpp.
 #include "lgcn_common.hpp"
+#include "lgcn_blockscan.hpp"
 #include "lgcn_graphops.hpp"
 
 namespace lgcn {
-
-// ---------------------------------------------------------------- scan ----
-// Exclusive scan of int32: per-block scan + block totals, then an add-back in which every block sums the totals
-// before it (two launches; beyond 4096 blocks the totals are scanned by their own single-block launch first).
-constexpr int kScanThreads = 256;
-constexpr int kScanItems = 8;
-constexpr int kScanTile = kScanThreads * kScanItems;
-
-// Inclusive scan over the 64 lanes at VALU speed: Hillis-Steele inside every row of 16 lanes (DPP row_shr 1, 2, 4, 8: a lane
-// without a source lane adds 0), then the last lane of row 0 / 2 into rows 1 / 3 (row_bcast:15) and lane 31 into rows 2
-// and 3 (row_bcast:31).  (__shfl_up is ds_bpermute: an LDS round trip per step.)
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_add_from(int v) {
-    return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
-}
-__device__ __forceinline__ int wave_inclusive_scan(int v, int /*lane*/) {
-    v = dpp_add_from<0x111, 0xf>(v);
-    v = dpp_add_from<0x112, 0xf>(v);
-    v = dpp_add_from<0x114, 0xf>(v);
-    v = dpp_add_from<0x118, 0xf>(v);
-    v = dpp_add_from<0x142, 0xa>(v);
-    v = dpp_add_from<0x143, 0xc>(v);
-    return v;
-}
-
-// Block-wide exclusive scan of one value per thread; returns the exclusive
-// prefix, *total = block sum.  NT threads (multiple of 64, <= 1024).
-template <int NT>
-__device__ __forceinline__ int block_exclusive_scan(int v, int *total, int *lds /*[NT/64 + 1]*/) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int inc = wave_inclusive_scan(v, lane);
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    if (w == 0) {      // the wave totals are scanned by the first wave (it was a serial loop of one thread: 16 LDS round trips)
-        const int t = lane < NT / 64 ? lds[lane] : 0;
-        const int run = wave_inclusive_scan(t, lane);
-        if (lane < NT / 64) lds[lane] = run - t;
-        if (lane == NT / 64 - 1) lds[NT / 64] = run;
-    }
-    __syncthreads();
-    const int base = lds[w];
-    *total = lds[NT / 64];
-    __syncthreads();
-    return base + inc - v;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_blocks(const int32_t *in, int32_t *out,
-                                                              int32_t *sums, int64_t n) {
-    __shared__ int lds[kScanThreads / 64 + 1];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-    int v[kScanItems];
-    int s = 0;
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        v[i] = (base + i < n) ? in[base + i] : 0;
-        s += v[i];
-    }
-    int total;
-    int pre = block_exclusive_scan<kScanThreads>(s, &total, lds);
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        if (base + i < n) out[base + i] = pre;
-        pre += v[i];
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void k_scan_sums(int32_t *sums, int nb) {
-    __shared__ int lds[1024 / 64 + 1];
-    int carry = 0;
-    for (int c = 0; c < nb; c += 1024) {
-        const int i = c + threadIdx.x;
-        const int v = i < nb ? sums[i] : 0;
-        int total;
-        const int pre = block_exclusive_scan<1024>(v, &total, lds);
-        if (i < nb) sums[i] = pre + carry;
-        carry += total;
-    }
-}
-
-// Add-back with the scan of the block totals folded in: block b sums the totals of the blocks before it (a few
-// hundred at most at the plan's sizes) instead of waiting for a separate single-block scan launch.
-__global__ __launch_bounds__(kScanThreads) void k_scan_add_prefix(int32_t *out, const int32_t *sums, int64_t n) {
-    __shared__ int lds[kScanThreads / 64 + 1];
-    int part = 0;
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += kScanThreads) part += sums[i];
-    int add;
-    block_exclusive_scan<kScanThreads>(part, &add, lds);
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i)
-        if (base + i < n) out[base + i] += add;
-}
-
-__global__ __launch_bounds__(kScanThreads) void k_scan_add(int32_t *out, const int32_t *sums, int64_t n) {
-    const int add = sums[blockIdx.x];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + (int64_t)threadIdx.x * kScanItems;
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i)
-        if (base + i < n) out[base + i] += add;
-}
-
-inline int64_t scan_ws_elems(int64_t n) { return (n + kScanTile - 1) / kScanTile + 1; }
-
-// out may alias in.
-static int exclusive_scan(const int32_t *in, int32_t *out, int64_t n, int32_t *sums, hipStream_t st) {
-    if (n <= 0) return LGCN_OK;
-    const int64_t nb = (n + kScanTile - 1) / kScanTile;
-    if (nb > 0x7fffffff) return LGCN_ESHAPE;
-    hipLaunchKernelGGL(k_scan_blocks, dim3((unsigned)nb), dim3(kScanThreads), 0, st, in, out, sums, n);
-    if (nb > 4096) {          // very long inputs: scan the block totals in their own launch
-        hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, st, sums, (int)nb);
-        hipLaunchKernelGGL(k_scan_add, dim3((unsigned)nb), dim3(kScanThreads), 0, st, out, sums, n);
-    } else if (nb > 1) {
-        hipLaunchKernelGGL(k_scan_add_prefix, dim3((unsigned)nb), dim3(kScanThreads), 0, st, out, sums, n);
-    }
-    return launch_status();
-}
 
 // -------------------------------------------------------- graph_gather ----
 __global__ __launch_bounds__(256) void k_graph_gather(const int64_t *in, int64_t n,
@@ -132,14 +16,7 @@ __global__ __launch_bounds__(256) void k_graph_gather(const int64_t *in, int64_t
                                                       int n_seg, int64_t *out64, int32_t *out32) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n;
          e += (int64_t)gridDim.x * blockDim.x) {
-        // last segment with seg_off[s] <= e (empty segments are skipped by
-        // taking the LAST one: seg_off is non-decreasing)
-        int lo = 0, hi = n_seg;  // invariant: seg_off[lo] <= e < seg_off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (seg_off[mid] <= e) lo = mid; else hi = mid;
-        }
-        const int64_t v = in[e] + seg_base[lo];
+        const int64_t v = in[e] + seg_base[find_seg(seg_off, n_seg, e)];
         if (out64) out64[e] = v;
         if (out32) out32[e] = (int32_t)v;
     }
@@ -195,15 +72,6 @@ __global__ __launch_bounds__(256) void k_csr_sort_rows(const int32_t *rowptr, in
 }
 
 // -------------------------------------------------------- pair search -----
-__device__ __forceinline__ int find_scene(const int32_t *off, int n_scenes, int g) {
-    int lo = 0, hi = n_scenes;  // off[lo] <= g < off[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= g) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // lanegcn.py:676-678: dist = a - c; sqrt((dist ** 2).sum(2)) <= th, fp32, no FMA.
 __device__ __forceinline__ bool within(float ax, float ay, float cx, float cy, float th) {
     const float dx = __fsub_rn(ax, cx), dy = __fsub_rn(ay, cy);
@@ -226,7 +94,7 @@ __device__ __forceinline__ void pairs_rows_body(const float2 *agt, const int32_t
     const int lane = threadIdx.x & 63;
     const int g = row_block * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (g >= n_agt) return;
-    const int sc = find_scene(agt_off, n_scenes, g);
+    const int sc = find_seg(agt_off, n_scenes, g);
     // offset tables are caller data: a table that does not describe this job (stale memory under a captured graph)
     // must not take a load or a store out of bounds
     int c0 = ctx_off[sc], c1 = ctx_off[sc + 1];
@@ -392,12 +260,7 @@ struct IndexParams {
 };
 
 __device__ __forceinline__ int64_t to_global(const IndexParams &p, int64_t i) {
-    int lo = 0, hi = p.n_seg;                 // last segment with seg_off[s] <= i (as k_graph_gather)
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (p.seg_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return p.idx_local[i] + p.seg_base[lo];
+    return p.idx_local[i] + p.seg_base[find_seg(p.seg_off, p.n_seg, i)];      // as k_graph_gather
 }
 
 template <int PASS>     // 0: count, 1: fill
@@ -458,10 +321,8 @@ __global__ __launch_bounds__(1024) void k_index_scan(const IndexParams p) {
         if (j.n_agt == 0 && threadIdx.x == 0) j.rowptr_q[0] = 0;
         return;
     }
-    // keys in front of this tile: the totals of the tiles in front of it (<= 1024: one per thread)
-    const int part = (int)threadIdx.x < bid ? (int)p.cnt[p.n_keys1 + threadIdx.x] : 0;
-    int before;
-    block_exclusive_scan<1024>(part, &before, lds);
+    // keys in front of this tile: the totals of the tiles in front of it (<= 1024: one per thread; bid is blockIdx.x here)
+    const int before = block_base<1024>(p.cnt + p.n_keys1, 1, lds);
     const int64_t b = (int64_t)bid * kIdxScanTile + 4 * (int64_t)threadIdx.x;
     int v[4], sum = 0;
 #pragma unroll
@@ -671,6 +532,15 @@ static int pairs_job_check(const lgcn_pairs_job_t &q) {
     return LGCN_OK;
 }
 
+static PairsJob to_device_job(const lgcn_pairs_job_t &q) {
+    PairsJob d;
+    d.agt = (const float2 *)q.agt_ctrs; d.agt_off = q.agt_off;
+    d.ctx = (const float2 *)q.ctx_ctrs; d.ctx_off = q.ctx_off;
+    d.n_scenes = q.n_scenes; d.n_agt = (int)q.n_agt; d.n_ctx = (int)q.n_ctx; d.legacy = q.legacy_offsets; d.th = q.dist_th;
+    d.hi = q.hi; d.wi = q.wi; d.cap = q.cap; d.n_pairs = q.n_pairs; d.rowptr_q = q.rowptr; d.ws = q.ws;
+    return d;
+}
+
 int lgcn_pairs_build_multi(const lgcn_pairs_job_t *jobs, int n_jobs, void *stream) {
     if (n_jobs < 1 || n_jobs > 4) return LGCN_EINVAL;
     LGCN_CHECK_PTR(jobs);
@@ -681,11 +551,7 @@ int lgcn_pairs_build_multi(const lgcn_pairs_job_t *jobs, int n_jobs, void *strea
         const lgcn_pairs_job_t &q = jobs[k];
         const int rc = pairs_job_check(q);
         if (rc != LGCN_OK) return rc;
-        PairsJob &d = dj.j[k];
-        d.agt = (const float2 *)q.agt_ctrs; d.agt_off = q.agt_off;
-        d.ctx = (const float2 *)q.ctx_ctrs; d.ctx_off = q.ctx_off;
-        d.n_scenes = q.n_scenes; d.n_agt = (int)q.n_agt; d.n_ctx = (int)q.n_ctx; d.legacy = q.legacy_offsets; d.th = q.dist_th;
-        d.hi = q.hi; d.wi = q.wi; d.cap = q.cap; d.n_pairs = q.n_pairs; d.rowptr_q = q.rowptr; d.ws = q.ws;
+        dj.j[k] = to_device_job(q);
         if (q.n_agt > max_rows) max_rows = q.n_agt;
     }
     for (int k = n_jobs; k < 4; ++k) dj.j[k] = dj.j[0];
@@ -722,7 +588,7 @@ int lgcn_index_build(const lgcn_index_t *ph, void *stream) {
     if (q.n_rel < 1 || q.n_rel > LGCN_MAX_REL || q.n_nodes < 0 || q.n_seg < 1 || q.n_jobs < 0 || q.n_jobs > 4 || q.n_elem < 0)
         return LGCN_EINVAL;
     LGCN_CHECK_PTR(q.rowptr); LGCN_CHECK_PTR(q.cnt);
-    if (((uintptr_t)q.cnt & 7u) != 0) return LGCN_EALIGN;
+    if (misaligned(q.cnt, 7u)) return LGCN_EALIGN;
     if (q.n_jobs > 0) LGCN_CHECK_PTR(q.jobs);
     IndexParams p;
     p.idx_local = q.idx_local; p.seg_off = q.seg_off; p.seg_base = q.seg_base; p.n_seg = q.n_seg; p.n_rel = q.n_rel;
@@ -753,11 +619,7 @@ int lgcn_index_build(const lgcn_index_t *ph, void *stream) {
             const lgcn_pairs_job_t &jq = q.jobs[k];
             const int rc = pairs_job_check(jq);
             if (rc != LGCN_OK) return rc;
-            PairsJob &d = p.jobs.j[k];
-            d.agt = (const float2 *)jq.agt_ctrs; d.agt_off = jq.agt_off;
-            d.ctx = (const float2 *)jq.ctx_ctrs; d.ctx_off = jq.ctx_off;
-            d.n_scenes = jq.n_scenes; d.n_agt = (int)jq.n_agt; d.n_ctx = (int)jq.n_ctx; d.legacy = jq.legacy_offsets; d.th = jq.dist_th;
-            d.hi = jq.hi; d.wi = jq.wi; d.cap = jq.cap; d.n_pairs = jq.n_pairs; d.rowptr_q = jq.rowptr; d.ws = jq.ws;
+            p.jobs.j[k] = to_device_job(jq);
             p.job_blocks[k + 1] = p.job_blocks[k] + (int)((jq.n_agt + 3) / 4);
         } else {
             if (k > 0) p.jobs.j[k] = p.jobs.j[0];

@@ -3,8 +3,10 @@
 // -ffp-contract=off so that every distance is sub / mul / add / sqrt as numpy forms it.  See include/lgcn.h.
 //
 // Order never comes from an atomic: atomics here only count (integers), OR bits or take a minimum, whose results do not
-// depend on arrival order; the one cursor-style fill (k_roi_edge_fill_rows) is followed by a sort of every row.
+// depend on arrival order; the one cursor-style fill (k_roi_edge_fill_rows) is followed by a sort of every row.  The scans
+// (block-wide and device-wide) and the offset-table search are those of lgcn_blockscan.hpp.
 #include "lgcn_common.hpp"
+#include "lgcn_blockscan.hpp"
 
 namespace lgcn {
 
@@ -14,8 +16,6 @@ constexpr int kRoiMaxLevels = 4096;           // levels of one lane search (a cy
 constexpr int kRoiRel = 14;
 constexpr int kRoiSteps = 20;
 constexpr int kRoiThreads = 256;
-constexpr int kRoiScanItems = 4;
-constexpr int kRoiScanTile = 1024 * kRoiScanItems;
 constexpr int kStRange = 1, kStLevels = 2;
 constexpr int kRoiSumBlock = 128;             // numpy's PW_BLOCKSIZE: longer sums are split in halves
 constexpr int kRoiSumBuffer = 8192;           // numpy's default reduction buffer: longer sums go piece by piece
@@ -25,27 +25,24 @@ constexpr int kRoiSumDepth = 10;
 struct RoiWs {
     int32_t *cursor, *cnt, *sums, *lane_nodes, *node_rank, *col, *agent_lanes, *roi_lanes, *roi_lane_off;
     float *lane_len;
-    int64_t n_keys, n_scan, n_blocks, total;
+    int64_t n_keys, n_scan, total;
 };
-
-__host__ __device__ inline int64_t roi_up4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
 __host__ __device__ inline RoiWs roi_ws(int32_t *ws, int64_t N, int64_t L, int64_t E, int64_t slots, int64_t A) {
     RoiWs w;
     w.n_keys = kRoiRel * N;
     w.n_scan = w.n_keys + L + 1;
-    w.n_blocks = (w.n_scan + kRoiScanTile - 1) / kRoiScanTile;
     int64_t o = 0;
-    w.cursor = ws + o;       o += roi_up4(w.n_keys);
-    w.cnt = ws + o;          o += roi_up4(w.n_scan);
-    w.sums = ws + o;         o += roi_up4(w.n_blocks + 1);
-    w.lane_len = reinterpret_cast<float *>(ws + o); o += roi_up4(L);
-    w.lane_nodes = ws + o;   o += roi_up4(N);
-    w.node_rank = ws + o;    o += roi_up4(N);
-    w.col = ws + o;          o += roi_up4(E);
-    w.agent_lanes = ws + o;  o += roi_up4(A);
-    w.roi_lanes = ws + o;    o += roi_up4(slots);
-    w.roi_lane_off = ws + o; o += roi_up4(slots);
+    w.cursor = ws + o;       o += up4(w.n_keys);
+    w.cnt = ws + o;          o += up4(w.n_scan);
+    w.sums = ws + o;         o += up4(scan_ws_elems(w.n_scan));
+    w.lane_len = reinterpret_cast<float *>(ws + o); o += up4(L);
+    w.lane_nodes = ws + o;   o += up4(N);
+    w.node_rank = ws + o;    o += up4(N);
+    w.col = ws + o;          o += up4(E);
+    w.agent_lanes = ws + o;  o += up4(A);
+    w.roi_lanes = ws + o;    o += up4(slots);
+    w.roi_lane_off = ws + o; o += up4(slots);
     w.total = o;
     return w;
 }
@@ -65,74 +62,6 @@ __host__ __device__ inline RoiTabs roi_tabs(const int32_t *off, int S) {
     return t;
 }
 
-// largest s in [0, n) with tab[s] <= x (tab ascending, tab[0] = 0 <= x)
-__device__ __forceinline__ int roi_find_seg(const int32_t *tab, int n, int x) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid] <= x) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// Block-wide exclusive scan of one int per thread (blockDim.x a multiple of 64, <= 1024); lds [17].
-__device__ __forceinline__ int roi_wave_scan(int v, int lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(v, d, 64);
-        if (lane >= d) v += t;
-    }
-    return v;
-}
-__device__ __forceinline__ int roi_block_scan(int v, int *total, int *lds) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const int inc = roi_wave_scan(v, lane);
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    if (w == 0) {
-        const int t = lane < nw ? lds[lane] : 0;
-        const int run = roi_wave_scan(t, lane);
-        if (lane < nw) lds[lane] = run - t;
-        if (lane == nw - 1) lds[16] = run;
-    }
-    __syncthreads();
-    const int base = lds[w];
-    *total = lds[16];
-    __syncthreads();
-    return base + inc - v;
-}
-
-// ------------------------------------------------------------------ in-place exclusive scan (two launches)
-__global__ __launch_bounds__(1024) void k_roi_scan_blocks(int32_t *a, int32_t *sums, int64_t n) {
-    __shared__ int lds[17];
-    const int64_t base = (int64_t)blockIdx.x * kRoiScanTile + (int64_t)threadIdx.x * kRoiScanItems;
-    int v[kRoiScanItems], s = 0;
-#pragma unroll
-    for (int i = 0; i < kRoiScanItems; ++i) {
-        v[i] = base + i < n ? a[base + i] : 0;
-        s += v[i];
-    }
-    int total;
-    int pre = roi_block_scan(s, &total, lds);
-#pragma unroll
-    for (int i = 0; i < kRoiScanItems; ++i) {
-        if (base + i < n) a[base + i] = pre;
-        pre += v[i];
-    }
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void k_roi_scan_add(int32_t *a, const int32_t *sums, int64_t n) {
-    __shared__ int lds[17];
-    int part = 0;
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += 1024) part += sums[i];
-    int add;
-    roi_block_scan(part, &add, lds);
-    const int64_t base = (int64_t)blockIdx.x * kRoiScanTile + (int64_t)threadIdx.x * kRoiScanItems;
-#pragma unroll
-    for (int i = 0; i < kRoiScanItems; ++i)
-        if (base + i < n) a[base + i] += add;
-}
-
 // ------------------------------------------------------------------ lane tables
 // One thread per lane of the batch walks its scene's nodes (the loads are the same address across a scene's threads).
 __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_count(const lgcn_roi_t p, const RoiWs w) {
@@ -143,7 +72,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_count(const lgcn_roi_t
     }
     if (gl >= p.n_lanes) return;
     const RoiTabs t = roi_tabs(p.off_dev, p.n_scenes);
-    const int s = roi_find_seg(t.lane, p.n_scenes, gl);
+    const int s = find_seg(t.lane, p.n_scenes, gl);
     const int l = gl - t.lane[s];
     int c = 0;
     for (int i = t.node[s]; i < t.node[s + 1]; ++i) c += p.lane_idcs[i] == l;
@@ -226,7 +155,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_fill(const lgcn_roi_t 
     const int gl = blockIdx.x * kRoiThreads + threadIdx.x;
     if (gl >= p.n_lanes) return;
     const RoiTabs t = roi_tabs(p.off_dev, p.n_scenes);
-    const int s = roi_find_seg(t.lane, p.n_scenes, gl);
+    const int s = find_seg(t.lane, p.n_scenes, gl);
     const int l = gl - t.lane[s];
     const int32_t *lane_ptr = w.cnt + w.n_keys;
     const int base = lane_ptr[gl] - lane_ptr[0], end = lane_ptr[gl + 1] - lane_ptr[0];
@@ -249,7 +178,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_lane_fill(const lgcn_roi_t 
 // ------------------------------------------------------------------ the 14 relations as CSR rows (key = rel * N + node)
 __device__ __forceinline__ bool roi_edge_key(const lgcn_roi_t &p, const RoiTabs &t, int e, int *key, int *v_local) {
     const int S = p.n_scenes;
-    const int seg = roi_find_seg(t.edge, kRoiRel * S, e);
+    const int seg = find_seg(t.edge, kRoiRel * S, e);
     const int r = seg / S, s = seg - r * S;
     const int nn = t.node[s + 1] - t.node[s];
     const int u = p.edge_u[e], v = p.edge_v[e];
@@ -326,7 +255,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_search(const lgcn_roi_t p, 
     const int a = blockIdx.x, tid = threadIdx.x;
     const RoiTabs t = roi_tabs(p.off_dev, p.n_scenes);
     const int S = p.n_scenes;
-    const int s = roi_find_seg(t.agent, S, a);
+    const int s = find_seg(t.agent, S, a);
     const int nl = t.lane[s + 1] - t.lane[s], lb = t.lane[s];
     const int nb = t.node[s], nn = t.node[s + 1] - nb;
     const int W = (nl + 31) >> 5;
@@ -551,7 +480,7 @@ __device__ __forceinline__ RoiRef roi_ref(const lgcn_roi_t &p, const RoiWs &w, c
     q.a = p.roi_agent[r];
     q.ok = (unsigned)q.a < (unsigned)p.n_agents;
     if (!q.ok) return q;
-    q.s = roi_find_seg(t.agent, p.n_scenes, q.a);
+    q.s = find_seg(t.agent, p.n_scenes, q.a);
     q.nl = t.lane[q.s + 1] - t.lane[q.s];
     q.nb = t.node[q.s];
     q.nn = t.node[q.s + 1] - q.nb;
@@ -564,7 +493,7 @@ __device__ __forceinline__ RoiRef roi_ref(const lgcn_roi_t &p, const RoiWs &w, c
 }
 
 __global__ __launch_bounds__(kRoiThreads) void k_roi_nodes(const lgcn_roi_t p, const RoiWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kRoiThreads / 64 + 1];
     const int r = blockIdx.x, tid = threadIdx.x;
     const RoiTabs t = roi_tabs(p.off_dev, p.n_scenes);
     const RoiRef q = roi_ref(p, w, t, r);
@@ -586,7 +515,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_nodes(const lgcn_roi_t p, c
         if ((unsigned)l >= (unsigned)q.nl) l = -1;
         const int cnt = l >= 0 ? lane_ptr[l + 1] - lane_ptr[l] : 0;
         int total;
-        const int pre = roi_block_scan(cnt, &total, lds) + carry;
+        const int pre = block_exclusive_scan<kRoiThreads>(cnt, &total, lds) + carry;
         carry += total;
         if (l < 0) continue;
         w.roi_lane_off[q.slot + l] = pre;
@@ -658,7 +587,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_edge_count(const lgcn_roi_t
 }
 
 __global__ __launch_bounds__(kRoiThreads) void k_roi_edge_fill(const lgcn_roi_t p, const RoiWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kRoiThreads / 64 + 1];
     const int r = blockIdx.x / (kRoiRel + 1), rel = blockIdx.x % (kRoiRel + 1), tid = threadIdx.x;
     const RoiTabs t = roi_tabs(p.off_dev, p.n_scenes);
     const RoiRef q = roi_ref(p, w, t, r);
@@ -671,7 +600,7 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_edge_fill(const lgcn_roi_t 
         int c = 0;
         if (lu < q.n) c = rel == kRoiRel ? (p.near[q.base + lu] != 0) : roi_row(p, w, q, rel, lu, nullptr, 0);
         int total;
-        const int pre = roi_block_scan(c, &total, lds) + carry;
+        const int pre = block_exclusive_scan<kRoiThreads>(c, &total, lds) + carry;
         carry += total;
         if (c == 0 || (int64_t)pre + c > limit) continue;
         if (rel == kRoiRel) {
@@ -684,13 +613,6 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_edge_fill(const lgcn_roi_t 
 }
 
 // ------------------------------------------------------------------ host side
-static int roi_check_table(const int32_t *tab, int n, int64_t total) {
-    if (tab[0] != 0) return LGCN_EINVAL;
-    for (int i = 0; i < n; ++i)
-        if (tab[i + 1] < tab[i]) return LGCN_EINVAL;
-    return tab[n] == total ? LGCN_OK : LGCN_EINVAL;
-}
-
 // everything lgcn_roi_search reads; stage >= 2 adds the RoI tables, 3 the counts, 4 the edge outputs
 static int roi_validate(const lgcn_roi_t *p, int stage) {
     if (p == nullptr) return LGCN_EINVAL;
@@ -706,8 +628,8 @@ static int roi_validate(const lgcn_roi_t *p, int stage) {
     const int64_t totals[6] = {p->n_nodes, p->n_lanes, p->n_agents, p->n_slots, p->n_suc, p->n_pre};
     const int32_t *tabs[6] = {t.node, t.lane, t.agent, t.slot, t.suc, t.pre};
     for (int i = 0; i < 6; ++i)
-        if (int rc = roi_check_table(tabs[i], S, totals[i])) return rc;
-    if (int rc = roi_check_table(t.edge, kRoiRel * S, p->n_edges)) return rc;
+        if (int rc = check_table(tabs[i], S, totals[i])) return rc;
+    if (int rc = check_table(t.edge, kRoiRel * S, p->n_edges)) return rc;
     for (int s = 0; s < S; ++s) {
         const int64_t nl = t.lane[s + 1] - t.lane[s], na = t.agent[s + 1] - t.agent[s];
         if (nl > kRoiMaxLanes) return LGCN_ESHAPE;
@@ -741,10 +663,10 @@ static int roi_validate(const lgcn_roi_t *p, int stage) {
                            p->edge_u, p->edge_v, p->agent_nodes, p->agent_vel, p->roi_agent, p->roi_base, p->out_feats,
                            p->agent_feat, p->near, p->edge_cnt, p->edge_base, p->a2m_v};
     for (const void *q : words)
-        if (reinterpret_cast<uintptr_t>(q) & 3u) return LGCN_EALIGN;
+        if (misaligned(q, 3u)) return LGCN_EALIGN;
     const void *dwords[] = {p->node_mask, p->out_u, p->out_v};
     for (const void *q : dwords)
-        if (reinterpret_cast<uintptr_t>(q) & 7u) return LGCN_EALIGN;
+        if (misaligned(q, 7u)) return LGCN_EALIGN;
     return LGCN_OK;
 }
 
@@ -778,13 +700,12 @@ int lgcn_roi_search(const lgcn_roi_t *p, void *stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const RoiWs w = roi_ws(p->ws, p->n_nodes, p->n_lanes, p->n_edges, p->n_slots, p->n_agents);
     // cursor and the row counts are adjacent: one memset
-    if (hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * (size_t)(roi_up4(w.n_keys) + w.n_keys), st) != hipSuccess)
+    if (hipMemsetAsync(w.cursor, 0, sizeof(int32_t) * (size_t)(up4(w.n_keys) + w.n_keys), st) != hipSuccess)
         return launch_status();
     hipLaunchKernelGGL(k_roi_lane_count, dim3(roi_blocks(p->n_lanes + 1)), dim3(kRoiThreads), 0, st, *p, w);
     if (p->n_edges > 0)
         hipLaunchKernelGGL(k_roi_edge_rows, dim3(roi_blocks(p->n_edges)), dim3(kRoiThreads), 0, st, *p, w);
-    hipLaunchKernelGGL(k_roi_scan_blocks, dim3((unsigned)w.n_blocks), dim3(1024), 0, st, w.cnt, w.sums, w.n_scan);
-    hipLaunchKernelGGL(k_roi_scan_add, dim3((unsigned)w.n_blocks), dim3(1024), 0, st, w.cnt, w.sums, w.n_scan);
+    if (int rc = exclusive_scan(w.cnt, w.cnt, w.n_scan, w.sums, st)) return rc;
     if (p->n_lanes > 0)
         hipLaunchKernelGGL(k_roi_lane_fill, dim3(roi_blocks(p->n_lanes)), dim3(kRoiThreads), 0, st, *p, w);
     if (p->n_edges > 0) {

@@ -33,21 +33,21 @@ struct ScTrkWs {
 __host__ __device__ inline ScTrkWs sc_trk_ws(int32_t *ws, int64_t T) {
     ScTrkWs w;
     w.loc = ws;
-    w.keep = ws + sc_up4(T + 1);
-    w.sums = ws + 2 * sc_up4(T + 1);
+    w.keep = ws + up4(T + 1);
+    w.sums = ws + 2 * up4(T + 1);
     return w;
 }
 
 // One thread per track: which steps it holds, whether it is kept (step 19 present and inside pred_range), and the kept
 // tracks in front of it in its block.  keep word: 0 = dropped, else 1 + the first step of the run that ends at 19.
 __global__ __launch_bounds__(kScThreads) void k_scene_track_flag(const lgcn_scene_tracks_t p, const ScTrkWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int T = p.n_tracks, S = p.n_scenes;
     const int t = blockIdx.x * kScThreads + threadIdx.x;
     const int32_t *trk_off = p.off_dev, *row_off = p.off_dev + (S + 1);
     int v[1] = {0}, word = 0;
     if (t < T) {
-        const int s = sc_find_seg(trk_off, S, t);
+        const int s = find_seg(trk_off, S, t);
         unsigned long long mask = 0;
         bool dup = false;
         int r19 = -1;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kScThreads) void k_scene_track_flag(const lgcn_scen
 }
 
 __global__ __launch_bounds__(kScThreads) void k_scene_track_fill(const lgcn_scene_tracks_t p, const ScTrkWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int T = p.n_tracks, S = p.n_scenes;
     const int t = blockIdx.x * kScThreads + threadIdx.x;
     const int32_t *trk_off = p.off_dev, *row_off = p.off_dev + (S + 1);
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kScThreads) void k_scene_track_fill(const lgcn_scen
         p.head[S] = (int)o;
         return;
     }
-    const int s = sc_find_seg(trk_off, S, t);
+    const int s = find_seg(trk_off, S, t);
     if (t == trk_off[s]) p.head[s] = (int)o;
     const int word = w.keep[t];
     if (word == 0 || o >= T) return;
@@ -160,14 +160,14 @@ struct ScLaneWs {
 __host__ __device__ inline ScLaneWs sc_lane_ws(int32_t *ws, int64_t n_cand, int64_t n_rank) {
     ScLaneWs w;
     int64_t o = 0;
-    w.rank_of = ws + o; o += sc_up4(n_rank);
-    w.node_of = ws + o; o += sc_up4(n_rank);
-    w.keep = ws + o;    o += sc_up4(n_cand + 1);
-    w.loc = ws + o;     o += 4 * sc_up4(n_cand + 1);
-    w.glob = ws + o;    o += 4 * sc_up4(n_cand + 1);
-    w.loc2 = ws + o;    o += 4 * sc_up4(n_cand + 1);
-    w.sums = ws + o;    o += 4 * sc_up4(sc_blocks(n_cand + 1));
-    w.sums2 = ws + o;   o += 4 * sc_up4(sc_blocks(n_cand + 1));
+    w.rank_of = ws + o; o += up4(n_rank);
+    w.node_of = ws + o; o += up4(n_rank);
+    w.keep = ws + o;    o += up4(n_cand + 1);
+    w.loc = ws + o;     o += 4 * up4(n_cand + 1);
+    w.glob = ws + o;    o += 4 * up4(n_cand + 1);
+    w.loc2 = ws + o;    o += 4 * up4(n_cand + 1);
+    w.sums = ws + o;    o += 4 * up4(sc_blocks(n_cand + 1));
+    w.sums2 = ws + o;   o += 4 * up4(sc_blocks(n_cand + 1));
     w.total = o;
     return w;
 }
@@ -191,7 +191,7 @@ struct ScCand {
 };
 __device__ __forceinline__ ScCand sc_cand(const lgcn_scene_lanes_t &p, const ScTabs &t, int c) {
     ScCand q;
-    q.s = sc_find_seg(t.cand_off, p.n_scenes, c);
+    q.s = find_seg(t.cand_off, p.n_scenes, c);
     const lgcn_lane_table_t *tb = p.tabs_dev + t.scene_tab[q.s];
     q.lane = p.explicit_ids ? t.cand[c] : c - t.cand_off[q.s];
     q.tp = sc_topo(tb->topo_dev, tb->n_lanes, tb->n_pred);
@@ -205,7 +205,7 @@ __device__ __forceinline__ ScCand sc_cand(const lgcn_scene_lanes_t &p, const ScT
 // One thread per candidate lane: its extent in the scene frame against the pred_range rectangle (data.py:231-233), and
 // the block-local scans of (kept lanes, their nodes, their predecessor and successor entries).
 __global__ __launch_bounds__(kScThreads) void k_scene_lane_flag(const lgcn_scene_lanes_t p, const ScLaneWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int c = blockIdx.x * kScThreads + threadIdx.x;
     const ScTabs t = sc_tabs(p.off_dev, p.n_scenes);
     int v[4] = {0, 0, 0, 0};
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(kScThreads) void k_scene_lane_flag(const lgcn_scene
 
 // The scans made global; every kept lane's rank and first node by table row; per scene the offsets for the host.
 __global__ __launch_bounds__(kScThreads) void k_scene_lane_rank(const lgcn_scene_lanes_t p, const ScLaneWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int c = blockIdx.x * kScThreads + threadIdx.x;
     const ScTabs t = sc_tabs(p.off_dev, p.n_scenes);
     int base[4];
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kScThreads) void k_scene_lane_rank(const lgcn_scene
 
 // kept predecessors / successors / left / right of every kept lane: a read of the rank array per neighbour
 __global__ __launch_bounds__(kScThreads) void k_scene_lane_count(const lgcn_scene_lanes_t p, const ScLaneWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int c = blockIdx.x * kScThreads + threadIdx.x;
     const ScTabs t = sc_tabs(p.off_dev, p.n_scenes);
     int v[4] = {0, 0, 0, 0};
@@ -297,7 +297,7 @@ __global__ __launch_bounds__(kScThreads) void k_scene_lane_count(const lgcn_scen
 }
 
 __global__ __launch_bounds__(kScThreads) void k_scene_lane_fill(const lgcn_scene_lanes_t p, const ScLaneWs w) {
-    __shared__ int lds[17];
+    __shared__ int lds[kScThreads / 64 + 1];
     const int c = blockIdx.x * kScThreads + threadIdx.x;
     const ScTabs t = sc_tabs(p.off_dev, p.n_scenes);
     int base[4];
@@ -410,8 +410,8 @@ static int sc_tracks_validate(const lgcn_scene_tracks_t *p) {
     if (p->n_tracks > 0x7fffffff / 64 || p->n_scenes > 0x7fffffff / 16) return LGCN_ESHAPE;
     LGCN_CHECK_PTR(p->off_host);
     const int32_t *trk_off = p->off_host, *row_off = p->off_host + (p->n_scenes + 1);
-    if (int rc = sc_check_table(trk_off, p->n_scenes, p->n_tracks)) return rc;
-    if (int rc = sc_check_table(row_off, p->n_tracks, p->n_rows)) return rc;
+    if (int rc = check_table(trk_off, p->n_scenes, p->n_tracks)) return rc;
+    if (int rc = check_table(row_off, p->n_tracks, p->n_rows)) return rc;
     for (int s = 0; s < p->n_scenes; ++s)
         if (trk_off[s + 1] == trk_off[s]) return LGCN_EINVAL;          // every scene holds its agent
     LGCN_CHECK_PTR(p->off_dev); LGCN_CHECK_PTR(p->frame); LGCN_CHECK_PTR(p->ws); LGCN_CHECK_PTR(p->head);
@@ -420,7 +420,7 @@ static int sc_tracks_validate(const lgcn_scene_tracks_t *p) {
     LGCN_CHECK_ALIGN16(p->xy); LGCN_CHECK_ALIGN16(p->ws);
     const void *words[] = {p->off_dev, p->step, p->frame, p->head, p->feats, p->obs, p->ctrs, p->gt};
     for (const void *q : words)
-        if (sc_misaligned(q, 3u)) return LGCN_EALIGN;
+        if (misaligned(q, 3u)) return LGCN_EALIGN;
     return LGCN_OK;
 }
 
@@ -430,12 +430,12 @@ static int sc_table_validate(const lgcn_lane_table_t *tb) {
     LGCN_CHECK_PTR(tb->topo_host); LGCN_CHECK_PTR(tb->topo_dev);
     if (tb->n_pts > 0) LGCN_CHECK_PTR(tb->pts);
     LGCN_CHECK_ALIGN16(tb->pts);
-    if (sc_misaligned(tb->topo_dev, 3u) || sc_misaligned(tb->topo_host, 3u)) return LGCN_EALIGN;
+    if (misaligned(tb->topo_dev, 3u) || misaligned(tb->topo_host, 3u)) return LGCN_EALIGN;
     const int L = tb->n_lanes;
     const ScTopo tp = sc_topo(tb->topo_host, L, tb->n_pred);
-    if (int rc = sc_check_table(tp.pt_off, L, tb->n_pts)) return rc;
-    if (int rc = sc_check_table(tp.pred_off, L, tb->n_pred)) return rc;
-    if (int rc = sc_check_table(tp.succ_off, L, tb->n_succ)) return rc;
+    if (int rc = check_table(tp.pt_off, L, tb->n_pts)) return rc;
+    if (int rc = check_table(tp.pred_off, L, tb->n_pred)) return rc;
+    if (int rc = check_table(tp.succ_off, L, tb->n_succ)) return rc;
     for (int l = 0; l < L; ++l) {
         if (tp.pt_off[l + 1] - tp.pt_off[l] < 2) return LGCN_EINVAL;
         if (tp.left[l] < -1 || tp.left[l] >= L || tp.right[l] < -1 || tp.right[l] >= L) return LGCN_EINVAL;
@@ -464,8 +464,8 @@ static int sc_lanes_validate(const lgcn_scene_lanes_t *p, int stage) {
         if (int rc = sc_table_validate(p->tabs_host + i)) return rc;
     const int S = p->n_scenes;
     const ScTabs t = sc_tabs(p->off_host, S);
-    if (int rc = sc_check_table(t.cand_off, S, p->n_cand)) return rc;
-    if (int rc = sc_check_table(t.rank_off, S, p->n_rank)) return rc;
+    if (int rc = check_table(t.cand_off, S, p->n_cand)) return rc;
+    if (int rc = check_table(t.rank_off, S, p->n_rank)) return rc;
     int64_t most = 0;      // what the int32 scans can reach at most: every point and neighbour entry of every scene's table
     for (int s = 0; s < S; ++s) {
         if (t.scene_tab[s] < 0 || t.scene_tab[s] >= p->n_tables) return LGCN_EINVAL;
@@ -484,8 +484,8 @@ static int sc_lanes_validate(const lgcn_scene_lanes_t *p, int stage) {
         }
     }
     LGCN_CHECK_ALIGN16(p->ws);
-    if (sc_misaligned(p->tabs_dev, 7u) || sc_misaligned(p->off_dev, 3u) || sc_misaligned(p->frame, 3u) ||
-        sc_misaligned(p->head, 3u))
+    if (misaligned(p->tabs_dev, 7u) || misaligned(p->off_dev, 3u) || misaligned(p->frame, 3u) ||
+        misaligned(p->head, 3u))
         return LGCN_EALIGN;
     if (stage < 2) return LGCN_OK;
     if (p->n_nodes < 0 || p->cap_pre < 0 || p->cap_suc < 0 || p->cap_pre_pairs < 0 || p->cap_suc_pairs < 0 ||
@@ -504,11 +504,11 @@ static int sc_lanes_validate(const lgcn_scene_lanes_t *p, int stage) {
     if (p->cap_right_pairs > 0) LGCN_CHECK_PTR(p->right_pairs);
     const void *words[] = {p->head2, p->ctrs, p->feats, p->turn, p->control, p->intersect};
     for (const void *q : words)
-        if (sc_misaligned(q, 3u)) return LGCN_EALIGN;
+        if (misaligned(q, 3u)) return LGCN_EALIGN;
     const void *dwords[] = {p->lane_idcs, p->pre_u, p->pre_v, p->suc_u, p->suc_v, p->pre_pairs, p->suc_pairs, p->left_pairs,
                             p->right_pairs};
     for (const void *q : dwords)
-        if (sc_misaligned(q, 7u)) return LGCN_EALIGN;
+        if (misaligned(q, 7u)) return LGCN_EALIGN;
     return LGCN_OK;
 }
 
@@ -521,7 +521,7 @@ extern "C" {
 int64_t lgcn_scene_tracks_ws_elems(int64_t n_tracks) {
     if (n_tracks < 0) return LGCN_EINVAL;
     if (n_tracks > 0x7fffffff / 64) return LGCN_ESHAPE;
-    return 2 * sc_up4(n_tracks + 1) + sc_up4(sc_blocks(n_tracks + 1));
+    return 2 * up4(n_tracks + 1) + up4(sc_blocks(n_tracks + 1));
 }
 
 int lgcn_scene_tracks(const lgcn_scene_tracks_t *p, void *stream) {
@@ -555,7 +555,7 @@ int lgcn_scene_lanes_rank(const lgcn_scene_lanes_t *p, void *stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const ScLaneWs w = sc_lane_ws(p->ws, p->n_cand, p->n_rank);
     if (p->n_rank > 0 &&       // rank_of and node_of are adjacent: one memset to -1
-        hipMemsetAsync(w.rank_of, 0xff, sizeof(int32_t) * (size_t)(2 * sc_up4(p->n_rank)), st) != hipSuccess)
+        hipMemsetAsync(w.rank_of, 0xff, sizeof(int32_t) * (size_t)(2 * up4(p->n_rank)), st) != hipSuccess)
         return launch_status();
     const dim3 grid((unsigned)sc_blocks((int64_t)p->n_cand + 1));
     hipLaunchKernelGGL(k_scene_lane_flag, grid, dim3(kScThreads), 0, st, *p, w);

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "lgcn_common.hpp"
+#include "lgcn_blockscan.hpp"
 
 namespace lgcn {
 
@@ -50,16 +51,6 @@ struct StoreGrid {
     uint32_t first[6];
 };
 
-// last k in [0, n) with off[k] <= x, for off[0] = 0 <= x < off[n]: empty runs (off[k] == off[k + 1]) are skipped
-__device__ __forceinline__ int store_find(const int64_t *__restrict__ off, int n, int64_t x) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (off[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // one picked scene's entry of the augmentation table: Rm row-major, then rot' row-major (include/lgcn.h)
 struct StoreAug {
     float4 rm, rot;
@@ -85,7 +76,7 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
 
     if (kind == 0) {                      // one node row: ctrs, feats, turn [.,2], control, intersect
         if (i >= b.n_nodes) return;
-        const int j = store_find(t.node_off, B, i);
+        const int j = find_seg(t.node_off, B, i);
         const int64_t r = t.node_src[j] + (i - t.node_off[j]);
         if constexpr (AUG) {
             const float4 rm = aug[j].rm;
@@ -100,7 +91,7 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         b.intersect[i] = s.intersect[r];
     } else if (kind == 1) {               // one actor: ctrs, and the scene's rot / orig
         if (i >= b.n_actors) return;
-        const int j = store_find(t.actor_off, B, i);
+        const int j = find_seg(t.actor_off, B, i);
         const int64_t r = t.actor_src[j] + (i - t.actor_off[j]);
         const int64_t sc = t.scene[j];
         if constexpr (AUG) {
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         if (i >= b.n_actors * kActorRow) return;
         const int64_t a = i / kActorRow;
         const int e = (int)(i - a * kActorRow);
-        const int j = store_find(t.actor_off, B, a);
+        const int j = find_seg(t.actor_off, B, a);
         const int64_t r = t.actor_src[j] + (a - t.actor_off[j]);
         const int c = e / 20, step = e - c * 20;
         if (AUG && c < 2) {                // channels 0 / 1 are the step's (x, y): both are read, one component is written
@@ -131,7 +122,7 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         }
     } else if (kind == 3) {               // one element of idx_local, widened
         if (i >= b.n_elem) return;
-        const int64_t k = store_find(t.seg_off, (int)G, i);
+        const int64_t k = find_seg(t.seg_off, (int)G, i);
         const int64_t r = t.seg_src[k] + (i - t.seg_off[k]);
         const int32_t *src = ((k / B) & 1) ? s.edge_v : s.edge_u;     // segment k = (relation * 2 + u|v) * B + scene
         b.idx_local[i] = (int64_t)src[r];
@@ -176,7 +167,7 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_pack(const lgcn_store_p
         const int64_t i = (int64_t)blk * kStoreThreads + threadIdx.x;
         if (i >= p.n_dst) return;
         const PackTab t = pack_tab(p.tab_dev, p.n_seg, p.n_src);
-        const int k = store_find(t.seg_off, (int)p.n_seg, i);
+        const int k = find_seg(t.seg_off, (int)p.n_seg, i);
         const int64_t s = t.seg_src[k];
         const int64_t r = t.seg_at[k] + (i - t.seg_off[k]);
         const int64_t kind = t.src_kind[s];
@@ -254,8 +245,8 @@ static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, St
     const void *words[] = {s->control, s->intersect, s->actor_feats, s->gt_preds, s->edge_u, s->edge_v, b->control,
                            b->intersect, b->node_off, b->actor_off, b->actor_feats, b->gt_preds};
     for (const void *q : words)
-        if (reinterpret_cast<uintptr_t>(q) & 3u) return LGCN_EALIGN;
-    if (reinterpret_cast<uintptr_t>(b->tab_host) & 7u) return LGCN_EALIGN;
+        if (misaligned(q, 3u)) return LGCN_EALIGN;
+    if (misaligned(b->tab_host, 7u)) return LGCN_EALIGN;
 
     const int64_t items[5] = {b->n_nodes, b->n_actors, b->n_actors * kActorRow, b->n_elem, 2 * (B + 1) + 2 * G + 1};
     int64_t at = 0;
@@ -278,11 +269,11 @@ static int pack_validate(const lgcn_store_pack_t *p, uint32_t *frame_first, uint
     LGCN_CHECK_PTR(p->tab_host); LGCN_CHECK_PTR(p->tab_dev);
     if (p->n_dst > 0) LGCN_CHECK_PTR(p->dst);
     if (p->n_scenes > 0) { LGCN_CHECK_PTR(p->frame); LGCN_CHECK_PTR(p->rot); LGCN_CHECK_PTR(p->orig); }
-    if (reinterpret_cast<uintptr_t>(p->tab_host) & 7u) return LGCN_EALIGN;
+    if (misaligned(p->tab_host, 7u)) return LGCN_EALIGN;
     LGCN_CHECK_ALIGN16(p->tab_dev);
     LGCN_CHECK_ALIGN16(p->rot);
-    if ((reinterpret_cast<uintptr_t>(p->frame) & 7u) || (reinterpret_cast<uintptr_t>(p->orig) & 7u)) return LGCN_EALIGN;
-    if (reinterpret_cast<uintptr_t>(p->dst) & 3u) return LGCN_EALIGN;
+    if (misaligned(p->frame, 7u) || misaligned(p->orig, 7u)) return LGCN_EALIGN;
+    if (misaligned(p->dst, 3u)) return LGCN_EALIGN;
 
     const PackTab t = pack_tab(p->tab_host, p->n_seg, p->n_src);
     for (int64_t s = 0; s < p->n_src; ++s) {

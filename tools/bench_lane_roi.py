@@ -18,8 +18,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-# lgcn_roi_search: 1 memset + 8 kernels; lgcn_roi_nodes, lgcn_roi_edge_count, lgcn_roi_edge_fill: 1 kernel each; two
-# zero fills (the status / count buffer, a2m.u)
+# lgcn_roi_search: 1 memset + 8 kernels (7 where one scan tile holds every row count: not at these sizes); lgcn_roi_nodes,
+# lgcn_roi_edge_count, lgcn_roi_edge_fill: 1 kernel each; two zero fills (the status / count buffer, a2m.u)
 DEVICE_OPS = {"kernels": 11, "memsets": 1, "fills": 2, "size_readbacks": 2}
 
 

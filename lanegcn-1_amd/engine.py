@@ -182,6 +182,10 @@ def host_actor_inputs(scenes):
     return t(feats), t(rot), t(orig), [len(s["ctrs"]) for s in scenes]
 
 
+# stage name -> the state key of its output (forward(stages=True) returns them under the stage's name)
+_STAGE_OUT = {"map_net": "nodes", "a2m": "nodes_a2m", "m2m": "nodes_m2m", "m2a": "actors_m2a", "a2a": "actors_a2a"}
+
+
 class HotPathEngine:
     """graph_gather -> MapNet -> A2M -> M2M -> M2A -> A2A on the HIP kernels, sync-free."""
 
@@ -204,10 +208,10 @@ class HotPathEngine:
         # Pair capacities (rows of hi / wi and of every [cap, 128] pair-row buffer of a forward).  "bound": sum_i t_i s_i,
         # can never overflow (265 MB of pair rows per A2M layer at S2, untouched but reserved).  "tight" (default):
         # 1.25 x the largest pair count this engine has seen per set, at least 4,096 (the bound until a count is known)
-        # -- learnt by capture() from its eager warm-up forwards (one host read each) and by forward_guarded() /
-        # Net.forward's host read; a forward whose count exceeds it comes back with a negative n_pairs (the kernels keep
-        # to the capacity), learn_pair_counts(out) says so and grows the capacity, the caller runs again; a captured
-        # graph has to be captured again.
+        # -- learnt by capture() from its eager warm-up forwards (one host read each) and by host_checks() behind
+        # forward_guarded() / Net.forward; a forward whose count exceeds it comes back with a negative n_pairs (the
+        # kernels keep to the capacity), learn_pair_counts(out) says so and grows the capacity, the caller runs again;
+        # a captured graph has to be captured again.
         self.pair_caps = os.environ.get("LGCN_PAIR_CAPS", "tight")
         self._pair_seen = [0, 0, 0]
 
@@ -229,181 +233,173 @@ class HotPathEngine:
         """actors: [A,128] ActorNet output.  Returns {"nodes", "actors"} (+ every stage if stages).
         mapnet_only: stop after MapNet (BASELINE config "MapNet LaneConv only"): graph_gather + plan + MapNet."""
         if mapnet_only:
-            g64, _ = ops.graph_gather_indices(fb.idx_local, fb.seg_off, fb.seg_base)
-            plan = ops.csr_build([g64[a:b] for (a, b), _ in fb.rel_slices], [g64[a:b] for _, (a, b) in fb.rel_slices],
-                                 fb.n_nodes)
-            feat = M.lane_conv(self.map_net.fuse, self.map_net.stem(fb.node_ctrs, fb.node_feats), plan, fb.num_scales,
-                               impl=self.lane_impl)
-            return {"nodes": feat, "actors": actors}
-        cfg = self.config
+            st, fns = self.stage_functions(fb, actors, plan_only=True)
+            for _, fn in fns[:2]:
+                fn()
+            return {"nodes": st["nodes"], "actors": actors}
+        if self.branches and self._side is None:
+            self._side = torch.cuda.Stream()
+        st, fns = self.stage_functions(fb, actors, tight=True, counters=self._counters, guard=True,
+                                       side=self._side if self.branches else None)
         out = {}
-        main = torch.cuda.current_stream()
-        side = None
-        if self.branches:
-            if self._side is None:
-                self._side = torch.cuda.Stream()
-            side = self._side
+        for name, fn in fns:
+            fn()
+            if stages and name in _STAGE_OUT:
+                out[name] = st[_STAGE_OUT[name]]
+        out["nodes"], out["actors"] = st["nodes_m2m"], st["actors_a2a"]
+        out["n_pairs"] = [p.n_pairs for p in st["pairs"]]
+        # range check of the 16-bit-plane modes, on the device and part of every (captured) forward: bit 0 of
+        # out["nonfinite"] is set when a feature row came out NaN / inf (ops.guarded / host_checks act on it)
+        ops.check_finite(st["flag"], out["nodes"], out["actors"])
+        out["nonfinite"] = st["flag"]
+        return out
+
+    @torch.no_grad()
+    def stage_functions(self, fb: FlatBatch, actors: torch.Tensor, tight: bool = False, counters=None,
+                        guard: bool = False, side: Optional[torch.cuda.Stream] = None, plan_only: bool = False):
+        """The forward cut at the reference's module boundaries: returns (state, [(name, fn)]); fn() runs one stage on
+        the tensors the previous stages left in `state`.  forward() runs them in order; called as (fb, actors) they are
+        what a per-stage measurement captures (run them in order once before capturing any of them in a graph): pair
+        buffers of the bound capacities and key counters of the stages' own (state["_cnt"]: a stage's captured graph is
+        replayed alone).  forward()'s arguments -- tight: pair buffers of the tight capacities; counters: fb -> the
+        key-counter buffer; guard: state["flag"], the range guard's word, cleared by the index stage; side: the stream
+        of the parallel branches; plan_only: the index stage builds the CSR plan alone (mapnet_only)."""
+        cfg, st = self.config, {}
         dev = fb.node_ctrs.device
+        main = torch.cuda.current_stream() if side is not None else None
         searches = ((fb.node_ctrs, fb.node_off, fb.actor_ctrs, fb.actor_off, cfg["actor2map_dist"], fb.cap_a2m),
                     (fb.actor_ctrs, fb.actor_off, fb.node_ctrs, fb.node_off, cfg["map2actor_dist"], fb.cap_a2m),
                     (fb.actor_ctrs, fb.actor_off, fb.actor_ctrs, fb.actor_off, cfg["actor2actor_dist"], fb.cap_a2a))
-        if self.pair_caps == "tight":      # nothing seen yet for a set: the bound (the first forward cannot overflow)
+        if tight and self.pair_caps == "tight":      # nothing seen yet for a set: the bound (the first forward cannot overflow)
             searches = tuple(s[:5] + (min(s[5], self._cap(i)) if self._pair_seen[i] > 0 else s[5],) for i, s in enumerate(searches))
-        bufs = [ops.pairs_alloc(s[0].shape[0], fb.n_scenes, s[5], dev) for s in searches]   # on the main stream
-        if side is not None:
-            side.wait_stream(main)
-        if side is None and ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
-            # graph_gather (lanegcn.py:171-209) + CSR plan + the three pair searches: four launches in all
-            flag = torch.empty(1, dtype=torch.int32, device=dev)       # the range guard's flag, cleared by the first launch
-            plan, pairs = ops.index_build(fb.idx_local, fb.seg_off, fb.seg_base, fb.rel_slices, fb.n_nodes, searches,
-                                          self.legacy_offsets, bufs=bufs, cnt=self._counters(fb), clear_word=flag)
-        else:
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            with torch.cuda.stream(side if side is not None else main):
-                pairs = ops.pairs_build_multi(searches, self.legacy_offsets, bufs=bufs)   # three sets, three launches
-            g64, _ = ops.graph_gather_indices(fb.idx_local, fb.seg_off, fb.seg_base)
-            us = [g64[a:b] for (a, b), _ in fb.rel_slices]
-            vs = [g64[a:b] for _, (a, b) in fb.rel_slices]
-            plan = ops.csr_build(us, vs, fb.n_nodes)
-        # MapNet (lanegcn.py:311-363)
-        feat = self.map_net.stem(fb.node_ctrs, fb.node_feats)
-        feat = M.lane_conv(self.map_net.fuse, feat, plan, fb.num_scales, impl=self.lane_impl)
-        if stages:
-            out["map_net"] = feat
-        # A2M (lanegcn.py:385-407)
+        # launches folded across the Att layers of the three blocks (lanegcn.att_block): 7 row-block launches + M2A's
+        # ctx-heads; one rule for the whole pipeline
         fold = side is None and M._fold_ok(actors) and fb.n_nodes > 0
-        if fold:      # launches folded across the Att layers of the three blocks (lanegcn.att_block): 7 row-block launches + M2A's ctx-heads
-            # M2A's U of layer 0 depends on `actors` alone: it rides in A2M's first launch, off M2A's critical path
-            feat, u_m2a = self.a2m.run(feat, fb.turn, fb.control, fb.intersect, actors, pairs[0],
-                                       extra=self.m2a.att[0].u_kw(actors))
-        else:
-            feat = self.a2m.fuse_meta(feat, fb.turn, fb.control, fb.intersect)
+
+        def index():
+            if plan_only:
+                return gather_plan()
+            bufs = [ops.pairs_alloc(s[0].shape[0], fb.n_scenes, s[5], dev) for s in searches]   # on the main stream
+            if side is not None:
+                side.wait_stream(main)
+            if side is None and ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
+                # graph_gather (lanegcn.py:171-209) + CSR plan + the three pair searches: four launches in all
+                if guard:
+                    st["flag"] = torch.empty(1, dtype=torch.int32, device=dev)      # cleared by the first launch
+                cnt = counters(fb) if counters is not None else st.get("_cnt")
+                if cnt is None:
+                    cnt = st["_cnt"] = ops.index_counters(fb.n_nodes, len(fb.rel_slices), dev)
+                st["plan"], st["pairs"] = ops.index_build(fb.idx_local, fb.seg_off, fb.seg_base, fb.rel_slices, fb.n_nodes,
+                                                          searches, self.legacy_offsets, bufs=bufs, cnt=cnt,
+                                                          clear_word=st.get("flag"))
+                return
+            if guard:
+                st["flag"] = torch.zeros(1, dtype=torch.int32, device=dev)
+            with torch.cuda.stream(side):      # (None: the current stream)
+                st["pairs"] = ops.pairs_build_multi(searches, self.legacy_offsets, bufs=bufs)   # three sets, three launches
+            gather_plan()
+
+        def gather_plan():
+            g64, _ = ops.graph_gather_indices(fb.idx_local, fb.seg_off, fb.seg_base)
+            st["plan"] = ops.csr_build([g64[a:b] for (a, b), _ in fb.rel_slices],
+                                       [g64[a:b] for _, (a, b) in fb.rel_slices], fb.n_nodes)
+
+        def lane(fuse, feat):
+            return M.lane_conv(fuse, feat, st["plan"], fb.num_scales, impl=self.lane_impl)
+
+        def layers(atts, act, ctx, ps):      # the per-layer route; ctx None: the targets are their own context (A2A)
+            for att in atts:
+                act = att.run(act, act if ctx is None else ctx, ps, side)
+            return act
+
+        def map_net():      # lanegcn.py:311-363
+            st["nodes"] = lane(self.map_net.fuse, self.map_net.stem(fb.node_ctrs, fb.node_feats))
+
+        def a2m():      # lanegcn.py:385-407
+            if fold:      # M2A's U of layer 0 depends on `actors` alone: it rides in A2M's first launch, off M2A's critical path
+                st["nodes_a2m"], st["u_m2a"] = self.a2m.run(st["nodes"], fb.turn, fb.control, fb.intersect, actors,
+                                                            st["pairs"][0], extra=self.m2a.att[0].u_kw(actors))
+                return
+            feat = self.a2m.fuse_meta(st["nodes"], fb.turn, fb.control, fb.intersect)
             if side is not None:
                 main.wait_stream(side)            # the pair sets are needed from here on
-            for att in self.a2m.att:
-                feat = att.run(feat, actors, pairs[0], side)
-        if stages:
-            out["a2m"] = feat
-        # M2M (lanegcn.py:445-480)
-        feat = M.lane_conv(self.m2m.fuse, feat, plan, fb.num_scales, impl=self.lane_impl)
-        if stages:
-            out["m2m"] = feat
-        # M2A (lanegcn.py:502-513)
-        act = actors
-        if fold:
-            # M2A's last tail also emits U / V of A2A's first layer (its targets and context are M2A's output rows)
-            # (it starts with the V rows of both layers: one weight-stationary launch over the lane nodes)
-            act, uv = M.att_block(self.m2a.att, act, feat, pairs[1], next_att=self.a2a.att[0], next_ctx_is_out=True, u0=u_m2a)
-            if stages:
-                out["m2a"] = act
-            act, _ = M.att_block(self.a2a.att, act, act, pairs[2], uv=uv, ctx_is_agts=True)
-        else:
-            for att in self.m2a.att:
-                act = att.run(act, feat, pairs[1], side)
-            if stages:
-                out["m2a"] = act
-            # A2A (lanegcn.py:534-545)
-            for att in self.a2a.att:
-                act = att.run(act, act, pairs[2], side)
-        if stages:
-            out["a2a"] = act
-        out["nodes"], out["actors"] = feat, act
-        out["n_pairs"] = [p.n_pairs for p in pairs]
-        # range check of the 16-bit-plane modes, on the device and part of every (captured) forward: bit 0 of
-        # out["nonfinite"] is set when a feature row came out NaN / inf (ops.guarded / forward_guarded act on it)
-        ops.check_finite(flag, feat, act)
-        out["nonfinite"] = flag
-        return out
+            st["nodes_a2m"], st["u_m2a"] = layers(self.a2m.att, feat, actors, st["pairs"][0]), None
+
+        def m2m():      # lanegcn.py:445-480
+            st["nodes_m2m"] = lane(self.m2m.fuse, st["nodes_a2m"])
+
+        def m2a():      # lanegcn.py:502-513
+            if fold:
+                # M2A's last tail also emits U / V of A2A's first layer (its targets and context are M2A's output rows)
+                # (it starts with the V rows of both layers: one weight-stationary launch over the lane nodes)
+                st["actors_m2a"], st["uv_a2a"] = M.att_block(self.m2a.att, actors, st["nodes_m2m"], st["pairs"][1],
+                                                             next_att=self.a2a.att[0], next_ctx_is_out=True, u0=st["u_m2a"])
+                return
+            st["actors_m2a"], st["uv_a2a"] = layers(self.m2a.att, actors, st["nodes_m2m"], st["pairs"][1]), None
+
+        def a2a():      # lanegcn.py:534-545
+            act = st["actors_m2a"]
+            if fold:
+                st["actors_a2a"] = M.att_block(self.a2a.att, act, act, st["pairs"][2], uv=st["uv_a2a"], ctx_is_agts=True)[0]
+                return
+            st["actors_a2a"] = layers(self.a2a.att, act, None, st["pairs"][2])
+
+        return st, [("index", index), ("map_net", map_net), ("a2m", a2m), ("m2m", m2m), ("m2a", m2a), ("a2a", a2a)]
 
     def _cap(self, i: int) -> int:
         """Tight capacity of pair set i (A2M, M2A, A2A): 1.25 x the largest count seen, at least 4,096, in 1,024s."""
         want = max(4096, int(self._pair_seen[i] * 1.25) + 1)
         return (want + 1023) // 1024 * 1024
 
-    def learn_pair_counts(self, out: Dict[str, torch.Tensor]) -> bool:
-        """Host side of the tight pair capacities: reads the forward's three pair counts (one device->host copy), keeps
-        the largest per set; True when a count exceeded its capacity (negative n_pairs: the forward's features are
-        those of a truncated pair set and must be recomputed with the grown capacity)."""
-        counts = torch.stack([c.view(()) for c in out["n_pairs"]]).tolist()
+    def _record(self, counts) -> bool:
+        """Keep the largest magnitude per pair set; True when a count is negative (its capacity was exceeded)."""
         over = False
         for i, c in enumerate(counts):
             over = over or c < 0
             self._pair_seen[i] = max(self._pair_seen[i], abs(int(c)))
         return over
 
-    def forward_guarded(self, fb: FlatBatch, actors: torch.Tensor, **kw) -> Dict[str, torch.Tensor]:
-        """forward() + the host side of the range guard: reads the flag (one 4-byte device->host copy) and re-runs an
-        f16x2 forward that left fp16's range in bf16x3, or raises, as ops.set_guard() says.  With tight pair capacities
-        it also reads the pair counts and re-runs a forward that overflowed them."""
-        out = self.forward(fb, actors, **kw)
-        if self.pair_caps == "tight" and not kw.get("mapnet_only") and self.learn_pair_counts(out):
-            out = self.forward(fb, actors, **kw)
-            if self.learn_pair_counts(out):
-                raise ops.L.LgcnError("pair capacity still exceeded after growing it")
-        if ops.get_guard() == "off" or ops.get_mma() != "f16x2" or int(out["nonfinite"].item()) == 0:
+    def learn_pair_counts(self, out: Dict[str, torch.Tensor]) -> bool:
+        """Host side of the tight pair capacities: reads the forward's three pair counts (one device->host copy), keeps
+        the largest per set; True when a count exceeded its capacity (negative n_pairs: the forward's features are
+        those of a truncated pair set and must be recomputed with the grown capacity)."""
+        return self._record(torch.stack([c.view(()) for c in out["n_pairs"]]).tolist())
+
+    def host_checks(self, out: Dict, rerun, strict: bool = False, on_regrow=None) -> Dict:
+        """The host side of a forward's device-side checks -> the output that passed them.  `out`: a forward's output
+        with its range-guard flag ("nonfinite") and pair counts ("n_pairs"): one device->host read of the four words;
+        an output without them (the map-only forward) has nothing to check.  rerun() runs the same forward again in
+        the matrix mode current at the call and returns its output.
+          tight pair capacities: the counts are recorded; a forward that overflowed (negative count: the features of
+            a truncated pair set) calls on_regrow() and runs again with the grown capacities;
+          range guard (ops.set_guard): an f16x2 forward that left fp16's range runs again in bf16x3, or raises.  The
+            re-run has fp32's exponent range in every stage: non-finite values that survive it were in the inputs or
+            the weights, and are returned as they are -- what the reference does with them;
+          strict: a pair set without a pair raises like torch.cat([]) at the reference's lanegcn.py:688."""
+        if "nonfinite" not in out or "n_pairs" not in out:
             return out
-        if ops.get_guard() == "raise":
-            raise ops.L.LgcnError("non-finite features in f16x2 mode: an operand left fp16's range (|x| >= 65520)")
-        with ops.mma_scope("bf16x3"):
-            return self.forward(fb, actors, **kw)
+        read = lambda o: torch.cat([o["nonfinite"].view(1)] + [c.view(1) for c in o["n_pairs"]]).tolist()
+        flag, *counts = read(out)
+        if self.pair_caps == "tight" and self._record(counts):
+            if on_regrow is not None:
+                on_regrow()
+            out = rerun()
+            flag, *counts = read(out)
+            if self._record(counts):
+                raise LgcnError("pair capacity still exceeded after growing it")
+        if flag != 0 and ops.get_mma() == "f16x2" and ops.get_guard() != "off":
+            if ops.get_guard() == "raise":
+                raise LgcnError("non-finite features in f16x2 mode: an operand left fp16's range (|x| >= 65520)")
+            with ops.mma_scope("bf16x3"):
+                out = rerun()
+            counts = read(out)[1:]
+        if strict and 0 in counts:
+            raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
+        return out
 
-    @torch.no_grad()
-    def stage_functions(self, fb: FlatBatch, actors: torch.Tensor):
-        """The same forward cut at the reference's module boundaries, for per-stage measurement: returns
-        (state, [(name, fn)]); fn() runs one stage on the tensors the previous stages left in `state`
-        (run them in order once before capturing any of them in a graph)."""
-        cfg, st = self.config, {}
-
-        def index():
-            searches = ((fb.node_ctrs, fb.node_off, fb.actor_ctrs, fb.actor_off, cfg["actor2map_dist"], fb.cap_a2m),
-                        (fb.actor_ctrs, fb.actor_off, fb.node_ctrs, fb.node_off, cfg["map2actor_dist"], fb.cap_a2m),
-                        (fb.actor_ctrs, fb.actor_off, fb.actor_ctrs, fb.actor_off, cfg["actor2actor_dist"], fb.cap_a2a))
-            if ops.index_fused_ok(fb.n_nodes, len(fb.rel_slices), sum(fb.n_edges)):
-                cnt = st.get("_cnt")             # the stage's own counters (its captured graph is replayed alone)
-                if cnt is None:
-                    cnt = st["_cnt"] = ops.index_counters(fb.n_nodes, len(fb.rel_slices), fb.node_ctrs.device)
-                st["plan"], st["pairs"] = ops.index_build(fb.idx_local, fb.seg_off, fb.seg_base, fb.rel_slices, fb.n_nodes,
-                                                          searches, self.legacy_offsets, cnt=cnt)
-                return
-            st["pairs"] = ops.pairs_build_multi(searches, self.legacy_offsets)
-            g64, _ = ops.graph_gather_indices(fb.idx_local, fb.seg_off, fb.seg_base)
-            st["plan"] = ops.csr_build([g64[a:b] for (a, b), _ in fb.rel_slices],
-                                       [g64[a:b] for _, (a, b) in fb.rel_slices], fb.n_nodes)
-
-        def map_net():
-            st["nodes"] = M.lane_conv(self.map_net.fuse, self.map_net.stem(fb.node_ctrs, fb.node_feats), st["plan"],
-                                      fb.num_scales, impl=self.lane_impl)
-
-        def a2m():      # as in forward(): the first launch also emits M2A's U of layer 0
-            args = (st["nodes"], fb.turn, fb.control, fb.intersect, actors, st["pairs"][0])
-            if M._fold_ok(actors) and fb.n_nodes > 0:
-                st["nodes_a2m"], st["u_m2a"] = self.a2m.run(*args, extra=self.m2a.att[0].u_kw(actors))
-            else:
-                st["nodes_a2m"], st["u_m2a"] = self.a2m.run(*args), None
-
-        def m2m():
-            st["nodes_m2m"] = M.lane_conv(self.m2m.fuse, st["nodes_a2m"], st["plan"], fb.num_scales, impl=self.lane_impl)
-
-        def m2a():      # as in forward(): the last tail also emits A2A's first U / V
-            if M._fold_ok(st["nodes_m2m"]):
-                st["actors_m2a"], st["uv_a2a"] = M.att_block(self.m2a.att, actors, st["nodes_m2m"], st["pairs"][1],
-                                                             next_att=self.a2a.att[0], next_ctx_is_out=True, u0=st.get("u_m2a"))
-                return
-            act = actors
-            for att in self.m2a.att:
-                act = att.run(act, st["nodes_m2m"], st["pairs"][1])
-            st["actors_m2a"], st["uv_a2a"] = act, None
-
-        def a2a():
-            act = st["actors_m2a"]
-            if M._fold_ok(act):
-                st["actors_a2a"] = M.att_block(self.a2a.att, act, act, st["pairs"][2], uv=st["uv_a2a"], ctx_is_agts=True)[0]
-                return
-            for att in self.a2a.att:
-                act = att.run(act, act, st["pairs"][2])
-            st["actors_a2a"] = act
-
-        return st, [("index", index), ("map_net", map_net), ("a2m", a2m), ("m2m", m2m), ("m2a", m2a), ("a2a", a2a)]
+    def forward_guarded(self, fb: FlatBatch, actors: torch.Tensor, **kw) -> Dict[str, torch.Tensor]:
+        """forward() behind host_checks(): one 16-byte device->host read."""
+        return self.host_checks(self.forward(fb, actors, **kw), lambda: self.forward(fb, actors, **kw))
 
     def capture(self, fb: FlatBatch, actors: torch.Tensor, warmup: int = 2, **fwd_kw):
         """Capture one forward into a hipGraph.  Returns (graph, outputs); ``graph.replay()`` re-runs
@@ -460,7 +456,7 @@ class FullNetEngine:
 
     @torch.no_grad()
     def forward(self, fb: FlatBatch, actor_feats: torch.Tensor, rot: torch.Tensor, orig: torch.Tensor,
-                sizes: List[int], return_pairs: bool = False) -> Dict[str, torch.Tensor]:
+                sizes: List[int]) -> Dict[str, torch.Tensor]:
         """Returns {"cls": [A,6], "reg": [A,6,30,2]} for all actors of the batch (scene i = rows
         sum(sizes[:i]) .. sum(sizes[:i+1])), reg already in world coordinates."""
         net = self.net
@@ -482,7 +478,7 @@ class FullNetEngine:
         res = {"cls": cls, "reg": reg, "nonfinite": hot["nonfinite"]}
         ops.check_finite(hot["nonfinite"], reg.reshape(-1), cls.reshape(-1), bit=2)      # PredNet's row blocks too
         # device counts of the three pair sets (A2M, M2A, A2A): Att.strict's check and the tight pair capacities
-        # (negative = capacity exceeded, HotPathEngine.learn_pair_counts); `return_pairs` is kept for callers of round 2
+        # (negative = capacity exceeded, HotPathEngine.learn_pair_counts)
         res["n_pairs"] = hot["n_pairs"]
         return res
 

@@ -961,6 +961,13 @@ def _own_outputs(gout: Dict) -> Dict:
     return out
 
 
+def _need_nodes(n_nodes: int, n_edges, num_scales: int):
+    """The reference's MapNet fails with KeyError("node_idcs") on a batch without a lane node or without an edge in its
+    widest pre / suc relation (lanegcn.py:312-322): decided here from the counts, before any launch."""
+    if n_nodes == 0 or n_edges[2 * num_scales - 2] == 0 or n_edges[2 * num_scales - 1] == 0:
+        raise KeyError("node_idcs")
+
+
 def _net_replay_or_run(self, eng, hfb, feats, rot, orig, sizes):
     """Whole-Net forward for one host-packed batch (engine.HostFlatBatch + host actor tensors).  A batch whose shapes
     (and the weights' versions) equal the previous call's is captured in a hipGraph once and replayed from then on
@@ -980,19 +987,16 @@ def _net_replay_or_run(self, eng, hfb, feats, rot, orig, sizes):
         return gfb, _own_outputs(gout)
     fb = hfb.to()
     dev = fb.node_ctrs.device
-    ns = fb.num_scales
-    if fb.n_nodes == 0 or fb.n_edges[2 * ns - 2] == 0 or fb.n_edges[2 * ns - 1] == 0:
-        raise KeyError("node_idcs")
+    _need_nodes(fb.n_nodes, fb.n_edges, fb.num_scales)
     gin = tuple(t.to(dev, non_blocking=True) for t in (feats, rot, orig))
     if Net.graph_cache and st["last"] == sig:      # second time in a row: worth capturing
         # thread_local: CUDA activity of OTHER threads (a DataLoader's pin_memory thread) must not abort the capture
-        g, gout = eng.capture(fb, *gin, sizes, warmup=1, tune_convs=False, return_pairs=Att.strict,
-                              capture_error_mode="thread_local")
+        g, gout = eng.capture(fb, *gin, sizes, warmup=1, tune_convs=False, capture_error_mode="thread_local")
         st.update(sig=sig, graph=(g, fb, gin, gout))
         g.replay()
         return fb, _own_outputs(gout)
     st["last"] = sig
-    return fb, eng.forward(fb, *gin, sizes, return_pairs=Att.strict)
+    return fb, eng.forward(fb, *gin, sizes)
 
 
 class Net(nn.Module):
@@ -1014,35 +1018,42 @@ class Net(nn.Module):
         if not ops.wants_grad(*ops.module_params(self)) and len(data["feats"]) > 0 and sum(len(x) for x in data["ctrs"]) > 0:
             return self._forward_inference(data)
         actors, actor_idcs = actor_gather(gpu(data["feats"]))
-        actor_ctrs = gpu(data["ctrs"])
-        actors = self.actor_net(actors)
         # graph_gather takes the scenes as they come (CPU or GPU, int16 or int64): one concatenation and
         # one H2D per array instead of utils.gpu's per-leaf copies (lanegcn.py:134)
-        graph = graph_gather(to_long(data["graph"]))
-        nodes, node_idcs, node_ctrs = self.map_net(graph)
-        nodes = self.a2m(nodes, graph, actors, actor_idcs, actor_ctrs)
-        nodes = self.m2m(nodes, graph)
-        actors = self.m2a(actors, actor_idcs, actor_ctrs, nodes, node_idcs, node_ctrs)
-        actors = self.a2a(actors, actor_idcs, actor_ctrs)
-        out = self.pred_net(actors, actor_idcs, actor_ctrs)
+        out = self._modules_forward(actors, actor_idcs, gpu(data["ctrs"]), graph_gather(to_long(data["graph"])))
         rot, orig = gpu(data["rot"]), gpu(data["orig"])
         for i in range(len(out["reg"])):        # back to world coordinates (:147-150)
             out["reg"][i] = torch.matmul(out["reg"][i], rot[i]) + orig[i].view(1, 1, 1, -1)
         return out
 
+    def _modules_forward(self, actors: Tensor, actor_idcs, actor_ctrs, graph: Dict) -> Dict[str, List[Tensor]]:
+        """The seven modules in the reference's order (lanegcn.py:135-146), recorded by autograd -> PredNet's output in
+        the scenes' own frames."""
+        actors = self.actor_net(actors)
+        nodes, node_idcs, node_ctrs = self.map_net(graph)
+        nodes = self.a2m(nodes, graph, actors, actor_idcs, actor_ctrs)
+        nodes = self.m2m(nodes, graph)
+        actors = self.m2a(actors, actor_idcs, actor_ctrs, nodes, node_idcs, node_ctrs)
+        actors = self.a2a(actors, actor_idcs, actor_ctrs)
+        return self.pred_net(actors, actor_idcs, actor_ctrs)
+
     graph_cache = True
     _replay_or_run = _net_replay_or_run
+
+    def _full_engine(self):
+        """This net's engine.FullNetEngine, made on first use (kept out of the module tree: net.__dict__["_engine"])."""
+        eng = self.__dict__.get("_engine")
+        if eng is None:
+            from .engine import FullNetEngine
+            eng = self.__dict__["_engine"] = FullNetEngine(self)
+        return eng
 
     def _forward_inference(self, data: Dict) -> Dict[str, List[Tensor]]:
         """No-grad fast path of forward(): the batch is collated flat on the host (one H2D per array) and run
         through engine.FullNetEngine -- same arithmetic and same outputs as the module path, without its
         per-scene tensor ops.  Error behaviour is kept: KeyError when pre[5] / suc[5] is empty
         (lanegcn.py:312-322) and, while Att.strict, RuntimeError when a fusion block has no pair (:688)."""
-        from .engine import FullNetEngine, collate_flat
-        eng = self.__dict__.get("_engine")
-        if eng is None:
-            eng = FullNetEngine(self)
-            self.__dict__["_engine"] = eng
+        eng = self._full_engine()
         flat = getattr(data, "flat", None)
         if flat is not None:      # packed by this package's collate_fn (in the DataLoader worker)
             hfb, (feats, rot, orig, sizes) = flat
@@ -1055,10 +1066,7 @@ class Net(nn.Module):
                        "graph": _tree_cpu(s["graph"])} for s in scenes]
             hfb = collate_flat_host(scenes)
             feats, rot, orig, sizes = host_actor_inputs(scenes)
-        m = hfb.meta
-        ns = m["num_scales"]
-        if m["n_nodes"] == 0 or m["n_edges"][2 * ns - 2] == 0 or m["n_edges"][2 * ns - 1] == 0:
-            raise KeyError("node_idcs")
+        _need_nodes(hfb.meta["n_nodes"], hfb.meta["n_edges"], hfb.meta["num_scales"])
         fb, out = self._replay_or_run(eng, hfb, feats, rot, orig, sizes)
         return self._finish_inference(eng, fb, out, feats, rot, orig, sizes)
 
@@ -1071,36 +1079,14 @@ class Net(nn.Module):
         return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
 
     def _check_inference(self, eng, fb, out, feats, rot, orig, sizes) -> Dict:
-        """The host-side checks of _finish_inference (one device->host read; the pair-capacity regrow and the range
-        guard run the forward again) -> the flat engine output that passed them: cls [A, M], reg [A, M, T, 2]."""
-        # one device->host read for the host-side checks: the range guard's flag and the three pair counts
-        host = torch.cat([out["nonfinite"].view(1)] + [c.view(1) for c in out["n_pairs"]]).tolist()
-        if eng.hot.pair_caps == "tight":
-            seen = eng.hot._pair_seen
-            over = any(int(c) < 0 for c in host[1:])
-            for i, c in enumerate(host[1:]):
-                seen[i] = max(seen[i], abs(int(c)))
-            if over:      # a pair set outgrew its (tight) capacity: the features are those of a truncated set -- grow, run again
-                self.__dict__.get("_graph_state", {}).update(sig=None, graph=None, last=None)
-                dev = fb.node_ctrs.device
-                out = eng.forward(fb, feats.to(dev), rot.to(dev), orig.to(dev), sizes)
-                host = torch.cat([out["nonfinite"].view(1)] + [c.view(1) for c in out["n_pairs"]]).tolist()
-                if any(int(c) < 0 for c in host[1:]):
-                    raise L.LgcnError("pair capacity still exceeded after growing it")
-        if ops.get_guard() != "off" and ops.get_mma() == "f16x2" and host[0] != 0:
-            # an operand left fp16's range: the forward comes back with NaN rows; policy = re-run in bf16x3 or raise
-            if ops.get_guard() == "raise":
-                raise L.LgcnError("non-finite outputs in f16x2 mode: an operand left fp16's range (|x| >= 65520)")
-            dev = fb.node_ctrs.device
-            with ops.mma_scope("bf16x3"):
-                out = eng.forward(fb, feats.to(dev), rot.to(dev), orig.to(dev), sizes, return_pairs=Att.strict)
-            # the re-run has fp32's exponent range in every stage (outside f16x2 ActorNet runs its exact fp32 units when
-            # ActorNet.exact is set and the MIOpen path otherwise, see ActorNet._hip_ok): non-finite values that survive it were in the inputs or the weights, and are returned as
-            # they are -- what the reference does with them
-            host = [0] + torch.stack(out["n_pairs"]).flatten().tolist()
-        if Att.strict and any(int(c) == 0 for c in host[1:]):
-            raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
-        return out
+        """The host-side checks of _finish_inference (engine.HotPathEngine.host_checks: one device->host read; the
+        pair-capacity regrow, which drops the cached graph, and the range guard run the forward again -- outside f16x2
+        ActorNet runs its exact fp32 units when ActorNet.exact is set and the MIOpen path otherwise, see
+        ActorNet._hip_ok) -> the flat engine output that passed them: cls [A, M], reg [A, M, T, 2]."""
+        dev = fb.node_ctrs.device
+        return eng.hot.host_checks(
+            out, lambda: eng.forward(fb, feats.to(dev), rot.to(dev), orig.to(dev), sizes), strict=Att.strict,
+            on_regrow=lambda: self.__dict__.get("_graph_state", {}).update(sig=None, graph=None, last=None))
 
     def forward_store(self, store, indices) -> Dict[str, List[Tensor]]:
         """No-grad forward of the scenes `indices` of a flatfile.DeviceSceneStore: the batch is cut out of the resident
@@ -1124,21 +1110,15 @@ class Net(nn.Module):
         """forward_store before its outputs are cut into per-scene lists -> (fb, ex, out): the FlatBatch and the extras of
         store.batch(indices), and the flat engine output behind the host-side checks (out["cls"] [A, M], out["reg"]
         [A, M, T, 2] in world coordinates, actor rows in batch order).  Errors as forward_store's."""
-        from .engine import FullNetEngine
-        eng = self.__dict__.get("_engine")
-        if eng is None:
-            eng = FullNetEngine(self)
-            self.__dict__["_engine"] = eng
+        eng = self._full_engine()
         plan = store.plan(indices) if plan is None else plan
-        ns = plan.num_scales
-        if plan.n_nodes == 0 or plan.n_edges[2 * ns - 2] == 0 or plan.n_edges[2 * ns - 1] == 0:
-            raise KeyError("node_idcs")
+        _need_nodes(plan.n_nodes, plan.n_edges, plan.num_scales)
         if plan.n_actors == 0:
             raise L.LgcnError("forward_store: the picked scenes hold no actor")
         with torch.no_grad():
             fb, ex = store.batch(indices, plan=plan)
             feats, rot, orig, sizes = ex["actor_feats"], ex["rot"], ex["orig"], ex["sizes"]
-            out = eng.forward(fb, feats, rot, orig, sizes, return_pairs=Att.strict)
+            out = eng.forward(fb, feats, rot, orig, sizes)
             return fb, ex, self._check_inference(eng, fb, out, feats, rot, orig, sizes)
 
     def forward_store_train(self, store, indices, rot_dt=None):
@@ -1151,9 +1131,7 @@ class Net(nn.Module):
         forward_store's, decided from the plan before any launch; a store without gt_preds raises LgcnError."""
         from .engine import flat_graph
         plan = store.plan(indices)
-        ns = plan.num_scales
-        if plan.n_nodes == 0 or plan.n_edges[2 * ns - 2] == 0 or plan.n_edges[2 * ns - 1] == 0:
-            raise KeyError("node_idcs")
+        _need_nodes(plan.n_nodes, plan.n_edges, plan.num_scales)
         if plan.n_actors == 0:
             raise L.LgcnError("forward_store_train: the picked scenes hold no actor")
         if not store.has_gt:
@@ -1162,14 +1140,7 @@ class Net(nn.Module):
         sizes = ex["sizes"]
         actor_idcs = list(torch.split(torch.arange(fb.n_actors, device=fb.actor_ctrs.device), sizes))
         actor_ctrs = list(torch.split(fb.actor_ctrs, sizes))
-        actors = self.actor_net(ex["actor_feats"])
-        graph = flat_graph(fb)
-        nodes, node_idcs, node_ctrs = self.map_net(graph)
-        nodes = self.a2m(nodes, graph, actors, actor_idcs, actor_ctrs)
-        nodes = self.m2m(nodes, graph)
-        actors = self.m2a(actors, actor_idcs, actor_ctrs, nodes, node_idcs, node_ctrs)
-        actors = self.a2a(actors, actor_idcs, actor_ctrs)
-        out = self.pred_net(actors, actor_idcs, actor_ctrs)
+        out = self._modules_forward(ex["actor_feats"], actor_idcs, actor_ctrs, flat_graph(fb))
         # the scene's rot / orig: the row of its first actor (the batch holds them per actor)
         first = plan.actor_off[:-1].tolist()
         rot = [ex["rot"][o] if n else None for o, n in zip(first, sizes)]

@@ -1005,6 +1005,15 @@ int lgcn_gather_rows(const float *src, const int32_t *idx, const int32_t *n_dev,
  * The host side reads the flag once per forward and re-runs a flagged forward in LGCN_MMA_BF16X3 (ops.py: guarded).
  */
 int lgcn_check_finite(const float *a, int64_t na, const float *b, int64_t nb, int32_t *flag, int bit, void *stream);
+/*
+ * The same check over the REAL rows of a padded batch (lgcn_store_gather_pad): a holds na / row_a rows of row_a floats,
+ * of which the first rows_a[0] are looked at (rows_a: one int64 on the device, read by the kernel and clamped to
+ * [0, na / row_a]); b, nb, row_b, rows_b likewise.  The grid depends on na + nb alone, so the launch is the same for
+ * every batch of one capacity.  LGCN_EINVAL: a negative size, bit 0, a NULL pointer next to a non-zero size, a row
+ * length that is not positive or does not divide its size; LGCN_EALIGN: a, b not 16-byte, rows_a, rows_b not 8-byte aligned.
+ */
+int lgcn_check_finite_rows(const float *a, int64_t na, int64_t row_a, const int64_t *rows_a, const float *b, int64_t nb,
+                           int64_t row_b, const int64_t *rows_b, int32_t *flag, int bit, void *stream);
 
 /*
  * Exact-fp32 form of lgcn_conv1d_gn / lgcn_conv1d_gn_train (reference layers.py:40-62 Conv1d, 142-190 the halves of Res1d;
@@ -1305,6 +1314,23 @@ int lgcn_roi_edge_fill(const lgcn_roi_t *p, void *stream);
  * else is lgcn_store_gather's output, byte for byte.  Checked first: all that lgcn_store_gather checks, with the same
  * codes; then aug_host or aug_dev NULL, a non-finite entry of aug_host (LGCN_EINVAL), aug_dev not 16-byte aligned
  * (LGCN_EALIGN).  n_scenes == 0 returns as lgcn_store_gather does, without looking at the tables.
+ *
+ * lgcn_store_gather_pad: the same launch (the same kernel body, its third instantiation) for a batch padded to fixed
+ * capacities.  The batch describes B + 1 = n_scenes scenes: B picked ones and, last, the FILLER scene, whose table
+ * entries carry a negative source (node_src, actor_src, scene, and seg_src of its 2 R segments) and the lengths that
+ * bring every total to its capacity: n_nodes, n_actors, n_elem are the capacities, the same for every batch, and so are
+ * all kernel arguments and the grid -- only the contents of tab_dev change, which makes the launch replayable from a
+ * captured graph.  The filler's rows are written without reading the store: node_ctrs (1e6, 1e6), every other node
+ * array 0; its i-th actor has actor_ctrs (-1e6 - 256 i, -1e6), actor_feats, gt_preds, has_preds, orig 0 and rot the
+ * identity; element e of a filler segment is e mod n_f (n_f = the filler's nodes): the scene-local self-loops of its
+ * nodes.  Every element of every output array is written.  The real scenes' rows are lgcn_store_gather's.
+ *   lgcn_store_pad_check(s, b, tab_host): host only, launches nothing, works without a GPU.  Everything
+ *   lgcn_store_gather checks, with the same codes, on the table `tab_host` (b->tab_host is not read) for the B picked
+ *   scenes; and: n_scenes < 2, n_nodes or n_actors 0 (the filler owns at least one node and one actor), a picked scene
+ *   with a negative source or a last scene without one (LGCN_EINVAL); a filler with fewer than one node, one actor or
+ *   zero elements in a segment -- the pick does not fit the capacities (LGCN_ESHAPE).
+ *   lgcn_store_gather_pad(s, b, stream): checks the sizes, pointers and alignment as above and launches.  It reads
+ *   neither b->tab_host nor any host table: call lgcn_store_pad_check on the words before they are uploaded to tab_dev.
  */
 typedef struct {
     int64_t n_scenes, n_nodes, n_actors, n_edges;
@@ -1327,6 +1353,8 @@ int64_t lgcn_store_table_elems(int64_t n_scenes, int64_t n_rel);
 int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream);
 int lgcn_store_gather_aug(const lgcn_store_t *s, const lgcn_store_batch_t *b, const float *aug_host, const float *aug_dev,
                           void *stream);
+int lgcn_store_pad_check(const lgcn_store_t *s, const lgcn_store_batch_t *b, const int64_t *tab_host);
+int lgcn_store_gather_pad(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream);
 
 /*
  * lgcn_store_pack: the write side of the store.  ONE launch packs G = n_seg index runs, each a contiguous piece of one

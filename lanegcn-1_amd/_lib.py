@@ -287,6 +287,7 @@ SIGNATURES = {
     "lgcn_gather_sum": (C.c_int, [_P, _P, _P, _L, _P, _P]),
     "lgcn_pair_add": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _P, _P]),
     "lgcn_check_finite": (C.c_int, [_P, _L, _P, _L, _P, _I, _P]),
+    "lgcn_check_finite_rows": (C.c_int, [_P, _L, _L, _P, _P, _L, _L, _P, _P, _I, _P]),
     "lgcn_mapnet_input": (C.c_int, [_P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _I, _P, _P]),
     "lgcn_att_pairs_train": (C.c_int, [_P, _P, _P, _P, _P, _L] + [_P] * 10 + [_F, _P, _P, _P]),
@@ -353,6 +354,8 @@ SIGNATURES = {
     "lgcn_store_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_gather": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
     "lgcn_store_gather_aug": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P, _P, _P]),
+    "lgcn_store_pad_check": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
+    "lgcn_store_gather_pad": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
     "lgcn_store_pack_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_pack": (C.c_int, [C.POINTER(StorePack), _P]),
     "lgcn_scene_tracks_ws_elems": (C.c_int64, [_L]),

@@ -393,8 +393,16 @@ __global__ __launch_bounds__(256) void k_pair_add(const float4 *__restrict__ c, 
 // tensors per launch.  The 16-bit-plane matrix modes have fp16's / bf16's range: an overflow shows up as NaN rows
 // in the stage outputs (the kernels' ReLU keeps NaN), this is how a caller looks for them without a device->host
 // copy of the features.
+// ROWS (lgcn_check_finite_rows): only the first rows_a[0] rows of row_a floats of a (rows_b[0] of row_b of b) are
+// looked at, the counts read on the device and clamped to na / nb -- the real rows of a padded batch.
+template <bool ROWS>
 __global__ __launch_bounds__(256) void k_check_finite(const float *__restrict__ a, int64_t na, const float *__restrict__ b,
-                                                      int64_t nb, int32_t *flag, int bit) {
+                                                      int64_t nb, int32_t *flag, int bit, const int64_t *__restrict__ rows_a,
+                                                      int64_t row_a, const int64_t *__restrict__ rows_b, int64_t row_b) {
+    if constexpr (ROWS) {
+        if (na > 0) { const int64_t r = rows_a[0]; na = r <= 0 ? 0 : (r >= na / row_a ? na : r * row_a); }
+        if (nb > 0) { const int64_t r = rows_b[0]; nb = r <= 0 ? 0 : (r >= nb / row_b ? nb : r * row_b); }
+    }
     bool bad = false;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     // finite <=> (v - v) == 0 (inf - inf and NaN - NaN are NaN); whole float4s first, then the <= 3 leftover floats
@@ -538,7 +546,33 @@ int lgcn_check_finite(const float *a, int64_t na, const float *b, int64_t nb, in
     int64_t blocks = ((na + nb) / 4 + 1023) / 1024;      // four float4 per thread
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_check_finite, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, na, b, nb, flag, bit);
+    hipLaunchKernelGGL(k_check_finite<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, na, b, nb, flag, bit,
+                       static_cast<const int64_t *>(nullptr), (int64_t)0, static_cast<const int64_t *>(nullptr), (int64_t)0);
+    return launch_status();
+}
+
+int lgcn_check_finite_rows(const float *a, int64_t na, int64_t row_a, const int64_t *rows_a, const float *b, int64_t nb,
+                           int64_t row_b, const int64_t *rows_b, int32_t *flag, int bit, void *stream) {
+    if (na < 0 || nb < 0 || bit == 0) return LGCN_EINVAL;
+    if (na + nb == 0) return LGCN_OK;
+    LGCN_CHECK_PTR(flag);
+    if (na) {
+        LGCN_CHECK_PTR(a); LGCN_CHECK_PTR(rows_a);
+        if (row_a <= 0 || na % row_a != 0) return LGCN_EINVAL;
+        LGCN_CHECK_ALIGN16(a);
+        if ((reinterpret_cast<uintptr_t>(rows_a) & 7u) != 0) return LGCN_EALIGN;
+    }
+    if (nb) {
+        LGCN_CHECK_PTR(b); LGCN_CHECK_PTR(rows_b);
+        if (row_b <= 0 || nb % row_b != 0) return LGCN_EINVAL;
+        LGCN_CHECK_ALIGN16(b);
+        if ((reinterpret_cast<uintptr_t>(rows_b) & 7u) != 0) return LGCN_EALIGN;
+    }
+    int64_t blocks = ((na + nb) / 4 + 1023) / 1024;      // sized by the capacities: the same grid for every batch
+    if (blocks < 1) blocks = 1;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(k_check_finite<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, na, b, nb, flag, bit,
+                       rows_a, row_a, rows_b, row_b);
     return launch_status();
 }
 

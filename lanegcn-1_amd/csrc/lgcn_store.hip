@@ -9,6 +9,10 @@
 // lgcn_store_gather_aug is the same kernel body (k_store_gather<true>) with the reference's training rotation on the way
 // through: coordinates are turned by the pick's Rm, rot comes from the per-batch table instead of the store.
 //
+// lgcn_store_gather_pad is its third instantiation (k_store_gather<false, true>): the table's last scene is the filler
+// scene of a padded batch (negative sources), whose rows are written from constants instead of read from the store, so
+// that every batch has the same sizes and the launch -- arguments and grid -- is the same for any pick.
+//
 // lgcn_store_pack (k_store_pack) is the write side: one launch packs index runs of int16 / int32 / int64 sources into the
 // store's int32 edge arrays and cuts rot / orig out of a batch's frame rows.  Same shape of kernel: the grid lies over
 // output words, a thread finds its run by binary search, the source descriptors are read from the device table.
@@ -62,8 +66,14 @@ __device__ __forceinline__ float2 store_turn(float2 p, float4 rm) {
                        __fadd_rn(__fmul_rn(p.x, rm.y), __fmul_rn(p.y, rm.w)));
 }
 
-// AUG = false is lgcn_store_gather (aug is not read); AUG = true turns the picked scene j by aug[j] on the way through
-template <bool AUG>
+// the filler scene of a padded batch: nodes far on one side, actors far on the other and 256 m
+// apart (farther than every distance threshold), all features zero
+constexpr float kFillNode = 1e6f;
+__device__ __forceinline__ float2 store_fill_actor(int64_t i) { return make_float2((float)(-1000000 - 256 * i), -1e6f); }
+
+// AUG = false is lgcn_store_gather (aug is not read); AUG = true turns the picked scene j by aug[j] on the way through;
+// PAD: a scene with a negative source is the filler (the last one; lgcn_store_pad_check), written without reading the store
+template <bool AUG, bool PAD>
 __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store_t s, const lgcn_store_batch_t b,
                                                                 const StoreGrid g, const StoreAug *__restrict__ aug) {
     const int B = b.n_scenes;
@@ -78,6 +88,14 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         if (i >= b.n_nodes) return;
         const int j = find_seg(t.node_off, B, i);
         const int64_t r = t.node_src[j] + (i - t.node_off[j]);
+        if (PAD && t.node_src[j] < 0) {
+            reinterpret_cast<float2 *>(b.node_ctrs)[i] = make_float2(kFillNode, kFillNode);
+            reinterpret_cast<float2 *>(b.node_feats)[i] = make_float2(0.f, 0.f);
+            reinterpret_cast<float2 *>(b.turn)[i] = make_float2(0.f, 0.f);
+            b.control[i] = 0.f;
+            b.intersect[i] = 0.f;
+            return;
+        }
         if constexpr (AUG) {
             const float4 rm = aug[j].rm;
             reinterpret_cast<float2 *>(b.node_ctrs)[i] = store_turn(reinterpret_cast<const float2 *>(s.node_ctrs)[r], rm);
@@ -94,6 +112,12 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         const int j = find_seg(t.actor_off, B, i);
         const int64_t r = t.actor_src[j] + (i - t.actor_off[j]);
         const int64_t sc = t.scene[j];
+        if (PAD && t.actor_src[j] < 0) {
+            reinterpret_cast<float2 *>(b.actor_ctrs)[i] = store_fill_actor(i - t.actor_off[j]);
+            reinterpret_cast<float4 *>(b.rot)[i] = make_float4(1.f, 0.f, 0.f, 1.f);
+            reinterpret_cast<float2 *>(b.orig)[i] = make_float2(0.f, 0.f);
+            return;
+        }
         if constexpr (AUG) {
             reinterpret_cast<float2 *>(b.actor_ctrs)[i] = store_turn(reinterpret_cast<const float2 *>(s.actor_ctrs)[r], aug[j].rm);
             reinterpret_cast<float4 *>(b.rot)[i] = aug[j].rot;
@@ -109,6 +133,14 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         const int j = find_seg(t.actor_off, B, a);
         const int64_t r = t.actor_src[j] + (a - t.actor_off[j]);
         const int c = e / 20, step = e - c * 20;
+        if (PAD && t.actor_src[j] < 0) {
+            b.actor_feats[i] = 0.f;
+            if (s.gt_preds != nullptr) {
+                b.gt_preds[i] = 0.f;
+                if (e < kHasRow) b.has_preds[a * kHasRow + e] = 0;
+            }
+            return;
+        }
         if (AUG && c < 2) {                // channels 0 / 1 are the step's (x, y): both are read, one component is written
             const float *xy = s.actor_feats + r * kActorRow + step * 3;
             const float2 q = store_turn(make_float2(xy[0], xy[1]), aug[j].rm);
@@ -124,6 +156,10 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_gather(const lgcn_store
         if (i >= b.n_elem) return;
         const int64_t k = find_seg(t.seg_off, (int)G, i);
         const int64_t r = t.seg_src[k] + (i - t.seg_off[k]);
+        if (PAD && t.seg_src[k] < 0) {      // filler edge e: the self-loop of its node e mod n_f (both the u and the v segment)
+            b.idx_local[i] = (i - t.seg_off[k]) % (t.node_off[B] - t.node_off[B - 1]);
+            return;
+        }
         const int32_t *src = ((k / B) & 1) ? s.edge_v : s.edge_u;     // segment k = (relation * 2 + u|v) * B + scene
         b.idx_local[i] = (int64_t)src[r];
     } else {                              // the offset arrays: node_off, actor_off, seg_off, seg_base
@@ -188,11 +224,19 @@ __global__ __launch_bounds__(kStoreThreads) void k_store_pack(const lgcn_store_p
 }
 
 // ------------------------------------------------------------------ host side
-// prefix sums off[0..n] from 0 to total; src[i] + (off[i + 1] - off[i]) inside [0, limit]
-static int store_check_runs(const int64_t *off, const int64_t *src, int64_t n, int64_t total, int64_t limit) {
+// prefix sums off[0..n] from 0 to total; src[i] + (off[i + 1] - off[i]) inside [0, limit].  pad_every > 0: every
+// pad_every-th run is the filler's (a padded batch): a negative source and at least pad_min elements, else the pick does
+// not fit the capacities; no other run may have a negative source
+static int store_check_runs(const int64_t *off, const int64_t *src, int64_t n, int64_t total, int64_t limit,
+                            int64_t pad_every = 0, int64_t pad_min = 0) {
     if (off[0] != 0) return LGCN_EINVAL;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t len = off[i + 1] - off[i];
+        if (pad_every > 0 && i % pad_every == pad_every - 1) {
+            if (src[i] >= 0) return LGCN_EINVAL;
+            if (len < pad_min) return LGCN_ESHAPE;
+            continue;
+        }
         if (len < 0) return LGCN_EINVAL;
         if (src[i] < 0 || src[i] > limit || len > limit - src[i]) return LGCN_EINVAL;
     }
@@ -201,10 +245,14 @@ static int store_check_runs(const int64_t *off, const int64_t *src, int64_t n, i
 
 static inline int64_t store_blocks(int64_t n) { return (n + kStoreThreads - 1) / kStoreThreads; }
 
-static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, StoreGrid *grid) {
+// tab: the host table to check (nullptr: none is read, lgcn_store_gather_pad); pad: the batch is a padded one, its last
+// scene the filler
+static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, StoreGrid *grid, const int64_t *tab, bool pad,
+                          bool need_tab = true) {
     if (s == nullptr || b == nullptr) return LGCN_EINVAL;
     if (s->n_scenes < 0 || s->n_nodes < 0 || s->n_actors < 0 || s->n_edges < 0) return LGCN_EINVAL;
     if (b->n_scenes < 0 || b->n_rel < 0 || b->n_nodes < 0 || b->n_actors < 0 || b->n_elem < 0) return LGCN_EINVAL;
+    if (pad && (b->n_scenes < 2 || b->n_nodes == 0 || b->n_actors == 0)) return LGCN_EINVAL;
     if (b->n_scenes == 0) return (b->n_nodes | b->n_actors | b->n_elem) ? LGCN_EINVAL : LGCN_OK;
     const int64_t lim = 0x7fffffff;
     if (b->n_nodes > lim || b->n_actors > lim / kActorRow || b->n_elem > lim) return LGCN_ESHAPE;
@@ -218,7 +266,8 @@ static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, St
     if (s->n_actors > 0) { LGCN_CHECK_PTR(s->actor_ctrs); LGCN_CHECK_PTR(s->actor_feats); }
     if (s->n_scenes > 0) { LGCN_CHECK_PTR(s->rot); LGCN_CHECK_PTR(s->orig); }
     if (s->n_edges > 0) { LGCN_CHECK_PTR(s->edge_u); LGCN_CHECK_PTR(s->edge_v); }
-    LGCN_CHECK_PTR(b->tab_host); LGCN_CHECK_PTR(b->tab_dev);
+    if (need_tab) LGCN_CHECK_PTR(tab);
+    LGCN_CHECK_PTR(b->tab_dev);
     LGCN_CHECK_PTR(b->node_off); LGCN_CHECK_PTR(b->actor_off); LGCN_CHECK_PTR(b->seg_off);
     if (G > 0) LGCN_CHECK_PTR(b->seg_base);
     if (b->n_nodes > 0) {
@@ -232,12 +281,16 @@ static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, St
     if (b->n_elem > 0) LGCN_CHECK_PTR(b->idx_local);
 
     // the table, read on the host: nothing in it becomes an address before it is known to lie inside the store
-    const StoreTab t = store_tab(b->tab_host, B, G);
-    if (int rc = store_check_runs(t.node_off, t.node_src, B, b->n_nodes, s->n_nodes)) return rc;
-    if (int rc = store_check_runs(t.actor_off, t.actor_src, B, b->n_actors, s->n_actors)) return rc;
-    if (int rc = store_check_runs(t.seg_off, t.seg_src, G, b->n_elem, s->n_edges)) return rc;
-    for (int64_t j = 0; j < B; ++j)
-        if (t.scene[j] < 0 || t.scene[j] >= s->n_scenes) return LGCN_EINVAL;
+    if (tab != nullptr) {
+        const StoreTab t = store_tab(tab, B, G);
+        const int64_t every = pad ? B : 0;
+        if (int rc = store_check_runs(t.node_off, t.node_src, B, b->n_nodes, s->n_nodes, every, 1)) return rc;
+        if (int rc = store_check_runs(t.actor_off, t.actor_src, B, b->n_actors, s->n_actors, every, 1)) return rc;
+        if (int rc = store_check_runs(t.seg_off, t.seg_src, G, b->n_elem, s->n_edges, every, 0)) return rc;
+        for (int64_t j = 0; j < B - (pad ? 1 : 0); ++j)
+            if (t.scene[j] < 0 || t.scene[j] >= s->n_scenes) return LGCN_EINVAL;
+        if (pad && t.scene[B - 1] >= 0) return LGCN_EINVAL;
+    }
 
     const void *quads[] = {s->node_ctrs, s->node_feats, s->turn, s->actor_ctrs, s->rot, s->orig, b->tab_dev, b->node_ctrs,
                            b->node_feats, b->turn, b->actor_ctrs, b->rot, b->orig, b->idx_local, b->seg_off, b->seg_base};
@@ -246,7 +299,7 @@ static int store_validate(const lgcn_store_t *s, const lgcn_store_batch_t *b, St
                            b->intersect, b->node_off, b->actor_off, b->actor_feats, b->gt_preds};
     for (const void *q : words)
         if (misaligned(q, 3u)) return LGCN_EALIGN;
-    if (misaligned(b->tab_host, 7u)) return LGCN_EALIGN;
+    if (misaligned(tab, 7u)) return LGCN_EALIGN;
 
     const int64_t items[5] = {b->n_nodes, b->n_actors, b->n_actors * kActorRow, b->n_elem, 2 * (B + 1) + 2 * G + 1};
     int64_t at = 0;
@@ -312,9 +365,9 @@ int64_t lgcn_store_table_elems(int64_t n_scenes, int64_t n_rel) {
 
 int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream) {
     StoreGrid grid;
-    if (int rc = store_validate(s, b, &grid)) return rc;
+    if (int rc = store_validate(s, b, &grid, b == nullptr ? nullptr : b->tab_host, false)) return rc;
     if (b->n_scenes == 0) return LGCN_OK;
-    hipLaunchKernelGGL(k_store_gather<false>, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((k_store_gather<false, false>), dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
                        *s, *b, grid, static_cast<const StoreAug *>(nullptr));
     return launch_status();
 }
@@ -322,14 +375,27 @@ int lgcn_store_gather(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *
 int lgcn_store_gather_aug(const lgcn_store_t *s, const lgcn_store_batch_t *b, const float *aug_host, const float *aug_dev,
                           void *stream) {
     StoreGrid grid;
-    if (int rc = store_validate(s, b, &grid)) return rc;
+    if (int rc = store_validate(s, b, &grid, b == nullptr ? nullptr : b->tab_host, false)) return rc;
     if (b->n_scenes == 0) return LGCN_OK;
     LGCN_CHECK_PTR(aug_host); LGCN_CHECK_PTR(aug_dev);
     for (int64_t k = 0; k < 8 * (int64_t)b->n_scenes; ++k)
         if (!std::isfinite(aug_host[k])) return LGCN_EINVAL;
     LGCN_CHECK_ALIGN16(aug_dev);
-    hipLaunchKernelGGL(k_store_gather<true>, dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((k_store_gather<true, false>), dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
                        *s, *b, grid, reinterpret_cast<const StoreAug *>(aug_dev));
+    return launch_status();
+}
+
+int lgcn_store_pad_check(const lgcn_store_t *s, const lgcn_store_batch_t *b, const int64_t *tab_host) {
+    StoreGrid grid;
+    return store_validate(s, b, &grid, tab_host, true);
+}
+
+int lgcn_store_gather_pad(const lgcn_store_t *s, const lgcn_store_batch_t *b, void *stream) {
+    StoreGrid grid;
+    if (int rc = store_validate(s, b, &grid, nullptr, true, false)) return rc;
+    hipLaunchKernelGGL((k_store_gather<false, true>), dim3(grid.first[5]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream),
+                       *s, *b, grid, static_cast<const StoreAug *>(nullptr));
     return launch_status();
 }
 

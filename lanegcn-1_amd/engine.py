@@ -11,6 +11,7 @@ from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import os
+import time
 
 import numpy as np
 import torch
@@ -44,6 +45,9 @@ class FlatBatch:
     n_edges: List[int]
     _buf: Optional[torch.Tensor] = None     # the one device byte buffer the arrays are views of (collate_flat)
     node_sizes: Optional[List[int]] = None  # nodes per scene, on the host (what flat_graph splits by)
+    # a padded batch (flatfile.PaddedSlot): (nodes, actors) of its REAL scenes as one-element int64 device tensors (words of
+    # the slot's table) -- the range guard looks at those rows only; the filler's rows are never anyone's result
+    real_rows: Optional[tuple] = None
 
     def buf_view(self) -> Optional[torch.Tensor]:
         return self._buf
@@ -250,7 +254,7 @@ class HotPathEngine:
         out["n_pairs"] = [p.n_pairs for p in st["pairs"]]
         # range check of the 16-bit-plane modes, on the device and part of every (captured) forward: bit 0 of
         # out["nonfinite"] is set when a feature row came out NaN / inf (ops.guarded / host_checks act on it)
-        ops.check_finite(st["flag"], out["nodes"], out["actors"])
+        ops.check_finite(st["flag"], out["nodes"], out["actors"], rows=fb.real_rows)
         out["nonfinite"] = st["flag"]
         return out
 
@@ -476,7 +480,10 @@ class FullNetEngine:
             cls = torch.cat(out["cls"], 0)
             reg = torch.einsum("amtk,akj->amtj", reg, rot) + orig.view(-1, 1, 1, 2)
         res = {"cls": cls, "reg": reg, "nonfinite": hot["nonfinite"]}
-        ops.check_finite(hot["nonfinite"], reg.reshape(-1), cls.reshape(-1), bit=2)      # PredNet's row blocks too
+        if fb.real_rows is None:
+            ops.check_finite(hot["nonfinite"], reg.reshape(-1), cls.reshape(-1), bit=2)      # PredNet's row blocks too
+        else:
+            ops.check_finite(hot["nonfinite"], reg, cls, bit=2, rows=(fb.real_rows[1], fb.real_rows[1]))
         # device counts of the three pair sets (A2M, M2A, A2A): Att.strict's check and the tight pair capacities
         # (negative = capacity exceeded, HotPathEngine.learn_pair_counts)
         res["n_pairs"] = hot["n_pairs"]
@@ -507,3 +514,152 @@ class FullNetEngine:
         finally:
             torch.backends.cudnn.benchmark = prev
         return graph, out
+
+
+class StoreReplay:
+    """Whole-Net no-grad forwards of picks of a flatfile.DeviceSceneStore through ONE captured graph: every pick is padded
+    to the fixed capacities `caps` (flatfile.StoreCaps), so the padded gather and
+    FullNetEngine.forward are captured once and replayed for any pick that fits -- per pick one plan, one table check,
+    one upload and one graph.replay(), then the one 16-byte host read of the device-side checks.
+
+    forward(indices) -> (fb, ex, out) with the meaning of Net.forward_store_flat, restricted to the REAL rows: fb describes
+    the B picked scenes (n_scenes, n_nodes, n_actors, node_off / actor_off [B + 1] and the node / actor arrays cut to the
+    real rows; its index arrays -- idx_local, seg_off, seg_base, rel_slices -- stay the padded batch's), ex and out["cls"],
+    out["reg"] are views of the first A rows.  They are valid until the next forward() of this object; own=True returns
+    clones.  The first `warm` fitting picks (at least one: the weight packs are made outside a capture) run eagerly on
+    the padded batch and teach the pair capacities; the next one captures.  A pick that does not fit or has another
+    length, a pair capacity exceeded and the range guard's flag send the pick to net.forward_store_flat (which regrows /
+    reroutes as ever); after an overflow the graph is dropped and captured again with the grown capacity.  The graph is
+    also dropped when the matrix mode, a kernel implementation switch, Att.strict or a parameter's version changes.
+    Errors are forward_store's, decided from the real totals before any launch.  `stats` counts the routes (captures,
+    replays, eager_warm, eager_nofit, eager_overflow, eager_guard) and holds, as means over the padded runs, the pad share
+    (filler rows / capacity) of nodes, actors and edges and the host's milliseconds per pick up to the host read."""
+
+    def __init__(self, net, store, caps, warm: int = 2):
+        from .flatfile import PaddedSlot
+        self.net, self.store, self.caps = net, store, caps
+        self.warm = max(int(warm), 1)
+        self.slot = PaddedSlot(store, caps)
+        self._graph = self._sig = None
+        self._warm_left = self.warm
+        self.stats = dict(captures=0, replays=0, eager_warm=0, eager_nofit=0, eager_overflow=0, eager_guard=0,
+                          pad_nodes=0.0, pad_actors=0.0, pad_edges=0.0, host_ms=0.0)
+        self._padded = 0
+        self._pad_sum = [0.0, 0.0, 0.0, 0.0]
+
+    def _signature(self):
+        A, N = M.ActorNet, M.PredNet
+        return (ops.get_mma(), ops.att_pairs_impl(), ops.laneconv_impl(), M.Att.strict, A.impl, A.exact, N.impl,
+                self.net._full_engine().hot.pair_caps, sum(p._version for p in ops.module_params(self.net)))
+
+    def graph_pool_bytes(self) -> int:
+        """Bytes allocated in the capture's private memory pool (the graph's buffers; 0 before a capture)."""
+        return 0 if self._graph is None else self._graph[3]
+
+    def _padded_batch(self, plan):
+        """The padded FlatBatch / extras over the slot's arrays.  Pair capacities: the bound of ANY pick that fits (a
+        capture must hold for the next pick too), which the engine cuts to its tight capacity."""
+        fb, ex = self.slot.flat_batch(plan), self.slot.extras(plan)
+        fb.cap_a2m, fb.cap_a2a = self.caps.nodes * self.caps.actors, self.caps.actors * self.caps.actors
+        return fb, ex
+
+    @staticmethod
+    def _stable_convs():
+        """Context of this object's own forwards, eager and captured: no solver search (tune_convs=False) and MIOpen's
+        deterministic solvers only.  Where ActorNet runs on MIOpen (the matrix modes other than f16x2 without
+        ActorNet.exact) its default solvers differ from call to call on the same input (1e-6 in the features, 3e-5 in reg
+        measured); with this a replayed graph equals the eager forward of the same padded batch bit for bit."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def cm():
+            cd = torch.backends.cudnn
+            prev = cd.benchmark, cd.deterministic
+            cd.benchmark, cd.deterministic = False, True
+            try:
+                yield
+            finally:
+                cd.benchmark, cd.deterministic = prev
+        return cm()
+
+    def _capture(self, eng, fb, ex):
+        torch.cuda.synchronize()
+        before = torch.cuda.memory_allocated()
+        with self._stable_convs(), eng.hot.own_counters(fb) as cnt:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                self.slot.launch()
+                out = eng.forward(fb, ex["actor_feats"], ex["rot"], ex["orig"], ex["sizes"])
+        pool = max(torch.cuda.memory_allocated() - before, 0)      # what the capture's private pool holds for the graph
+        self._graph = (graph, out, (fb, ex, cnt), pool)      # the graph holds their addresses
+        self.stats["captures"] += 1
+
+    def _eager(self, indices, why: str, own: bool):
+        self.stats[why] += 1
+        fb, ex, out = self.net.forward_store_flat(self.store, indices)
+        return fb, ex, ({"cls": out["cls"].clone(), "reg": out["reg"].clone()} if own else out)
+
+    @torch.no_grad()
+    def forward(self, indices, own: bool = False):
+        from .flatfile import StoreFitError
+        t0 = time.perf_counter()
+        net, hot = self.net, self.net._full_engine().hot
+        eng = net._full_engine()
+        if eng.hot.branches:
+            raise LgcnError("StoreReplay: HotPathEngine.branches must stay off (one stream, one captured graph)")
+        try:
+            plan = self.store.plan(indices, caps=self.caps)
+        except StoreFitError:
+            return self._eager(indices, "eager_nofit", own)
+        M._need_nodes(plan.real_nodes, plan.real_edges, plan.num_scales)
+        if plan.real_actors == 0:
+            raise LgcnError("forward_store: the picked scenes hold no actor")
+        sig = self._signature()
+        if sig != self._sig:
+            self._graph, self._sig = None, sig
+            self._warm_left = max(self._warm_left, 1)         # new packs / kernels: once eagerly before a capture
+        B, N, A = self.caps.batch, plan.real_nodes, plan.real_actors
+        with torch.cuda.device(self.store.device):
+            self.slot.upload(plan)
+            fb, ex = self._padded_batch(plan)
+            if self._graph is None and self._warm_left > 0:
+                self._warm_left -= 1
+                route = "eager_warm"
+                self.slot.launch()
+                with self._stable_convs():
+                    out = eng.forward(fb, ex["actor_feats"], ex["rot"], ex["orig"], ex["sizes"])
+            else:
+                route = "replays"
+                if self._graph is None:
+                    self._capture(eng, fb, ex)
+                graph, out = self._graph[0], self._graph[1]
+                graph.replay()
+            host_ms = (time.perf_counter() - t0) * 1e3        # the host's work of this pick, up to the read that waits
+            # the one host read: the range guard's word and the three pair counts
+            flag, *counts = torch.cat([out["nonfinite"].view(1)] + [c.view(1) for c in out["n_pairs"]]).tolist()
+        if hot.pair_caps == "tight" and hot._record(counts):
+            self._graph = None                                # sized for fewer pairs: capture again, later
+            return self._eager(indices, "eager_overflow", own)
+        if flag != 0 and ops.get_mma() == "f16x2" and ops.get_guard() != "off":
+            return self._eager(indices, "eager_guard", own)
+        a_f = self.caps.actors - A                            # the filler's A2A self-pairs are nobody's context
+        if M.Att.strict and (counts[0] == 0 or counts[1] == 0 or counts[2] - a_f == 0):
+            raise RuntimeError("torch.cat(): expected a non-empty list of Tensors")
+        self.stats[route] += 1
+        self._padded += 1
+        for i, share in enumerate(((self.caps.nodes - N) / self.caps.nodes, a_f / self.caps.actors,
+                                   1.0 - sum(plan.real_edges) / max(sum(self.caps.edges), 1), host_ms)):
+            self._pad_sum[i] += share
+            self.stats[("pad_nodes", "pad_actors", "pad_edges", "host_ms")[i]] = self._pad_sum[i] / self._padded
+        cut = lambda t, n: t[:n].clone() if own else t[:n]
+        real = FlatBatch(n_scenes=B, n_nodes=N, n_actors=A, num_scales=plan.num_scales, rel_slices=plan.rel_slices,
+                         cap_a2m=plan.cap_a2m - (self.caps.nodes - N) * a_f, cap_a2a=plan.cap_a2a - a_f * a_f,
+                         n_edges=plan.real_edges,
+                         node_sizes=np.diff(plan.node_off[:B + 1]).tolist(),
+                         **{k: cut(getattr(fb, k), N) for k in ("node_ctrs", "node_feats", "turn", "control", "intersect")},
+                         actor_ctrs=cut(fb.actor_ctrs, A), node_off=cut(fb.node_off, B + 1), actor_off=cut(fb.actor_off, B + 1),
+                         idx_local=fb.idx_local, seg_off=fb.seg_off, seg_base=fb.seg_base)
+        rex = {k: (cut(v, A) if torch.is_tensor(v) else v) for k, v in ex.items()}
+        rex["sizes"] = list(plan.sizes[:B])
+        return real, rex, {"cls": cut(out["cls"], A), "reg": cut(out["reg"], A), "nonfinite": out["nonfinite"],
+                           "n_pairs": out["n_pairs"]}

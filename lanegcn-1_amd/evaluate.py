@@ -206,7 +206,7 @@ class ActorEvaluator(Evaluator):
 
 
 def evaluate_store(net, store, batch_size: int, evaluator: Optional[Evaluator] = None, indices=None, on_batch=None,
-                   actors: bool = False) -> Evaluator:
+                   actors: bool = False, replay: bool = False) -> Evaluator:
     """Run `net` over the scenes `indices` (default: all) of a flatfile.DeviceSceneStore in batches of `batch_size` (the
     last one may be shorter) and record every scene in `evaluator` (default: a new one for the whole store, sized by
     net.config).  Per batch: store.plan, store.batch, the whole-Net forward of Net.forward_store with its one host read
@@ -214,7 +214,11 @@ def evaluate_store(net, store, batch_size: int, evaluator: Optional[Evaluator] =
     Evaluator.update.  A batch whose scenes hold no actor at all is skipped: its slots stay `not evaluated`.
     `on_batch(out, fb, ex)`, if given, sees every evaluated batch's flat outputs (train_dp.py takes the validation loss there).
     actors=True: the default evaluator is an ActorEvaluator.for_store (every actor of the split); an evaluator passed in, of
-    either class, is used as it is."""
+    either class, is used as it is.
+    replay=True: the full batches are padded to the capacities flatfile.StoreCaps.for_picks finds over them (so every one
+    fits) and run through one engine.StoreReplay -- a captured graph replayed per batch; a shorter last batch goes the
+    eager way.  Same records; Evaluator.update stays outside the graph.  `replay` may also be a StoreReplay of this net,
+    this store and this batch size, to be reused across calls."""
     if not store.has_gt:
         raise LgcnError("evaluate_store: the store holds no gt_preds / has_preds to evaluate against")
     if batch_size < 1:
@@ -228,13 +232,24 @@ def evaluate_store(net, store, batch_size: int, evaluator: Optional[Evaluator] =
     if isinstance(evaluator, ActorEvaluator) and not np.array_equal(evaluator.actor_off, store.actor_off):
         raise LgcnError("evaluate_store: the evaluator's actor_off is not the store's")
     idx = np.arange(len(store), dtype=np.int64) if indices is None else np.asarray(indices, dtype=np.int64).reshape(-1)
+    if replay is True:
+        from .engine import StoreReplay
+        from .flatfile import StoreCaps
+        full = idx[:len(idx) // batch_size * batch_size].reshape(-1, batch_size)
+        replay = StoreReplay(net, store, StoreCaps.for_picks(store, full)) if len(full) else None
+    replay = replay or None
+    if replay is not None and (replay.net is not net or replay.store is not store):
+        raise LgcnError("evaluate_store: the StoreReplay was made for another net or another store")
     with torch.no_grad():
         for i in range(0, len(idx), batch_size):
             pick = idx[i:i + batch_size]
             plan = store.plan(pick)
             if plan.n_actors == 0:
                 continue
-            fb, ex, out = net.forward_store_flat(store, pick, plan=plan)
+            if replay is not None and len(pick) == replay.caps.batch:
+                fb, ex, out = replay.forward(pick)
+            else:
+                fb, ex, out = net.forward_store_flat(store, pick, plan=plan)
             evaluator.update(out["reg"], out["cls"], fb, ex, pick)
             if on_batch is not None:
                 on_batch(out, fb, ex)

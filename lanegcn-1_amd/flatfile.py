@@ -21,9 +21,13 @@ reference's rot_aug does (data.py:39-65), the device store inside that same laun
 A DeviceSceneStore is also made on the device: from_arrays wraps existing device tensors (data_raw.build_store ends
 there), concat merges stores (merge_tables is its host half; one ops.store_pack launch merges the edge arrays), and save
 writes the file that write_scenes would write for the store's scenes.
+
+Padded batches: StoreCaps fixes the sizes of a batch, plan_batch(..., caps=) / batch_padded cut a
+pick plus one filler scene to exactly those sizes, and PaddedSlot holds the buffers that every such batch reuses -- what
+engine.StoreReplay needs to replay one captured graph for ragged picks.
 """
 from dataclasses import dataclass
-from typing import Dict, List, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -223,6 +227,11 @@ class StorePlan:
     n_rel: int
     n_elem: int
     table: np.ndarray
+    # a padded plan (plan_batch(..., caps=)): n_scenes counts the filler scene, the totals above are the capacities, and
+    # these are the totals of the picked scenes alone
+    real_nodes: Optional[int] = None
+    real_actors: Optional[int] = None
+    real_edges: Optional[List[int]] = None
 
     @property
     def n_seg(self) -> int:
@@ -249,9 +258,85 @@ class StorePlan:
 _I32_MAX = 2 ** 31 - 1
 
 
-def plan_batch(node_off, actor_off, edge_off, rel_off, num_scales: int, indices) -> StorePlan:
+def _tables(src):
+    """(node_off, actor_off, edge_off) int64 of a store or of anything that holds its tables as keys or attributes."""
+    get = (lambda k: src[k]) if isinstance(src, dict) or hasattr(src, "files") else (lambda k: getattr(src, k))
+    return tuple(np.asarray(get(k), np.int64) for k in ("node_off", "actor_off", "edge_off"))
+
+
+def _pick_totals(tables, picks):
+    """Totals of every pick of `picks` [P, B] (scene indices): nodes [P], actors [P], edges [P, R]."""
+    node_off, actor_off, edge_off = tables
+    picks = np.asarray(picks, np.int64)
+    return ((node_off[picks + 1] - node_off[picks]).sum(1), (actor_off[picks + 1] - actor_off[picks]).sum(1),
+            (edge_off[:, picks + 1] - edge_off[:, picks]).sum(2).T)
+
+
+class StoreFitError(LgcnError):
+    """A pick that does not fit a StoreCaps (its length, or a total beyond a capacity)."""
+
+
+@dataclass(frozen=True)
+class StoreCaps:
+    """Fixed sizes of a PADDED batch: `batch` picked scenes plus one filler scene hold exactly
+    `nodes` nodes, `actors` actors and `edges[r]` edges in relation r.  A pick of totals N, A, E_r fits when it has `batch`
+    scenes, N + 1 <= nodes, A + 1 <= actors (the filler always owns one node and one actor) and E_r <= edges[r].  The
+    constructors return the exact maxima, not rounded up."""
+    batch: int
+    nodes: int
+    actors: int
+    edges: Tuple[int, ...]
+
+    @classmethod
+    def _over(cls, tables, picks):
+        picks = np.asarray(picks, np.int64)
+        if picks.ndim != 2 or picks.shape[0] == 0 or picks.shape[1] == 0:
+            raise LgcnError("StoreCaps: picks must be a non-empty list of picks of one positive length")
+        S = len(tables[0]) - 1
+        if int(picks.min()) < 0 or int(picks.max()) >= S:
+            raise IndexError("store: scene index outside [0, %d)" % S)
+        n, a, e = _pick_totals(tables, picks)
+        return cls(batch=int(picks.shape[1]), nodes=int(n.max()) + 1, actors=int(a.max()) + 1,
+                   edges=tuple(int(x) for x in e.max(0)))
+
+    @classmethod
+    def for_picks(cls, store_or_tables, picks) -> "StoreCaps":
+        """The smallest capacities that every pick of `picks` (each of the same length B) fits."""
+        return cls._over(_tables(store_or_tables), picks)
+
+    @classmethod
+    def for_size(cls, store_or_tables, batch_size: int, draws: int = 1000, seed: int = 0) -> "StoreCaps":
+        """for_picks over `draws` picks of `batch_size` scenes drawn uniformly (with repeats) by default_rng(seed): the
+        same capacities for the same arguments.  A later pick may still exceed them (it then does not fit)."""
+        tables = _tables(store_or_tables)
+        if int(batch_size) < 1 or int(draws) < 1:
+            raise LgcnError("StoreCaps.for_size: batch_size and draws must be positive")
+        picks = np.random.default_rng(seed).integers(0, len(tables[0]) - 1, (int(draws), int(batch_size)))
+        return cls._over(tables, picks)
+
+    def misfit(self, n_scenes: int, nodes: int, actors: int, edges) -> Optional[str]:
+        """What of a pick with these totals does not fit (None: it fits)."""
+        if n_scenes != self.batch:
+            return "%d scenes for a batch of %d" % (n_scenes, self.batch)
+        if len(edges) != len(self.edges):
+            return "%d relations for capacities of %d" % (len(edges), len(self.edges))
+        if nodes + 1 > self.nodes:
+            return "%d nodes (+ 1 of the filler) for a capacity of %d" % (nodes, self.nodes)
+        if actors + 1 > self.actors:
+            return "%d actors (+ 1 of the filler) for a capacity of %d" % (actors, self.actors)
+        for r, (e, cap) in enumerate(zip(edges, self.edges)):
+            if e > cap:
+                return "%d edges in relation %d for a capacity of %d" % (e, r, cap)
+        return None
+
+
+def plan_batch(node_off, actor_off, edge_off, rel_off, num_scales: int, indices, caps: Optional[StoreCaps] = None) -> StorePlan:
     """Host half of DeviceSceneStore.batch: from a store's offset tables (the arrays of the same names in the file) and
-    the picked scenes to a StorePlan.  Vectorised numpy over small tables; needs no GPU."""
+    the picked scenes to a StorePlan.  Vectorised numpy over small tables; needs no GPU.
+    caps: the plan of the PADDED batch -- the picked scenes and, last, the filler scene that brings every total to its
+    capacity (its table entries: source -1).  rel_slices are then the fixed blocks of caps.edges[r] elements, sizes has
+    B + 1 entries, real_nodes / real_actors / real_edges are the picked scenes' totals.  StoreFitError (an LgcnError) names
+    what does not fit."""
     if len(indices) == 0:
         raise LgcnError("store: an empty pick has no batch")
     idx = np.asarray(indices)
@@ -261,20 +346,35 @@ def plan_batch(node_off, actor_off, edge_off, rel_off, num_scales: int, indices)
     S = len(node_off) - 1
     if int(idx.min()) < 0 or int(idx.max()) >= S:
         raise IndexError("store: scene index outside [0, %d)" % S)
-    B, R = len(idx), int(edge_off.shape[0])
+    R = int(edge_off.shape[0])
+    node_src, actor_src, scene = node_off[idx], actor_off[idx], idx
+    n_nodes, n_act = node_off[idx + 1] - node_src, actor_off[idx + 1] - actor_src
+    lo = edge_off[:, idx]                                               # [R, B]
+    seg_len, seg_src = edge_off[:, idx + 1] - lo, lo + np.asarray(rel_off)[:R, None]
+    real = {}
+    if caps is not None:
+        N, A, E = int(n_nodes.sum()), int(n_act.sum()), seg_len.sum(1)
+        why = caps.misfit(len(idx), N, A, E.tolist())
+        if why is not None:
+            raise StoreFitError("store: the pick does not fit the capacities: " + why)
+        real = dict(real_nodes=N, real_actors=A, real_edges=[int(e) for e in E])
+        minus = np.array([-1], np.int64)
+        node_src, actor_src, scene = (np.concatenate([x, minus]) for x in (node_src, actor_src, scene))
+        n_nodes, n_act = np.append(n_nodes, caps.nodes - N), np.append(n_act, caps.actors - A)
+        seg_len = np.concatenate([seg_len, (np.asarray(caps.edges, np.int64) - E)[:, None]], 1)
+        seg_src = np.concatenate([seg_src, np.full((R, 1), -1, np.int64)], 1)
+    B = len(scene)
     G = 2 * R * B
     tab = np.empty(5 * B + 2 * G + 3, np.int64)
     t_node_off, t_actor_off = tab[:B + 1], tab[B + 1:2 * B + 2]
     t_node_src, t_actor_src, t_scene = tab[2 * B + 2:3 * B + 2], tab[3 * B + 2:4 * B + 2], tab[4 * B + 2:5 * B + 2]
     t_seg_off, t_seg_src = tab[5 * B + 2:5 * B + G + 3], tab[5 * B + G + 3:]
-    t_node_src[:], t_actor_src[:], t_scene[:] = node_off[idx], actor_off[idx], idx
-    n_nodes, n_act = node_off[idx + 1] - t_node_src, actor_off[idx + 1] - t_actor_src
+    t_node_src[:], t_actor_src[:], t_scene[:] = node_src, actor_src, scene
     t_node_off[0] = t_actor_off[0] = t_seg_off[0] = 0
     np.cumsum(n_nodes, out=t_node_off[1:])
     np.cumsum(n_act, out=t_actor_off[1:])
-    lo = edge_off[:, idx]                                               # [R, B]
-    t_seg_src.reshape(R, 2, B)[:] = (lo + np.asarray(rel_off)[:R, None])[:, None, :]
-    np.cumsum(np.broadcast_to((edge_off[:, idx + 1] - lo)[:, None, :], (R, 2, B)).reshape(-1), out=t_seg_off[1:])
+    t_seg_src.reshape(R, 2, B)[:] = seg_src[:, None, :]
+    np.cumsum(np.broadcast_to(seg_len[:, None, :], (R, 2, B)).reshape(-1), out=t_seg_off[1:])
     total_n, total_a, n_elem = int(t_node_off[-1]), int(t_actor_off[-1]), int(t_seg_off[-1])
     if total_n > _I32_MAX or 60 * total_a > _I32_MAX or n_elem > _I32_MAX or G > _I32_MAX:
         raise LgcnError("store: a batch of %d nodes, %d actors and %d index elements is past 32-bit offsets"
@@ -284,7 +384,7 @@ def plan_batch(node_off, actor_off, edge_off, rel_off, num_scales: int, indices)
     return StorePlan(
         n_scenes=B, n_nodes=total_n, n_actors=total_a, num_scales=int(num_scales), rel_slices=rel_slices,
         n_edges=[u[1] - u[0] for u, _ in rel_slices], cap_a2m=int(np.dot(n_nodes, n_act)), cap_a2a=int(np.dot(n_act, n_act)),
-        sizes=n_act.tolist(), n_rel=R, n_elem=n_elem, table=tab)
+        sizes=n_act.tolist(), n_rel=R, n_elem=n_elem, table=tab, **real)
 
 
 def merge_tables(parts) -> Dict:
@@ -347,6 +447,19 @@ def _carve(spec, device):
         # one op per array (a slice, a dtype view and a reshape are three, and sixteen arrays make them the call's cost)
         views[name] = typed[dt].as_strided(shp, strides[::-1], o // dt.itemsize)
     return buf, views
+
+
+def _batch_spec(B, N, A, E, G, has_gt):
+    """(name, dtype, shape) of the arrays of a batch's two carved buffers: the FlatBatch arrays and the extras."""
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    flat = (("node_ctrs", f32, (N, 2)), ("node_feats", f32, (N, 2)), ("turn", f32, (N, 2)), ("control", f32, (N,)),
+            ("intersect", f32, (N,)), ("actor_ctrs", f32, (A, 2)), ("node_off", i32, (B + 1,)),
+            ("actor_off", i32, (B + 1,)), ("idx_local", i64, (E,)), ("seg_off", i64, (G + 1,)), ("seg_base", i64, (G,)))
+    assert tuple(n for n, _, _ in flat) == _FLAT_ARRAYS
+    extra = (("actor_feats", f32, (A, 3, 20)), ("rot", f32, (A, 2, 2)), ("orig", f32, (A, 2)))
+    if has_gt:
+        extra += (("gt_preds", f32, (A, 30, 2)), ("has_preds", torch.bool, (A, 30)))
+    return flat, extra
 
 
 class DeviceSceneStore:
@@ -448,8 +561,26 @@ class DeviceSceneStore:
         """Whether the store holds gt_preds / has_preds (a training step needs them)."""
         return self._job.has_gt
 
-    def plan(self, indices) -> StorePlan:
-        return plan_batch(self.node_off, self.actor_off, self.edge_off, self.rel_off, self.num_scales, indices)
+    def plan(self, indices, caps: Optional[StoreCaps] = None) -> StorePlan:
+        return plan_batch(self.node_off, self.actor_off, self.edge_off, self.rel_off, self.num_scales, indices, caps=caps)
+
+    def batch_padded(self, indices, caps: StoreCaps, slot: "PaddedSlot" = None, plan: StorePlan = None):
+        """-> (FlatBatch, extras) of the pick PADDED to `caps`: the B picked scenes and one filler scene (DESIGN.md section
+        3.10) that brings every total to its capacity -- byte for byte FlatSceneFile.batch(pick + [F]) of a store that also
+        holds that filler scene as scene F.  Every padded batch of one `caps` has the same sizes.  slot: a PaddedSlot of
+        this store and these capacities, filled in place (one host-to-device copy of the table, one launch, nothing
+        allocated; the arrays returned are the slot's, valid until it is filled again); None: a new one.  plan: this
+        pick's plan(indices, caps=caps).  StoreFitError when the pick does not fit."""
+        p = self.plan(indices, caps=caps) if plan is None else plan
+        if p.real_nodes is None:
+            raise LgcnError("store: batch_padded needs the plan of a padded batch (plan(indices, caps=caps))")
+        slot = PaddedSlot(self, caps) if slot is None else slot
+        if slot.store is not self or slot.caps != caps:
+            raise LgcnError("store: the slot was made for another store or other capacities")
+        with torch.cuda.device(self.device):
+            slot.upload(p)
+            slot.launch()
+        return slot.flat_batch(p), slot.extras(p)
 
     def batch(self, indices, plan: StorePlan = None, rot_dt=None):
         """-> (FlatBatch, extras) as FlatSceneFile.batch(indices, device, rot_dt) returns them.  The FlatBatch arrays are
@@ -459,14 +590,8 @@ class DeviceSceneStore:
         p = self.plan(indices) if plan is None else plan
         B, N, A, E, G = p.n_scenes, p.n_nodes, p.n_actors, p.n_elem, p.n_seg
         theta_new, aug = (None, None) if rot_dt is None else _pick_aug(self.theta, p.table[4 * B + 2:5 * B + 2], rot_dt)
-        f32, i32, i64 = torch.float32, torch.int32, torch.int64
-        flat = (("node_ctrs", f32, (N, 2)), ("node_feats", f32, (N, 2)), ("turn", f32, (N, 2)), ("control", f32, (N,)),
-                ("intersect", f32, (N,)), ("actor_ctrs", f32, (A, 2)), ("node_off", i32, (B + 1,)),
-                ("actor_off", i32, (B + 1,)), ("idx_local", i64, (E,)), ("seg_off", i64, (G + 1,)), ("seg_base", i64, (G,)))
-        assert tuple(n for n, _, _ in flat) == _FLAT_ARRAYS
-        extra = (("actor_feats", f32, (A, 3, 20)), ("rot", f32, (A, 2, 2)), ("orig", f32, (A, 2)))
-        if self._job.has_gt:
-            extra += (("gt_preds", f32, (A, 30, 2)), ("has_preds", torch.bool, (A, 30)))
+        i64, f32 = torch.int64, torch.float32
+        flat, extra = _batch_spec(B, N, A, E, G, self._job.has_gt)
         with torch.cuda.device(self.device):
             # the table goes through pinned memory of its own: the host allocator hands a block out again only after the
             # copies queued from it have run, so back-to-back calls never share staging
@@ -496,3 +621,62 @@ class DeviceSceneStore:
         if aug is not None:
             extras["theta"] = theta_new
         return fb, extras
+
+
+class PaddedSlot:
+    """Everything a padded batch of one store and one StoreCaps needs, made once: the pinned stage of the per-batch table,
+    the device table, the two carved buffers (FlatBatch arrays, extras) and the launch's arguments.  upload(plan) checks
+    the plan's table (lgcn_store_pad_check) and queues its copy to the device; launch() queues the gather.  Both on the
+    current stream; neither allocates.  Since all sizes are the capacities, the launch is the same for every pick and can
+    be captured in a graph once -- a replay reads whatever table the last upload left on the device.
+    Staging rule: the pinned stage is reused, so an event is recorded behind every copy and upload() waits for it on the
+    host before it rewrites the stage -- a second upload cannot overwrite words that a queued copy has not read yet."""
+
+    def __init__(self, store: DeviceSceneStore, caps: StoreCaps):
+        R = 2 * store.num_scales + 2
+        if len(caps.edges) != R or caps.batch < 1 or caps.nodes < 1 or caps.actors < 1 or min(caps.edges) < 0:
+            raise LgcnError("store: capacities of %d relations for a store of %d, or a capacity below the filler's one node "
+                            "and one actor" % (len(caps.edges), R))
+        self.store, self.caps = store, caps
+        B1, N, A, E = caps.batch + 1, caps.nodes, caps.actors, 2 * int(sum(caps.edges))
+        G = 2 * R * B1
+        self._spec = _batch_spec(B1, N, A, E, G, store.has_gt)
+        with torch.cuda.device(store.device):
+            T = ops.store_table_elems(B1, R)
+            self.stage = torch.empty(T, dtype=torch.int64, pin_memory=True)
+            self.tab_dev = torch.empty(T, dtype=torch.int64, device=store.device)
+            self.buf, self.out = _carve(self._spec[0], store.device)
+            self.extra_buf, ex = _carve(self._spec[1], store.device)
+            self.out.update(ex)
+            # node_off[B] and actor_off[B] of the table: the real scenes' rows, where the range guard reads them
+            self.real_rows = (self.tab_dev[B1 - 1:B1], self.tab_dev[2 * B1:2 * B1 + 1])
+            self._copied = torch.cuda.Event()
+            self._pending = False
+            self.job = ops.StorePadJob(store._job, self.tab_dev, B1, R, N, A, E, self.out)
+
+    def upload(self, plan: StorePlan) -> None:
+        if plan.real_nodes is None or plan.table.size != self.stage.numel() or plan.n_nodes != self.caps.nodes \
+                or plan.n_actors != self.caps.actors or tuple(plan.n_edges) != tuple(self.caps.edges):
+            raise LgcnError("store: the plan is not a padded plan of this slot's capacities")
+        if self._pending:
+            self._copied.synchronize()      # the staging rule: the queued copy has read the stage
+        self.stage.numpy()[:] = plan.table
+        self.job.check(self.stage)
+        self.tab_dev.copy_(self.stage, non_blocking=True)
+        self._copied.record()
+        self._pending = True
+
+    def launch(self) -> None:
+        self.job.launch()
+
+    def flat_batch(self, plan: StorePlan) -> FlatBatch:
+        """The padded batch's FlatBatch over the slot's arrays (its host-side fields are the plan's)."""
+        return FlatBatch(n_scenes=plan.n_scenes, n_nodes=plan.n_nodes, n_actors=plan.n_actors, num_scales=plan.num_scales,
+                         rel_slices=plan.rel_slices, cap_a2m=plan.cap_a2m, cap_a2a=plan.cap_a2a, n_edges=plan.n_edges,
+                         _buf=self.buf, node_sizes=np.diff(plan.node_off).tolist(), real_rows=self.real_rows,
+                         **{n: self.out[n] for n in _FLAT_ARRAYS})
+
+    def extras(self, plan: StorePlan) -> Dict:
+        ex = {n: self.out[n] for n, _, _ in self._spec[1]}
+        ex["sizes"] = list(plan.sizes)
+        return ex

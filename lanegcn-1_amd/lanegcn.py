@@ -1088,12 +1088,19 @@ class Net(nn.Module):
             out, lambda: eng.forward(fb, feats.to(dev), rot.to(dev), orig.to(dev), sizes), strict=Att.strict,
             on_regrow=lambda: self.__dict__.get("_graph_state", {}).update(sig=None, graph=None, last=None))
 
-    def forward_store(self, store, indices) -> Dict[str, List[Tensor]]:
+    def forward_store(self, store, indices, replay=None) -> Dict[str, List[Tensor]]:
         """No-grad forward of the scenes `indices` of a flatfile.DeviceSceneStore: the batch is cut out of the resident
         store by one launch (no per-scene host work, no scene dicts) and run eagerly through engine.FullNetEngine.
         Output and error behaviour are those of forward(data) on the same scenes: per-scene lists in world coordinates,
-        KeyError when pre[5] / suc[5] is empty, RuntimeError under Att.strict when a fusion block has no pair."""
-        fb, ex, out = self.forward_store_flat(store, indices)
+        KeyError when pre[5] / suc[5] is empty, RuntimeError under Att.strict when a fusion block has no pair.
+        replay: an engine.StoreReplay of this net and this store -- the pick is padded to its fixed capacities and runs
+        through its one captured graph (same outputs; the lists are views that the next call with `replay` overwrites)."""
+        if replay is not None:
+            if replay.net is not self or replay.store is not store:
+                raise L.LgcnError("forward_store: the StoreReplay was made for another net or another store")
+            fb, ex, out = replay.forward(indices)
+        else:
+            fb, ex, out = self.forward_store_flat(store, indices)
         sizes = [int(a) for a in ex["sizes"]]
         return {"cls": list(torch.split(out["cls"], sizes)), "reg": list(torch.split(out["reg"], sizes))}
 

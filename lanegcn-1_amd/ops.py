@@ -97,11 +97,21 @@ def get_guard() -> str:
     return _guard
 
 
-def check_finite(flag: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, bit: int = 1):
-    """flag[0] |= bit when a (or b) holds a NaN / inf (lgcn_check_finite); enqueued, no synchronisation."""
+def check_finite(flag: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, bit: int = 1, rows=None):
+    """flag[0] |= bit when a (or b) holds a NaN / inf (lgcn_check_finite); enqueued, no synchronisation.
+    rows: (rows_a, rows_b), one-element int64 device tensors -- only the first rows_a[0] rows of a (dimension 0) and
+    rows_b[0] of b are looked at, the counts read on the device (lgcn_check_finite_rows: the real rows of a padded batch,
+    engine.FlatBatch.real_rows)."""
     lib = L.load()
     a = _dev(a, torch.float32, "a")
     b = None if b is None else _dev(b, torch.float32, "b")
+    if rows is not None:
+        ra, rb = (_dev(r, torch.int64, "rows") for r in rows)
+        row = lambda t: t.numel() // t.shape[0] if t.numel() else 1
+        L.check(lib.lgcn_check_finite_rows(_ptr(a), a.numel(), row(a), _ptr(ra), _ptr(b), 0 if b is None else b.numel(),
+                                           1 if b is None else row(b), _ptr(rb), _ptr(flag), bit, _stream()),
+                "lgcn_check_finite_rows")
+        return
     L.check(lib.lgcn_check_finite(_ptr(a), a.numel(), _ptr(b), 0 if b is None else b.numel(), _ptr(flag), bit, _stream()),
             "lgcn_check_finite")
 
@@ -2343,9 +2353,21 @@ def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n
         raise L.LgcnError("store_gather: the store lives on %s, which is not the current device" % (job.device,))
     if tab_host.numel() != tab_dev.numel() or tab_host.numel() != store_table_elems(n_scenes, n_rel):
         raise L.LgcnError("store_gather: the table must hold lgcn_store_table_elems(n_scenes, n_rel) entries")
+    b = _store_batch(job, tab_dev, n_scenes, n_rel, n_nodes, n_actors, n_elem, out)
+    b.tab_host = tab_host.data_ptr()
+    if aug_host is None:
+        L.check(L.load().lgcn_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_store_gather")
+    else:
+        L.check(L.load().lgcn_store_gather_aug(C.byref(job.p), C.byref(b), aug_host.data_ptr(), aug_dev.data_ptr(), _stream()),
+                "lgcn_store_gather_aug")
+
+
+def _store_batch(job: StoreJob, tab_dev: torch.Tensor, n_scenes: int, n_rel: int, n_nodes: int, n_actors: int, n_elem: int,
+                 out: dict) -> "L.StoreBatch":
+    """The lgcn_store_batch_t of a gather into ``out`` (tab_host is left to the caller), its outputs checked."""
     b = L.StoreBatch()
     b.n_scenes, b.n_rel, b.n_nodes, b.n_actors, b.n_elem = n_scenes, n_rel, n_nodes, n_actors, n_elem
-    b.tab_host, b.tab_dev = tab_host.data_ptr(), tab_dev.data_ptr()
+    b.tab_dev = tab_dev.data_ptr()
     n_seg = 2 * n_rel * n_scenes
     f32, i32, i64 = torch.float32, torch.int32, torch.int64
     want = dict(node_ctrs=(f32, 2 * n_nodes), node_feats=(f32, 2 * n_nodes), turn=(f32, 2 * n_nodes), control=(f32, n_nodes),
@@ -2364,11 +2386,34 @@ def store_gather(job: StoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n
         if v.numel() != n or (v.dtype != dt if dt is not None else v.element_size() != 1):
             raise L.LgcnError("store_gather: %s must hold %d elements of %s, got %d of %s" % (k, n, dt or "one byte", v.numel(), v.dtype))
         setattr(b, k, v.data_ptr() if n else None)
-    if aug_host is None:
-        L.check(L.load().lgcn_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_store_gather")
-    else:
-        L.check(L.load().lgcn_store_gather_aug(C.byref(job.p), C.byref(b), aug_host.data_ptr(), aug_dev.data_ptr(), _stream()),
-                "lgcn_store_gather_aug")
+    return b
+
+
+class StorePadJob:
+    """The lgcn_store_batch_t of a PADDED batch (lgcn_store_gather_pad: n_scenes = picked scenes + the filler, the totals
+    are the capacities), built once per slot: ``check(tab_host)`` is lgcn_store_pad_check on a host table (no launch, no
+    GPU work), ``launch()`` the gather on the current stream from the words that are in ``tab_dev`` by then.  Arguments as
+    store_gather's."""
+
+    def __init__(self, job: StoreJob, tab_dev: torch.Tensor, n_scenes: int, n_rel: int, n_nodes: int, n_actors: int,
+                 n_elem: int, out: dict):
+        tab_dev = _dev(tab_dev, torch.int64, "store tab_dev")
+        if tab_dev.device != job.device or tab_dev.numel() != store_table_elems(n_scenes, n_rel):
+            raise L.LgcnError("store_gather_pad: tab_dev must hold lgcn_store_table_elems(n_scenes, n_rel) entries on the "
+                              "store's device")
+        self.job, self.tab_dev, self.out = job, tab_dev, dict(out)      # (the struct holds their addresses)
+        self.b = _store_batch(job, tab_dev, n_scenes, n_rel, n_nodes, n_actors, n_elem, out)
+
+    def check(self, tab_host: torch.Tensor) -> None:
+        if tab_host.is_cuda or tab_host.dtype != torch.int64 or not tab_host.is_contiguous() \
+                or tab_host.numel() != self.tab_dev.numel():
+            raise L.LgcnError("store_gather_pad: tab_host must be a contiguous int64 host tensor of tab_dev's size")
+        L.check(L.load().lgcn_store_pad_check(C.byref(self.job.p), C.byref(self.b), tab_host.data_ptr()), "lgcn_store_pad_check")
+
+    def launch(self) -> None:
+        if self.job.device.index != torch.cuda.current_device():
+            raise L.LgcnError("store_gather_pad: the store lives on %s, which is not the current device" % (self.job.device,))
+        L.check(L.load().lgcn_store_gather_pad(C.byref(self.job.p), C.byref(self.b), _stream()), "lgcn_store_gather_pad")
 
 
 def store_pack_table_elems(n_seg: int, n_src: int) -> int:

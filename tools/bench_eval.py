@@ -3,6 +3,7 @@ evaluation launches alone.
 
     python tools/bench_eval.py [--scenes 256] [--batch 32] [--rounds 30] [--warmup 5] [--reps 3] [--slots 39472]
     python tools/bench_eval.py --actors [--actor-slots 631552]
+    python tools/bench_eval.py --ragged [--replay]
 
 The store and the protocol of tools/bench_store.py: `scenes` synthetic scenes of S2's per-scene size (324 nodes, 50
 actors), batches of `batch`; one process measures, the two loops alternating, `reps` times over.
@@ -15,6 +16,12 @@ actors), batches of `batch`; one process measures, the two loops alternating, `r
   (c) and (d) are medians over `rounds` launches after `warmup`, each behind a queued 256 MB fill (the stream is busy while
   the host enqueues, so the interval is the launch and not the host's call).  Per figure the JSON line carries the median of the `reps`
 values and their lowest and highest (the spread between repetitions).
+
+--ragged: the scenes' sizes differ (2..4 roads, 20..80 actors drawn per scene), as a real split's do.
+--replay (without --actors): also (a') scenes_per_s_replay, evaluate_store(..., replay=StoreReplay) over the same
+windows, alternating with (a) -- (a) of the same run is its baseline; the line then carries replay_stats (routes, mean
+pad shares, host ms per batch) and graph_pool_mb of the last window.  The StoreReplay is made per window (capacities
+over the window's batches) before the timed region; its warm-up batches capture the graph.
 
 --actors: the same store and protocol for the evaluation of EVERY actor (evaluate.ActorEvaluator; every actor of the
 synthetic store is fully observed, the most work a row can be):
@@ -44,6 +51,8 @@ def main():
     ap.add_argument("--slots", type=int, default=39472)
     ap.add_argument("--actors", action="store_true", help="measure the evaluation of every actor against the agent-only one")
     ap.add_argument("--actor-slots", type=int, default=16 * 39472)
+    ap.add_argument("--ragged", action="store_true")
+    ap.add_argument("--replay", action="store_true")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -58,7 +67,12 @@ def main():
         raise SystemExit("bench_eval.py measures on the GPU; none found")
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "split.npz")
-        write_scenes(path, gen.synth_batch("S2", seed=0, n_scenes=args.scenes))
+        if args.ragged:
+            srng = np.random.default_rng(0)
+            scenes = [gen.synth_scene(srng, [6] * int(srng.integers(2, 5)), int(srng.integers(20, 81))) for _ in range(args.scenes)]
+        else:
+            scenes = gen.synth_batch("S2", seed=0, n_scenes=args.scenes)
+        write_scenes(path, scenes)
         store = DeviceSceneStore(path)
     torch.manual_seed(0)
     net = M.Net(M.config).cuda().eval()
@@ -72,12 +86,19 @@ def main():
         """The scene indices of one window: `n_batches` batches without a repeat inside a batch."""
         return [rng.permutation(args.scenes)[:args.batch].astype(np.int64) for _ in range(n_batches)]
 
-    def evaluate_rate(window, actors=False):
+    last_replay = []
+
+    def evaluate_rate(window, actors=False, replay=False):
         ev = ActorEvaluator.for_store(store, cfg) if actors else Evaluator(len(store), cfg["num_mods"], cfg["num_preds"])
-        evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[:args.warmup]))
+        if replay:
+            from lanegcn_amd.engine import StoreReplay
+            from lanegcn_amd.flatfile import StoreCaps
+            replay = StoreReplay(net, store, StoreCaps.for_picks(store, window))
+            last_replay[:] = [replay]
+        evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[:args.warmup]), replay=replay)
         sync()
         t0 = time.perf_counter()
-        evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[args.warmup:]))
+        evaluate_store(net, store, args.batch, ev, indices=np.concatenate(window[args.warmup:]), replay=replay)
         res = ev.summary()
         sync()
         return args.rounds * args.batch / (time.perf_counter() - t0), res
@@ -170,9 +191,12 @@ def main():
     for r in range(args.reps):
         window = picks()
         got = {}
-        for name in (("evaluate", "manual") if r % 2 else ("manual", "evaluate")):
-            rate, got[name] = (evaluate_rate if name == "evaluate" else manual_rate)(window)
-            reps["scenes_per_s_" + name].append(rate)
+        names = ("evaluate", "manual") + (("replay",) if args.replay else ())
+        for name in (names if r % 2 else names[::-1]):
+            rate, got[name] = manual_rate(window) if name == "manual" else evaluate_rate(window, replay=name == "replay")
+            reps.setdefault("scenes_per_s_" + name, []).append(rate)
+        if args.replay and got["replay"] != got["evaluate"]:
+            raise SystemExit("bench_eval.py: the replay route's summary differs from the eager one's")
         # the two loops scored the same scenes: K = 1 / K = num_mods minADE, minFDE against ade1, fde1, ade, fde
         s, m = got["evaluate"], got["manual"]
         mine = (s[1]["minADE"], s[1]["minFDE"], s[cfg["num_mods"]]["minADE"], s[cfg["num_mods"]]["minFDE"])
@@ -192,7 +216,11 @@ def main():
         big.rec[:, 4:4 + 3 * cfg["num_mods"]] = torch.rand((args.slots, 3 * cfg["num_mods"]), device="cuda")
         reps["eval_reduce_us"].append(launch_us(lambda: ops.eval_reduce(big.rec, 2.0, big._out, big._cnt, big._err_mix)))
     res = {"scenes": args.scenes, "batch": args.batch, "rounds": args.rounds, "warmup": args.warmup, "reps": args.reps,
-           "reduce_slots": args.slots, "metrics_rel_diff_between_loops": float("%.3g" % agree)}
+           "reduce_slots": args.slots, "metrics_rel_diff_between_loops": float("%.3g" % agree), "ragged": args.ragged}
+    if last_replay:
+        rp = last_replay[0]
+        res.update(replay_stats={k: (round(v, 4) if isinstance(v, float) else v) for k, v in rp.stats.items()},
+                   graph_pool_mb=round(rp.graph_pool_bytes() / 1e6, 2))
     for k, v in reps.items():
         digits = 1 if k.startswith("scenes") else 2
         res[k] = {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}

@@ -88,6 +88,9 @@ def main(argv=None):
                     help="a flat store with gt_preds (the validation split), resident on the device: with --eval the whole store "
                          "is evaluated (Argoverse's forecasting metrics for K = num_mods and K = 1); without it, validation "
                          "runs from this store instead of the dataset")
+    ap.add_argument("--eval-replay", action="store_true",
+                    help="with --eval --eval-store: pad every full batch to fixed sizes and replay one captured graph "
+                         "(evaluate_store(..., replay=True)); same records")
     ap.add_argument("--save-preds", default="", type=str, metavar="FILE.npz",
                     help="with --eval --eval-store: write index, preds [n, num_mods, num_preds, 2] and scores [n, num_mods]")
     ap.add_argument("--eval-actors", action="store_true",
@@ -147,7 +150,8 @@ def main(argv=None):
         else:
             ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"], keep_preds=bool(args.save_preds))
         net.eval()
-        evaluate_store(net, eval_store, config["val_batch_size"], ev, indices=store_eval_picks(len(eval_store), rank, world))
+        evaluate_store(net, eval_store, config["val_batch_size"], ev, indices=store_eval_picks(len(eval_store), rank, world),
+                       replay=args.eval_replay)
         ev.merge()
         if args.eval_actors:
             for who in ("all", "agent", "others"):

@@ -1619,6 +1619,56 @@ int lgcn_eval_actors(const float *reg, const float *cls, const float *gt, const 
 int lgcn_eval_reduce_sel(const float *rec, int64_t n_slots, double miss_thr, int who, int max_missing, double *out,
                          int64_t *cnt, int32_t *err, void *stream);
 
+/*
+ * Drivable-area compliance (DAC), the map-side column of Argoverse's table, in the launch that writes the record.
+ * A city's drivable area: a raster da_mat [h, w] (drivable iff == 1) and the first two rows m[6] = se2[0, 0..2],
+ * se2[1, 0..2] of Argoverse's npyimage_to_city_se2, applied as stored to city coordinates.  A point (x, y) fp32 is INSIDE iff
+ *   cx = rintf(x), cy = rintf(y) (round half to even, as np.round);
+ *   u = cx m[0] + cy m[1] + m[2], v = cx m[3] + cy m[4] + m[5] in float64, unfused, left to right;
+ *   iu = trunc(u), iv = trunc(v); 0 < iu < w and 0 < iv < h, both compared in float64 (row 0 and column 0 are left out as
+ *   Argoverse leaves them out; a huge or NaN coordinate is outside, never an overflow); raster[off + iv w + iu] != 0.
+ * Mode j of a row is COMPLIANT iff every step t < horizon of reg[a, j] is inside; has plays no part.
+ *   lgcn_da_city_t: off = the first byte of the city's raster in `raster`, h, w, m.
+ *   lgcn_drivable_t: raster = the cities' rasters back to back, raster_bytes bytes of (da_mat == 1), on the device; city
+ *   [n_cities] on the device and city_host, the same table on the host (every check below reads the host copy; the
+ *   kernel reads the device copy, the two must agree); scene_city [B] int32 on the device: the city id of each scene of
+ *   the batch, -1 = no map.
+ * lgcn_eval_scenes_da / lgcn_eval_actors_da: lgcn_eval_scenes / lgcn_eval_actors with two more floats in the record:
+ *   [30] sum_j 2^j [mode j compliant], j < M <= 8 (exact)   [31] 1 when the scene's city has a raster
+ *   both 0 for a record of flag 0 or 2 and for a scene of city id -1.  The other 30 floats, traj and score are bit for
+ *   bit what the entries without `da` write (which leave [30], [31] at 0).  A city id outside [-1, n_cities) sets err [1]
+ *   to 1; that row's record is written with [30] = [31] = 0.  No atomics, no second launch.
+ *   Checked before any launch, after every check of the sibling: LGCN_EINVAL (da or one of its pointers null, n_cities < 1,
+ *   raster_bytes < 0, a city with h or w < 1, off < 0 or a non-finite m in the host copy, a raster that does not lie
+ *   inside raster_bytes), LGCN_ESHAPE (h or w > 2^31 - 1), LGCN_EALIGN (city or scene_city not 16-byte aligned).
+ *   B == 0 / n_actors == 0: LGCN_OK, nothing launched, `da` not looked at.
+ * lgcn_eval_dac_reduce: one launch per summary: dac [9] int64: dac[k - 1] = sum over the counted records with M >= k of
+ *   popcount([30] & (2^k - 1)), dac[8] = n_dac, the counted records: flag 1, [31] == 1, kept by the selection (who,
+ *   max_missing) of lgcn_eval_reduce_sel (who = 0 and max_missing >= horizon keep all).  DAC_k of the split =
+ *   dac[k - 1] / (k n_dac).  Integer sums: exact, whatever the order.  LGCN_EINVAL (null pointer, n_slots < 0, who outside
+ *   0..2, max_missing < 0), LGCN_ESHAPE (n_slots > 2^31 - 1), LGCN_EALIGN; n_slots == 0: LGCN_OK, nothing launched.
+ */
+typedef struct {
+    int64_t off, h, w;
+    double m[6];
+} lgcn_da_city_t;
+typedef struct {
+    const uint8_t *raster;
+    int64_t raster_bytes;
+    const lgcn_da_city_t *city, *city_host;
+    int32_t n_cities;
+    const int32_t *scene_city;
+} lgcn_drivable_t;
+int lgcn_eval_scenes_da(const float *reg, const float *cls, const float *gt, const unsigned char *has,
+                        const int32_t *actor_off, const int64_t *slot, int64_t n_scenes, int n_mod, int n_t, int horizon,
+                        int64_t n_slots, float *rec, float *traj, float *score, int32_t *err, const lgcn_drivable_t *da,
+                        void *stream);
+int lgcn_eval_actors_da(const float *reg, const float *cls, const float *gt, const unsigned char *has,
+                        const int32_t *actor_off, const int64_t *slot_base, int64_t n_actors, int64_t n_scenes, int n_mod,
+                        int n_t, int horizon, int64_t n_slots, float *rec, float *traj, float *score, int32_t *err,
+                        const lgcn_drivable_t *da, void *stream);
+int lgcn_eval_dac_reduce(const float *rec, int64_t n_slots, int who, int max_missing, int64_t *dac, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

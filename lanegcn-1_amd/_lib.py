@@ -246,6 +246,15 @@ class CrossBatch(C.Structure):     # lgcn_cross_batch_t
     ]
 
 
+class DaCity(C.Structure):         # lgcn_da_city_t
+    _fields_ = [("off", C.c_int64), ("h", C.c_int64), ("w", C.c_int64), ("m", C.c_double * 6)]
+
+
+class Drivable(C.Structure):       # lgcn_drivable_t
+    _fields_ = [("raster", C.c_void_p), ("raster_bytes", C.c_int64), ("city", C.c_void_p), ("city_host", C.c_void_p),
+                ("n_cities", C.c_int32), ("scene_city", C.c_void_p)]
+
+
 OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2
 OPT_KINDS = {"adam": OPT_ADAM, "adamw": OPT_ADAMW, "sgd": OPT_SGD}
 
@@ -374,6 +383,9 @@ SIGNATURES = {
     "lgcn_eval_reduce": (C.c_int, [_P, _L, _D, _P, _P, _P, _P]),
     "lgcn_eval_actors": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     "lgcn_eval_reduce_sel": (C.c_int, [_P, _L, _D, _I, _I, _P, _P, _P, _P]),
+    "lgcn_eval_scenes_da": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _L, _P, _P, _P, _P, C.POINTER(Drivable), _P]),
+    "lgcn_eval_actors_da": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _I, _L, _P, _P, _P, _P, C.POINTER(Drivable), _P]),
+    "lgcn_eval_dac_reduce": (C.c_int, [_P, _L, _I, _I, _P, _P]),
 }
 
 _lib = None

@@ -435,4 +435,6 @@ def build_store(raws, tables, config, lane_ids=None):
     arrays = dict(node_ctrs=out["ctrs"], node_feats=out["feats"], turn=out["turn"], control=out["control"],
                   intersect=out["intersect"], actor_ctrs=tjob.ctrs[:n_a], actor_feats=tjob.feats[:n_a], rot=rot, orig=orig,
                   gt_preds=tjob.gt[:n_a], has_preds=tjob.has[:n_a], edge_u=packed[:E], edge_v=packed[E:])
-    return DeviceSceneStore.from_arrays(arrays, h[:, 1], a_off, edge_off, rel_off, num_scales, theta)
+    store = DeviceSceneStore.from_arrays(arrays, h[:, 1], a_off, edge_off, rel_off, num_scales, theta)
+    store.scene_city = [r["city"] for r in raws]      # for evaluate_store(..., drivable=): the map each scene is looked up in
+    return store

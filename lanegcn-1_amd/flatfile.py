@@ -475,6 +475,7 @@ class DeviceSceneStore:
         self.num_scales = int(a["num_scales"])
         self.node_off, self.actor_off = np.asarray(a["node_off"], np.int64), np.asarray(a["actor_off"], np.int64)
         self.edge_off, self.rel_off = np.asarray(a["edge_off"], np.int64), np.asarray(a["rel_off"], np.int64)
+        self.scene_city = None                       # the file format holds no cities (data_raw.build_store knows them)
         if not torch.cuda.is_available():
             raise LgcnError("DeviceSceneStore needs a GPU (the HIP hot path has no CPU fallback); plan_batch does not")
         self.device = torch.device("cuda" if device is None else device)
@@ -499,6 +500,7 @@ class DeviceSceneStore:
         self.node_off, self.actor_off, self.edge_off, self.rel_off = i64(node_off), i64(actor_off), i64(edge_off), i64(rel_off)
         self.n_scenes, self.num_scales = len(self.node_off) - 1, int(num_scales)
         self.theta = None if theta is None else np.ascontiguousarray(theta, np.float64).reshape(-1)
+        self.scene_city = None                       # a plain attribute, never saved: one city name per scene, or None
         arrays = dict(arrays)
         if "has_preds" in arrays and arrays["has_preds"].dtype == torch.bool:
             arrays["has_preds"] = arrays["has_preds"].view(torch.uint8)
@@ -537,7 +539,10 @@ class DeviceSceneStore:
             ops.store_pack([t["edge_u"].reshape(-1) for t in parts] + [t["edge_v"].reshape(-1) for t in parts],
                            np.concatenate([m["seg_part"], m["seg_part"] + P]), np.tile(m["seg_at"], 2), np.tile(m["seg_len"], 2), edges)
         arrays["edge_u"], arrays["edge_v"] = edges[:E], edges[E:]
-        return cls.from_arrays(arrays, m["node_off"], m["actor_off"], m["edge_off"], m["rel_off"], m["num_scales"], m["theta"])
+        self = cls.from_arrays(arrays, m["node_off"], m["actor_off"], m["edge_off"], m["rel_off"], m["num_scales"], m["theta"])
+        if all(getattr(s, "scene_city", None) is not None for s in stores):
+            self.scene_city = [c for s in stores for c in s.scene_city]
+        return self
 
     def save(self, path: str) -> None:
         """Write the store as the `.npz` that write_scenes(path, scenes, theta=...) writes for its scenes: same keys, dtypes,

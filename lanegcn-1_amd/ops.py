@@ -2627,6 +2627,7 @@ def scene_lanes_fill(job: SceneLanesJob, totals, head2: torch.Tensor) -> dict:
 # ------------------------------------------------------------------ forecasting metrics of a split (lanegcn_amd.evaluate)
 EVAL_REC = 32          # floats of one scene's record (include/lgcn.h, lgcn_eval_scenes)
 EVAL_MAX_MOD = 8
+EVAL_MAX_T = 64
 
 
 def _eval_arg(t, dtype, shape, name):
@@ -2741,3 +2742,64 @@ def eval_reduce_sel(rec, miss_thr: float, who: int, max_missing: int, out, cnt, 
         return
     L.check(L.load().lgcn_eval_reduce_sel(_ptr(rec), n_slots, float(miss_thr), int(who), int(max_missing), _ptr(out), _ptr(cnt),
                                           _ptr(err), _stream()), "lgcn_eval_reduce_sel")
+
+
+# ------------------------------------------------------------------ drivable-area compliance (lgcn_eval_*_da)
+EVAL_DAC_OUT = 9       # lgcn_eval_dac_reduce's int64 words: the counts at K = 1..8, then n_dac
+
+
+def _eval_drivable(name, da, scene_city, B, device):
+    """The lgcn_drivable_t of `da` (an evaluate.DrivableArea moved to the device) and the batch's scene_city int32 [B]."""
+    if getattr(da, "raster_dev", None) is None or da.raster_dev.device != device:
+        raise L.LgcnError("%s: the DrivableArea must be moved to %s first (DrivableArea.to)" % (name, device))
+    scene_city = _eval_arg(scene_city, torch.int32, (B,), name + " scene_city")
+    if scene_city.device != device:
+        raise L.LgcnError("%s: scene_city must live on %s" % (name, device))
+    d = L.Drivable(da.raster_dev.data_ptr(), da.raster_dev.numel(), da.table_dev.data_ptr(), C.addressof(da.table),
+                   len(da.table), scene_city.data_ptr())
+    return d, scene_city
+
+
+def eval_scenes_da(reg, cls, gt, has, actor_off, slot, horizon: int, rec, traj=None, score=None, err=None, da=None,
+                   scene_city=None) -> None:
+    """lgcn_eval_scenes_da: eval_scenes plus the record floats [30] (the bitmask of the modes that stay on the drivable area
+    of the scene's city) and [31] (the city has a raster).  da: an evaluate.DrivableArea on the device; scene_city [B] int32 on
+    the device, -1 for a scene without a map.  err is also set by a city id that `da` does not hold."""
+    (reg, cls, gt, has, actor_off, slot, rec, traj, score, err), A, B, M, T, n_slots = _eval_batch_args(
+        "eval_scenes_da", reg, cls, gt, has, actor_off, slot, rec, traj, score, err)
+    d, scene_city = _eval_drivable("eval_scenes_da", da, scene_city, B, reg.device)
+    if A == 0 and B > 0:
+        reg, cls, gt, has = rec, rec, rec, rec
+    L.check(L.load().lgcn_eval_scenes_da(_ptr(reg), _ptr(cls), _ptr(gt), _ptr(has), _ptr(actor_off), _ptr(slot), B, M, T,
+                                         int(horizon), n_slots, _ptr(rec), _ptr(traj), _ptr(score), _ptr(err), C.byref(d),
+                                         _stream()), "lgcn_eval_scenes_da")
+
+
+def eval_actors_da(reg, cls, gt, has, actor_off, slot_base, horizon: int, rec, traj=None, score=None, err=None, da=None,
+                   scene_city=None) -> None:
+    """lgcn_eval_actors_da: eval_actors plus the record floats [30], [31] of eval_scenes_da, for every actor row."""
+    (reg, cls, gt, has, actor_off, slot_base, rec, traj, score, err), A, B, M, T, n_slots = _eval_batch_args(
+        "eval_actors_da", reg, cls, gt, has, actor_off, slot_base, rec, traj, score, err)
+    d, scene_city = _eval_drivable("eval_actors_da", da, scene_city, B, reg.device)
+    L.check(L.load().lgcn_eval_actors_da(_ptr(reg), _ptr(cls), _ptr(gt), _ptr(has), _ptr(actor_off), _ptr(slot_base), A, B, M, T,
+                                         int(horizon), n_slots, _ptr(rec), _ptr(traj), _ptr(score), _ptr(err), C.byref(d),
+                                         _stream()), "lgcn_eval_actors_da")
+
+
+def eval_dac_reduce(rec, who: int, max_missing: int, dac) -> None:
+    """lgcn_eval_dac_reduce: one launch on the current stream: dac [9] int64: dac[k - 1] = the compliant modes among the first
+    k over the counted records (flag 1, a raster, kept by the selection), dac[8] = the counted records."""
+    if rec.dim() != 2:
+        raise L.LgcnError("eval_dac_reduce: rec must be [n_slots, %d]" % EVAL_REC)
+    n_slots = rec.shape[0]
+    rec = _eval_out(rec, torch.float32, (n_slots, EVAL_REC), "eval_dac_reduce rec")
+    dac = _eval_out(dac, torch.int64, (EVAL_DAC_OUT,), "eval_dac_reduce dac")
+    if dac is None:
+        raise L.LgcnError("eval_dac_reduce: dac is required")
+    if int(who) not in (0, 1, 2) or int(max_missing) < 0:
+        raise L.LgcnError("eval_dac_reduce: who must be 0, 1 or 2 and max_missing >= 0, got %s" % ((who, max_missing),))
+    if n_slots == 0:
+        dac.zero_()
+        return
+    L.check(L.load().lgcn_eval_dac_reduce(_ptr(rec), n_slots, int(who), int(max_missing), _ptr(dac), _stream()),
+            "lgcn_eval_dac_reduce")

@@ -28,7 +28,13 @@ synthetic store is fully observed, the most work a row can be):
   (e) scenes_per_s_actors    evaluate_store(actors=True) + summary(), alternating with (a) in the same process
   (f) eval_actors_us         lgcn_eval_actors for one batch (1,600 actor rows) next to (c) on the same batch
   (g) eval_reduce_sel_us     lgcn_eval_reduce_sel (who = others, every evaluated record kept) over `actor-slots` records
-                             (631,552 = 16 per scene of (d)'s split), next to lgcn_eval_reduce over the same table"""
+                             (631,552 = 16 per scene of (d)'s split), next to lgcn_eval_reduce over the same table
+
+--dac (with or without --actors): drivable-area compliance on a synthetic raster (two cities of 2,048 x 2,048 cells, 16 m
+blocks of which about two in three are drivable, the scenes alternating between them):
+  (h) scenes_per_s_dac       evaluate_store + summary() with drivable=, alternating with the same loop without it ((a) or (e))
+  (i) eval_*_da_us           the _da launch for one batch next to the plain launch on the same batch
+  (j) eval_dac_reduce_us     lgcn_eval_dac_reduce over `slots` (`actor-slots`) records next to the plain reduce"""
 import argparse
 import json
 import os
@@ -51,6 +57,7 @@ def main():
     ap.add_argument("--slots", type=int, default=39472)
     ap.add_argument("--actors", action="store_true", help="measure the evaluation of every actor against the agent-only one")
     ap.add_argument("--actor-slots", type=int, default=16 * 39472)
+    ap.add_argument("--dac", action="store_true", help="measure drivable-area compliance against the same evaluation without it")
     ap.add_argument("--ragged", action="store_true")
     ap.add_argument("--replay", action="store_true")
     args = ap.parse_args()
@@ -88,8 +95,18 @@ def main():
 
     last_replay = []
 
-    def evaluate_rate(window, actors=False, replay=False):
-        ev = ActorEvaluator.for_store(store, cfg) if actors else Evaluator(len(store), cfg["num_mods"], cfg["num_preds"])
+    def drivable_area():
+        from lanegcn_amd.evaluate import DrivableArea
+        drng = np.random.default_rng(2)
+        se2 = np.array([[1., 0., 1024.], [0., 1., 1024.], [0., 0., 1.]])
+        da = DrivableArea({c: (np.kron(drng.random((128, 128)) < 2 / 3, np.ones((16, 16), bool)), se2) for c in ("A", "B")})
+        return dict(drivable=da.to("cuda"), scene_city=np.arange(len(store), dtype=np.int32) % 2)
+
+    da_kw = drivable_area() if args.dac else {}
+
+    def evaluate_rate(window, actors=False, replay=False, dac=False):
+        kw = da_kw if dac else {}
+        ev = ActorEvaluator.for_store(store, cfg, **kw) if actors else Evaluator(len(store), cfg["num_mods"], cfg["num_preds"], **kw)
         if replay:
             from lanegcn_amd.engine import StoreReplay
             from lanegcn_amd.flatfile import StoreCaps
@@ -150,6 +167,52 @@ def main():
         big.rec[:, 3] = (torch.arange(n, device="cuda") % 3).float()
         big.rec[:, 4:4 + 3 * cfg["num_mods"]] = torch.rand((n, 3 * cfg["num_mods"]), device="cuda")
         return big
+
+    if args.dac:
+        base = "actors" if args.actors else "evaluate"
+        launch = "eval_actors" if args.actors else "eval_scenes"
+        plain_reduce = "eval_reduce_sel" if args.actors else "eval_reduce"
+        n_red = args.actor_slots if args.actors else args.slots
+        reps = {"scenes_per_s_" + base: [], "scenes_per_s_dac": [], launch + "_us": [], launch + "_da_us": [],
+                plain_reduce + "_us": [], "eval_dac_reduce_us": []}
+        got = {}
+        for r in range(args.reps):
+            window = picks()
+            for dac in ((False, True) if r % 2 else (True, False)):
+                rate, got[dac] = evaluate_rate(window, actors=args.actors, dac=dac)
+                reps["scenes_per_s_" + ("dac" if dac else base)].append(rate)
+            n_mod = cfg["num_mods"]
+            if got[True][n_mod]["minFDE"] != got[False][n_mod]["minFDE"]:
+                raise SystemExit("bench_eval.py: the evaluation with a map scored other records than the one without")
+            pick = window[0]
+            with torch.no_grad():
+                fb, ex, out = net.forward_store_flat(store, pick)
+            ev = ActorEvaluator.for_store(store, cfg, **da_kw) if args.actors else Evaluator(len(store), n_mod, cfg["num_preds"], **da_kw)
+            rows = torch.from_numpy(store.actor_off[pick] if args.actors else pick).cuda()
+            city = torch.from_numpy(da_kw["scene_city"][pick]).cuda()
+            tensors = (out["reg"], out["cls"], ex["gt_preds"], ex["has_preds"], fb.actor_off, rows, ev.horizon, ev.rec, None, None, ev._err_slot)
+            plain_fn, da_fn = (ops.eval_actors, ops.eval_actors_da) if args.actors else (ops.eval_scenes, ops.eval_scenes_da)
+            reps[launch + "_us"].append(launch_us(lambda: plain_fn(*tensors)))
+            reps[launch + "_da_us"].append(launch_us(lambda: da_fn(*tensors, da_kw["drivable"], city)))
+            big = filled(n_red)
+            big.rec[:, 30] = torch.randint(0, 1 << n_mod, (n_red,), device="cuda").float()
+            big.rec[:, 31] = 1.0
+            dac_out = torch.zeros(ops.EVAL_DAC_OUT, dtype=torch.int64, device="cuda")
+            if args.actors:
+                reps[plain_reduce + "_us"].append(launch_us(lambda: ops.eval_reduce_sel(
+                    big.rec, 2.0, ops.EVAL_WHO["others"], big.horizon - 1, big._out, big._cnt4, big._err_mix)))
+                reps["eval_dac_reduce_us"].append(launch_us(lambda: ops.eval_dac_reduce(big.rec, ops.EVAL_WHO["others"], big.horizon - 1, dac_out)))
+            else:
+                reps[plain_reduce + "_us"].append(launch_us(lambda: ops.eval_reduce(big.rec, 2.0, big._out, big._cnt, big._err_mix)))
+                reps["eval_dac_reduce_us"].append(launch_us(lambda: ops.eval_dac_reduce(big.rec, 0, ops.EVAL_MAX_T, dac_out)))
+        res = {"scenes": args.scenes, "batch": args.batch, "rounds": args.rounds, "warmup": args.warmup, "reps": args.reps,
+               "actors": args.actors, "rows_per_batch": int(fb.n_actors if args.actors else fb.n_scenes), "reduce_slots": n_red,
+               "DAC": {k: float("%.6g" % got[True][k]["DAC"]) for k in (n_mod, 1)}, "n_dac": got[True]["n_dac"]}
+        for k, v in reps.items():
+            digits = 1 if k.startswith("scenes") else 2
+            res[k] = {"median": round(statistics.median(v), digits), "min": round(min(v), digits), "max": round(max(v), digits)}
+        print(json.dumps(res))
+        return
 
     if args.actors:
         reps = {"scenes_per_s_evaluate": [], "scenes_per_s_actors": [], "eval_scenes_us": [], "eval_actors_us": [],

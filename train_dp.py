@@ -99,6 +99,10 @@ def main(argv=None):
                          "and holds every actor")
     ap.add_argument("--min-obs", type=int, default=1, metavar="N",
                     help="with --eval-actors: an actor counts only with at least N observed future steps")
+    ap.add_argument("--eval-drivable", default="", type=str, metavar="FILE.npz",
+                    help="with --eval --eval-store: also print DAC (drivable-area compliance) per K.  The file holds cities "
+                         "[C] (names), raster/<city> and se2/<city> (Argoverse's two arrays per city) and scene_city [S] int32 "
+                         "(the city id of every scene of the store, -1: no map); INTEGRATION.md shows how to write it")
     ap.add_argument("--rot-size", type=float, default=None, metavar="X",
                     help="turn every picked scene by rand() * X per step (needs a store written with theta=True); default: "
                          "config['rot_size'] when config['rot_aug'] is set, else no augmentation")
@@ -144,11 +148,18 @@ def main(argv=None):
         from lanegcn_amd.evaluate import Evaluator, evaluate_store
         from lanegcn_amd.flatfile import DeviceSceneStore
         eval_store = DeviceSceneStore(args.eval_store)
+        da = {}
+        if args.eval_drivable:
+            from lanegcn_amd.evaluate import DrivableArea
+            with np.load(args.eval_drivable) as z:
+                cities = [str(c) for c in z["cities"]]
+                da = dict(drivable=DrivableArea({c: (z["raster/" + c], z["se2/" + c]) for c in cities}),
+                          scene_city=z["scene_city"].astype(np.int32))
         if args.eval_actors:
             from lanegcn_amd.evaluate import ActorEvaluator
-            ev = ActorEvaluator.for_store(eval_store, config, keep_preds=bool(args.save_preds))
+            ev = ActorEvaluator.for_store(eval_store, config, keep_preds=bool(args.save_preds), **da)
         else:
-            ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"], keep_preds=bool(args.save_preds))
+            ev = Evaluator(len(eval_store), config["num_mods"], config["num_preds"], keep_preds=bool(args.save_preds), **da)
         net.eval()
         evaluate_store(net, eval_store, config["val_batch_size"], ev, indices=store_eval_picks(len(eval_store), rank, world),
                        replay=args.eval_replay)

@@ -1270,6 +1270,18 @@ int lgcn_roi_search(const lgcn_roi_t *p, void *stream);
 int lgcn_roi_nodes(const lgcn_roi_t *p, void *stream);
 int lgcn_roi_edge_count(const lgcn_roi_t *p, void *stream);
 int lgcn_roi_edge_fill(const lgcn_roi_t *p, void *stream);
+/*
+ * lgcn_roi_edge_fill_graph (1 launch, in the place of lgcn_roi_edge_fill): the same rows, written as the indices of the
+ * batch's MERGED block-diagonal graph, which the reference forms on the host from per-RoI arrays (data_lrcnn.py:690-844
+ * builds them, lanercnn.py:122-231 -- subgraph_gather -- offsets and concatenates them): out_u / out_v = local index +
+ * roi_base[r]; a2m_u [n_out_a2m] = r, a2m_v [n_out_a2m] = local node + roi_base[r], both int64 and arguments of this
+ * entry (lgcn_roi_t is unchanged; its int32 a2m_v is not read).  edge_base may place the rows anywhere; given
+ * RELATION-major (relation k of every RoI back to back in RoI order, then relation k + 1) every relation of the batch
+ * graph is one run of out_u / out_v, in the order a concatenation over the RoIs gives.  Same kernel body (a template
+ * flag), no further atomic or LDS.  Checks and codes: lgcn_roi_edge_fill's stage, a2m_v standing where its a2m_v stands,
+ * a2m_u like it (NULL with n_out_a2m > 0: LGCN_EINVAL; not 8-byte aligned: LGCN_EALIGN).
+ */
+int lgcn_roi_edge_fill_graph(const lgcn_roi_t *p, int64_t *a2m_u, int64_t *a2m_v, void *stream);
 
 /*
  * Device-resident scene store: the arrays of a flat store (lanegcn_amd/flatfile.py: S scenes, concatenated) stay in

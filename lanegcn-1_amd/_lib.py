@@ -360,6 +360,7 @@ SIGNATURES = {
     "lgcn_roi_nodes": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_roi_edge_count": (C.c_int, [C.POINTER(Roi), _P]),
     "lgcn_roi_edge_fill": (C.c_int, [C.POINTER(Roi), _P]),
+    "lgcn_roi_edge_fill_graph": (C.c_int, [C.POINTER(Roi), _P, _P, _P]),
     "lgcn_store_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_gather": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
     "lgcn_store_gather_aug": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P, _P, _P]),

@@ -586,7 +586,12 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_edge_count(const lgcn_roi_t
     if (tid == 0) p.edge_cnt[blockIdx.x] = s_cnt;
 }
 
-__global__ __launch_bounds__(kRoiThreads) void k_roi_edge_fill(const lgcn_roi_t p, const RoiWs w) {
+// kGraph = false: RoI-local (u, v) at the host's edge_base, a2m_v int32 (lgcn_roi_edge_fill).  kGraph = true: the indices
+// of the batch's merged block-diagonal graph (lgcn_roi_edge_fill_graph): u and v shifted by the RoI's node offset,
+// a2m as (RoI number, shifted node) in the int64 arrays g_u / g_v -- the same rows at the same scan positions, so where a
+// row holds one edge consecutive lanes still write consecutive words of out_u / out_v.
+template <bool kGraph>
+__global__ __launch_bounds__(kRoiThreads) void k_roi_edge_fill(const lgcn_roi_t p, const RoiWs w, int64_t *g_u, int64_t *g_v) {
     __shared__ int lds[kRoiThreads / 64 + 1];
     const int r = blockIdx.x / (kRoiRel + 1), rel = blockIdx.x % (kRoiRel + 1), tid = threadIdx.x;
     const RoiTabs t = roi_tabs(p.off_dev, p.n_scenes);
@@ -604,10 +609,22 @@ __global__ __launch_bounds__(kRoiThreads) void k_roi_edge_fill(const lgcn_roi_t 
         carry += total;
         if (c == 0 || (int64_t)pre + c > limit) continue;
         if (rel == kRoiRel) {
-            p.a2m_v[pre] = lu;
+            if (kGraph) {
+                g_u[pre] = r;
+                g_v[pre] = (int64_t)q.base + lu;
+            } else {
+                p.a2m_v[pre] = lu;
+            }
         } else {
             roi_row(p, w, q, rel, lu, p.out_v + pre, c);
-            for (int j = 0; j < c; ++j) p.out_u[pre + j] = lu;
+            if (kGraph) {
+                for (int j = 0; j < c; ++j) {
+                    p.out_v[pre + j] += q.base;
+                    p.out_u[pre + j] = (int64_t)q.base + lu;
+                }
+            } else {
+                for (int j = 0; j < c; ++j) p.out_u[pre + j] = lu;
+            }
         }
     }
 }
@@ -737,8 +754,24 @@ int lgcn_roi_edge_fill(const lgcn_roi_t *p, void *stream) {
     if (int rc = roi_validate(p, 4)) return rc;
     if (p->n_rois == 0) return LGCN_OK;
     const RoiWs w = roi_ws(p->ws, p->n_nodes, p->n_lanes, p->n_edges, p->n_slots, p->n_agents);
-    hipLaunchKernelGGL(k_roi_edge_fill, dim3((unsigned)(p->n_rois * (kRoiRel + 1))), dim3(kRoiThreads), 0,
-                       static_cast<hipStream_t>(stream), *p, w);
+    hipLaunchKernelGGL(k_roi_edge_fill<false>, dim3((unsigned)(p->n_rois * (kRoiRel + 1))), dim3(kRoiThreads), 0,
+                       static_cast<hipStream_t>(stream), *p, w, nullptr, nullptr);
+    return launch_status();
+}
+
+// Replaces, with lane_roi_flat on the Python side, the reference's per-RoI index arrays (data_lrcnn.py:690-844) and their
+// merge into one block-diagonal graph (lanercnn.py:122-231, subgraph_gather): the merged indices are written here.
+int lgcn_roi_edge_fill_graph(const lgcn_roi_t *p, int64_t *a2m_u, int64_t *a2m_v, void *stream) {
+    if (p == nullptr) return LGCN_EINVAL;
+    lgcn_roi_t g = *p;      // stage 4 of the sibling, with the int64 a2m_v in the place of its int32 one
+    g.a2m_v = reinterpret_cast<int32_t *>(a2m_v);
+    if (int rc = roi_validate(&g, 4)) return rc;
+    if (g.n_rois > 0 && g.n_out_a2m > 0) LGCN_CHECK_PTR(a2m_u);
+    if (misaligned(a2m_u, 7u) || misaligned(a2m_v, 7u)) return LGCN_EALIGN;
+    if (g.n_rois == 0) return LGCN_OK;
+    const RoiWs w = roi_ws(g.ws, g.n_nodes, g.n_lanes, g.n_edges, g.n_slots, g.n_agents);
+    hipLaunchKernelGGL(k_roi_edge_fill<true>, dim3((unsigned)(g.n_rois * (kRoiRel + 1))), dim3(kRoiThreads), 0,
+                       static_cast<hipStream_t>(stream), g, w, a2m_u, a2m_v);
     return launch_status();
 }
 

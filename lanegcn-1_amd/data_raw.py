@@ -397,7 +397,7 @@ def build_scenes(raws, tables, config, device=True, cross=True, lane_ids=None, b
     return scenes
 
 
-def build_store(raws, tables, config, lane_ids=None):
+def build_store(raws, tables, config, lane_ids=None, lanes=False):
     """Raw scenes to a flatfile.DeviceSceneStore that holds them, without leaving the device: the launches and host
     reads of build_scenes(..., device=True, cross=True, batched=True) (2 size read-backs, ops.read_back num_scales - 1
     times for the dilation and once for left / right) and then ONE more launch, ops.store_pack, which writes the store's
@@ -409,7 +409,13 @@ def build_store(raws, tables, config, lane_ids=None):
 
     The store equals DeviceSceneStore(path) after write_scenes(path, build_scenes(..., device=False), theta=True), byte for
     byte; plan, batch (with and without rot_dt), Net.forward_store*, evaluate_store, concat and save work on it.
-    raws, tables, lane_ids and the errors: as build_scenes; an empty batch is an LgcnError."""
+    raws, tables, lane_ids and the errors: as build_scenes; an empty batch is an LgcnError.
+
+    lanes=True also keeps, as the plain attribute store.lane_arrays (never saved, like scene_city), what the fork's lane-RoI
+    extraction reads beyond the store's own arrays, all of it the builder's flat tensors as they are: lane_idcs [N] int64
+    (scene-local lane of every node), suc_pairs / pre_pairs [P, 2] int64 (scene-local lane pairs, the used part) with their
+    per-scene offsets suc_off / pre_off [S + 1], lane_off [S + 1] (lanes per scene) and obs [A, 20, 3] (obs_trajs of the
+    kept tracks).  The store's arrays and tables are the same bytes either way."""
     from .flatfile import DeviceSceneStore
     dev = _need_gpu("build_store")
     raws = list(raws)
@@ -437,4 +443,10 @@ def build_store(raws, tables, config, lane_ids=None):
                   gt_preds=tjob.gt[:n_a], has_preds=tjob.has[:n_a], edge_u=packed[:E], edge_v=packed[E:])
     store = DeviceSceneStore.from_arrays(arrays, h[:, 1], a_off, edge_off, rel_off, num_scales, theta)
     store.scene_city = [r["city"] for r in raws]      # for evaluate_store(..., drivable=): the map each scene is looked up in
+    store.lane_arrays = None
+    if lanes:
+        cuts = _cuts(h, h2)
+        store.lane_arrays = dict(lane_idcs=out["lane_idcs"], obs=tjob.obs[:n_a], lane_off=np.asarray(h[:, 0], np.int64),
+                                 **{k: out[k][:int(cuts[k][-1])] for k in ("suc_pairs", "pre_pairs")},
+                                 suc_off=np.asarray(cuts["suc_pairs"], np.int64), pre_off=np.asarray(cuts["pre_pairs"], np.int64))
     return store

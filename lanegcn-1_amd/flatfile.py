@@ -476,6 +476,7 @@ class DeviceSceneStore:
         self.node_off, self.actor_off = np.asarray(a["node_off"], np.int64), np.asarray(a["actor_off"], np.int64)
         self.edge_off, self.rel_off = np.asarray(a["edge_off"], np.int64), np.asarray(a["rel_off"], np.int64)
         self.scene_city = None                       # the file format holds no cities (data_raw.build_store knows them)
+        self.lane_arrays = None                      # nor the lane arrays of the fork (data_raw.build_store(..., lanes=True))
         if not torch.cuda.is_available():
             raise LgcnError("DeviceSceneStore needs a GPU (the HIP hot path has no CPU fallback); plan_batch does not")
         self.device = torch.device("cuda" if device is None else device)
@@ -501,6 +502,7 @@ class DeviceSceneStore:
         self.n_scenes, self.num_scales = len(self.node_off) - 1, int(num_scales)
         self.theta = None if theta is None else np.ascontiguousarray(theta, np.float64).reshape(-1)
         self.scene_city = None                       # a plain attribute, never saved: one city name per scene, or None
+        self.lane_arrays = None                      # likewise: the fork's lane arrays, or None
         arrays = dict(arrays)
         if "has_preds" in arrays and arrays["has_preds"].dtype == torch.bool:
             arrays["has_preds"] = arrays["has_preds"].view(torch.uint8)

@@ -39,6 +39,7 @@ from . import autograd as A
 from . import ops
 from . import lanegcn as _base
 from .data import collate_fn
+from .data_lrcnn import RoiBatch
 from .lanegcn import _fuse_modules, _gn, build_pairs, lane_conv, lane_conv_train, lane_plan, lane_plan_t, rel_keys
 from .layers import Linear
 from .utils import Optimizer, StepLR, gpu, to_long
@@ -122,7 +123,12 @@ def subgraph_gather(subgraphs_in_batch) -> Dict:
     dict, key for key.  The 28 local index arrays of every RoI and its two a2m arrays are offset by ONE
     lgcn_graph_gather launch over one concatenation (segment base: the RoI's node offset, or the RoI's number for
     a2m.u) instead of hundreds of adds and cats.  Leaves may be numpy arrays, CPU or GPU tensors, int16 / int32 / int64.
-    A relation without edges comes out as an empty int64 tensor (the reference's float zeros((0,)) is not mirrored)."""
+    A relation without edges comes out as an empty int64 tensor (the reference's float zeros((0,)) is not mirrored).
+
+    A data_lrcnn.RoiBatch in the place of the lists (the flat route) already holds the merged graph: the same dict comes
+    out of views of its buffers, without a launch or a concatenation (_subgraph_views)."""
+    if isinstance(subgraphs_in_batch, RoiBatch):
+        return _subgraph_views(subgraphs_in_batch)
     graph = subgraph_bookkeeping(subgraphs_in_batch)
     dev = torch.device("cuda", torch.cuda.current_device())
     counts = graph["counts"]
@@ -153,6 +159,25 @@ def subgraph_gather(subgraphs_in_batch) -> Dict:
     for k1 in ("left", "right"):
         graph[k1] = {"u": next(it), "v": next(it)}
     graph["a2m"] = {"u": next(it), "v": next(it)}
+    return graph
+
+
+def _subgraph_views(rb: RoiBatch) -> Dict:
+    """subgraph_gather's dict out of a RoiBatch: its host bookkeeping, S-way splits of the flat feature buffers and one
+    slice per relation of the four index arrays.  The number of tensor ops depends on the scenes, never on the RoIs."""
+    graph = rb.bookkeeping()
+    nodes = [hi - lo for lo, hi in graph["batch_spans"]]
+    graph["node_idcs"] = torch.arange(graph["num_nodes"], device=rb.feats.device)
+    graph["feats"] = list(rb.feats.split(nodes))
+    graph["agent_feat"] = list(rb.agent_feat.split(graph["num_atgs_per_batch"]))
+    graph["ctrs"] = list(rb.feats[:, :2].split(nodes))
+    graph["dirs"] = list(rb.feats[:, 2:4].split(nodes))
+    graph["pose"] = list(rb.feats[:, :4].split(nodes))
+    graph["agent_vel"] = list(rb.agent_vel)
+    ext = rb.rel_ext.tolist()
+    rel = [{"u": rb.u[lo:hi], "v": rb.v[lo:hi]} for lo, hi in zip(ext[:-1], ext[1:])]
+    graph["pre"], graph["suc"], graph["left"], graph["right"] = rel[0:6], rel[6:12], rel[12], rel[13]
+    graph["a2m"] = {"u": rb.a2m_u, "v": rb.a2m_v}
     return graph
 
 
@@ -454,7 +479,8 @@ class Interactor(nn.Module):
 
 class Net(nn.Module):
     """The fork model (reference lanercnn.py:85-119): LaneInput -> LaneRoI -> Interactor -> LaneRoI -> Decode on a batch
-    as collate_fn delivers it (per-scene lists, on the CPU or the GPU).  Under no_grad every stage runs its inference
+    as collate_fn delivers it (per-scene lists, on the CPU or the GPU; data["subgraphs"] may be a data_lrcnn.RoiBatch, the
+    flat route, and forward_raw starts from raw tracks).  Under no_grad every stage runs its inference
     launches (with the modules' own range guard); under autograd their Functions, honouring Decode.train_hip and the
     other *.train_hip switches."""
 
@@ -468,8 +494,39 @@ class Net(nn.Module):
         self.decode = Decode(config)
 
     def forward(self, data: Dict) -> Dict[str, Tensor]:
-        graph = graph_gather(data["graph"])
-        graph_roi = subgraph_gather(data["subgraphs"])
+        return self._modules_forward(graph_gather(data["graph"]), subgraph_gather(data["subgraphs"]), data)
+
+    def forward_raw(self, raws, tables, lane_ids=None, horizon_buffer=20.):
+        """Raw scenes (data_raw's raw-scene dicts and {city: LaneTable}) to the fork's predictions without a scene dict,
+        a per-RoI view or a host collate -> (out, data).  data_raw.build_store(..., lanes=True) with this net's config,
+        the lane RoIs of all its scenes as one data_lrcnn.RoiBatch (store_roi_inputs + lane_roi_flat), the main graph from
+        engine.flat_graph of the store's batch plus the fork's num_nodes / counts / pose, then the modules of forward() in
+        its order -- under no_grad their inference launches, under autograd their Functions, as in forward().
+        `out`: forward()'s dict, equal to forward(collate_fn(generate_lane_roi_batch(build_scenes(...), device=True))).
+        `data`: what Decode read and Loss reads -- ctrs, feats, obs_trajs, gt_preds, has_preds per scene as views of the
+        store's arrays, valid_agent_ids (int16, S views of one upload) -- and "subgraphs", the RoiBatch.  Errors: build_store's, the RoI
+        stage's, and LgcnError naming the scene when every agent of a scene drops."""
+        from . import data_lrcnn, data_raw
+        from .engine import flat_graph
+        store = data_raw.build_store(raws, tables, self.config, lane_ids=lane_ids, lanes=True)
+        rb = data_lrcnn.lane_roi_flat(*data_lrcnn.store_roi_inputs(store), horizon_buffer)
+        fb, _ = store.batch(np.arange(len(store)))
+        graph = flat_graph(fb)
+        sizes = [int(n) for n in fb.node_sizes]
+        graph["num_nodes"] = sizes
+        graph["counts"] = [int(v) for v in np.cumsum([0] + sizes[:-1])]
+        graph["pose"] = list(torch.cat([fb.node_ctrs, fb.node_feats], -1).split(sizes))
+        a, n_act = store._job.t, np.diff(store.actor_off).tolist()
+        ids = torch.from_numpy((rb.agents - rb.agent_off[rb.scene_of]).astype(np.int16)).to(fb.node_ctrs.device)
+        data = {"ctrs": list(a["actor_ctrs"].split(n_act)), "feats": list(a["actor_feats"].split(n_act)),
+                "obs_trajs": list(store.lane_arrays["obs"].split(n_act)),
+                "valid_agent_ids": list(ids.split(rb.rois_per_scene.tolist())), "subgraphs": rb}
+        if store.has_gt:
+            data["gt_preds"] = list(a["gt_preds"].split(n_act))
+            data["has_preds"] = list(a["has_preds"].view(torch.bool).split(n_act))
+        return self._modules_forward(graph, subgraph_gather(rb), data), data
+
+    def _modules_forward(self, graph: Dict, graph_roi: Dict, data: Dict) -> Dict[str, Tensor]:
         roi_feat = self.input(graph_roi)
         roi_feat = self.roi_net1(roi_feat, graph_roi)
         roi_feat = self.interactor(graph, graph_roi, roi_feat)

@@ -2289,6 +2289,25 @@ def roi_edge_fill(job: RoiJob, edge_base: torch.Tensor, n_out_edges: int, n_out_
     return job.out_u, job.out_v, job.a2m_v
 
 
+def roi_edge_fill_graph(job: RoiJob, edge_base: torch.Tensor, n_out_edges: int, n_out_a2m: int):
+    """lgcn_roi_edge_fill_graph: (u, v [n_out_edges], a2m_u, a2m_v [n_out_a2m], all int64) -- the indices of the batch's
+    merged block-diagonal graph (node index + the RoI's node offset; a2m_u = the RoI's number) at the offsets edge_base
+    [R, 15] int32.  With a relation-major edge_base every relation of the batch graph is one run of u / v."""
+    p, dev = job.p, job.ws.device
+    job.edge_base = _dev(edge_base, torch.int32, "edge_base")
+    if job.edge_base.numel() != p.n_rois * (ROI_REL + 1):
+        raise L.LgcnError("roi_edge_fill_graph: edge_base must be [R, 15]")
+    job.out_u = torch.empty(int(n_out_edges), dtype=torch.int64, device=dev)
+    job.out_v = torch.empty(int(n_out_edges), dtype=torch.int64, device=dev)
+    job.a2m_u64 = torch.empty(int(n_out_a2m), dtype=torch.int64, device=dev)
+    job.a2m_v64 = torch.empty(int(n_out_a2m), dtype=torch.int64, device=dev)
+    p.n_out_edges, p.n_out_a2m = int(n_out_edges), int(n_out_a2m)
+    p.edge_base, p.out_u, p.out_v = job.edge_base.data_ptr(), job.out_u.data_ptr(), job.out_v.data_ptr()
+    L.check(L.load().lgcn_roi_edge_fill_graph(C.byref(p), job.a2m_u64.data_ptr(), job.a2m_v64.data_ptr(), _stream()),
+            "lgcn_roi_edge_fill_graph")
+    return job.out_u, job.out_v, job.a2m_u64, job.a2m_v64
+
+
 # ------------------------------------------------------------------ device-resident scene store (flatfile.DeviceSceneStore)
 STORE_FLOATS = ("node_ctrs", "node_feats", "turn", "control", "intersect", "actor_ctrs", "actor_feats", "rot", "orig")
 

@@ -16,7 +16,12 @@ inputs it receives inside the forward, pair search included) and one JSON line. 
                                          launches of one step each (torch.profiler, after the timed steps), the peak of
                                          torch.cuda.max_memory_allocated over one step each, and the largest relative
                                          difference of the loss and of any parameter gradient between the two
-  --others                               with --train: RowBlockFn.train_hip and Decode.train_hip on for both variants"""
+  --others                               with --train: RowBlockFn.train_hip and Decode.train_hip on for both variants
+  --raw                                  instead: raw tracks to predictions.  Net.forward_raw (resident store, flat RoIs) against
+                                         the dict route (data_raw.build_scenes(batched=True) -> generate_lane_roi_batch(device=True)
+                                         -> collate_fn -> Net.forward) on --scenes raw scenes of 21 tracks in the synthetic city of
+                                         tests/scene_build_cases.py, alternating call by call in one process: --reps repetitions of
+                                         the median of --steps calls, lowest - highest, and whether the outputs are equal"""
 import argparse
 import json
 import os
@@ -114,8 +119,60 @@ def train_mode(args):
     print(json.dumps(res), flush=True)
 
 
+def raw_mode(args):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import scene_build_cases as SC
+    from lanegcn_amd import data_lrcnn as D
+    from lanegcn_amd import data_raw
+    torch.manual_seed(0)
+    net = R.Net(R.config).cuda().eval()
+    maps = SC.golden_inputs(500)[1]
+    tables = {c: data_raw.LaneTable.from_lanes(m).to("cuda") for c, m in maps.items()}
+    raws, seed = [], 0
+    while len(raws) < args.scenes:      # scenes in which at least one agent keeps a lane RoI
+        r = SC.extra_scene(seed)
+        seed += 1
+        if len(D.generate_lane_roi_batch(data_raw.build_scenes([r], tables, net.config, batched=True), device=True)[0]["subgraphs"]):
+            raws.append(r)
+
+    def run(flat):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            if flat:
+                out = net.forward_raw(raws, tables)[0]
+            else:
+                scenes = D.generate_lane_roi_batch(data_raw.build_scenes(raws, tables, net.config, batched=True), device=True)
+                out = net(gen.collate_fn(scenes))
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    names = {"dict": False, "raw": True}
+    for _ in range(args.warmup):
+        for flat in names.values():
+            run(flat)
+    meds = {k: [] for k in names}
+    for _ in range(args.reps):
+        times = {k: [] for k in names}
+        for _ in range(args.steps):
+            for k, flat in names.items():
+                times[k].append(run(flat)[0])
+        for k in names:
+            meds[k].append(float(np.median(times[k])))
+    a, b = run(False)[1], run(True)[1]
+    rb = net.forward_raw(raws, tables)[1]["subgraphs"]
+    launches = {k: count_launches(lambda flat=flat: run(flat)) for k, flat in names.items()}
+    res = {"metric": "raw tracks -> lanercnn.Net predictions, %d scenes, %d RoIs, %d RoI nodes" % (len(raws), rb.n_rois, int(rb.roi_base[-1])),
+           "mma": ops.get_mma(), "steps": args.steps, "median_ms": meds,
+           "lowest_highest_ms": {k: [min(v), max(v)] for k, v in meds.items()}, "launches_per_call": launches,
+           "outputs_equal": bool(all(torch.equal(a[k], b[k]) for k in a))}
+    print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--raw", action="store_true")
+    ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--scenes", type=int, default=10)
     ap.add_argument("--agents", type=int, default=12)
     ap.add_argument("--roads", default="6,6,6")
@@ -129,6 +186,8 @@ def main():
         ops.set_mma(args.mma)
     if args.train:
         return train_mode(args)
+    if args.raw:
+        return raw_mode(args)
     torch.manual_seed(0)
     net = R.Net(R.config).cuda().eval()
     data = make_batch(args.scenes, args.agents, [int(v) for v in args.roads.split(",")])

@@ -3,6 +3,8 @@ lanegcn_amd.lanercnn.Decode beside a stock-op restatement of the reference's loo
 walk over the sorted nodes of every RoI with one host read per visited node, one .item() per agent, and the trajectory
 arithmetic as ~80 elementwise ATen launches.  Both share the module's weights and its LanePooling; the two heads of the
 stock side are F.linear + F.group_norm.  Prints the medians and one JSON line.  A number for DESIGN.md; no bar.
+The kernels' results at this shape (RoIs of 300 nodes and beyond: second passes of the 256-thread loops) are checked by
+tests/test_gpu_goal_decode_edges.py, not here.
 
   --agents N --nodes M   interest agents and nodes per RoI (default 32 x 300)
   --steps K --warmup W   timed and untimed forwards per variant, alternating call by call

@@ -1409,6 +1409,66 @@ int64_t lgcn_store_pack_table_elems(int64_t n_seg, int64_t n_src);
 int lgcn_store_pack(const lgcn_store_pack_t *p, void *stream);
 
 /*
+ * Resident lane-RoI store (lanegcn_amd/data_lrcnn.py: RoiStore): the lane RoIs of S scenes,
+ * extracted once, stay in device memory, and lgcn_roi_store_gather cuts the merged RoI graph (data_lrcnn.RoiBatch) and
+ * the per-RoI agent rows of any B picked scenes out of them in ONE launch.  Pure data movement: every output equals
+ * what the extraction gives for the picked scenes alone, byte for byte.
+ *
+ * lgcn_roi_store_t (device pointers, all read-only; scene s owns one block of node rows and one block of RoIs):
+ *   feats [n_nodes,8] fp32, node_mask [n_nodes] int32; agent_feat [n_rois,80], ctrs [n_rois,2], actor_feats, obs
+ *   [n_rois,20,3], gt_preds [n_rois,30,2] fp32, has_preds [n_rois,30] bytes (gt_preds and has_preds: both or neither,
+ *   NULL = the store has none); edge_u, edge_v [n_edges] int32, relation-major (pre 0..5, suc 0..5, left, right), the
+ *   scenes back to back inside a relation; a2m_u, a2m_v [n_a2m] int32, scene after scene.  All indices are SCENE-LOCAL:
+ *   the row within the block of the scene's RoI nodes, and for a2m_u the RoI's number within the scene.
+ *
+ * lgcn_roi_store_batch_t: B = n_scenes picked scenes (repeats allowed), G = 30 B index segments; segment q * B + j is
+ *   run q of the j-th picked scene: q = 0..13 u of relation q, q = 14..27 v of relation q - 14, q = 28 a2m_u, q = 29 a2m_v.
+ *   tab_host / tab_dev: the per-batch table, lgcn_roi_store_table_elems(B) = 4 B + 2 G + 3 int64, the same on the host
+ *   (validated) and on the device (read by the kernel):
+ *       node_off [B + 1], roi_off [B + 1]   prefix sums of the OUTPUT node rows / RoI rows, from 0 to n_nodes / n_rois
+ *       node_src [B], roi_src [B]           first node row / first RoI of the picked scene in the store
+ *       seg_off [G + 1]                     prefix sums of idx, from 0 to n_elem
+ *       seg_src [G]                         first element of the segment in edge_u / edge_v / a2m_u / a2m_v
+ *   Outputs (device): feats [n_nodes,8], node_mask [n_nodes] int64, agent_feat [n_rois,80], ctrs, actor_feats, obs,
+ *   gt_preds, has_preds as in the store, and idx [n_elem] int64 = the resident int32 + the base of the picked scene:
+ *   node_off[j], or roi_off[j] for a2m_u.  idx thus holds u (relation-major for the pick), v, a2m_u, a2m_v of the
+ *   pick's merged graph back to back.
+ *
+ * One launch over output elements (16-byte pieces of the float rows, 2-byte pieces of has_preds, one index each); a
+ * thread finds its scene / segment by binary search in the table, so B and G are not bounded by a wave, a workgroup or
+ * LDS.  Every element of every output is written.  No atomics, no allocation, no host synchronisation.
+ *
+ * Checked before anything is launched: NULL struct, a negative size, a NULL pointer next to a non-zero size, only one
+ * of gt_preds / has_preds, a prefix sum that does not start at 0, decreases or ends elsewhere than its total, a source
+ * run outside the store (LGCN_EINVAL); 2 n_nodes, 81 n_rois, n_elem, G or the table beyond 2^31 - 1 (LGCN_ESHAPE);
+ * pointers not aligned to 16 bytes (the float rows but ctrs, tab_dev), 8 bytes (ctrs, node_mask and idx of the batch,
+ * tab_host), 4 bytes (the resident int32 arrays) or 2 bytes (has_preds) (LGCN_EALIGN).  n_scenes == 0 with all totals 0
+ * returns LGCN_OK without a launch.
+ * lgcn_roi_store_table_elems: LGCN_EINVAL for a negative argument, LGCN_ESHAPE beyond 2^31 - 1 elements.
+ */
+typedef struct {
+    int64_t n_scenes, n_nodes, n_rois, n_edges, n_a2m;
+    const float *feats;
+    const int32_t *node_mask;
+    const float *agent_feat;
+    const int32_t *edge_u, *edge_v, *a2m_u, *a2m_v;
+    const float *ctrs, *actor_feats, *obs, *gt_preds;
+    const unsigned char *has_preds;
+} lgcn_roi_store_t;
+typedef struct {
+    int64_t n_scenes, n_nodes, n_rois, n_elem;
+    const int64_t *tab_host, *tab_dev;
+    float *feats;
+    int64_t *node_mask;
+    float *agent_feat;
+    int64_t *idx;
+    float *ctrs, *actor_feats, *obs, *gt_preds;
+    unsigned char *has_preds;
+} lgcn_roi_store_batch_t;
+int64_t lgcn_roi_store_table_elems(int64_t n_scenes);
+int lgcn_roi_store_gather(const lgcn_roi_store_t *s, const lgcn_roi_store_batch_t *b, void *stream);
+
+/*
  * Scene construction for a BATCH of raw scenes (lanegcn_amd/data_raw.py): tracks to actor arrays
  * (reference data.py:148-217, ArgoDataset.get_obj_feats) and map lanes to the scale-0 lane graph (data.py:220-361,
  * ArgoDataset.get_lane_graph up to :353; the dilated scales stay lgcn_bool_square*).

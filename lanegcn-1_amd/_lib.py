@@ -191,6 +191,26 @@ class StorePack(C.Structure):     # lgcn_store_pack_t
     ]
 
 
+class RoiStore(C.Structure):      # lgcn_roi_store_t
+    _fields_ = [
+        ("n_scenes", C.c_int64), ("n_nodes", C.c_int64), ("n_rois", C.c_int64), ("n_edges", C.c_int64), ("n_a2m", C.c_int64),
+        ("feats", C.c_void_p), ("node_mask", C.c_void_p), ("agent_feat", C.c_void_p),
+        ("edge_u", C.c_void_p), ("edge_v", C.c_void_p), ("a2m_u", C.c_void_p), ("a2m_v", C.c_void_p),
+        ("ctrs", C.c_void_p), ("actor_feats", C.c_void_p), ("obs", C.c_void_p), ("gt_preds", C.c_void_p),
+        ("has_preds", C.c_void_p),
+    ]
+
+
+class RoiStoreBatch(C.Structure):     # lgcn_roi_store_batch_t
+    _fields_ = [
+        ("n_scenes", C.c_int64), ("n_nodes", C.c_int64), ("n_rois", C.c_int64), ("n_elem", C.c_int64),
+        ("tab_host", C.c_void_p), ("tab_dev", C.c_void_p),
+        ("feats", C.c_void_p), ("node_mask", C.c_void_p), ("agent_feat", C.c_void_p), ("idx", C.c_void_p),
+        ("ctrs", C.c_void_p), ("actor_feats", C.c_void_p), ("obs", C.c_void_p), ("gt_preds", C.c_void_p),
+        ("has_preds", C.c_void_p),
+    ]
+
+
 class SceneTracks(C.Structure):    # lgcn_scene_tracks_t
     _fields_ = [
         ("n_scenes", C.c_int32), ("n_tracks", C.c_int32), ("n_rows", C.c_int32), ("pad_", C.c_int32),
@@ -368,6 +388,8 @@ SIGNATURES = {
     "lgcn_store_gather_pad": (C.c_int, [C.POINTER(Store), C.POINTER(StoreBatch), _P]),
     "lgcn_store_pack_table_elems": (C.c_int64, [_L, _L]),
     "lgcn_store_pack": (C.c_int, [C.POINTER(StorePack), _P]),
+    "lgcn_roi_store_table_elems": (C.c_int64, [_L]),
+    "lgcn_roi_store_gather": (C.c_int, [C.POINTER(RoiStore), C.POINTER(RoiStoreBatch), _P]),
     "lgcn_scene_tracks_ws_elems": (C.c_int64, [_L]),
     "lgcn_scene_tracks": (C.c_int, [C.POINTER(SceneTracks), _P]),
     "lgcn_scene_topo_elems": (C.c_int64, [_L, _L, _L]),

@@ -16,6 +16,9 @@
 // lgcn_store_pack (k_store_pack) is the write side: one launch packs index runs of int16 / int32 / int64 sources into the
 // store's int32 edge arrays and cuts rot / orig out of a batch's frame rows.  Same shape of kernel: the grid lies over
 // output words, a thread finds its run by binary search, the source descriptors are read from the device table.
+//
+// lgcn_roi_store_gather (k_roi_store_gather) is the fork's gather: the merged lane-RoI graph and the per-RoI agent rows of
+// any pick out of a resident RoI store whose indices are scene-local.  Same shape of kernel, three kinds of item.
 #include <cmath>
 
 #include "lgcn_common.hpp"
@@ -349,6 +352,167 @@ static int pack_validate(const lgcn_store_pack_t *p, uint32_t *frame_first, uint
     return LGCN_OK;
 }
 
+// ------------------------------------------------------------------ lgcn_roi_store_gather
+// The fork's counterpart: the lane RoIs of a split stay resident with SCENE-LOCAL int32 indices (row within the block of
+// the scene's RoI nodes; for a2m_u the RoI's number within the scene), and one launch cuts the merged graph of any pick
+// out of them: copy the run, add the base of the picked scene.
+constexpr int kRoiRel = 14;                       // induced relations of an RoI (pre 0..5, suc 0..5, left, right)
+constexpr int kRoiSegs = 2 * kRoiRel + 2;         // index runs per picked scene: u and v of each relation, a2m_u, a2m_v
+constexpr int kRoiAgentQuads = 20;                // float4 of one agent_feat row [80]
+constexpr int kRoiTrackQuads = 15;                // float4 of one actor_feats / obs [20,3] or gt_preds [30,2] row
+constexpr int kRoiHasPairs = kHasRow / 2;         // 2-byte pieces of one has_preds row (rows start on even bytes only)
+constexpr int kRoiSlots = kRoiAgentQuads + 2 * kRoiTrackQuads + 1;          // + ctrs: items of one RoI row without gt
+constexpr int kRoiSlotsGt = kRoiSlots + kRoiTrackQuads + kRoiHasPairs;      // + gt_preds, has_preds
+
+// the per-batch table, int64 (B picked scenes, G = 30 B segments ordered (run, scene): u of relation 0..13, v of
+// relation 0..13, a2m_u, a2m_v)
+struct RoiStoreTab {
+    const int64_t *node_off, *roi_off;      // [B + 1] prefix sums of the OUTPUT node rows / RoI rows
+    const int64_t *node_src, *roi_src;      // [B] first node row / first RoI of the picked scene in the store
+    const int64_t *seg_off;                 // [G + 1] prefix sums of idx
+    const int64_t *seg_src;                 // [G] first element of the segment in its resident array
+    int64_t total;
+};
+
+__host__ __device__ inline RoiStoreTab roi_store_tab(const int64_t *t, int64_t B) {
+    const int64_t G = kRoiSegs * B;
+    RoiStoreTab s;
+    s.node_off = t;
+    s.roi_off = s.node_off + B + 1;
+    s.node_src = s.roi_off + B + 1;
+    s.roi_src = s.node_src + B;
+    s.seg_off = s.roi_src + B;
+    s.seg_src = s.seg_off + G + 1;
+    s.total = 4 * B + 2 * G + 3;
+    return s;
+}
+
+// block ranges of the three kinds of item: node half-rows, RoI row pieces, index elements
+struct RoiStoreGrid {
+    uint32_t first[4];
+};
+
+__global__ __launch_bounds__(kStoreThreads) void k_roi_store_gather(const lgcn_roi_store_t s, const lgcn_roi_store_batch_t b,
+                                                                    const RoiStoreGrid g) {
+    const int B = (int)b.n_scenes;
+    const RoiStoreTab t = roi_store_tab(b.tab_dev, B);
+    const uint32_t blk = blockIdx.x;
+    int kind = 0;
+    while (kind < 2 && blk >= g.first[kind + 1]) ++kind;
+    const int64_t i = (int64_t)(blk - g.first[kind]) * kStoreThreads + threadIdx.x;
+
+    if (kind == 0) {                      // half a node row: 16 of the 32 bytes of feats; the first half widens node_mask
+        if (i >= 2 * b.n_nodes) return;
+        const int64_t row = i >> 1;
+        const int j = find_seg(t.node_off, B, row);
+        const int64_t r = t.node_src[j] + (row - t.node_off[j]);
+        reinterpret_cast<float4 *>(b.feats)[i] = reinterpret_cast<const float4 *>(s.feats)[2 * r + (i & 1)];
+        if ((i & 1) == 0) b.node_mask[row] = (int64_t)s.node_mask[r];
+    } else if (kind == 1) {               // one piece of an RoI row: a float4, the float2 of ctrs, two bytes of has_preds
+        const int slots = s.gt_preds != nullptr ? kRoiSlotsGt : kRoiSlots;
+        if (i >= b.n_rois * slots) return;
+        const int64_t a = i / slots;
+        int e = (int)(i - a * slots);
+        const int j = find_seg(t.roi_off, B, a);
+        const int64_t r = t.roi_src[j] + (a - t.roi_off[j]);
+        if (e < kRoiAgentQuads) {
+            reinterpret_cast<float4 *>(b.agent_feat)[a * kRoiAgentQuads + e] =
+                reinterpret_cast<const float4 *>(s.agent_feat)[r * kRoiAgentQuads + e];
+            return;
+        }
+        e -= kRoiAgentQuads;
+        if (e < kRoiTrackQuads) {
+            reinterpret_cast<float4 *>(b.actor_feats)[a * kRoiTrackQuads + e] =
+                reinterpret_cast<const float4 *>(s.actor_feats)[r * kRoiTrackQuads + e];
+            return;
+        }
+        e -= kRoiTrackQuads;
+        if (e < kRoiTrackQuads) {
+            reinterpret_cast<float4 *>(b.obs)[a * kRoiTrackQuads + e] = reinterpret_cast<const float4 *>(s.obs)[r * kRoiTrackQuads + e];
+            return;
+        }
+        e -= kRoiTrackQuads;
+        if (e == 0) {
+            reinterpret_cast<float2 *>(b.ctrs)[a] = reinterpret_cast<const float2 *>(s.ctrs)[r];
+            return;
+        }
+        e -= 1;
+        if (e < kRoiTrackQuads) {
+            reinterpret_cast<float4 *>(b.gt_preds)[a * kRoiTrackQuads + e] =
+                reinterpret_cast<const float4 *>(s.gt_preds)[r * kRoiTrackQuads + e];
+            return;
+        }
+        e -= kRoiTrackQuads;
+        reinterpret_cast<uint16_t *>(b.has_preds)[a * kRoiHasPairs + e] =
+            reinterpret_cast<const uint16_t *>(s.has_preds)[r * kRoiHasPairs + e];
+    } else {                              // one index element: resident int32 + the base of the picked scene
+        if (i >= b.n_elem) return;
+        const int64_t G = (int64_t)kRoiSegs * B;
+        const int64_t k = find_seg(t.seg_off, (int)G, i);
+        const int64_t r = t.seg_src[k] + (i - t.seg_off[k]);
+        const int run = (int)(k / B);                         // segment k = run * B + scene
+        const int j = (int)(k - (int64_t)run * B);
+        const int32_t *src = run < kRoiRel ? s.edge_u : run < 2 * kRoiRel ? s.edge_v : run == 2 * kRoiRel ? s.a2m_u : s.a2m_v;
+        const int64_t base = run == 2 * kRoiRel ? t.roi_off[j] : t.node_off[j];
+        b.idx[i] = (int64_t)src[r] + base;
+    }
+}
+
+static int roi_store_validate(const lgcn_roi_store_t *s, const lgcn_roi_store_batch_t *b, RoiStoreGrid *grid) {
+    if (s == nullptr || b == nullptr) return LGCN_EINVAL;
+    if (s->n_scenes < 0 || s->n_nodes < 0 || s->n_rois < 0 || s->n_edges < 0 || s->n_a2m < 0) return LGCN_EINVAL;
+    if (b->n_scenes < 0 || b->n_nodes < 0 || b->n_rois < 0 || b->n_elem < 0) return LGCN_EINVAL;
+    if (b->n_scenes == 0) return (b->n_nodes | b->n_rois | b->n_elem) ? LGCN_EINVAL : LGCN_OK;
+    const int64_t lim = 0x7fffffff;
+    if (b->n_nodes > lim / 2 || b->n_rois > lim / kRoiSlotsGt || b->n_elem > lim) return LGCN_ESHAPE;
+    if (lgcn_roi_store_table_elems(b->n_scenes) < 0) return LGCN_ESHAPE;       // (so G and the table fit 32 bits)
+    const int64_t B = b->n_scenes, G = kRoiSegs * B;
+    if ((s->gt_preds == nullptr) != (s->has_preds == nullptr)) return LGCN_EINVAL;
+    if (s->n_nodes > 0) { LGCN_CHECK_PTR(s->feats); LGCN_CHECK_PTR(s->node_mask); }
+    if (s->n_rois > 0) { LGCN_CHECK_PTR(s->agent_feat); LGCN_CHECK_PTR(s->ctrs); LGCN_CHECK_PTR(s->actor_feats); LGCN_CHECK_PTR(s->obs); }
+    if (s->n_edges > 0) { LGCN_CHECK_PTR(s->edge_u); LGCN_CHECK_PTR(s->edge_v); }
+    if (s->n_a2m > 0) { LGCN_CHECK_PTR(s->a2m_u); LGCN_CHECK_PTR(s->a2m_v); }
+    LGCN_CHECK_PTR(b->tab_host); LGCN_CHECK_PTR(b->tab_dev);
+    if (b->n_nodes > 0) { LGCN_CHECK_PTR(b->feats); LGCN_CHECK_PTR(b->node_mask); }
+    if (b->n_rois > 0) {
+        LGCN_CHECK_PTR(b->agent_feat); LGCN_CHECK_PTR(b->ctrs); LGCN_CHECK_PTR(b->actor_feats); LGCN_CHECK_PTR(b->obs);
+        if (s->gt_preds != nullptr) { LGCN_CHECK_PTR(b->gt_preds); LGCN_CHECK_PTR(b->has_preds); }
+    }
+    if (b->n_elem > 0) LGCN_CHECK_PTR(b->idx);
+    if (misaligned(b->tab_host, 7u)) return LGCN_EALIGN;
+
+    // the table, read on the host: nothing in it becomes an address before it is known to lie inside the store
+    const RoiStoreTab t = roi_store_tab(b->tab_host, B);
+    if (int rc = store_check_runs(t.node_off, t.node_src, B, b->n_nodes, s->n_nodes)) return rc;
+    if (int rc = store_check_runs(t.roi_off, t.roi_src, B, b->n_rois, s->n_rois)) return rc;
+    if (t.seg_off[0] != 0) return LGCN_EINVAL;
+    for (int64_t k = 0; k < G; ++k) {
+        const int64_t len = t.seg_off[k + 1] - t.seg_off[k], at = t.seg_src[k];
+        const int64_t limit = k < 2 * kRoiRel * B ? s->n_edges : s->n_a2m;
+        if (len < 0 || at < 0 || at > limit || len > limit - at) return LGCN_EINVAL;
+    }
+    if (t.seg_off[G] != b->n_elem) return LGCN_EINVAL;
+
+    const void *quads[] = {s->feats, s->agent_feat, s->actor_feats, s->obs, s->gt_preds, b->tab_dev, b->feats, b->agent_feat,
+                           b->actor_feats, b->obs, b->gt_preds};
+    for (const void *q : quads) LGCN_CHECK_ALIGN16(q);
+    if (misaligned(s->ctrs, 7u) || misaligned(b->ctrs, 7u) || misaligned(b->node_mask, 7u) || misaligned(b->idx, 7u)) return LGCN_EALIGN;
+    const void *words[] = {s->node_mask, s->edge_u, s->edge_v, s->a2m_u, s->a2m_v};
+    for (const void *q : words)
+        if (misaligned(q, 3u)) return LGCN_EALIGN;
+    if (misaligned(s->has_preds, 1u) || misaligned(b->has_preds, 1u)) return LGCN_EALIGN;
+
+    const int64_t items[3] = {2 * b->n_nodes, b->n_rois * (s->gt_preds != nullptr ? kRoiSlotsGt : kRoiSlots), b->n_elem};
+    int64_t at = 0;
+    for (int k = 0; k < 3; ++k) {
+        grid->first[k] = (uint32_t)at;
+        at += store_blocks(items[k]);
+    }
+    if (at > lim) return LGCN_ESHAPE;
+    grid->first[3] = (uint32_t)at;
+    return LGCN_OK;
+}
+
 }  // namespace lgcn
 
 using namespace lgcn;
@@ -411,6 +575,22 @@ int lgcn_store_pack(const lgcn_store_pack_t *p, void *stream) {
     if (int rc = pack_validate(p, &frame_first, &n_blocks)) return rc;
     if (n_blocks == 0) return LGCN_OK;
     hipLaunchKernelGGL(k_store_pack, dim3(n_blocks), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream), *p, frame_first);
+    return launch_status();
+}
+
+int64_t lgcn_roi_store_table_elems(int64_t n_scenes) {
+    if (n_scenes < 0) return LGCN_EINVAL;
+    const int64_t lim = 0x7fffffff;
+    if (n_scenes > lim / 64) return LGCN_ESHAPE;
+    const int64_t total = roi_store_tab(nullptr, n_scenes).total;
+    return total > lim ? (int64_t)LGCN_ESHAPE : total;
+}
+
+int lgcn_roi_store_gather(const lgcn_roi_store_t *s, const lgcn_roi_store_batch_t *b, void *stream) {
+    RoiStoreGrid grid;
+    if (int rc = roi_store_validate(s, b, &grid)) return rc;
+    if (b->n_scenes == 0 || grid.first[3] == 0) return LGCN_OK;
+    hipLaunchKernelGGL(k_roi_store_gather, dim3(grid.first[3]), dim3(kStoreThreads), 0, static_cast<hipStream_t>(stream), *s, *b, grid);
     return launch_status();
 }
 

@@ -281,16 +281,9 @@ class RoiBatch:
         return out
 
 
-def lane_roi_flat(t, off, horizon_buffer=20.):
-    """The lane RoIs of a batch straight from flat arrays -> RoiBatch.  t, off: the inputs of ops.RoiJob as they are (the
-    scenes' arrays concatenated on the device with scene-local int32 indices, and the host offset table of
-    include/lgcn.h).  roi_search / roi_nodes / roi_edge_count as generate_lane_roi_batch runs them, with its two size
-    read-backs, checks and messages; then ops.roi_edge_fill_graph at a relation-major edge_base writes the indices of the
-    merged graph, so that nothing is split per RoI or concatenated again: 11 kernel launches, one memset and one zero
-    fill per batch.  LgcnError, naming the scene, for a scene none of whose agents keeps an RoI (the list route fails
-    there later, on an assert of subgraph_bookkeeping)."""
-    if not torch.cuda.is_available():
-        raise L.LgcnError("data_lrcnn.lane_roi_flat needs a GPU (the lane-RoI kernels have no CPU fallback)")
+def _roi_extract(t, off, horizon_buffer, allow_empty):
+    """The body of lane_roi_flat -> the arguments of RoiBatch, in its order.  allow_empty (RoiStore): a scene none of whose
+    agents keeps an RoI is no error -- it simply owns no RoI; without a single RoI nothing more is launched."""
     job = ops.RoiJob(t, off, horizon_buffer)
     S, A_ = job.S, job.A
     if S == 0:
@@ -310,8 +303,13 @@ def lane_roi_flat(t, off, horizon_buffer=20.):
     R = len(valid)
     scene_of = np.searchsorted(agent_off, valid, side="right") - 1
     per_scene = np.bincount(scene_of, minlength=S)
-    if (per_scene == 0).any():
+    if (per_scene == 0).any() and not allow_empty:
         raise L.LgcnError("lane_roi_flat: scene %d has no lane RoI (every agent dropped)" % int(np.flatnonzero(per_scene == 0)[0]))
+    if R == 0:
+        i64 = lambda: torch.zeros(0, dtype=torch.int64, device=dev)
+        f32 = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        return (f32(0, 8), i64(), f32(0, 80), i64(), i64(), i64(), i64(), np.zeros(0, np.int64), scene_of, valid, agent_off,
+                np.zeros(0, np.float32), np.zeros(ops.ROI_REL + 1, np.int64), np.zeros((0, ops.ROI_REL + 1), np.int64))
     sizes = counts[valid].astype(np.int64)
     roi_base = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
     if roi_base[-1] > 0x7fffffff:
@@ -321,40 +319,64 @@ def lane_roi_flat(t, off, horizon_buffer=20.):
     cnt = ops.roi_edge_count(job).cpu().numpy().astype(np.int64)          # read-back 2: edge counts
     base, rel_ext, n_a2m = relation_major_tables(cnt)
     u, v, a2m_u, a2m_v = ops.roi_edge_fill_graph(job, torch.from_numpy(base).to(dev), int(rel_ext[-1]), n_a2m)
-    return RoiBatch(feats, node_mask, agent_feat, u, v, a2m_u, a2m_v, sizes, scene_of, valid, agent_off, vel[valid], rel_ext, cnt)
+    return feats, node_mask, agent_feat, u, v, a2m_u, a2m_v, sizes, scene_of, valid, agent_off, vel[valid], rel_ext, cnt
 
 
-def store_roi_inputs(store):
+def lane_roi_flat(t, off, horizon_buffer=20.):
+    """The lane RoIs of a batch straight from flat arrays -> RoiBatch.  t, off: the inputs of ops.RoiJob as they are (the
+    scenes' arrays concatenated on the device with scene-local int32 indices, and the host offset table of
+    include/lgcn.h).  roi_search / roi_nodes / roi_edge_count as generate_lane_roi_batch runs them, with its two size
+    read-backs, checks and messages; then ops.roi_edge_fill_graph at a relation-major edge_base writes the indices of the
+    merged graph, so that nothing is split per RoI or concatenated again: 11 kernel launches, one memset and one zero
+    fill per batch.  LgcnError, naming the scene, for a scene none of whose agents keeps an RoI (the list route fails
+    there later, on an assert of subgraph_bookkeeping)."""
+    if not torch.cuda.is_available():
+        raise L.LgcnError("data_lrcnn.lane_roi_flat needs a GPU (the lane-RoI kernels have no CPU fallback)")
+    return RoiBatch(*_roi_extract(t, off, horizon_buffer, False))
+
+
+def store_roi_inputs(store, scenes=None):
     """(t, off) of ops.RoiJob / lane_roi_flat from a flatfile.DeviceSceneStore that data_raw.build_store(..., lanes=True)
-    made, for ALL its scenes: the node and actor arrays are the store's own tensors; the int32 scene-local edges come out
-    of the store's relation-major edge_u / edge_v by one concatenation of 14 relation blocks (the store orders pre0, suc0,
-    pre1, ..., left, right; the RoI kernels pre 0..5, suc 0..5, left, right), the agents' steps and positions by one
-    strided copy each; the offset table from the store's host tables.  Nothing per scene.  LgcnError for a store without
-    the lane arrays."""
+    made, for ALL its scenes, or for the scenes [lo, hi) of scenes=(lo, hi): the node and actor arrays are the store's own
+    tensors (slices of them); the int32 scene-local edges come out of the store's relation-major edge_u / edge_v by one
+    concatenation of 14 relation blocks (the store orders pre0, suc0, pre1, ..., left, right; the RoI kernels pre 0..5,
+    suc 0..5, left, right), the agents' steps and positions by one strided copy each; the offset table from the store's
+    host tables.  Nothing per scene.  LgcnError for a store without the lane arrays."""
     la = getattr(store, "lane_arrays", None)
     if la is None:
         raise L.LgcnError("lane RoIs need the lane arrays of the store: build it with data_raw.build_store(..., lanes=True)")
     ns, S, a = store.num_scales, store.n_scenes, store._job.t
     if 2 * ns + 2 != ops.ROI_REL:
         raise L.LgcnError("lane RoIs need a store of 6 scales, got %d" % ns)
+    lo, hi = (0, S) if scenes is None else (int(scenes[0]), int(scenes[1]))
+    if not 0 <= lo <= hi <= S:
+        raise L.LgcnError("store_roi_inputs: scenes [%d, %d) of a store of %d" % (lo, hi, S))
     order = [2 * k for k in range(ns)] + [2 * k + 1 for k in range(ns)] + [2 * ns, 2 * ns + 1]
     ro = store.rel_off.tolist()
-    n_agents, n_lanes = np.diff(store.actor_off), np.diff(la["lane_off"])
+    cut = lambda tab: np.asarray(tab, np.int64)[lo:hi + 1] - int(tab[lo])       # the range's own prefix sums
+    node_off, actor_off, lane_off = cut(store.node_off), cut(store.actor_off), cut(la["lane_off"])
+    n_agents, n_lanes = np.diff(actor_off), np.diff(lane_off)
     csum = lambda sizes: np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
-    off = np.concatenate([store.node_off, la["lane_off"], store.actor_off, csum(n_agents * n_lanes), la["suc_off"], la["pre_off"],
-                          csum(np.diff(store.edge_off[order], axis=1).reshape(-1))])
+    off = np.concatenate([node_off, lane_off, actor_off, csum(n_agents * n_lanes), cut(la["suc_off"]), cut(la["pre_off"]),
+                          csum(np.diff(store.edge_off[order][:, lo:hi + 1], axis=1).reshape(-1))])
     if off.max() > 0x7fffffff:
         raise L.LgcnError("generate_lane_roi: the batch is too large for 32-bit offsets")
     cap = ops.roi_max_lanes()
-    if S and n_lanes.max() > cap:
+    if hi > lo and n_lanes.max() > cap:
         b = int(np.argmax(n_lanes))
-        raise L.LgcnError("generate_lane_roi: scene %d has %d lanes, the lane-RoI kernels take at most %d" % (b, n_lanes[b], cap))
-    t = dict(ctrs=a["node_ctrs"], feats=a["node_feats"], turn=a["turn"], control=a["control"], intersect=a["intersect"],
-             lane_idcs=la["lane_idcs"].to(torch.int32), a_ctrs=a["actor_ctrs"],
-             a_feats=a["actor_feats"][:, :, :2].contiguous(), a_obs=la["obs"][:, :, :2].contiguous(),
-             suc_pairs=la["suc_pairs"].to(torch.int32), pre_pairs=la["pre_pairs"].to(torch.int32),
-             edge_u=torch.cat([a["edge_u"][ro[k]:ro[k + 1]] for k in order]),
-             edge_v=torch.cat([a["edge_v"][ro[k]:ro[k + 1]] for k in order]))
+        raise L.LgcnError("generate_lane_roi: scene %d has %d lanes, the lane-RoI kernels take at most %d" % (lo + b, n_lanes[b], cap))
+    def rows(x, tab):         # rows of the range; the RoI kernels read 16-byte vectors, so a slice off that grid is copied
+        x = x[int(tab[lo]):int(tab[hi])]
+        return x if x.data_ptr() % 16 == 0 else x.clone()
+    nodes, actors = (lambda x: rows(x, store.node_off)), (lambda x: rows(x, store.actor_off))
+    eo = store.edge_off
+    edges = lambda x: torch.cat([x[ro[k] + int(eo[k, lo]):ro[k] + int(eo[k, hi])] for k in order])
+    t = dict(ctrs=nodes(a["node_ctrs"]), feats=nodes(a["node_feats"]), turn=nodes(a["turn"]), control=nodes(a["control"]),
+             intersect=nodes(a["intersect"]), lane_idcs=nodes(la["lane_idcs"]).to(torch.int32), a_ctrs=actors(a["actor_ctrs"]),
+             a_feats=actors(a["actor_feats"])[:, :, :2].contiguous(), a_obs=actors(la["obs"])[:, :, :2].contiguous(),
+             suc_pairs=rows(la["suc_pairs"], la["suc_off"]).to(torch.int32),
+             pre_pairs=rows(la["pre_pairs"], la["pre_off"]).to(torch.int32),
+             edge_u=edges(a["edge_u"]), edge_v=edges(a["edge_v"]))
     return t, off.astype(np.int32)
 
 
@@ -384,3 +406,329 @@ def generate_lane_roi(data, horizon_buffer=20., max_vel_threshold=2.78):
     occurrence; distance ties go to the smaller node index) and the limits."""
     generate_lane_roi_batch([data], horizon_buffer)
     return data
+
+
+# ------------------------------------------------------------------ the resident RoI store (DESIGN.md section 3.10)
+_I32_MAX = 2 ** 31 - 1
+_ROI_TABLES = ("first_roi", "node_off", "edge_off", "sizes", "agent_vel", "edge_cnt", "agent_ids")
+
+
+def _csum(x):
+    return np.concatenate([[0], np.cumsum(x, dtype=np.int64)])
+
+
+def roi_store_tables(n_scenes, sizes, scene_of, agent_ids, agent_vel, edge_cnt):
+    """Host tables of a RoiStore over n_scenes scenes from the per-RoI tables of an extraction (RoIs in scene order):
+    first_roi, node_off [S + 1] (first RoI / first node row of every scene), edge_off [15, S + 1] (per relation, then a2m:
+    prefix sums of the scenes' edges), and the per-RoI sizes [R], agent_vel [R] fp32, edge_cnt [R, 15], agent_ids [R]
+    (scene-local id of the RoI's agent).  A scene may hold 0 RoIs.  Plain numpy; needs no GPU."""
+    K = ops.ROI_REL + 1
+    sizes, scene_of, agent_ids = (np.asarray(x, np.int64).reshape(-1) for x in (sizes, scene_of, agent_ids))
+    edge_cnt = np.asarray(edge_cnt, np.int64).reshape(-1, K)
+    R, S = len(sizes), int(n_scenes)
+    if not (len(scene_of) == len(agent_ids) == len(edge_cnt) == len(np.asarray(agent_vel).reshape(-1)) == R):
+        raise L.LgcnError("RoiStore: the per-RoI tables must have one length")
+    if R and (scene_of.min() < 0 or scene_of.max() >= S or (np.diff(scene_of) < 0).any()):
+        raise L.LgcnError("RoiStore: RoIs out of scene order, or of a scene outside the store")
+    first_roi = _csum(np.bincount(scene_of, minlength=S))
+    node_off = _csum(sizes)[first_roi]
+    ends = np.concatenate([np.zeros((1, K), np.int64), np.cumsum(edge_cnt, 0, dtype=np.int64)])[first_roi]      # [S + 1, 15]
+    return dict(first_roi=first_roi, node_off=node_off, edge_off=np.ascontiguousarray(ends.T), sizes=sizes,
+                agent_vel=np.ascontiguousarray(agent_vel, np.float32).reshape(-1), edge_cnt=edge_cnt, agent_ids=agent_ids)
+
+
+class RoiPlan:
+    """Everything of one pick of a RoiStore that is not a device array: the table lgcn_roi_store_gather reads
+    (include/lgcn.h: node_off, roi_off [B + 1], node_src, roi_src [B], seg_off [30 B + 1], seg_src [30 B], int64), the
+    totals, and the host tables of the pick's RoiBatch."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def plan_roi_batch(tables, indices) -> RoiPlan:
+    """Host half of RoiStore.batch: from a store's tables (a dict or anything that holds them as attributes) and the picked
+    scenes to a RoiPlan.  Repeats and any order are allowed.  Vectorised numpy over the tables; needs no GPU.  LgcnError
+    for an empty pick, an index outside the store, a picked scene without an RoI (naming the scene) and totals beyond
+    2^31 - 1."""
+    get = (lambda k: tables[k]) if isinstance(tables, dict) or hasattr(tables, "files") else (lambda k: getattr(tables, k))
+    first_roi, node_off, edge_off = (np.asarray(get(k), np.int64) for k in ("first_roi", "node_off", "edge_off"))
+    K, Q = ops.ROI_REL, ops.ROI_STORE_SEGS
+    idx = np.asarray(indices)
+    if idx.size == 0:
+        raise L.LgcnError("RoiStore: an empty pick has no batch")
+    if idx.ndim != 1 or idx.dtype.kind not in "iu":
+        raise L.LgcnError("RoiStore: indices must be a flat sequence of integers")
+    idx = idx.astype(np.int64, copy=False)
+    S = len(first_roi) - 1
+    if int(idx.min()) < 0 or int(idx.max()) >= S:
+        raise L.LgcnError("RoiStore: scene index outside [0, %d)" % S)
+    roi_src, node_src = first_roi[idx], node_off[idx]
+    n_roi, n_node = first_roi[idx + 1] - roi_src, node_off[idx + 1] - node_src
+    if (n_roi == 0).any():
+        raise L.LgcnError("RoiStore: scene %d has no lane RoI (every agent dropped)" % int(idx[np.flatnonzero(n_roi == 0)[0]]))
+    B = len(idx)
+    G = Q * B
+    if B > _I32_MAX // 64:
+        raise L.LgcnError("RoiStore: a pick of %d scenes is past 32-bit offsets" % B)
+    lo = edge_off[:, idx]                                               # [15, B]
+    seg_len = edge_off[:, idx + 1] - lo
+    rel_at = np.concatenate([_csum(edge_off[:K, -1])[:K], [0]])         # where a relation starts in edge_u; a2m has its own arrays
+    seg_src = lo + rel_at[:, None]
+    runs = [slice(0, K), slice(0, K), slice(K, K + 1), slice(K, K + 1)]             # u, v, a2m_u, a2m_v
+    tab = np.empty(4 * B + 2 * G + 3, np.int64)
+    t_node_off, t_roi_off = tab[:B + 1], tab[B + 1:2 * B + 2]
+    tab[2 * B + 2:3 * B + 2], tab[3 * B + 2:4 * B + 2] = node_src, roi_src
+    t_seg_off, t_seg_src = tab[4 * B + 2:4 * B + G + 3], tab[4 * B + G + 3:]
+    t_node_off[0] = t_roi_off[0] = t_seg_off[0] = 0
+    np.cumsum(n_node, out=t_node_off[1:])
+    np.cumsum(n_roi, out=t_roi_off[1:])
+    np.cumsum(np.concatenate([seg_len[r] for r in runs]).reshape(-1), out=t_seg_off[1:])
+    t_seg_src[:] = np.concatenate([seg_src[r] for r in runs]).reshape(-1)
+    n_nodes, n_rois, n_elem = int(t_node_off[-1]), int(t_roi_off[-1]), int(t_seg_off[-1])
+    if 2 * n_nodes > _I32_MAX or 81 * n_rois > _I32_MAX or n_elem > _I32_MAX:
+        raise L.LgcnError("RoiStore: a batch of %d nodes, %d RoIs and %d index elements is past 32-bit offsets"
+                          % (n_nodes, n_rois, n_elem))
+    pick = np.repeat(roi_src - t_roi_off[:-1], n_roi) + np.arange(n_rois, dtype=np.int64)         # the store's RoI of every output RoI
+    rel_ext = _csum(seg_len[:K].sum(1))
+    return RoiPlan(n_scenes=B, n_nodes=n_nodes, n_rois=n_rois, n_edges=int(rel_ext[-1]), n_a2m=int(seg_len[K].sum()),
+                   n_elem=n_elem, table=tab, first_roi=t_roi_off.copy(), rois_per_scene=n_roi, rel_ext=rel_ext,
+                   scene_of=np.repeat(np.arange(B, dtype=np.int64), n_roi), sizes=np.asarray(get("sizes"), np.int64)[pick],
+                   agent_vel=np.asarray(get("agent_vel"), np.float32)[pick], edge_cnt=np.asarray(get("edge_cnt"), np.int64)[pick],
+                   agent_ids=np.asarray(get("agent_ids"), np.int64)[pick])
+
+
+def merge_roi_tables(parts) -> dict:
+    """Host half of RoiStore.concat: the tables of the store that holds the scenes of `parts` (RoiStores, dicts or loaded
+    `.npz` with the tables of roi_store_tables) in part order, and the runs that merge the parts' edge_u (or edge_v)
+    relation-major: seg_part, seg_at, seg_len [14 * P] in the order (relation, part).  LgcnError for an empty list."""
+    parts = list(parts)
+    if not parts:
+        raise L.LgcnError("RoiStore: concat of an empty list")
+    get = lambda p, k: p[k] if isinstance(p, dict) or hasattr(p, "files") else getattr(p, k)
+    i64 = lambda p, k: np.asarray(get(p, k), np.int64)
+    K, P = ops.ROI_REL, len(parts)
+    ends = {k: np.stack([i64(p, k)[..., -1] for p in parts]) for k in ("first_roi", "node_off", "edge_off")}     # [P] / [P, 15]
+    bases = {k: np.cumsum(v, 0) - v for k, v in ends.items()}
+    chain = lambda k: np.concatenate([[0]] + [i64(p, k)[1:] + base for p, base in zip(parts, bases[k])])
+    edge_off = np.concatenate([np.zeros((K + 1, 1), np.int64)] + [i64(p, "edge_off")[:, 1:] + b[:, None]
+                                                                 for p, b in zip(parts, bases["edge_off"])], 1)
+    rel = ends["edge_off"][:, :K]                                        # [P, 14]: a part's edges per relation
+    at = np.cumsum(rel, 1) - rel                                         # where the relation starts in the part's edge_u
+    out = dict(first_roi=chain("first_roi"), node_off=chain("node_off"), edge_off=edge_off,
+               sizes=np.concatenate([i64(p, "sizes") for p in parts]),
+               agent_vel=np.concatenate([np.asarray(get(p, "agent_vel"), np.float32).reshape(-1) for p in parts]),
+               edge_cnt=np.concatenate([i64(p, "edge_cnt").reshape(-1, K + 1) for p in parts]),
+               agent_ids=np.concatenate([i64(p, "agent_ids") for p in parts]))
+    out.update(seg_part=np.tile(np.arange(P, dtype=np.int64), K), seg_at=np.ascontiguousarray(at.T).reshape(-1),
+               seg_len=np.ascontiguousarray(rel.T).reshape(-1))
+    return out
+
+
+class RoiStore:
+    """The lane RoIs of a split, extracted ONCE and resident in device memory: `batch(indices)` hands the RoiBatch (and
+    the per-RoI agent rows) of any pick of scenes to lanercnn.Net from one small table upload and ONE launch
+    (ops.roi_store_gather), on the current stream, without a synchronisation or a device -> host read.
+
+    Device (ops.RoiStoreJob): feats [T, 8], node_mask [T] int32, agent_feat [R, 80]; edge_u, edge_v [E] int32,
+    relation-major (pre 0..5, suc 0..5, left, right) with the scenes back to back inside a relation; a2m_u, a2m_v [M]
+    int32; per RoI the rows of its agent: ctrs [R, 2], actor_feats, obs [R, 20, 3] and, both or neither, gt_preds
+    [R, 30, 2], has_preds [R, 30].  All indices are SCENE-LOCAL (row within the block of the scene's RoI nodes; a2m_u: the
+    RoI's number within the scene), so a gather is a copy plus one base per picked scene, and concat re-extracts nothing.
+    Host (numpy): the tables of roi_store_tables.  A scene none of whose agents keeps an RoI is in the store with 0 RoIs;
+    it cannot be picked (`usable()` lists the scenes that can)."""
+
+    # -------------------------------------------------------------- building
+    @classmethod
+    def from_arrays(cls, arrays, tables):
+        """A store over device tensors that already exist (nothing is copied) and the host tables that describe them."""
+        self = object.__new__(cls)
+        i64 = lambda x: np.ascontiguousarray(x, np.int64)
+        self.first_roi, self.node_off, self.edge_off = i64(tables["first_roi"]), i64(tables["node_off"]), i64(tables["edge_off"])
+        self.sizes, self.agent_ids = i64(tables["sizes"]).reshape(-1), i64(tables["agent_ids"]).reshape(-1)
+        self.edge_cnt = i64(tables["edge_cnt"]).reshape(-1, ops.ROI_REL + 1)
+        self.agent_vel = np.ascontiguousarray(tables["agent_vel"], np.float32).reshape(-1)
+        self.n_scenes = len(self.first_roi) - 1
+        arrays = dict(arrays)
+        if "has_preds" in arrays and arrays["has_preds"].dtype == torch.bool:
+            arrays["has_preds"] = arrays["has_preds"].view(torch.uint8)
+        self._job = job = ops.RoiStoreJob(arrays, self.n_scenes)
+        self.device, self.nbytes, p, K = job.device, job.nbytes, job.p, ops.ROI_REL
+        R = len(self.sizes)
+        if self.n_scenes < 0 or self.node_off.shape != (self.n_scenes + 1,) or self.edge_off.shape != (K + 1, self.n_scenes + 1) \
+                or not (len(self.agent_ids) == len(self.edge_cnt) == len(self.agent_vel) == R) \
+                or int(self.first_roi[-1]) != R or p.n_rois != R or int(self.node_off[-1]) != p.n_nodes \
+                or int(self.sizes.sum()) != p.n_nodes or int(self.edge_off[:K, -1].sum()) != p.n_edges \
+                or int(self.edge_off[K, -1]) != p.n_a2m or not np.array_equal(self.edge_cnt.sum(0), self.edge_off[:, -1]):
+            raise L.LgcnError("RoiStore: the tables do not describe the arrays")
+        return self
+
+    @classmethod
+    def from_inputs(cls, t, off, horizon_buffer=20., rows=None):
+        """The store of the scenes that (t, off) describe: the inputs of ops.RoiJob / lane_roi_flat, and the launches
+        lane_roi_flat runs (one shared body), once.  rows: the scenes' per-agent arrays on the device, concatenated in
+        scene order -- ctrs [A, 2], feats [A, 20, 3], obs_trajs [A, 20, 3] and, both or neither, gt_preds [A, 30, 2],
+        has_preds [A, 30] -- of which the store keeps the rows of the agents that keep an RoI.  rows=None: only what `t`
+        holds can be kept -- ctrs, and the (x, y) columns of feats / obs_trajs with the third column (the step flag,
+        which the RoI kernels do not read) zero; no gt.  Results, checks and messages are lane_roi_flat's, but for a scene
+        none of whose agents keeps an RoI, which is recorded as holding 0 RoIs."""
+        if not torch.cuda.is_available():
+            raise L.LgcnError("data_lrcnn.RoiStore needs a GPU (the lane-RoI kernels have no CPU fallback)")
+        feats, node_mask, agent_feat, u, v, a2m_u, a2m_v, sizes, scene_of, valid, agent_off, vel, _, cnt = \
+            _roi_extract(t, off, horizon_buffer, True)
+        S, K, dev = len(agent_off) - 1, ops.ROI_REL, feats.device
+        tb = roi_store_tables(S, sizes, scene_of, valid - agent_off[scene_of], vel, cnt)
+        # merged-graph indices -> scene-local: one subtraction per array, the owner's base from the host tables
+        node_base, roi_base = tb["node_off"][scene_of], tb["first_roi"][scene_of]              # per RoI: its scene's bases
+        rel_cnt, a2m_cnt = np.ascontiguousarray(cnt[:, :K].T).reshape(-1), cnt[:, K]
+        owner = np.concatenate([np.repeat(np.tile(node_base, K), rel_cnt), np.repeat(node_base, a2m_cnt), np.repeat(roi_base, a2m_cnt)])
+        owner = torch.from_numpy(owner).to(dev)
+        E, M = int(rel_cnt.sum()), int(a2m_cnt.sum())
+        arrays = dict(feats=feats, node_mask=node_mask.to(torch.int32), agent_feat=agent_feat,
+                      edge_u=(u - owner[:E]).to(torch.int32), edge_v=(v - owner[:E]).to(torch.int32),
+                      a2m_u=(a2m_u - owner[E + M:]).to(torch.int32), a2m_v=(a2m_v - owner[E:E + M]).to(torch.int32))
+        keep = torch.from_numpy(np.ascontiguousarray(valid, np.int64)).to(dev)
+        if rows is None:
+            pad = lambda x: torch.cat([x, torch.zeros_like(x[:, :, :1])], 2)
+            rows = dict(ctrs=t["a_ctrs"], feats=pad(t["a_feats"]), obs_trajs=pad(t["a_obs"]))
+        if ("gt_preds" in rows) != ("has_preds" in rows):
+            raise L.LgcnError("RoiStore: gt_preds and has_preds come together")
+        names = dict(ctrs="ctrs", actor_feats="feats", obs="obs_trajs", gt_preds="gt_preds", has_preds="has_preds")
+        for k, src in names.items():
+            if src in rows:
+                x = rows[src]
+                if not (torch.is_tensor(x) and x.is_cuda) or x.shape[0] != int(agent_off[-1]):
+                    raise L.LgcnError("RoiStore: rows[%r] must be a device tensor with one row per agent" % src)
+                x = x.view(torch.uint8) if x.dtype == torch.bool else x
+                arrays[k] = x.index_select(0, keep).contiguous()
+        return cls.from_arrays(arrays, tb)
+
+    @classmethod
+    def from_store(cls, store, horizon_buffer=20., chunk=None):
+        """The store of all scenes of a flatfile.DeviceSceneStore that data_raw.build_store(..., lanes=True) made
+        (store_roi_inputs); the per-RoI agent rows come from the store's own tensors.  chunk: scenes per extraction pass,
+        which bounds the workspace of lgcn_roi_search; the parts are merged by concat.  None: one pass."""
+        S = len(store)
+        if S == 0:
+            raise L.LgcnError("lane_roi_flat: no scene in the batch")
+        chunk = S if chunk is None else int(chunk)
+        if chunk < 1:
+            raise L.LgcnError("RoiStore.from_store: chunk must be positive")
+        la, a, parts = getattr(store, "lane_arrays", None), store._job.t, []
+        for lo in range(0, S, chunk):
+            hi = min(S, lo + chunk)
+            t, off = store_roi_inputs(store, (lo, hi))
+            cut = lambda x: x[int(store.actor_off[lo]):int(store.actor_off[hi])]
+            rows = dict(ctrs=cut(a["actor_ctrs"]), feats=cut(a["actor_feats"]), obs_trajs=cut(la["obs"]))
+            if store.has_gt:
+                rows.update(gt_preds=cut(a["gt_preds"]), has_preds=cut(a["has_preds"]))
+            with torch.cuda.device(store.device):
+                parts.append(cls.from_inputs(t, off, horizon_buffer, rows))
+        return parts[0] if len(parts) == 1 else cls.concat(parts)
+
+    @classmethod
+    def concat(cls, stores):
+        """One store that holds the scenes of `stores` in part order: the store of all those scenes extracted at once.
+        The relation-major edge arrays are merged by ONE ops.store_pack launch over P x 2 x 14 runs, every other array by
+        one concatenation, the tables on the host (merge_roi_tables).  LgcnError, before any launch: an empty list,
+        parts on different devices, or that differ in having gt_preds."""
+        stores = list(stores)
+        if not stores:
+            raise L.LgcnError("RoiStore: concat of an empty list")
+        if len({str(s.device) for s in stores}) != 1:
+            raise L.LgcnError("RoiStore: concat of parts on different devices")
+        if len({bool(s.has_gt) for s in stores}) != 1:
+            raise L.LgcnError("RoiStore: concat of parts with and without gt_preds")
+        m = merge_roi_tables(stores)
+        P, dev = len(stores), stores[0].device
+        parts = [s._job.t for s in stores]
+        with torch.cuda.device(dev):
+            arrays = {k: torch.cat([t[k] for t in parts]) for k in parts[0] if k not in ("edge_u", "edge_v")}
+            E = int(m["seg_len"].sum())
+            edges = torch.empty(2 * E, dtype=torch.int32, device=dev)
+            ops.store_pack([t["edge_u"] for t in parts] + [t["edge_v"] for t in parts],
+                           np.concatenate([m["seg_part"], m["seg_part"] + P]), np.tile(m["seg_at"], 2), np.tile(m["seg_len"], 2), edges)
+        arrays["edge_u"], arrays["edge_v"] = edges[:E], edges[E:]
+        return cls.from_arrays(arrays, m)
+
+    # -------------------------------------------------------------- the file
+    def save(self, path: str) -> None:
+        """Write the store as a plain `.npz` of its arrays and tables (one device -> host copy per array)."""
+        out = {k: getattr(self, k) for k in _ROI_TABLES}
+        for k, v in self._job.t.items():
+            out[k] = v.cpu().numpy()
+        if "has_preds" in out:
+            out["has_preds"] = out["has_preds"].view(bool)
+        np.savez(path, **out)
+
+    @classmethod
+    def load(cls, path: str, device=None):
+        """The store that save() wrote, resident on `device` (None: the current one).  load followed by save reproduces the
+        file's arrays byte for byte."""
+        if not torch.cuda.is_available():
+            raise L.LgcnError("data_lrcnn.RoiStore needs a GPU (the HIP hot path has no CPU fallback)")
+        dev = torch.device("cuda" if device is None else device)
+        if dev.index is None:
+            dev = torch.device(dev.type, torch.cuda.current_device())
+        with np.load(path) as f:
+            tables = {k: f[k] for k in _ROI_TABLES}
+            host = {k: np.ascontiguousarray(f[k]) for k in f.files if k not in _ROI_TABLES}
+        if "has_preds" in host:
+            host["has_preds"] = host["has_preds"].view(np.uint8)
+        self = cls.from_arrays({k: torch.from_numpy(v).to(dev) for k, v in host.items()}, tables)
+        torch.cuda.synchronize(dev)              # resident before any stream reads it
+        return self
+
+    # -------------------------------------------------------------- reading
+    def __len__(self):
+        return self.n_scenes
+
+    @property
+    def has_gt(self) -> bool:
+        return self._job.has_gt
+
+    @property
+    def n_rois(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def rois_per_scene(self) -> np.ndarray:
+        return np.diff(self.first_roi)
+
+    def usable(self) -> np.ndarray:
+        """The scenes that hold at least one RoI -- the ones a sampler may pick."""
+        return np.flatnonzero(self.rois_per_scene > 0)
+
+    def plan(self, indices) -> RoiPlan:
+        return plan_roi_batch(self, indices)
+
+    def batch(self, indices, plan: RoiPlan = None):
+        """-> (RoiBatch, rows) of the picked scenes, as lane_roi_flat gives the RoiBatch for those scenes alone, but for
+        agents = arange(R') and agent_off = first_roi' (the rows hold the kept agents only, so valid_agent_ids(b) is
+        arange(R_b)).  rows: the gathered per-RoI agent arrays ctrs [R', 2], feats, obs_trajs [R', 20, 3] and, if the store
+        has them, gt_preds [R', 30, 2], has_preds [R', 30] bool; and agent_ids, per picked scene the original scene-local
+        ids (int16) of its kept agents.  One table upload from pinned memory and one launch on the current stream; no
+        synchronisation, no device -> host read.  `plan`: this pick's plan(), if the caller already has it."""
+        p = self.plan(indices) if plan is None else plan
+        T, R, dev = p.n_nodes, p.n_rois, self.device
+        f32, i64 = torch.float32, torch.int64
+        with torch.cuda.device(dev):
+            stage = torch.empty(p.table.size, dtype=i64, pin_memory=True)          # staging of its own, as DeviceSceneStore.batch
+            stage.numpy()[:] = p.table
+            tab_dev = torch.empty(p.table.size, dtype=i64, device=dev)
+            tab_dev.copy_(stage, non_blocking=True)
+            new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+            out = dict(feats=new((T, 8), f32), node_mask=new((T,), i64), agent_feat=new((R, 80), f32), idx=new((p.n_elem,), i64),
+                       ctrs=new((R, 2), f32), actor_feats=new((R, 20, 3), f32), obs=new((R, 20, 3), f32))
+            if self.has_gt:
+                out.update(gt_preds=new((R, 30, 2), f32), has_preds=new((R, 30), torch.bool))
+            ops.roi_store_gather(self._job, stage, tab_dev, p.n_scenes, T, R, p.n_elem, out)
+        E, M, idx = p.n_edges, p.n_a2m, out["idx"]
+        rb = RoiBatch(out["feats"], out["node_mask"], out["agent_feat"], idx[:E], idx[E:2 * E], idx[2 * E:2 * E + M],
+                      idx[2 * E + M:], p.sizes, p.scene_of, np.arange(R, dtype=np.int64), p.first_roi, p.agent_vel, p.rel_ext,
+                      p.edge_cnt)
+        rows = dict(ctrs=out["ctrs"], feats=out["actor_feats"], obs_trajs=out["obs"],
+                    agent_ids=np.split(p.agent_ids.astype(np.int16), p.first_roi[1:-1]))
+        if self.has_gt:
+            rows.update(gt_preds=out["gt_preds"], has_preds=out["has_preds"])
+        return rb, rows

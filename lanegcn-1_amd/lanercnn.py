@@ -507,15 +507,9 @@ class Net(nn.Module):
         store's arrays, valid_agent_ids (int16, S views of one upload) -- and "subgraphs", the RoiBatch.  Errors: build_store's, the RoI
         stage's, and LgcnError naming the scene when every agent of a scene drops."""
         from . import data_lrcnn, data_raw
-        from .engine import flat_graph
         store = data_raw.build_store(raws, tables, self.config, lane_ids=lane_ids, lanes=True)
         rb = data_lrcnn.lane_roi_flat(*data_lrcnn.store_roi_inputs(store), horizon_buffer)
-        fb, _ = store.batch(np.arange(len(store)))
-        graph = flat_graph(fb)
-        sizes = [int(n) for n in fb.node_sizes]
-        graph["num_nodes"] = sizes
-        graph["counts"] = [int(v) for v in np.cumsum([0] + sizes[:-1])]
-        graph["pose"] = list(torch.cat([fb.node_ctrs, fb.node_feats], -1).split(sizes))
+        graph, fb = self._store_graph(store, np.arange(len(store)))
         a, n_act = store._job.t, np.diff(store.actor_off).tolist()
         ids = torch.from_numpy((rb.agents - rb.agent_off[rb.scene_of]).astype(np.int16)).to(fb.node_ctrs.device)
         data = {"ctrs": list(a["actor_ctrs"].split(n_act)), "feats": list(a["actor_feats"].split(n_act)),
@@ -524,6 +518,40 @@ class Net(nn.Module):
         if store.has_gt:
             data["gt_preds"] = list(a["gt_preds"].split(n_act))
             data["has_preds"] = list(a["has_preds"].view(torch.bool).split(n_act))
+        return self._modules_forward(graph, subgraph_gather(rb), data), data
+
+    @staticmethod
+    def _store_graph(store, indices):
+        """The main graph of a pick of a DeviceSceneStore as the modules read it: engine.flat_graph of store.batch(indices)
+        plus the fork's num_nodes / counts / pose -> (graph, the FlatBatch)."""
+        from .engine import flat_graph
+        fb, _ = store.batch(indices)
+        graph = flat_graph(fb)
+        sizes = [int(n) for n in fb.node_sizes]
+        graph["num_nodes"] = sizes
+        graph["counts"] = [int(v) for v in np.cumsum([0] + sizes[:-1])]
+        graph["pose"] = list(torch.cat([fb.node_ctrs, fb.node_feats], -1).split(sizes))
+        return graph, fb
+
+    def forward_store(self, store, rois, indices):
+        """The fork's predictions for a pick of scenes from two RESIDENT stores -> (out, data): `store`, a
+        flatfile.DeviceSceneStore (the main graph: store.batch(indices), one launch), and `rois`, the data_lrcnn.RoiStore
+        of the same scenes (the lane RoIs: rois.batch(indices), one launch) -- no lane search, no device -> host read
+        before the modules.  Repeats and any order are allowed; every picked scene must hold an RoI (rois.usable()).
+        `out`: what forward_raw gives for the picked scenes alone.  `data`: ctrs, feats, obs_trajs and, with gt,
+        gt_preds / has_preds as per-scene views of the gathered per-RoI rows (the kept agents only, so valid_agent_ids
+        is an int16 arange per scene), agent_ids (the original scene-local ids) and "subgraphs", the RoiBatch; Loss works
+        on the pair.  Follows the autograd context as forward() does."""
+        if len(store) != len(rois):
+            raise L.LgcnError("forward_store: the scene store holds %d scenes, the RoI store %d" % (len(store), len(rois)))
+        plan = rois.plan(indices)                 # first: it names a picked scene without an RoI before anything is launched
+        graph, fb = self._store_graph(store, indices)
+        rb, rows = rois.batch(indices, plan=plan)
+        per = rb.rois_per_scene.tolist()
+        ids = np.arange(rb.n_rois, dtype=np.int64) - np.repeat(rb.first_roi[:-1], rb.rois_per_scene)
+        ids = torch.from_numpy(ids.astype(np.int16)).to(fb.node_ctrs.device)
+        data = {k: list(rows[k].split(per)) for k in ("ctrs", "feats", "obs_trajs", "gt_preds", "has_preds") if k in rows}
+        data.update(valid_agent_ids=list(ids.split(per)), agent_ids=rows["agent_ids"], subgraphs=rb)
         return self._modules_forward(graph, subgraph_gather(rb), data), data
 
     def _modules_forward(self, graph: Dict, graph_roi: Dict, data: Dict) -> Dict[str, Tensor]:

@@ -2514,6 +2514,85 @@ def store_pack(sources, seg_src, seg_at, seg_len, dst: torch.Tensor, frame: torc
     return store_pack_launch(StorePackJob(sources, seg_src, seg_at, seg_len, dst, frame, rot, orig))
 
 
+# ------------------------------------------------------------------ resident lane-RoI store (data_lrcnn.RoiStore)
+ROI_STORE_SEGS = 2 * ROI_REL + 2        # index runs per picked scene: u and v of the 14 relations, a2m_u, a2m_v
+
+
+def roi_store_table_elems(n_scenes: int) -> int:
+    """int64 entries of the per-batch table of lgcn_roi_store_gather for n_scenes picked scenes."""
+    n = int(L.load().lgcn_roi_store_table_elems(int(n_scenes)))
+    if n < 0:
+        L.check(n, "lgcn_roi_store_table_elems")
+    return n
+
+
+class RoiStoreJob:
+    """A resident RoI store's lgcn_roi_store_t with the device tensors it points to.  ``t``: feats [T,8] fp32, node_mask
+    [T] int32, agent_feat [R,80], ctrs [R,2], actor_feats, obs [R,20,3] fp32, edge_u, edge_v [E], a2m_u, a2m_v [M] int32
+    (scene-local) and, both or neither, gt_preds [R,30,2] fp32 and has_preds [R,30] uint8."""
+    FLOATS = ("feats", "agent_feat", "ctrs", "actor_feats", "obs")
+    INTS = ("node_mask", "edge_u", "edge_v", "a2m_u", "a2m_v")
+
+    def __init__(self, t: dict, n_scenes: int):
+        kinds = {k: torch.float32 for k in self.FLOATS}
+        kinds.update({k: torch.int32 for k in self.INTS})
+        if ("gt_preds" in t) != ("has_preds" in t):
+            raise L.LgcnError("roi store: gt_preds and has_preds come together")
+        if "gt_preds" in t:
+            kinds.update(gt_preds=torch.float32, has_preds=torch.uint8)
+        self.t = {k: _dev(t[k], dt, "roi store " + k) for k, dt in kinds.items()}
+        T, R = self.t["node_mask"].numel(), self.t["agent_feat"].shape[0]
+        shapes = dict(feats=(T, 8), agent_feat=(R, 80), ctrs=(R, 2), actor_feats=(R, 20, 3), obs=(R, 20, 3),
+                      edge_v=tuple(self.t["edge_u"].shape), a2m_v=tuple(self.t["a2m_u"].shape), gt_preds=(R, 30, 2),
+                      has_preds=(R, 30))
+        for k, v in self.t.items():
+            if k in shapes and tuple(v.shape) != shapes[k]:
+                raise L.LgcnError("roi store: %s must be %s, got %s" % (k, shapes[k], tuple(v.shape)))
+        p = self.p = L.RoiStore()
+        p.n_scenes, p.n_nodes, p.n_rois = int(n_scenes), T, R
+        p.n_edges, p.n_a2m = self.t["edge_u"].numel(), self.t["a2m_u"].numel()
+        for k, v in self.t.items():
+            setattr(p, k, v.data_ptr() if v.numel() else None)
+        self.has_gt = "gt_preds" in self.t
+        self.device = self.t["feats"].device
+        self.nbytes = sum(v.numel() * v.element_size() for v in self.t.values())
+
+
+def roi_store_gather(job: RoiStoreJob, tab_host: torch.Tensor, tab_dev: torch.Tensor, n_scenes: int, n_nodes: int,
+                     n_rois: int, n_elem: int, out: dict) -> None:
+    """lgcn_roi_store_gather: one launch on the current stream fills ``out`` (name -> device tensor, the output fields
+    of lgcn_roi_store_batch_t) with the pick that the table describes.  ``tab_host``: the int64 table on the host,
+    validated by the library before the launch; ``tab_dev``: the same words on the device (the caller has queued the
+    copy on the current stream)."""
+    if tab_host.is_cuda or tab_host.dtype != torch.int64 or not tab_host.is_contiguous():
+        raise L.LgcnError("roi_store_gather: tab_host must be a contiguous int64 host tensor")
+    tab_dev = _dev(tab_dev, torch.int64, "roi store tab_dev")
+    if tab_dev.device != job.device or tab_dev.device.index != torch.cuda.current_device():
+        raise L.LgcnError("roi_store_gather: the store lives on %s, which is not the current device" % (job.device,))
+    if tab_host.numel() != tab_dev.numel() or tab_host.numel() != roi_store_table_elems(n_scenes):
+        raise L.LgcnError("roi_store_gather: the table must hold lgcn_roi_store_table_elems(n_scenes) entries")
+    b = L.RoiStoreBatch()
+    b.n_scenes, b.n_nodes, b.n_rois, b.n_elem = n_scenes, n_nodes, n_rois, n_elem
+    b.tab_host, b.tab_dev = tab_host.data_ptr(), tab_dev.data_ptr()
+    f32, i64 = torch.float32, torch.int64
+    want = dict(feats=(f32, 8 * n_nodes), node_mask=(i64, n_nodes), agent_feat=(f32, 80 * n_rois), idx=(i64, n_elem),
+                ctrs=(f32, 2 * n_rois), actor_feats=(f32, 60 * n_rois), obs=(f32, 60 * n_rois))
+    if job.has_gt:
+        want.update(gt_preds=(f32, 60 * n_rois), has_preds=(None, 30 * n_rois))
+    if set(out) != set(want):
+        raise L.LgcnError("roi_store_gather: outputs must be %s, got %s" % (sorted(want), sorted(out)))
+    for k, v in out.items():
+        dt, n = want[k]
+        if not v.is_cuda or not v.is_contiguous() or v.device != job.device:
+            raise L.LgcnError("roi_store_gather: %s must be a contiguous CUDA tensor on the store's device (the HIP hot "
+                              "path has no CPU fallback)" % k)
+        if v.numel() != n or (v.dtype != dt if dt is not None else v.element_size() != 1):
+            raise L.LgcnError("roi_store_gather: %s must hold %d elements of %s, got %d of %s"
+                              % (k, n, dt or "one byte", v.numel(), v.dtype))
+        setattr(b, k, v.data_ptr() if n else None)
+    L.check(L.load().lgcn_roi_store_gather(C.byref(job.p), C.byref(b), _stream()), "lgcn_roi_store_gather")
+
+
 # ------------------------------------------------------------------ scene construction (data_raw: get_obj_feats / get_lane_graph)
 def _i32_table(off, what):
     import numpy as np

@@ -1,10 +1,14 @@
 """Raw scenes to a resident store and a flat file, on the device: the job of the reference's preprocess_data.py.
 
-    python tools/build_store.py --out split.npz [--raws raws.npz --tables tables.npz] [--batch 32] [--scenes 256]
+    python tools/build_store.py --out split.npz [--rois rois.npz] [--raws raws.npz --tables tables.npz] [--batch 32] [--scenes 256]
 
 Per batch of `--batch` raw scenes one data_raw.build_store, then ONE DeviceSceneStore.concat and ONE save: no scene dict
 and no copy to the host before the save's one copy per array.  The file is what flatfile.write_scenes(..., theta=True)
 writes for the same scenes; FlatSceneFile and DeviceSceneStore read it.
+
+--rois OUT.npz also extracts the fork's lane RoIs: every batch is built with lanes=True and its data_lrcnn.RoiStore made
+right after it, while the batch's lane arrays exist (they are never saved and do not survive the concat); ONE
+RoiStore.concat and ONE save at the end.  data_lrcnn.RoiStore.load reads the file; scene i of it is scene i of --out.
 
 Inputs are plain `.npz` files (the reader of the Argoverse CSVs and the map API stay out of scope):
   --raws    city [S] (strings), trk_off [S + 1] (tracks per scene, the agent first), row_off [T + 1] (rows per track),
@@ -58,17 +62,21 @@ def read_inputs(raws_path, tables_path):
     return raws, tables
 
 
-def build(raws, tables, config, batch):
-    """-> (the store of all `raws`, its parts): build_store per batch of `batch` scenes, one concat."""
+def build(raws, tables, config, batch, rois=False):
+    """-> (the store of all `raws`, its parts, the RoiStore of all `raws` or None): build_store per batch of `batch` scenes
+    and, with rois, the batch's RoiStore while its lane arrays exist; one concat each."""
     from lanegcn_amd import data_raw as D
+    from lanegcn_amd.data_lrcnn import RoiStore
     from lanegcn_amd.flatfile import DeviceSceneStore
-    parts = [D.build_store(raws[i:i + batch], tables, config) for i in range(0, len(raws), batch)]
-    return DeviceSceneStore.concat(parts), parts
+    parts = [D.build_store(raws[i:i + batch], tables, config, lanes=rois) for i in range(0, len(raws), batch)]
+    roi_store = RoiStore.concat([RoiStore.from_store(p) for p in parts]) if rois else None
+    return DeviceSceneStore.concat(parts), parts, roi_store
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
+    ap.add_argument("--rois", help="also write the lane-RoI store of the same scenes (data_lrcnn.RoiStore) to this .npz")
     ap.add_argument("--raws")
     ap.add_argument("--tables")
     ap.add_argument("--batch", type=int, default=32)
@@ -89,12 +97,18 @@ def main():
     tables = {k: v.to("cuda") for k, v in tables.items()}
     config = {"pred_range": args.pred_range, "num_scales": args.num_scales, "cross_dist": args.cross_dist}
     t0 = time.perf_counter()
-    store, parts = build(raws, tables, config, args.batch)
+    store, parts, rois = build(raws, tables, config, args.batch, rois=args.rois is not None)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     store.save(args.out)
+    extra = {}
+    if rois is not None:
+        rois.save(args.rois)
+        extra = {"rois_out": args.rois if args.rois.endswith(".npz") else args.rois + ".npz", "rois": rois.n_rois,
+                 "roi_nodes": int(rois.node_off[-1]), "usable_scenes": int(len(rois.usable())),
+                 "roi_store_mb": round(rois.nbytes / 1e6, 2)}
     t2 = time.perf_counter()
-    print(json.dumps({"out": args.out if args.out.endswith(".npz") else args.out + ".npz", "scenes": len(store), "parts": len(parts),
+    print(json.dumps({**extra, "out": args.out if args.out.endswith(".npz") else args.out + ".npz", "scenes": len(store), "parts": len(parts),
                       "nodes": int(store.node_off[-1]), "actors": int(store.actor_off[-1]), "edges": int(store.rel_off[-1]),
                       "store_mb": round(store.nbytes / 1e6, 2), "build_ms": round((t1 - t0) * 1e3, 1),
                       "save_ms": round((t2 - t1) * 1e3, 1)}))

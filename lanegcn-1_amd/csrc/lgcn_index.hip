@@ -79,77 +79,15 @@ __device__ __forceinline__ bool within(float ax, float ay, float cx, float cy, f
     return __fsqrt_rn(d2) <= th;
 }
 
-// One wave per target row.  PASS 0 counts, PASS 1 writes (hi, wi) and the segment table of the later
-// index_add_(0, hi, .):  rowptr_q[h] = first p with hi[p] >= h.  hi is non-decreasing and a row g of a scene that
-// advances the numbering owns h = hval(g), so rowptr_q[hval(g)] = rowptr[g]; rows of scenes that do not advance
-// it (legacy: scenes without pairs) fill the tail [h_used, T), where no pair can follow: P.  rowptr_q[T] = P.
-template <int PASS>
-__device__ __forceinline__ void pairs_rows_body(const float2 *agt, const int32_t *agt_off,
-                                                const float2 *ctx, const int32_t *ctx_off,
-                                                int n_scenes, int n_agt, int n_ctx, float th,
-                                                int32_t *rowcnt, const int32_t *rowptr,
-                                                const int32_t *hi_base, const int32_t *wi_base,
-                                                int32_t *hi, int32_t *wi, int64_t cap, int legacy,
-                                                int32_t *rowptr_q, int row_block) {
-    const int lane = threadIdx.x & 63;
-    const int g = row_block * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (g >= n_agt) return;
-    const int sc = find_seg(agt_off, n_scenes, g);
-    // offset tables are caller data: a table that does not describe this job (stale memory under a captured graph)
-    // must not take a load or a store out of bounds
-    int c0 = ctx_off[sc], c1 = ctx_off[sc + 1];
-    c0 = c0 < 0 ? 0 : c0 > n_ctx ? n_ctx : c0;
-    c1 = c1 < c0 ? c0 : c1 > n_ctx ? n_ctx : c1;
-    const float2 a = agt[g];
-    int count = 0;
-    int64_t pos = 0;
-    int hval = 0, wbase = 0;
-    if (PASS == 1) {
-        pos = rowptr[g];
-        hval = g - agt_off[sc] + hi_base[sc];
-        wbase = wi_base[sc] - c0;
-        if (lane == 0) {
-            const int P = rowptr[n_agt];
-            int s0 = agt_off[sc], s1 = agt_off[sc + 1];
-            s0 = s0 < 0 ? 0 : s0 > n_agt ? n_agt : s0;
-            s1 = s1 < s0 ? s0 : s1 > n_agt ? n_agt : s1;
-            const bool advances = !legacy || rowptr[s1] - rowptr[s0] > 0;
-            const int q2 = hi_base[n_scenes] + g - hi_base[sc];
-            // a capacity below the true pair count (n_pairs comes back negative): the segment table describes the pairs
-            // that were kept, [0, cap) -- whatever walks it afterwards stays inside the caller's [cap, .] buffers
-            const int Pc = (int64_t)P > cap ? (int)cap : P;
-            if (advances) { if (hval >= 0 && hval <= n_agt) rowptr_q[hval] = pos > cap ? (int)cap : (int)pos; }
-            else if (q2 >= 0 && q2 <= n_agt) rowptr_q[q2] = Pc;
-            if (g == 0) rowptr_q[n_agt] = Pc;
-        }
-    }
-    for (int s0 = c0; s0 < c1; s0 += 64) {
-        const int s = s0 + lane;
-        bool ok = false;
-        if (s < c1) {
-            const float2 c = ctx[s];
-            ok = within(a.x, a.y, c.x, c.y, th);
-        }
-        const unsigned long long m = __ballot(ok);
-        if (PASS == 0) {
-            count += __popcll(m);
-        } else {
-            if (ok) {
-                const int64_t o = pos + __popcll(m & ((1ull << lane) - 1ull));
-                if (o < cap) { hi[o] = hval; wi[o] = s + wbase; }
-            }
-            pos += __popcll(m);
-        }
-    }
-    if (PASS == 0 && lane == 0) rowcnt[g] = count;
-}
-
-// Workspace layout of one pair search: rowptr_true [T+1] | hi_base [B+1] | wi_base [B]
+// Workspace layout of one pair search: rowptr_true [T+1] | hi_base [B+1] | wi_base [B].  The count pass leaves the rows'
+// raw counts in the caller's segment table rowptr_q [T+1] (an output that the fill pass writes in full afterwards), so
+// that the scan reads counts that no workgroup of its own launch overwrites.
 struct PairsJob {
     const float2 *agt; const int32_t *agt_off;
     const float2 *ctx; const int32_t *ctx_off;
     int n_scenes, n_agt, n_ctx, legacy;
     float th;
+    int lanes;                  // lanes per target row in the row passes: kShortLanes or 64 (pairs_row_lanes)
     int32_t *hi, *wi;
     int64_t cap;
     int32_t *n_pairs, *rowptr_q, *ws;
@@ -159,52 +97,189 @@ struct PairsJob {
 };
 struct PairsJobs { PairsJob j[4]; };
 
+// How many lanes a job gives each target row: kShortLanes at or below a mean context-list length (n_ctx / n_scenes) of
+// kShortMeanCtx, a whole wave above it.  The rule only chooses speed; every width gives the same words for any list.
+// Measured at S2 (mean list 50), count + fill launch: 64 lanes 9.3 + 9.0 us, 16 lanes 8.3 + 6.2, 8 lanes 8.4 + 6.8, 4 lanes
+// 8.5 + 8.5, one lane per row 9.8 + 16.9 (the row's serial walk of its list: 50 correctly rounded square roots).
+constexpr int kShortLanes = 16;
+constexpr int kShortMeanCtx = 64;       // four trips of the short body
+constexpr int kOffLds = 256;            // the row passes search agt_off in LDS when its n_scenes + 1 words fit
+static inline int pairs_row_lanes(int64_t n_ctx, int n_scenes) {
+    return n_ctx <= (int64_t)kShortMeanCtx * n_scenes ? kShortLanes : 64;
+}
+static inline int64_t pairs_row_blocks(int64_t n_agt, int lanes) {      // 256 / lanes rows per workgroup
+    const int rows = 256 / lanes;
+    return (n_agt + rows - 1) / rows;
+}
+
+// The context range of scene sc.  Offset tables are caller data: a table that does not describe this job (stale memory
+// under a captured graph) must not take a load or a store out of bounds.
+__device__ __forceinline__ void ctx_range(const PairsJob &j, int sc, int &c0, int &c1) {
+    c0 = j.ctx_off[sc]; c1 = j.ctx_off[sc + 1];
+    c0 = c0 < 0 ? 0 : c0 > j.n_ctx ? j.n_ctx : c0;
+    c1 = c1 < c0 ? c0 : c1 > j.n_ctx ? j.n_ctx : c1;
+}
+
+// Fill pass, once per target row g of scene sc: the segment table of the later index_add_(0, hi, .):
+// rowptr_q[h] = first p with hi[p] >= h.  hi is non-decreasing and a row g of a scene that advances the numbering owns
+// h = hval(g), so rowptr_q[hval(g)] = rowptr[g]; rows of scenes that do not advance it (legacy: scenes without pairs)
+// fill the tail [h_used, T), where no pair can follow: P.  rowptr_q[T] = P.
+__device__ __forceinline__ void pairs_row_segment(const PairsJob &j, int sc, int g, int hval, int64_t pos) {
+    const int32_t *rowptr = j.rp(), *hi_base = j.hi_base();
+    const int n_agt = j.n_agt;
+    const int P = rowptr[n_agt];
+    int s0 = j.agt_off[sc], s1 = j.agt_off[sc + 1];
+    s0 = s0 < 0 ? 0 : s0 > n_agt ? n_agt : s0;
+    s1 = s1 < s0 ? s0 : s1 > n_agt ? n_agt : s1;
+    const bool advances = !j.legacy || rowptr[s1] - rowptr[s0] > 0;
+    const int q2 = hi_base[j.n_scenes] + g - hi_base[sc];
+    // a capacity below the true pair count (n_pairs comes back negative): the segment table describes the pairs
+    // that were kept, [0, cap) -- whatever walks it afterwards stays inside the caller's [cap, .] buffers
+    const int Pc = (int64_t)P > j.cap ? (int)j.cap : P;
+    if (advances) { if (hval >= 0 && hval <= n_agt) j.rowptr_q[hval] = pos > j.cap ? (int)j.cap : (int)pos; }
+    else if (q2 >= 0 && q2 <= n_agt) j.rowptr_q[q2] = Pc;
+    if (g == 0) j.rowptr_q[n_agt] = Pc;
+}
+
+// W lanes per target row, 64 / W rows per wave: the W lanes test W context rows per trip and their bits of the wave's
+// ballot order the hits (ascending s).  PASS 0 counts, PASS 1 writes (hi, wi) and the row's word of the segment table.
+// W = 64 is one wave per row, for long context lists (M2A: a scene's lane nodes); a short list (A2M, A2A: a scene's ~50
+// actors) leaves most of such a wave idle around its private chain of dependent loads, so those jobs take fewer lanes
+// per row and with them fewer waves.  The rows of a wave may lie in different scenes: a group that runs out of context
+// rows leaves the loop, and the ballot shows its lanes as zeros.  s_off: kOffLds words of LDS for agt_off; every thread
+// of the workgroup makes the call (it holds __syncthreads()).
+template <int PASS, int W>
+__device__ __forceinline__ void pairs_rows_body(const PairsJob &j, int row_block, int *s_off) {
+    const bool staged = j.n_scenes + 1 <= kOffLds;          // the same in every thread
+    if (staged) {
+        if ((int)threadIdx.x <= j.n_scenes) s_off[threadIdx.x] = j.agt_off[threadIdx.x];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63, sub = lane & (W - 1);
+    const int g = row_block * (256 / W) + (int)threadIdx.x / W;
+    if (g >= j.n_agt) return;
+    const int sc = staged ? find_seg((const int *)s_off, j.n_scenes, g) : find_seg(j.agt_off, j.n_scenes, g);
+    int c0, c1;
+    ctx_range(j, sc, c0, c1);
+    const float2 a = j.agt[g];
+    int count = 0;
+    int64_t pos = 0;
+    int hval = 0, wbase = 0;
+    if (PASS == 1) {
+        pos = j.rp()[g];
+        hval = g - (staged ? s_off[sc] : j.agt_off[sc]) + j.hi_base()[sc];
+        wbase = j.wi_base()[sc] - c0;
+        if (sub == 0) pairs_row_segment(j, sc, g, hval, pos);
+    }
+    for (int s0 = c0; s0 < c1; s0 += W) {
+        const int s = s0 + sub;
+        bool ok = false;
+        if (s < c1) {
+            const float2 c = j.ctx[s];
+            ok = within(a.x, a.y, c.x, c.y, j.th);
+        }
+        unsigned long long m = __ballot(ok);
+        if (W < 64) m = (m >> (lane - sub)) & ((1ull << (W & 63)) - 1ull);      // the row's own lanes
+        if (PASS == 0) {
+            count += __popcll(m);
+        } else {
+            if (ok) {
+                const int64_t o = pos + __popcll(m & ((1ull << sub) - 1ull));
+                if (o < j.cap) { j.hi[o] = hval; j.wi[o] = s + wbase; }
+            }
+            pos += __popcll(m);
+        }
+    }
+    if (PASS == 0 && sub == 0) j.rowptr_q[g] = count;
+}
+
+template <int PASS>
+__device__ __forceinline__ void pairs_rows_any(const PairsJob &j, int row_block, int *s_off) {
+    if (j.lanes == kShortLanes) pairs_rows_body<PASS, kShortLanes>(j, row_block, s_off);
+    else pairs_rows_body<PASS, 64>(j, row_block, s_off);
+}
+
 // blockIdx.y selects the job; blocks past a job's rows return at once
 template <int PASS>
 __global__ __launch_bounds__(256) void k_pairs_rows(const PairsJobs jobs) {
-    const PairsJob &j = jobs.j[blockIdx.y];
-    pairs_rows_body<PASS>(j.agt, j.agt_off, j.ctx, j.ctx_off, j.n_scenes, j.n_agt, j.n_ctx, j.th, j.rp(), j.rp(), j.hi_base(),
-                          j.wi_base(), j.hi, j.wi, j.cap, j.legacy, j.rowptr_q, (int)blockIdx.x);
+    __shared__ int s_off[kOffLds];
+    pairs_rows_any<PASS>(jobs.j[blockIdx.y], (int)blockIdx.x, s_off);
 }
 
-// Single block: exclusive scan of the row counts in place (rp[0..T), rp[T] = P; each thread owns a contiguous
-// run), then the per-scene index bases (lanegcn.py:681-687; legacy: a scene without pairs does not advance the
-// running counts), hi_base[n_scenes] = rows numbered in all (h_used), and P.  The pair search has at most a few
-// 10^4 rows, so one block replaces four launches.
-__device__ __forceinline__ void pairs_scan_bases_body(int32_t *rp, int n_agt, const int32_t *agt_off,
-                                                      const int32_t *ctx_off, int n_scenes, int legacy, int64_t cap,
-                                                      int32_t *hi_base, int32_t *wi_base, int32_t *n_pairs) {
-    __shared__ int lds[1024 / 64 + 1];
-    // chunks of 4096 counts: every thread scans 4 consecutive ones (adjacent threads touch adjacent words)
-    int tot = 0;
-    for (int64_t c0 = 0; c0 <= n_agt; c0 += 4096) {
-        const int64_t b = c0 + 4 * (int64_t)threadIdx.x;
-        int v[4], sum = 0;
+// Row scan and per-scene bases of one pair job, in T / 4096 + 1 tile workgroups and one base workgroup (`part` past the
+// tiles).  Both read the rows' RAW counts (rowptr_q) and the caller's tables only, never what another workgroup of the
+// launch writes.
+//   * tile workgroup: walks the 4096-row chunks (1024 threads x 4 consecutive rows: adjacent threads touch adjacent
+//     words) up to its own; of those in front it only adds up the counts -- a few 10^4 ints at most, read directly, as
+//     block_base does for the key tiles' totals -- its own it scans into rp[].  The last one holds rp[T] = P and
+//     writes n_pairs.
+//   * base workgroup: the per-scene index bases (lanegcn.py:681-687; legacy: a scene without pairs does not advance
+//     the running counts) and hi_base[n_scenes] = rows numbered in all (h_used).  Whether a scene has a pair comes from
+//     the raw counts: every row with a count marks its scene, found in the staged piece of agt_off, 1024 scenes per trip.
+static inline int64_t pairs_scan_tiles(int64_t n_agt) { return n_agt / 4096 + 1; }
+
+__device__ __forceinline__ void pairs_scan_bases_body(const PairsJob &j, int64_t part, int *lds, int *s_aoff, int *s_flag) {
+    const int32_t *cnt = j.rowptr_q;
+    const int n_agt = j.n_agt, n_scenes = j.n_scenes;
+    if (part * 4096 <= n_agt) {
+        int32_t *rp = j.rp();
+        const int64_t t0 = part * 4096, b = t0 + 4 * (int64_t)threadIdx.x;
+        int v[4] = {0, 0, 0, 0}, front = 0;
+        // no branch on what is loaded: the loads of all chunks are in flight together
+#pragma unroll 4
+        for (int64_t c0 = 0; c0 <= n_agt; c0 += 4096) {
+            if (c0 > t0) break;                                // the same in every thread
+            const int64_t i = c0 + 4 * (int64_t)threadIdx.x;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[k] = b + k < n_agt ? rp[b + k] : 0;      // rp[T] holds no count
-            sum += v[k];
+            for (int k = 0; k < 4; ++k) {
+                const int x = i + k < n_agt ? cnt[i + k] : 0;  // word T holds no count
+                if (c0 == t0) v[k] = x; else front += x;
+            }
         }
-        int chunk;
-        int off = block_exclusive_scan<1024>(sum, &chunk, lds) + tot;
+        int before, chunk;
+        block_exclusive_scan<1024>(front, &before, lds);
+        int off = block_exclusive_scan<1024>(v[0] + v[1] + v[2] + v[3], &chunk, lds) + before;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (b + k <= n_agt) rp[b + k] = off;
             off += v[k];
         }
-        tot += chunk;
+        if (threadIdx.x == 0 && t0 + 4096 > n_agt) {           // the last tile
+            const int tot = before + chunk;
+            *j.n_pairs = (int64_t)tot > j.cap ? -tot : tot;
+            if (n_agt == 0) j.rowptr_q[0] = 0;                 // no rows: the fill pass never runs for this job
+        }
+        return;
     }
-    __syncthreads();    // the scanned table is read across threads below
+    int32_t *hi_base = j.hi_base(), *wi_base = j.wi_base();
     int carry_h = 0, carry_w = 0;
     for (int c = 0; c < n_scenes; c += 1024) {
-        const int i = c + threadIdx.x;
+        const int i = c + threadIdx.x, nsc = n_scenes - c < 1024 ? n_scenes - c : 1024;
+        for (int k = threadIdx.x; k <= nsc; k += 1024) {
+            const int a = j.agt_off[c + k];
+            s_aoff[k] = a < 0 ? 0 : a > n_agt ? n_agt : a;     // caller data: never index cnt[] out of bounds
+        }
+        if (threadIdx.x < nsc) s_flag[threadIdx.x] = 0;
+        __syncthreads();
+        if (j.legacy) {
+            const int r0 = s_aoff[0], r1 = s_aoff[nsc];
+            for (int r = r0 + 4 * (int)threadIdx.x; r < r1; r += 4096) {      // 4 consecutive rows: mostly one scene, one search
+                int x[4], any = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { x[k] = r + k < r1 ? cnt[r + k] : 0; any |= x[k]; }
+                if (any <= 0) continue;
+                const int sc = find_seg((const int *)s_aoff, nsc, r);
+                if (r + 3 < s_aoff[sc + 1]) { s_flag[sc] = 1; continue; }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x[k] > 0) s_flag[find_seg((const int *)s_aoff, nsc, r + k)] = 1;
+            }
+            __syncthreads();
+        }
         int th = 0, tw = 0;
         if (i < n_scenes) {
-            int a0 = agt_off[i], a1 = agt_off[i + 1];
-            a0 = a0 < 0 ? 0 : a0 > n_agt ? n_agt : a0;          // caller data: never index rp[] out of bounds
-            a1 = a1 < a0 ? a0 : a1 > n_agt ? n_agt : a1;
-            const bool nonempty = rp[a1] - rp[a0] > 0;
-            if (!legacy || nonempty) { th = a1 - a0; tw = ctx_off[i + 1] - ctx_off[i]; }
+            const int a0 = s_aoff[threadIdx.x], a1 = s_aoff[threadIdx.x + 1] < a0 ? a0 : s_aoff[threadIdx.x + 1];
+            if (!j.legacy || s_flag[threadIdx.x]) { th = a1 - a0; tw = j.ctx_off[i + 1] - j.ctx_off[i]; }
         }
         int tot_h, tot_w;
         const int ph = block_exclusive_scan<1024>(th, &tot_h, lds);
@@ -213,17 +288,14 @@ __device__ __forceinline__ void pairs_scan_bases_body(int32_t *rp, int n_agt, co
         carry_h += tot_h;
         carry_w += tot_w;
     }
-    if (threadIdx.x == 0) {
-        hi_base[n_scenes] = carry_h;
-        *n_pairs = (int64_t)tot > cap ? -tot : tot;
-    }
+    if (threadIdx.x == 0) hi_base[n_scenes] = carry_h;
 }
 
-__global__ __launch_bounds__(1024) void k_pairs_scan_bases(const PairsJobs jobs) {    // one block per job
-    const PairsJob &j = jobs.j[blockIdx.x];
-    pairs_scan_bases_body(j.rp(), j.n_agt, j.agt_off, j.ctx_off, j.n_scenes, j.legacy, j.cap, j.hi_base(), j.wi_base(),
-                          j.n_pairs);
-    if (j.n_agt == 0 && threadIdx.x == 0) j.rowptr_q[0] = 0;     // no rows: the fill pass never runs for this job
+// blockIdx.y selects the job; blockIdx.x: a tile of its row scan, the first one past its tiles its scene bases
+__global__ __launch_bounds__(1024) void k_pairs_scan_bases(const PairsJobs jobs) {
+    __shared__ int lds[1024 / 64 + 1], s_aoff[1024 + 1], s_flag[1024];
+    const PairsJob &j = jobs.j[blockIdx.y];
+    if ((int64_t)blockIdx.x <= (int64_t)j.n_agt / 4096 + 1) pairs_scan_bases_body(j, blockIdx.x, lds, s_aoff, s_flag);
 }
 
 // ------------------------------------------------- fused index pipeline -----
@@ -240,8 +312,11 @@ __global__ __launch_bounds__(1024) void k_pairs_scan_bases(const PairsJobs jobs)
 //   * the count pass also adds up the keys of every 4096-key scan tile (LDS histogram per workgroup, one global
 //     atomic per touched tile), so the scan is ONE launch of independent tiles: tile b adds the totals in front of it.
 //   * the pair searches' count / scan / fill bodies ride in the first three launches as extra workgroups.
+//   * the count pass searches the segment table in LDS when its pieces fit kIdxSegLds words (every workgroup stages
+//     it once: a few coalesced loads per thread instead of two chains of log2(n_seg) dependent global loads per edge).
 constexpr int kIdxScanTile = 4096;      // 1024 threads x 4 keys
 constexpr int kIdxMaxTiles = 1024;      // n_keys1 <= 2^22
+constexpr int kIdxSegLds = 2048;        // 16 KB of int64: S2 has 28 pieces per scene, 896
 
 struct IndexParams {
     const int64_t *idx_local, *seg_off, *seg_base;
@@ -255,30 +330,36 @@ struct IndexParams {
     int32_t *rowptr, *col;
     int edge_blocks, scan_blocks, n_jobs;
     int job_blocks[5];                        // prefix of the pair jobs' row-block counts
+    int job_tiles[5];                         // prefix of the pair jobs' row-scan tiles
     int32_t *clear_word;                      // optional word zeroed by the count pass
     PairsJobs jobs;
 };
 
-__device__ __forceinline__ int64_t to_global(const IndexParams &p, int64_t i) {
-    return p.idx_local[i] + p.seg_base[find_seg(p.seg_off, p.n_seg, i)];      // as k_graph_gather
+// as k_graph_gather; s_seg: the staged copy of seg_off (words 1 .. n_seg - 1, all that find_seg reads) or null
+__device__ __forceinline__ int64_t to_global(const IndexParams &p, const int64_t *s_seg, int64_t i) {
+    const int sg = s_seg ? find_seg(s_seg, p.n_seg, i) : find_seg(p.seg_off, p.n_seg, i);
+    return p.idx_local[i] + p.seg_base[sg];
 }
 
 template <int PASS>     // 0: count, 1: fill
 __global__ __launch_bounds__(256) void k_index_edges(const IndexParams p) {
-    __shared__ int s_tile[kIdxMaxTiles];
+    __shared__ int s_tile[kIdxMaxTiles];      // pair-search workgroups: the row body's offset table (kOffLds)
+    __shared__ int64_t s_seg[PASS == 0 ? kIdxSegLds : 1];
+    static_assert(kOffLds <= kIdxMaxTiles, "the row body's table lives in s_tile");
     const int bid = blockIdx.x;
     if (PASS == 0 && bid == 0 && threadIdx.x == 0 && p.clear_word) *p.clear_word = 0;
     if (bid >= p.edge_blocks) {               // pair-search workgroups
         const int b = bid - p.edge_blocks;
         int jn = 0;
         while (jn + 1 < p.n_jobs && b >= p.job_blocks[jn + 1]) ++jn;
-        const PairsJob &j = p.jobs.j[jn];
-        pairs_rows_body<PASS>(j.agt, j.agt_off, j.ctx, j.ctx_off, j.n_scenes, j.n_agt, j.n_ctx, j.th, j.rp(), j.rp(), j.hi_base(),
-                              j.wi_base(), j.hi, j.wi, j.cap, j.legacy, j.rowptr_q, b - p.job_blocks[jn]);
+        pairs_rows_any<PASS>(p.jobs.j[jn], b - p.job_blocks[jn], s_tile);
         return;
     }
+    const bool seg_lds = PASS == 0 && p.n_seg <= kIdxSegLds;
     if (PASS == 0) {
         for (int i = threadIdx.x; i < p.scan_blocks; i += blockDim.x) s_tile[i] = 0;
+        if (seg_lds)
+            for (int i = 1 + threadIdx.x; i < p.n_seg; i += blockDim.x) s_seg[i] = p.seg_off[i];
         __syncthreads();
     }
     const int64_t total = p.start[p.n_rel];
@@ -287,7 +368,8 @@ __global__ __launch_bounds__(256) void k_index_edges(const IndexParams p) {
         while (r + 1 < p.n_rel && e >= p.start[r + 1]) ++r;
         if (PASS == 0) {
             const int64_t le = e - p.start[r];
-            const int64_t u = to_global(p, p.u_off[r] + le), v = to_global(p, p.v_off[r] + le);
+            const int64_t *seg = seg_lds ? s_seg : nullptr;
+            const int64_t u = to_global(p, seg, p.u_off[r] + le), v = to_global(p, seg, p.v_off[r] + le);
             const bool ok = u >= 0 && u < p.n_nodes && v >= 0 && v < p.n_nodes;     // never index out of bounds
             p.uv[2 * e] = ok ? (int32_t)u : -1;
             p.uv[2 * e + 1] = (int32_t)v;
@@ -312,13 +394,13 @@ __global__ __launch_bounds__(256) void k_index_edges(const IndexParams p) {
 }
 
 __global__ __launch_bounds__(1024) void k_index_scan(const IndexParams p) {
-    __shared__ int lds[1024 / 64 + 1];
+    __shared__ int lds[1024 / 64 + 1], s_aoff[1024 + 1], s_flag[1024];
     const int bid = blockIdx.x;
-    if (bid >= p.scan_blocks) {               // one workgroup per pair search: row scan + per-scene bases
-        const PairsJob &j = p.jobs.j[bid - p.scan_blocks];
-        pairs_scan_bases_body(j.rp(), j.n_agt, j.agt_off, j.ctx_off, j.n_scenes, j.legacy, j.cap, j.hi_base(), j.wi_base(),
-                              j.n_pairs);
-        if (j.n_agt == 0 && threadIdx.x == 0) j.rowptr_q[0] = 0;
+    if (bid >= p.scan_blocks) {               // pair searches: per job its row-scan tiles and one workgroup for the bases
+        const int b = bid - p.scan_blocks;
+        int jn = 0;
+        while (jn + 1 < p.n_jobs && b >= p.job_tiles[jn + 1]) ++jn;
+        pairs_scan_bases_body(p.jobs.j[jn], b - p.job_tiles[jn], lds, s_aoff, s_flag);
         return;
     }
     // keys in front of this tile: the totals of the tiles in front of it (<= 1024: one per thread; bid is blockIdx.x here)
@@ -538,6 +620,7 @@ static PairsJob to_device_job(const lgcn_pairs_job_t &q) {
     d.ctx = (const float2 *)q.ctx_ctrs; d.ctx_off = q.ctx_off;
     d.n_scenes = q.n_scenes; d.n_agt = (int)q.n_agt; d.n_ctx = (int)q.n_ctx; d.legacy = q.legacy_offsets; d.th = q.dist_th;
     d.hi = q.hi; d.wi = q.wi; d.cap = q.cap; d.n_pairs = q.n_pairs; d.rowptr_q = q.rowptr; d.ws = q.ws;
+    d.lanes = pairs_row_lanes(q.n_ctx, q.n_scenes);
     return d;
 }
 
@@ -546,21 +629,22 @@ int lgcn_pairs_build_multi(const lgcn_pairs_job_t *jobs, int n_jobs, void *strea
     LGCN_CHECK_PTR(jobs);
     hipStream_t st = (hipStream_t)stream;
     PairsJobs dj;
-    int64_t max_rows = 0;
+    int64_t row_blocks = 0, tiles = 0;
     for (int k = 0; k < n_jobs; ++k) {
         const lgcn_pairs_job_t &q = jobs[k];
         const int rc = pairs_job_check(q);
         if (rc != LGCN_OK) return rc;
         dj.j[k] = to_device_job(q);
-        if (q.n_agt > max_rows) max_rows = q.n_agt;
+        const int64_t nb = pairs_row_blocks(q.n_agt, dj.j[k].lanes), nt = pairs_scan_tiles(q.n_agt);
+        if (nb > row_blocks) row_blocks = nb;
+        if (nt > tiles) tiles = nt;
     }
     for (int k = n_jobs; k < 4; ++k) dj.j[k] = dj.j[0];
-    // three launches for all jobs: count per target row, scan + per-scene bases (one block per job), fill
-    // (+ segment table).  A job without rows still gets rowptr[0] = P = 0 from the scan block.
-    const unsigned row_blocks = (unsigned)((max_rows + 3) / 4);
-    if (max_rows > 0) hipLaunchKernelGGL((k_pairs_rows<0>), dim3(row_blocks, n_jobs), dim3(256), 0, st, dj);
-    hipLaunchKernelGGL(k_pairs_scan_bases, dim3(n_jobs), dim3(1024), 0, st, dj);
-    if (max_rows > 0) hipLaunchKernelGGL((k_pairs_rows<1>), dim3(row_blocks, n_jobs), dim3(256), 0, st, dj);
+    // three launches for all jobs: count per target row, scan tiles + per-scene bases (one more block per job), fill
+    // (+ segment table).  A job without rows still gets rowptr[0] = P = 0 from its scan tile.
+    if (row_blocks > 0) hipLaunchKernelGGL((k_pairs_rows<0>), dim3((unsigned)row_blocks, n_jobs), dim3(256), 0, st, dj);
+    hipLaunchKernelGGL(k_pairs_scan_bases, dim3((unsigned)(tiles + 1), n_jobs), dim3(1024), 0, st, dj);
+    if (row_blocks > 0) hipLaunchKernelGGL((k_pairs_rows<1>), dim3((unsigned)row_blocks, n_jobs), dim3(256), 0, st, dj);
     return launch_status();
 }
 
@@ -614,16 +698,19 @@ int lgcn_index_build(const lgcn_index_t *ph, void *stream) {
     p.n_jobs = q.n_jobs;
     p.clear_word = q.clear_word;
     p.job_blocks[0] = 0;
+    p.job_tiles[0] = 0;
     for (int k = 0; k < 4; ++k) {
         if (k < q.n_jobs) {
             const lgcn_pairs_job_t &jq = q.jobs[k];
             const int rc = pairs_job_check(jq);
             if (rc != LGCN_OK) return rc;
             p.jobs.j[k] = to_device_job(jq);
-            p.job_blocks[k + 1] = p.job_blocks[k] + (int)((jq.n_agt + 3) / 4);
+            p.job_blocks[k + 1] = p.job_blocks[k] + (int)pairs_row_blocks(jq.n_agt, p.jobs.j[k].lanes);
+            p.job_tiles[k + 1] = p.job_tiles[k] + (int)pairs_scan_tiles(jq.n_agt) + 1;       // + the base workgroup
         } else {
             if (k > 0) p.jobs.j[k] = p.jobs.j[0];
             p.job_blocks[k + 1] = p.job_blocks[k];
+            p.job_tiles[k + 1] = p.job_tiles[k];
         }
     }
     if (q.n_jobs == 0) {
@@ -636,7 +723,7 @@ int lgcn_index_build(const lgcn_index_t *ph, void *stream) {
     const unsigned g13 = (unsigned)(p.edge_blocks + p.job_blocks[4]);
     if (g13 > 0) hipLaunchKernelGGL((k_index_edges<0>), dim3(g13), dim3(256), 0, st, p);
     else if (q.clear_word) { hipError_t e = hipMemsetAsync(q.clear_word, 0, 4, st); if (e != hipSuccess) return (int)e; }
-    hipLaunchKernelGGL(k_index_scan, dim3((unsigned)(p.scan_blocks + q.n_jobs)), dim3(1024), 0, st, p);
+    hipLaunchKernelGGL(k_index_scan, dim3((unsigned)(p.scan_blocks + p.job_tiles[4])), dim3(1024), 0, st, p);
     if (g13 > 0) hipLaunchKernelGGL((k_index_edges<1>), dim3(g13), dim3(256), 0, st, p);
     if (total > 0) hipLaunchKernelGGL(k_index_sort, dim3((unsigned)((nk1 + 255) / 256)), dim3(256), 0, st, p);
     return launch_status();

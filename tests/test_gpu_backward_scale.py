@@ -496,6 +496,41 @@ def test_pred_loss_fn(mods, mma_scope, mode):
         assert_anchored("pred_loss", base, stock(torch.float64), stock(torch.float32))
 
 
+@pytest.mark.parametrize("n", [1025, 4097])
+def test_pred_loss_past_the_grid(mods, mma_scope, n):
+    """1025 actors: more than one per thread of the forward's 1024-thread block.  4097: one more than the 4096 workgroups of
+    k_pred_loss_bwd, so workgroup 0 strides on to a second actor.  Gradients and both sums against the stock composition in
+    float64 at bar(error of the stock composition in fp32); the counts equal; zero exactly where float64 is zero."""
+    M, A, ops, L = mods
+    mma_scope("f32")
+    cls0, reg0, gt, has = pred_loss_inputs(n)
+    p = cuda_leaves(dict(cls=cls0, reg=reg0))
+    c_loss, r_loss, counts = A.PredLossFn.apply(p["cls"], p["reg"], gt.cuda(), has.cuda(), M.config)
+    d_outs = [torch.tensor(v, device="cuda") for v in UP[:2]]
+    got = dict(zip(p, torch.autograd.grad([c_loss, r_loss], list(p.values()), d_outs)))
+
+    def stock(dtype):
+        q = {k: v.to(dtype).clone().requires_grad_(True) for k, v in dict(cls=cls0, reg=reg0).items()}
+        lo = M.PredLoss(M.config)({"cls": [q["cls"]], "reg": [q["reg"]]}, [gt.to(dtype)], [has])
+        (UP[0] * lo["cls_loss"] + UP[1] * lo["reg_loss"]).backward()
+        return {k: v.grad for k, v in q.items()}, lo
+
+    ref, lo64 = stock(torch.float64)
+    cmp_, lo32 = stock(torch.float32)
+    assert_anchored("pred_loss A=%d" % n, got, ref, cmp_)
+    rel = lambda x, y: abs(x.item() - y.item()) / abs(y.item())
+    sums = [(k, rel(v, lo64[k]), rel(lo32[k], lo64[k])) for k, v in (("cls_loss", c_loss), ("reg_loss", r_loss))]
+    for k, e, ec in sums:
+        print("pred_loss A=%d %-10s hip %.3e stock fp32 %.3e" % (n, k, e, ec))
+    assert all(e <= B.bar(ec) for _, e, ec in sums), sums
+    assert counts.tolist() == [lo64["num_cls"], lo64["num_reg"]] == [lo32["num_cls"], lo32["num_reg"]] and min(counts.tolist()) > 0
+    for k in ref:                                          # dropped actors, unselected modes, unobserved steps
+        zero = ref[k] == 0
+        assert bool(zero[::5].all()), k                     # pred_loss_inputs: every fifth actor is never observed, so it is dropped
+        assert bool((got[k].cpu()[zero] == 0).all()), k
+        assert bool((got[k].cpu()[~zero] != 0).all()), k
+
+
 @pytest.mark.parametrize("mode", MODES)
 def test_roi_loss_fn(mods, mma_scope, mode):
     M, A, ops, L = mods

@@ -78,9 +78,10 @@ def test_roi_loss_kernels_on_the_reference_run(ops):
     check(ops, None, ref32, RM.reference(), "A=37")
 
 
-@pytest.mark.parametrize("rows", [1, 1025])
+@pytest.mark.parametrize("rows", [1, 1025, 4097])
 def test_roi_loss_kernels_on_tiled_rows(ops, rows):
-    """1025 agents: more than one agent per thread of the 1024-thread block, and the whole cross-thread tree."""
+    """1025 agents: more than one agent per thread of the 1024-thread block, and the whole cross-thread tree.  4097 agents:
+    one more than the 4096 workgroups of k_roi_loss_bwd, so workgroup 0 strides on to a second agent."""
     check(ops, rows, RM.reference(rows, torch.float32), RM.reference(rows), "A=%d" % rows)
 
 
